@@ -7,7 +7,14 @@ offline forward, wave -> wave (the caller loop of infer.py:60-76), synthetic N(0
 already resident in HBM, shipped checkpoint weights (tests/golden/params_dns3.f32).
 One "step" = one pass of the fused kernels over the batch = 256 x 251 = 64 256 frames per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, ONE timed region of exactly K steps, and
+the JSON line (`value`, `ms_per_step` and the fields derived from that region).  `--full` adds everything else listed
+below: five timed regions of K steps (the line reports the median one), HIP events on the dominant kernel inside them,
+the per-kernel pass, the roofline, the secondary legs and the CPU baseline.  `--repeats R` overrides the region count
+of either form.  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) so that two builds
+can be compared output for output: the inputs depend on the arguments alone.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (one process per GPU,
 `python -m torch.distributed.run` on 127.0.0.1, like the reference's own mp.spawn, train.py:461-471) BEFORE
@@ -19,7 +26,7 @@ Multi-GPU: utterances are independent, so every rank runs its own 256-clip shard
 data-path collective (weak scaling); torch.distributed (RCCL) is used only for the barrier and the
 max-over-ranks of the elapsed time.
 
-Besides the headline fields the JSON line carries
+With --full, besides the headline fields the JSON line carries
   roofline      the dominant kernel: algorithmic fp32 FLOPs per launch / average launch duration from HIP
                 events recorded on the launch stream inside the timed region, against the dense fp32 MFMA
                 peak (157.3 TFLOP/s, MI355X_MICROARCH.md); `traffic` = HBM bytes per launch from the
@@ -101,6 +108,22 @@ def train_hbm_bytes():
 
 TRAIN_HBM_BYTES_PER_STEP, TRAIN_HBM_SOURCE_FILE = train_hbm_bytes()
 WATCHDOG_EXIT_CODE = 3                                  # exit status of every rank when a watchdog had to cut a leg
+DUMP_LIMIT_BYTES = 64 * 10 ** 6                         # --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the enhanced waveforms of the last timed step, as a caller of forward_wave receives them, written
+    as DIR/enhanced.npy (float32, clips x samples; rank 0's shard).  Whole clips; where the batch exceeds
+    DUMP_LIMIT_BYTES, a fixed seeded choice of clips in batch order (and a clip longer than the whole budget: its head)."""
+    import numpy as np
+    y = out.detach().float().cpu().numpy()
+    B, n = y.shape
+    keep = max(1, min(B, DUMP_LIMIT_BYTES // (4 * n)))
+    if keep < B:
+        y = y[np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))]
+    y = y[:, :DUMP_LIMIT_BYTES // (4 * keep)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "enhanced.npy"), np.ascontiguousarray(y, dtype=np.float32))
 
 
 def _free_port():
@@ -1062,6 +1085,51 @@ def train_main(args):
     return 0
 
 
+def headline_roofline(dom, dom_ms, dom_launches, frames_per_step, ms_per_step, value, world):
+    """--full: the dominant kernel inside the headline timed region against the fp32 MFMA peak (module docstring)."""
+    flops_launch = 2.0 * MAC_PER_FRAME[dom] * frames_per_step
+    achieved = flops_launch / (dom_ms * 1e-3) / 1e12
+    traffic, traffic_source = None, None
+    for tag in (ROUND_TAG, "r05", "r04", "r03", "r02", "r01"):
+        tf = os.path.join(ROOT, "profiles", f"{tag}_hbm_traffic.json")
+        if os.path.exists(tf):
+            try:
+                traffic = json.load(open(tf)).get(dom, {}).get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+            if traffic is not None:
+                traffic_source = (f"profiles/{tag}_hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                  "this command on the builder's box (committed profile) -- a constant of the build, NOT "
+                                  "measured by the run that printed this line")
+                break
+    path_flop = (2.0 * MODEL_MAC_PER_FRAME + FFT_FLOP_PER_FRAME) * frames_per_step
+    roof = {
+        "bound": "mfma", "kernel": dom, "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS,
+        "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+        "traffic_source": traffic_source,
+        "flop_per_launch": flops_launch, "avg_launch_ms": round(dom_ms, 4), "launches": dom_launches,
+        # whole path against the same peak, from the headline's own step time (not from a sum of event times)
+        "path_tflops": round(path_flop / (ms_per_step * 1e-3) / 1e12, 3),
+        "path_frac": round(path_flop / (ms_per_step * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
+        "hbm_frac_at_boundary": round(value / world * 2048 / 1e9 / HBM_PEAK_GBS, 6),
+    }
+    if dom in MFMA_PER_FRAME:
+        # what the kernel EXECUTES on the matrix cores (frac above prices the algorithmic fp32 FLOPs against the fp32
+        # matrix peak, as the metric defines the work): zero padding of the 8->16 / 16->8 pointwise and K = 15
+        # tiles on the fp32 MFMA, and the dense 3x3 six times over on the bf16 pipe
+        f32x = 2048.0 * MFMA_PER_FRAME[dom] * frames_per_step
+        bfx = 16384.0 * BF16_MFMA_PER_FRAME.get(dom, 0.0) * frames_per_step
+        roof["executed_fp32_mfma_flop_per_launch"] = f32x
+        roof["executed_bf16_mfma_flop_per_launch"] = bfx
+        roof["executed_tflops"] = round((f32x + bfx) / (dom_ms * 1e-3) / 1e12, 1)
+        if bfx:
+            roof["executed_bf16_frac_of_bf16_peak"] = round(bfx / (dom_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)
+            roof["note"] = ("dense 3x3 and de_convs.3 on v_mfma_f32_16x16x32_bf16 from an exact 3-way bf16 split "
+                            "of both operands (6 products, fp32 accumulate; held to the float64 graph by "
+                            "tests/test_gpu_precision.py); pointwise convs on the fp32 MFMA")
+    return roof
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
@@ -1071,17 +1139,30 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=None,
                     help="clips per GPU (default: 256 for the headline, configs[1]; 512 for --mode train, configs[3])")
     ap.add_argument("--seconds", type=float, default=4.0, help="clip length")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each; the line reports the median one (and min / max)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the line reports the median one (and min / max).  "
+                         "Default: 1, or 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: repeated regions, per-kernel times, roofline, the "
+                         "secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/enhanced.npy (infer mode)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the stream/train/quant legs (profiling runs of the headline path)")
+                    help="with --full: skip the stream/train/quant legs (profiling runs of the headline path)")
     ap.add_argument("--mode", choices=["infer", "train"], default="infer",
-                    help="infer (default): the headline metric plus the secondary objects.  train: configs[3] only")
+                    help="infer (default): the headline metric (with --full, plus the secondary objects).  train: "
+                         "configs[3] only")
     ap.add_argument("--train-storage", choices=["f32", "bf16", "bf16_saves", "bf16_grads"], default="f32")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and args.mode == "train":
+        raise SystemExit("--dump-outputs writes the headline (infer) path's outputs; --mode train has none")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args, argv)                         # before torch / HIP are touched in this process
@@ -1146,16 +1227,18 @@ def main(argv=None):
         for _ in range(20):
             eng.forward_wave(wave, win, out=out)
         torch.cuda.synchronize()
-    # W warm-up steps with HIP events around every kernel: picks the dominant kernel
-    eng.timing_enable(True)
+    # W warm-up steps; with --full, HIP events around every kernel pick the dominant kernel
+    if args.full:
+        eng.timing_enable(True)
     for _ in range(max(args.warmup, 1)):
         eng.forward_wave(wave, win, out=out)
     sync_all()
-    kern_warm = eng.timing_read()
-    dom = max((k for k in kern_warm if k in MAC_PER_FRAME), key=lambda k: kern_warm[k][0])
-    # the timed region keeps only the dominant kernel's events (on the launch stream): each event pair costs a
-    # few microseconds of dispatch gap, one pair per kernel per step would be ~4 % of the step
-    eng.timing_enable(True, only=dom)
+    if args.full:
+        kern_warm = eng.timing_read()
+        dom = max((k for k in kern_warm if k in MAC_PER_FRAME), key=lambda k: kern_warm[k][0])
+        # the timed region keeps only the dominant kernel's events (on the launch stream): each event pair costs a
+        # few microseconds of dispatch gap, one pair per kernel per step would be ~4 % of the step
+        eng.timing_enable(True, only=dom)
     # R timed regions of EXACTLY K steps each, every one bracketed by barrier + synchronize on both sides and priced
     # with the slowest rank; the line reports min / median / max and `value` is the MEDIAN region (a single 20-50 ms
     # region is one sample of a box whose clocks move by a few percent)
@@ -1169,7 +1252,8 @@ def main(argv=None):
         sync_all()
         mine = time.perf_counter() - t0
         regions.append((max_over_ranks(mine, dev), mine))
-    dom_ms, dom_launches = eng.timing_read()[dom]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)                   # the last timed step's result, before anything else runs
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     med = order[(len(order) - 1) // 2]                         # the (lower) median region: an actually measured one
     elapsed = regions[med][0]                                  # the slowest rank defines the step time
@@ -1177,64 +1261,25 @@ def main(argv=None):
     host_all = gather_ranks(sorted(host_enqueue)[len(host_enqueue) // 2] * 1e6, world)
     numa_all = gather_ranks(numa, world) if world > 1 else None      # per rank: {"numa_node", "cpus", "bound"} or None
     region_ms = sorted(r[0] / args.steps * 1e3 for r in regions)
-    # the per-kernel split: ONE separate pass of K steps with an event pair around every kernel (all kernel_ms
-    # values come from here; its step time is reported next to the headline's)
-    eng.timing_enable(True)
-    sync_all()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.forward_wave(wave, win, out=out)
-    sync_all()
-    split_ms_per_step = (time.perf_counter() - t1) / args.steps * 1e3
-    kern = eng.timing_read()
-    eng.timing_enable(False)
+    if args.full:
+        dom_ms, dom_launches = eng.timing_read()[dom]
+        # the per-kernel split: ONE separate pass of K steps with an event pair around every kernel (all kernel_ms
+        # values come from here; its step time is reported next to the headline's)
+        eng.timing_enable(True)
+        sync_all()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.forward_wave(wave, win, out=out)
+        sync_all()
+        split_ms_per_step = (time.perf_counter() - t1) / args.steps * 1e3
+        kern = eng.timing_read()
+        eng.timing_enable(False)
     assert bool(torch.isfinite(out).all())
 
     line = None
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * frames_per_step * args.steps / elapsed
-        flops_launch = 2.0 * MAC_PER_FRAME[dom] * frames_per_step
-        achieved = flops_launch / (dom_ms * 1e-3) / 1e12
-        traffic, traffic_source = None, None
-        for tag in (ROUND_TAG, "r05", "r04", "r03", "r02", "r01"):
-            tf = os.path.join(ROOT, "profiles", f"{tag}_hbm_traffic.json")
-            if os.path.exists(tf):
-                try:
-                    traffic = json.load(open(tf)).get(dom, {}).get("hbm_bytes_per_launch")
-                except Exception:
-                    traffic = None
-                if traffic is not None:
-                    traffic_source = (f"profiles/{tag}_hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                      "this command on the builder's box (committed profile) -- a constant of the build, NOT "
-                                      "measured by the run that printed this line")
-                    break
-        path_flop = (2.0 * MODEL_MAC_PER_FRAME + FFT_FLOP_PER_FRAME) * frames_per_step
-        sum_ms = sum(v[0] for v in kern.values())
-        roof = {
-            "bound": "mfma", "kernel": dom, "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS,
-            "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-            "traffic_source": traffic_source,
-            "flop_per_launch": flops_launch, "avg_launch_ms": round(dom_ms, 4), "launches": dom_launches,
-            # whole path against the same peak, from the headline's own step time (not from a sum of event times)
-            "path_tflops": round(path_flop / (ms_per_step * 1e-3) / 1e12, 3),
-            "path_frac": round(path_flop / (ms_per_step * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
-            "hbm_frac_at_boundary": round(value / world * 2048 / 1e9 / HBM_PEAK_GBS, 6),
-        }
-        if dom in MFMA_PER_FRAME:
-            # what the kernel EXECUTES on the matrix cores (frac above prices the algorithmic fp32 FLOPs against the fp32
-            # matrix peak, as the metric defines the work): zero padding of the 8->16 / 16->8 pointwise and K = 15
-            # tiles on the fp32 MFMA, and the dense 3x3 six times over on the bf16 pipe
-            f32x = 2048.0 * MFMA_PER_FRAME[dom] * frames_per_step
-            bfx = 16384.0 * BF16_MFMA_PER_FRAME.get(dom, 0.0) * frames_per_step
-            roof["executed_fp32_mfma_flop_per_launch"] = f32x
-            roof["executed_bf16_mfma_flop_per_launch"] = bfx
-            roof["executed_tflops"] = round((f32x + bfx) / (dom_ms * 1e-3) / 1e12, 1)
-            if bfx:
-                roof["executed_bf16_frac_of_bf16_peak"] = round(bfx / (dom_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)
-                roof["note"] = ("dense 3x3 and de_convs.3 on v_mfma_f32_16x16x32_bf16 from an exact 3-way bf16 split "
-                                "of both operands (6 products, fp32 accumulate; held to the float64 graph by "
-                                "tests/test_gpu_precision.py); pointwise convs on the fp32 MFMA")
         line = {
             "metric": "16 kHz frames/sec (STFT->mask->iSTFT)",
             "value": round(value, 1),
@@ -1267,24 +1312,27 @@ def main(argv=None):
             # are asynchronous, so this is what N processes on one host contend with, not the step time
             "host_us_per_step": round(max(host_all), 1),
             "host_us_per_step_per_rank": [round(x, 1) for x in host_all],
-            "roofline": roof,
-            "kernel_ms": {k: round(v[0], 4) for k, v in kern.items()},
-            "sum_kernel_ms": round(sum_ms, 4),
-            "kernel_ms_note": f"all from ONE separate pass of {args.steps} steps with an event pair around every "
-                              f"kernel (that pass: {split_ms_per_step:.4f} ms/step); roofline.avg_launch_ms is "
-                              f"{dom}'s alone inside the headline timed region",
         }
+        if args.full:
+            line.update({
+                "roofline": headline_roofline(dom, dom_ms, dom_launches, frames_per_step, ms_per_step, value, world),
+                "kernel_ms": {k: round(v[0], 4) for k, v in kern.items()},
+                "sum_kernel_ms": round(sum(v[0] for v in kern.values()), 4),
+                "kernel_ms_note": f"all from ONE separate pass of {args.steps} steps with an event pair around every "
+                                  f"kernel (that pass: {split_ms_per_step:.4f} ms/step); roofline.avg_launch_ms is "
+                                  f"{dom}'s alone inside the headline timed region",
+            })
     get_line = lambda: line
 
     def put(name, val, into=None):                             # results join the line as they arrive: a watchdog
         if line is not None and val is not None:               # print carries every leg that finished
             (line if into is None else line.setdefault(into, {}))[name] = val
 
-    if shim and hasattr(shim, "secondary_legs"):
+    if args.full and shim and hasattr(shim, "secondary_legs"):
         # TEST ONLY: stand-in legs that fail or hang on one rank exercise run_leg / Watchdog on CPU over gloo
         for name, (fn, timeout_s) in shim.secondary_legs(rank, world).items():
             put(name, run_leg(name, fn, rank, world, get_line, timeout_s))
-    if not shim and not args.no_secondary:
+    if args.full and not shim and not args.no_secondary:
         # the host-link leg FIRST: it is what a serving process does from its start, and the duplex DMA rate depends on what
         # the process did before -- after the streaming-capacity leg (40 GB of state allocated and freed) both directions
         # at once run at 28 GB/s each and the served step takes 2.0-2.6 ms; in a fresh process 48 GB/s each and 1.47 ms
@@ -1317,7 +1365,7 @@ def main(argv=None):
         for storage in ("f32", "bf16", "bf16_saves", "bf16_grads"):
             put(storage, guarded_train_leg(storage, rank, world, get_line), into="train")
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not shim:
+        if world == 1 and args.full and not args.no_cpu_baseline and not shim:
             line["cpu_baseline"] = cpu_baseline(params)
             # a reported baseline, not the target: the CPU leg moves 2x from host to host on the pool, so the ratio says
             # no more than ">> 100x" (north_star's bar) -- it lives inside the object, not at the top of the line

@@ -119,6 +119,39 @@ def test_bench_refuses_mislabelled_world():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times ONE region of exactly --steps steps and carries none of --full's fields; --dump-outputs writes
+    what the last timed step computed, from inputs that the arguments alone fix (the same array plain and --full)."""
+    import numpy as np
+    import torch
+    env = dict(os.environ, OMP_NUM_THREADS="1", **_SHIM_ENV)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--batch", "4", "--seconds", "0.5"]
+    lines = {}
+    for form, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(args + ["--dump-outputs", str(tmp_path / form)] + extra, cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines[form] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+        assert d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert plain["repeats"]["regions"] == 1 and plain["repeats"]["steps_per_region"] == 3
+    assert not {"roofline", "kernel_ms", "sum_kernel_ms", "cpu_baseline"} & set(plain)
+    assert full["repeats"]["regions"] == 5 and {"roofline", "kernel_ms", "sum_kernel_ms"} <= set(full)
+    a, b = (np.load(tmp_path / form / "enhanced.npy") for form in ("plain", "full"))
+    n = 256 * (8000 // 256)
+    assert a.dtype == np.float32 and a.shape == (4, n) and np.array_equal(a, b)
+    torch.manual_seed(43)
+    wave = torch.randn(4, 8000) * 0.1
+    assert np.array_equal(a, (wave[:, :n] * 0.5).numpy())      # the shim's stand-in for forward_wave: wave x 0.5
+
+
 def test_bench_has_no_builtin_fake_engine():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "--cpu-stub" not in src and "class _Stub" not in src
@@ -313,7 +346,8 @@ def test_train_leg_prepare_has_no_optimizer_step():
 def test_secondary_leg_failing_on_one_rank_does_not_hang_or_lose_the_line():
     """Rank 1 raises inside a secondary leg before any collective: the leg reports the error per rank, the legs before
     and after it complete (priced with the slower rank's time) and the headline is intact."""
-    r = _torchrun([os.path.join(ROOT, "bench.py")] + _BENCH_ARGS, extra_env=dict(_SHIM_ENV, GTCRN_BENCH_TEST_LEGS="fail1"))
+    r = _torchrun([os.path.join(ROOT, "bench.py")] + _BENCH_ARGS + ["--full"],
+                  extra_env=dict(_SHIM_ENV, GTCRN_BENCH_TEST_LEGS="fail1"))
     assert r.returncode == 0, r.stderr[-2000:]
     d = _check_bench_line(r.stdout, 3, 1)
     assert d["second"] == {"error": {"1": "RuntimeError('simulated out-of-memory on rank 1')"}}
@@ -326,7 +360,7 @@ def test_secondary_leg_hanging_on_one_rank_is_cut_by_the_watchdog():
     """Rank 1 never returns from a secondary leg (the shape of a rank stuck in, or dead before, a collective): after the
     leg's time limit rank 0 prints the line as it stands -- headline and the finished leg -- and every rank exits with a
     non-zero status (a watchdog on a process that may hold the GPU must not report success; no re-exec)."""
-    r = _torchrun([os.path.join(ROOT, "bench.py")] + _BENCH_ARGS, timeout=120,
+    r = _torchrun([os.path.join(ROOT, "bench.py")] + _BENCH_ARGS + ["--full"], timeout=120,
                   extra_env=dict(_SHIM_ENV, GTCRN_BENCH_TEST_LEGS="hang1"))
     assert r.returncode != 0            # a rank hung: the line is kept, but the launcher / driver see a FAILED run
     d = _check_bench_line(r.stdout, 3, 1)

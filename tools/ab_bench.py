@@ -25,7 +25,8 @@ def run(variant, batch):
     env.pop("GTCRN_LIB_VARIANT", None)
     if variant:
         env["GTCRN_LIB_VARIANT"] = variant
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-secondary", "--no-cpu-baseline", "--batch", str(batch)]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-secondary", "--no-cpu-baseline",
+           "--batch", str(batch)]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, check=True).stdout
     d = json.loads(out.strip().splitlines()[-1])
     k = dict(d["kernel_ms"])
