@@ -75,6 +75,12 @@ def lib():
     L.gtcrn_stream_step.argtypes = [_vp, _vp, _vp, cl, cl, cl, _vp, cl, cl, cl, ci, ci, _vp]
     L.gtcrn_stream_import.argtypes = [_vp, _vp, ci, _vp, _vp, ctypes.POINTER(_vp), _vp]
     L.gtcrn_stream_export.argtypes = [_vp, _vp, ci, _vp, _vp, ctypes.POINTER(_vp), _vp]
+    L.gtcrn_wave_stream_state_bytes.restype = ctypes.c_size_t
+    L.gtcrn_wave_stream_reset.argtypes = [_vp, _vp, _vp, ci, _vp]
+    for fn in ("gtcrn_wave_stream_step", "gtcrn_wave_stream_step_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
+    for fn in ("gtcrn_wave_stream_flush", "gtcrn_wave_stream_flush_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, ci, _vp, cl, ci, _vp, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -469,6 +475,97 @@ class Engine:
                                            out.data_ptr(), osb, osf, ost, N, nfr, _stream_ptr()))
         return out
 
+    # ---- hop-level waveform streaming (contract: include/gtcrn_micro_hip.h, gtcrn_wave_stream_*) ----------------
+    @staticmethod
+    def wave_state_bytes():
+        return int(lib().gtcrn_wave_stream_state_bytes())
+
+    def new_wave_state(self, nstreams, window):
+        """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
+        counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
+        one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it)."""
+        import torch
+        n = int(nstreams)
+        if n < 1:
+            raise GtcrnError("nstreams must be >= 1")
+        if not isinstance(window, torch.Tensor):
+            window = torch.as_tensor(np.asarray(window, np.float32))
+        win = window.detach().to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous()
+        if win.dim() != 1 or win.numel() != 512:
+            raise GtcrnError(f"the window must hold 512 samples, got shape {tuple(window.shape)}")
+        if float(win[0]) != 0.0:
+            raise GtcrnError(f"the window must have window[0] == 0 (periodic Hann-type), got {float(win[0])!r}")
+        st = WaveStreamState(self.new_state(n),
+                             torch.empty((n, self.wave_state_bytes() // 4), device=win.device, dtype=torch.float32), win)
+        self.wave_stream_reset(st)
+        return st
+
+    def wave_stream_reset(self, state, lo=0, hi=None):
+        """Resets streams lo..hi-1 (both states) to the start of a new clip."""
+        hi = state.n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= state.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        with self._dev():
+            _check(lib().gtcrn_wave_stream_reset(self._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
+                                                 hi - lo, _stream_ptr()))
+
+    def _wave_rows(self, state, x, what):
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
+            raise GtcrnError(f"{what} must be a float32 or int16 CUDA (ROCm) tensor")
+        if x.device.index != self.device:
+            raise GtcrnError(f"{what} is on cuda:{x.device.index}, the model on cuda:{self.device}")
+        if not isinstance(state, WaveStreamState) or state.model.device != x.device:
+            raise GtcrnError("state must come from new_wave_state on the model's device")
+        if x.dim() != 2 or x.shape[0] != state.n:
+            raise GtcrnError(f"{what} must be ({state.n}, samples), got {tuple(x.shape)}")
+        if x.stride(1) != 1 and x.shape[1] > 1:
+            x = x.contiguous()
+        return x
+
+    @staticmethod
+    def _wave_out(out, like, cols):
+        import torch
+        if out is None:
+            return torch.empty((like.shape[0], cols), device=like.device, dtype=like.dtype)
+        if (not isinstance(out, torch.Tensor) or out.dtype != like.dtype or out.device != like.device
+                or tuple(out.shape) != (like.shape[0], cols) or out.stride(1) != 1):
+            raise GtcrnError(f"out must be a {like.dtype} tensor of shape ({like.shape[0]}, {cols}) with contiguous rows")
+        return out
+
+    def wave_stream_step(self, state, x, out=None):
+        """x (N, 256*nhops) float32 or int16 -> the enhanced (N, 256*nhops), same dtype, one hop late (call 0 of a
+        stream emits zeros).  Asynchronous on the current stream; no allocation when `out` is given and
+        reserve(N, nhops) was called (capturable)."""
+        import torch
+        x = self._wave_rows(state, x, "x")
+        L = x.shape[1]
+        if L < 256 or L % 256:
+            raise GtcrnError(f"x must hold a whole number of 256-sample hops per stream, got {L}")
+        out = self._wave_out(out, x, L)
+        fn = lib().gtcrn_wave_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step
+        with self._dev():
+            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
+                      out.stride(0), state.n, L // 256, state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def wave_stream_flush(self, state, tail, out=None):
+        """tail (N, r) float32 or int16, r = 0..255: the samples after the last whole hop -> the last 256 enhanced
+        samples of every stream.  Ends the streams (reset them before reuse)."""
+        import torch
+        tail = self._wave_rows(state, tail, "tail")
+        r = tail.shape[1]
+        if r > 255:
+            raise GtcrnError(f"the tail holds 0..255 samples, got {r}: push whole hops with wave_stream_step first")
+        out = self._wave_out(out, tail, 256)
+        fn = lib().gtcrn_wave_stream_flush_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush
+        with self._dev():
+            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
+                      tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n, state.window.data_ptr(),
+                      _stream_ptr()))
+        return out
+
     def _cache_ptrs(self, tcn_cache):
         flat = [tcn_cache[g][k] for g in range(2) for k in range(4)]
         for g in range(2):
@@ -555,6 +652,21 @@ class Engine:
             if n.value:
                 out[buf.value.decode()] = (float(ms.value), int(n.value))
         return out
+
+
+class WaveStreamState:
+    """The device state of hop-level waveform streams (Engine.new_wave_state): ``model`` (N, state_bytes/4), the state of
+    stream_step (importable / exportable as the reference's caches); ``wave`` (N, wave_state_bytes/4); and the checked
+    512-tap ``window`` every step and flush of these streams uses."""
+
+    def __init__(self, model, wave, window):
+        self.model = model
+        self.wave = wave
+        self.window = window
+
+    @property
+    def n(self):
+        return self.model.shape[0]
 
 
 def _pcm_pair(pcm, wave, who):

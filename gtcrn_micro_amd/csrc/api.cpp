@@ -46,10 +46,11 @@ struct Timing {
     hipEvent_t a = nullptr, b = nullptr;
 };
 // every timed launch records WHICH kernel it was (mixed offline / streaming calls keep their own rows)
-enum KernelId { K_STFT, K_ENCODER, K_GTCN1, K_GTCN2, K_DECODER, K_ISTFT, K_FRONT, K_ENCODER_GT, K_GTCN_MS, K_STREAM_MS, K_STREAM_WIDE, K_COUNT };
+enum KernelId { K_STFT, K_ENCODER, K_GTCN1, K_GTCN2, K_DECODER, K_ISTFT, K_FRONT, K_ENCODER_GT, K_GTCN_MS, K_STREAM_MS, K_STREAM_WIDE,
+                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_stft",  "k_encoder",    "k_gtcn1",   "k_gtcn2",    "k_decoder",
                                            "k_istft", "k_front",      "k_encoder_gt", "k_gtcn_ms", "k_stream_ms",
-                                           "k_stream_wide"};
+                                           "k_stream_wide", "k_wave_analysis", "k_wave_synthesis"};
 constexpr int kNumKernels = K_COUNT;
 
 }  // namespace
@@ -587,6 +588,76 @@ int gtcrn_stream_step(gtcrn_model* m, void* d_state, const float* d_spec_t, long
     rc = ensure_workspace(m, nstreams, nframes, s);
     if (rc) return rc;
     return run_model(m, d_spec_t, isb, isf, ist, d_spec_out_t, osb, osf, ost, nstreams, nframes, (float*)d_state, s);
+}
+
+// ---- hop-level waveform streaming: analysis -> the model step on the frame-major spectra -> synthesis, on one stream.
+// The hand-offs use the frame-major spectrogram workspace of forward_wave (d_spec_a / d_spec_b), which the streaming
+// forms of run_model never touch; ensure_workspace(N, nhops) sizes them.
+size_t gtcrn_wave_stream_state_bytes(void) { return sizeof(float) * gtk::WS_FLOATS; }
+
+int gtcrn_wave_stream_reset(gtcrn_model* m, void* d_state, void* d_wstate, int nstreams, void* stream) {
+    if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_reset: null model");
+    if (!d_state || !d_wstate || nstreams < 1) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_reset: null state or nstreams < 1");
+    int rc = check_model(m);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_state, 0, gtcrn_stream_state_bytes() * nstreams, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(d_wstate, 0, gtcrn_wave_stream_state_bytes() * nstreams, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C++" template <typename S>
+static int wave_stream_impl(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const S* d_in, long in_stride,
+                            S* d_out, long out_stride, int nstreams, int nhops, bool flush, int r, const float* d_win,
+                            void* stream) {
+    const std::string w(who);
+    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
+    if (!d_state || !d_wstate || !d_out || !d_win || (!d_in && !(flush && r == 0)))
+        return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, w + ": nstreams and nhops must be >= 1");
+    if (flush && (r < 0 || r > 255)) return fail(GTCRN_ERR_ARG, w + ": the tail holds r = 0..255 samples");
+    if (in_stride < (flush ? r : 256L * nhops) || out_stride < 256L * (flush ? 1 : nhops))
+        return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate)) & 15)
+        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    int rc = check_model(m);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = ensure_workspace(m, nstreams, nhops, s);
+    if (rc) return rc;
+    const long sb = (long)nhops * 514, sf = 2, st = 514;      // frame-major (N, nhops, 257, 2)
+    float* ws = static_cast<float*>(d_wstate);
+    Timer tm(m, s);
+    tm.begin(K_WAVE_ANALYSIS);
+    LAUNCH_TRY(gtk::launch_wave_analysis<S>(d_in, in_stride, nstreams, nhops, r, flush, ws, d_win, m->d_twid, m->d_spec_a, s));
+    tm.end();
+    rc = run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, nstreams, nhops, static_cast<float*>(d_state), s);
+    if (rc) return rc;
+    tm.begin(K_WAVE_SYNTHESIS);
+    LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, nstreams, nhops, r, flush, ws,
+                                             d_win, m->d_twid, s));
+    tm.end();
+    return 0;
+}
+
+int gtcrn_wave_stream_step(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_in, long in_stride, float* d_out,
+                           long out_stride, int nstreams, int nhops, const float* d_win, void* stream) {
+    return wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                                   nstreams, nhops, false, 0, d_win, stream);
+}
+int gtcrn_wave_stream_step_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_in, long in_stride,
+                                 short* d_out, long out_stride, int nstreams, int nhops, const float* d_win, void* stream) {
+    return wave_stream_impl<short>("gtcrn_wave_stream_step_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                                   nstreams, nhops, false, 0, d_win, stream);
+}
+int gtcrn_wave_stream_flush(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_tail, long tail_stride, int r,
+                            float* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return wave_stream_impl<float>("gtcrn_wave_stream_flush", m, d_state, d_wstate, d_tail, tail_stride, d_out, out_stride,
+                                   nstreams, 1, true, r, d_win, stream);
+}
+int gtcrn_wave_stream_flush_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_tail, long tail_stride, int r,
+                                  short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return wave_stream_impl<short>("gtcrn_wave_stream_flush_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                                   out_stride, nstreams, 1, true, r, d_win, stream);
 }
 
 static int state_convert(gtcrn_model* m, void* d_state, int nstreams, float* conv, float* tra,

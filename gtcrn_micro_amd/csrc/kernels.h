@@ -23,6 +23,16 @@ static_assert(NT2 % NW == 0, "tiles must divide evenly over the waves");
 constexpr int FRAMES_PER_WAVE = 2;   // frames each of the 4 waves of a k_stft workgroup transforms
 constexpr int ISTFT_BLOCKS = 7;      // hop blocks one k_istft workgroup emits (from 8 frames: 38 KB of LDS, 4 workgroups per CU)
 
+// per-stream state of hop-level waveform streaming (floats; gtcrn_wave_stream_*): the last 512 input samples (oldest
+// first), the windowed second half of the newest frame (the overlap-add tail), an int hop counter (saturating) + pad
+constexpr int WS_RING = 0;
+constexpr int WS_TAIL = 512;
+constexpr int WS_CNT = 768;
+constexpr int WS_FLOATS = 772;                   // 3088 B per stream, a multiple of 16
+constexpr int WS_CNT_MAX = 1 << 30;
+constexpr int WAVE_FRAMES = 2;                   // frames each of the 4 waves of a k_wave_analysis workgroup transforms
+static_assert(WS_FLOATS % 4 == 0, "16-byte aligned rows");
+
 // per-stream state (floats).  Rings are indexed by absolute frame number: the conv/TRA rings
 // hold 2 rows (row = frame & 1), TCN block k holds 2d rows (row = frame mod 2d, d = 2^k).
 constexpr int ST_POS = 0;                        // int frame counter (+3 pad)
@@ -49,6 +59,16 @@ int launch_stft(const float* wave, int B, long L, int T, const int* lens, const 
 int launch_pcm16_convert(const void* src, void* dst, long n, int dir, hipStream_t s);
 int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, const int* lens, const float* win,
                  const float* twid, float* wave, hipStream_t s);
+// hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
+// analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
+// (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
+// wstate (not on flush).  flush = the end-reflected last frame.
+template <typename S>
+int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
+                         const float* win, const float* twid, float* spec, hipStream_t s);
+template <typename S>
+int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
+                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s);
 // gspec += adjoint(iSTFT)(gwave): gwave (B, 256 (T-1)) is the gradient w.r.t. the iSTFT output ALREADY divided by
 // the window envelope; gspec (B,257,T,2 by strides) receives the gradient w.r.t. the spectrogram (accumulated).
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,

@@ -618,6 +618,201 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restric
     }
 }
 
+// ===================================================================== hop-level waveform streaming
+// The caller's torch.stft -> model loop -> torch.istft at one 256-sample hop per call (include/gtcrn_micro_hip.h,
+// gtcrn_wave_stream_step).  Frame t of torch.stft(center=True) is x[256t-256 : 256t+256]: at call k the library
+// frames hop k (with hop k-1 from the stream's input ring), the model steps it, and the synthesis emits hop block k-1
+// = second half of frame k-1 (the stored tail) + first half of frame k, / env.  Frame 0 is the start-reflected hop 0
+// whose one future sample, x[256], meets win[0] == 0 (it is read as 0).  The arithmetic is k_stft / k_front's (window
+// product, fft256<-1>, real split, Nyquist bin) and k_istft's (merge, fft256<1>, (z / 256) * win, acc / env)
+// expression for expression, so the stream equals gtcrn_forward_wave one hop late, bit for bit.
+// Samples are float or int16 (widened as / 32768, stored as clip(rint(y * 32768)): the PCM16 kernels' expressions).
+// FLUSH: the stream's last frame from the ring and r < 256 extra samples, end-reflected as reflect_idx does.
+template <typename S>
+__device__ __forceinline__ float wave_ld(const S* p) {
+    if constexpr (std::is_same<S, short>::value) return (float)*p * (1.0f / 32768.0f);
+    else return *p;
+}
+template <typename S>
+__device__ __forceinline__ void wave_st(S* p, float y) {
+    if constexpr (std::is_same<S, short>::value) *p = (short)(int)fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f);
+    else *p = y;
+}
+
+// One wave per (stream, hop) frame, WAVE_FRAMES frames per wave.  Reads the wave state, writes none of it (the
+// synthesis advances it, after the model step, on the same stream): frame-major spectra (N, nhops, 257, 2).
+template <typename S, bool FLUSH>
+__global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __restrict__ in, long in_stride, int N,
+                                                                 int nhops, int r, const float* __restrict__ wstate,
+                                                                 const float* __restrict__ win,
+                                                                 const float2* __restrict__ twid,
+                                                                 float* __restrict__ spec) {
+    __shared__ float2 s_tw[256];
+    __shared__ float2 s_tw512[256];
+    __shared__ float s_win[512];
+    __shared__ float2 s_buf[FFT_WAVES][2][256];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
+    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    __syncthreads();
+    const long nframes = (long)N * nhops;
+    const long base = (long)blockIdx.x * (FFT_WAVES * WAVE_FRAMES);
+    for (int it = 0; it < WAVE_FRAMES; ++it) {
+        const long fr = base + (long)it * FFT_WAVES + wv;
+        if (fr >= nframes) break;                                  // (wave uniform; no workgroup barrier follows)
+        const int n = (int)(fr / nhops), h = (int)(fr - (long)n * nhops);
+        const float* ws = wstate + (long)n * WS_FLOATS;
+        const int t = *reinterpret_cast<const int*>(ws + WS_CNT) + h;
+        const S* x = in + (long)n * in_stride;
+        float2* A = s_buf[wv][0];
+        float2* Bf = s_buf[wv][1];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int m = lane + 64 * q;
+            float2 c;
+            if constexpr (FLUSH) {
+                // [ring (last 512 samples) ++ tail (r samples)]: sample i of frame t sits at 256 + i, reflected at the end
+                const int rl = 512 + r;
+                int i0 = 256 + 2 * m, i1 = i0 + 1;
+                i0 = i0 >= rl ? 2 * (rl - 1) - i0 : i0;
+                i1 = i1 >= rl ? 2 * (rl - 1) - i1 : i1;
+                c.x = i0 < 512 ? ws[WS_RING + i0] : wave_ld(x + (i0 - 512));
+                c.y = i1 < 512 ? ws[WS_RING + i1] : wave_ld(x + (i1 - 512));
+            } else if (t == 0) {
+                // frame 0 = [x[256], x[255..1], x[0..255]]; x[256] is not here yet and meets win[0] == 0
+                if (q < 2) {
+                    const int i0 = 256 - 2 * m;
+                    c.x = i0 < 256 ? wave_ld(x + (i0 < 256 ? i0 : 255)) : 0.f;
+                    c.y = wave_ld(x + (i0 - 1));
+                } else {
+                    c.x = wave_ld(x + (2 * m - 256));
+                    c.y = wave_ld(x + (2 * m - 255));
+                }
+            } else if (q < 2) {
+                // the previous hop: the ring's newest 256 samples, or hop h - 1 of this call
+                if (h == 0) c = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * m);
+                else c = make_float2(wave_ld(x + 256L * (h - 1) + 2 * m), wave_ld(x + 256L * (h - 1) + 2 * m + 1));
+            } else {
+                c = make_float2(wave_ld(x + 256L * h + 2 * m - 256), wave_ld(x + 256L * h + 2 * m - 255));
+            }
+            float2 v;
+            v.x = c.x * s_win[2 * m];
+            v.y = c.y * s_win[2 * m + 1];
+            A[m] = v;
+        }
+        wave_lds_sync();
+        fft256<-1>(A, Bf, s_tw, lane);
+        float* o = spec + fr * 514;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = lane + 64 * q;
+            const float2 zk = A[k], zm = A[(256 - k) & 255];
+            const float2 ze = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+            const float2 zo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+            const float2 rr = cmul(s_tw512[k], zo);
+            *reinterpret_cast<float2*>(o + 2 * k) = make_float2(ze.x + rr.x, ze.y + rr.y);
+            if (k == 0)  // Nyquist bin: X[256] = Re Z[0] - Im Z[0]
+                *reinterpret_cast<float2*>(o + 512) = make_float2(zk.x - zk.y, 0.f);
+        }
+        wave_lds_sync();
+    }
+}
+
+// One wave per stream, its hops in order: merge, inverse FFT, window and / 256 as k_istft; the overlap-add runs in
+// registers (lane's first-half samples 2m, 2m+1, m = lane + 64 q, q < 2, meet the previous frame's 256 + 2m, 256 + 2m + 1,
+// which the same lane holds at q + 2).  Then the state advances: tail, input ring (last 512 samples), hop counter.
+// FLUSH emits the stream's last block and leaves the wave state as it is (the stream has ended).
+template <typename S, bool FLUSH>
+__global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
+                                                                  long in_stride, S* __restrict__ out, long out_stride,
+                                                                  int N, int nhops, int r, float* __restrict__ wstate,
+                                                                  const float* __restrict__ win,
+                                                                  const float2* __restrict__ twid) {
+    __shared__ float2 s_tw[256];
+    __shared__ float2 s_tw512[256];
+    __shared__ float s_win[512];
+    __shared__ float2 s_buf[FFT_WAVES][2][256];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
+    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    __syncthreads();
+    const int n = blockIdx.x * FFT_WAVES + wv;
+    if (n >= N) return;
+    float* ws = wstate + (long)n * WS_FLOATS;
+    const int c0 = *reinterpret_cast<const int*>(ws + WS_CNT);
+    // a flush of a stream that holds fewer than 257 samples has no block (gtcrn_forward_wave rejects such a clip)
+    const bool none = FLUSH && 256L * c0 + r < 257;
+    float2 prev[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) prev[q] = *reinterpret_cast<const float2*>(ws + WS_TAIL + 2 * (lane + 64 * q));
+    float env[2][2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = 2 * (lane + 64 * q) + e;
+            env[q][e] = s_win[256 + i] * s_win[256 + i] + s_win[i] * s_win[i];
+        }
+    float2* A = s_buf[wv][0];
+    float2* Bf = s_buf[wv][1];
+    S* o = out + (long)n * out_stride;
+    for (int h = 0; h < nhops; ++h) {
+        const float* x = spec + ((long)n * nhops + h) * 514;
+        // merge: Z[k] = Xe + i Xo (k_istft); the imaginary parts of DC and Nyquist are ignored
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = lane + 64 * q;
+            float2 xk = *reinterpret_cast<const float2*>(x + 2 * k);
+            float2 xm = *reinterpret_cast<const float2*>(x + 2 * (256 - k));
+            xm.y = -xm.y;
+            if (k == 0) { xk.y = 0.f; xm.y = 0.f; }
+            const float2 xe = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y + xm.y));
+            float2 w = s_tw512[k];
+            w.y = -w.y;
+            const float2 xo = cmul(make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y - xm.y)), w);
+            A[k] = make_float2(xe.x - xo.y, xe.y + xo.x);
+        }
+        wave_lds_sync();
+        fft256<1>(A, Bf, s_tw, lane);
+        float2 f[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int m = lane + 64 * q;
+            const float2 z = A[m];
+            f[q].x = (z.x * (1.0f / 256.0f)) * s_win[2 * m];
+            f[q].y = (z.y * (1.0f / 256.0f)) * s_win[2 * m + 1];
+        }
+        wave_lds_sync();     // A is rewritten by the next hop's merge
+        const bool zero = none || c0 + h == 0;     // call 0 of a stream emits zeros (the one-hop delay)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int m = lane + 64 * q;
+            const float a0 = prev[q].x + f[q].x, a1 = prev[q].y + f[q].y;
+            wave_st(o + 256L * h + 2 * m, zero ? 0.f : (env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
+            wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : (env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
+            prev[q] = f[q + 2];
+        }
+    }
+    if constexpr (FLUSH) return;
+    // the state: tail = the newest frame's windowed second half; ring = the last 512 input samples; counter (saturating)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) *reinterpret_cast<float2*>(ws + WS_TAIL + 2 * (lane + 64 * q)) = prev[q];
+    const S* xi = in + (long)n * in_stride + 256L * (nhops - 2);     // ring[j] = input sample 256 (nhops - 2) + j
+    float2 ring[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = 2 * (lane + 64 * q);
+        if (q < 2 && nhops == 1) ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);   // (this lane's own q + 2)
+        else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<float2*>(ws + WS_RING + 2 * (lane + 64 * q)) = ring[q];
+    if (lane == 0) {
+        const long c1 = (long)c0 + nhops;
+        *reinterpret_cast<int*>(ws + WS_CNT) = c1 > WS_CNT_MAX ? WS_CNT_MAX : (int)c1;
+    }
+}
+
 // ===================================================================== time spans (offline calls)
 // One workgroup per utterance fills the chip only when the batch is a multiple of the 256 CUs: B = 1 (the reference's own
 // call shape, infer.py:48) used ONE CU, B = 257 took two rounds.  Every temporal layer of the path is a FIR in time
@@ -4513,6 +4708,33 @@ int launch_stft(const float* wave, int B, long L, int T, const int* lens, const 
     GT_LAUNCH_CHECK();
     return 0;
 }
+
+template <typename S>
+int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
+                         const float* win, const float* twid, float* spec, hipStream_t s) {
+    const long nframes = (long)N * nhops;
+    const int per = FFT_WAVES * WAVE_FRAMES;
+    const int grid = (int)((nframes + per - 1) / per);
+    const float2* tw = reinterpret_cast<const float2*>(twid);
+    if (flush) hipLaunchKernelGGL((k_wave_analysis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, N, 1, r, wstate, win, tw, spec);
+    else hipLaunchKernelGGL((k_wave_analysis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, N, nhops, 0, wstate, win, tw, spec);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
+                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s) {
+    const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
+    const float2* tw = reinterpret_cast<const float2*>(twid);
+    if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw);
+    else hipLaunchKernelGGL((k_wave_synthesis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
+template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {

@@ -22,7 +22,9 @@ kernels per 16 ms frame for nothing.  So:
   reference mutates them in place) cannot be intercepted, so for that call pattern the
   export runs eagerly every frame (import is still skipped while they stay untouched).
 
-``init_state`` / ``step`` is the native form that leaves the state on the device.
+``init_state`` / ``step`` is the native form that leaves the state on the device; ``init_wave_state`` /
+``step_wave`` / ``flush_wave`` the same at the waveform: 256 samples (one hop) in, 256 enhanced out, one hop late
+(include/gtcrn_micro_hip.h, gtcrn_wave_stream_*).
 """
 import torch
 
@@ -225,3 +227,16 @@ class StreamGTCRNMicro(GTCRNMicro):
     def step(self, spec_t, state):
         """spec_t (N,257,n,2), n >= 1 new frames per stream; state from init_state (updated in place)."""
         return self.engine(spec_t.device).stream_step(state, spec_t)
+
+    def init_wave_state(self, nstreams, window, device="cuda"):
+        """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
+        of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's)."""
+        return self.engine(torch.device(device)).new_wave_state(nstreams, window)
+
+    def step_wave(self, x, state):
+        """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late."""
+        return self.engine(x.device).wave_stream_step(state, x)
+
+    def flush_wave(self, tail, state):
+        """tail (N, r), r = 0..255 samples after the last whole hop -> the last 256 enhanced samples per stream."""
+        return self.engine(tail.device).wave_stream_flush(state, tail)

@@ -153,6 +153,50 @@ int gtcrn_stream_import(gtcrn_model *m, void *d_state, int nstreams, const float
 int gtcrn_stream_export(gtcrn_model *m, const void *d_state, int nstreams, float *d_conv_cache,
                         float *d_tra_cache, float *const *d_tcn_cache8, void *stream);
 
+/* ---- hop-level waveform streaming --------------------------------------------------------------------------
+ * Replaces the caller loop around StreamGTCRNMicro.forward (gtcrn_micro_stream.py:596-646: torch.stft of the whole
+ * file, the model frame by frame, torch.istft of the whole result) for a live caller that has 256 samples (one hop,
+ * 16 ms at 16 kHz) at a time: nstreams streams, nhops >= 1 hops each per call, 256 * nhops samples in, as many out.
+ *
+ * Contract.  After a reset, with finite input and a window with win[0] == 0 (every periodic Hann-type window, e.g.
+ * torch.hann_window(512).pow(0.5) of infer.py:65 -- pass the same 512 floats the offline call gets), the output
+ * stream is gtcrn_forward_wave(x, win) delayed by exactly one hop, bit for bit:
+ *     out[n] = 0                                      0 <= n < 256
+ *     out[n] = gtcrn_forward_wave(x, win)[n - 256]    n >= 256
+ * Call k frames hop k (frame k of torch.stft(center=True) is x[256k-256 : 256k+256]), steps the model on it and emits
+ * block k-1: the second half of frame k-1 plus the first half of frame k over the window envelope.  Call 0 emits
+ * zeros; its frame 0 is the start-reflected hop 0, whose one future sample x[256] meets win[0] == 0.  A clip of
+ * L = 256 K + r >= 257 samples (r = 0..255) ends with ONE flush that takes the r extra samples, builds the last frame
+ * end-reflected (torch.stft's reflect padding) and emits 256 samples: the K steps and the flush give 256 (K + 1)
+ * samples, the last 256 K of which equal gtcrn_forward_wave.  A flush of a stream that received fewer than 257
+ * samples emits zeros.  The flush ends the stream: reset both states before it is used again.
+ *
+ * State.  d_state is the model state of gtcrn_stream_step (gtcrn_stream_state_bytes per stream, same layout: the
+ * reference's caches can be imported / exported around wave steps); d_wstate is the wave state,
+ * gtcrn_wave_stream_state_bytes per stream: the last 512 input samples (the end reflection reaches back 257), the
+ * overlap-add tail (256) and a hop counter.  Both 16-byte aligned; reset a sub-range of streams by offsetting the
+ * pointers.  The counter is per stream: the streams of one call may sit at different hop counts.
+ *
+ * Calls.  A step or flush is three launches on `stream` (analysis, the model step of gtcrn_stream_step in its form
+ * for nframes = nhops, synthesis), asynchronous, and does no allocation once gtcrn_model_reserve(nstreams, nhops) was
+ * called: capturable into a HIP graph.  d_in / d_out: row n of stream n at d_in + n * in_stride (256 * nhops samples)
+ * and d_out + n * out_stride (256 * nhops samples; the flush: d_tail + n * tail_stride, r samples -> 256 samples;
+ * d_tail may be NULL when r == 0).  The _pcm16 forms take and return int16 samples: widened as s / 32768 and
+ * stored as clip(rint(y * 32768)), i.e. equal to the float forms between gtcrn_pcm16_to_f32 and gtcrn_f32_to_pcm16.
+ * The library cannot read device memory without a synchronisation: win[0] == 0 is the caller's precondition.
+ * Null pointers, nstreams < 1, nhops < 1, r outside 0..255 and strides shorter than a row return GTCRN_ERR_ARG before
+ * anything is launched. */
+size_t gtcrn_wave_stream_state_bytes(void); /* per stream: input ring 512 + OLA tail 256 + hop counter, 16-B aligned */
+int gtcrn_wave_stream_reset(gtcrn_model *m, void *d_state, void *d_wstate, int nstreams, void *stream);
+int gtcrn_wave_stream_step(gtcrn_model *m, void *d_state, void *d_wstate, const float *d_in, long in_stride,
+                           float *d_out, long out_stride, int nstreams, int nhops, const float *d_win, void *stream);
+int gtcrn_wave_stream_step_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const short *d_in, long in_stride,
+                                 short *d_out, long out_stride, int nstreams, int nhops, const float *d_win, void *stream);
+int gtcrn_wave_stream_flush(gtcrn_model *m, void *d_state, void *d_wstate, const float *d_tail, long tail_stride, int r,
+                            float *d_out, long out_stride, int nstreams, const float *d_win, void *stream);
+int gtcrn_wave_stream_flush_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const short *d_tail, long tail_stride,
+                                  int r, short *d_out, long out_stride, int nstreams, const float *d_win, void *stream);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),

@@ -1,0 +1,140 @@
+"""Hop-level waveform streaming (gtcrn_wave_stream_step) against the spectral step (gtcrn_stream_step) it wraps.
+
+Same process, same GPU: for each stream count N, one hop (wave: 256 samples in / out; spectral: one 257-bin frame in /
+out) per stream and step, timed with device events over `--iters` steps, warm-up first, the two sides alternating for
+`--reps` repetitions; medians.  Also the per-call latency at N = 1, eager and under graph replay, and the compulsory
+bytes the two wave kernels add per stream-step (from shapes).  Writes profiles/wave_stream_bench.json.
+
+--trace-only N: just run wave steps at N streams (for `rocprofv3 --kernel-trace --stats -- python <this> --trace-only N`).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def traffic_per_stream_step(sample_bytes=4):
+    """Compulsory DRAM bytes the analysis + synthesis kernels add to one single-hop step of one stream."""
+    spec = 257 * 2 * 4
+    analysis = {"input hop": 256 * sample_bytes, "ring (previous hop)": 256 * 4, "hop counter": 4, "spectrum out": spec}
+    synthesis = {"spectrum in": spec, "tail in": 256 * 4, "ring (newest half) in": 256 * 4, "input hop": 256 * sample_bytes,
+                 "hop counter": 8, "output hop": 256 * sample_bytes, "tail out": 256 * 4, "ring out": 512 * 4}
+    return {"analysis": analysis, "synthesis": synthesis,
+            "total_bytes": sum(analysis.values()) + sum(synthesis.values())}
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def compare(eng, win, N, iters, reps):
+    from gtcrn_micro_amd._lib import empty_spec
+    eng.reserve(N, 1)
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    spec = empty_spec(N, 1, "cuda", frame_major=True)
+    spec.copy_(torch.randn(spec.shape, device="cuda", generator=gen) * 0.3)
+    sout = empty_spec(N, 1, "cuda", frame_major=True)
+    sst = eng.new_state(N)
+    wst = eng.new_wave_state(N, win)
+    spectral = lambda: eng.stream_step(sst, spec, out=sout)       # noqa: E731
+    wave = lambda: eng.wave_stream_step(wst, x, out=y)            # noqa: E731
+    for f in (spectral, wave):
+        timed(f, max(3, iters // 4))                              # warm-up
+    ts, tw = [], []
+    for _ in range(reps):
+        ts.append(timed(spectral, iters))
+        tw.append(timed(wave, iters))
+    ms_s, ms_w = statistics.median(ts), statistics.median(tw)
+    del sst, wst
+    torch.cuda.empty_cache()
+    return {"N": N, "spectral_step_ms": ms_s, "wave_step_ms": ms_w, "ratio": ms_w / ms_s,
+            "spectral_reps_ms": ts, "wave_reps_ms": tw, "iters": iters}
+
+
+def latency_n1(eng, win, iters):
+    eng.reserve(1, 1)
+    x = torch.randn(1, 256, device="cuda") * 0.1
+    y = torch.empty_like(x)
+    st = eng.new_wave_state(1, win)
+    step = lambda: eng.wave_stream_step(st, x, out=y)             # noqa: E731
+    timed(step, 50)
+    eager = [timed(step, iters) for _ in range(5)]
+    # host-side: the wall time of one call that ends in a synchronise
+    walls = []
+    for _ in range(200):
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    warm = eng.new_wave_state(1, win)
+    with torch.cuda.stream(s):
+        eng.wave_stream_step(warm, x, out=y)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, stream=s):
+            eng.wave_stream_step(st, x, out=y)
+    torch.cuda.synchronize()
+    timed(g.replay, 50)
+    graph = [timed(g.replay, iters) for _ in range(5)]
+    return {"eager_device_ms_per_call": statistics.median(eager), "eager_wall_ms_per_call_synced": statistics.median(walls),
+            "graph_replay_ms_per_call": statistics.median(graph), "iters": iters}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1,1024,16384,65536")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wave_stream_bench.json"))
+    ap.add_argument("--trace-only", type=int, default=0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("wave_stream_bench needs the GPU (nothing is measured on the CPU)")
+    from gtcrn_micro_amd import Engine
+    params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
+    eng = Engine(params, 0)
+    win = torch.hann_window(512).pow(0.5).cuda()
+    if a.trace_only:
+        N = a.trace_only
+        eng.reserve(N, 1)
+        st = eng.new_wave_state(N, win)
+        x = torch.randn(N, 256, device="cuda") * 0.1
+        y = torch.empty_like(x)
+        for _ in range(a.iters):
+            eng.wave_stream_step(st, x, out=y)
+        torch.cuda.synchronize()
+        return
+    res = {"device": torch.cuda.get_device_name(0), "traffic": traffic_per_stream_step(4),
+           "traffic_pcm16": traffic_per_stream_step(2)["total_bytes"], "compare": [], "latency_n1": None}
+    for N in [int(s) for s in a.sizes.split(",")]:
+        r = compare(eng, win, N, a.iters, a.reps)
+        print(json.dumps({k: v for k, v in r.items() if not k.endswith("reps_ms")}), flush=True)
+        res["compare"].append(r)
+    res["latency_n1"] = latency_n1(eng, win, 500)
+    print(json.dumps(res["latency_n1"]), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
