@@ -853,7 +853,9 @@ class Trainer:
         return loss, grad
 
     def tap(self, name):
-        """Train-mode activation of the most recent forward at a stage boundary, as (B,C,T,F)."""
+        """A tensor the most recent forward stored, as (B,C,T,F) float32: a stage boundary (en0..en4, tcn0..tcn7,
+        gtcn1, gtcn2, de0..de4), a decoder sum (sum0..sum4, where stored) or a unit's stored conv output
+        "<BatchNorm prefix>.y" (bf16 modes: the centred bf16 copy, no shift added back).  See gtcrn_train_tap."""
         import torch
         sh = (ctypes.c_long * 4)()
         _check(lib().gtcrn_train_tap(self._h, name.encode(), None, sh, None))

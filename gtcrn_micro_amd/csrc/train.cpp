@@ -86,6 +86,7 @@ struct Unit {                 // conv (dense or depthwise) + BatchNorm + activat
     // fusion bit 11: `a` holds activation + post (the next decoder layer's input x + skip, written by this unit's bn_act);
     // the plain activation is not stored
     const float* post = nullptr;
+    std::string bn_name;      // the BatchNorm's parameter prefix: this unit's y tap is bn_name + ".y"
 };
 
 struct GtBlock {              // GTConvBlock (models/gtcrn_micro.py:167-253)
@@ -226,6 +227,7 @@ void unit_params(gtcrn_trainer* t, Unit& u, const std::string& conv, const std::
     u.o_b = P(t, conv + ".bias");
     u.o_bn = P(t, bn + ".weight");
     u.o_slope = act.empty() ? -1 : P(t, act + ".weight");
+    u.bn_name = bn;
 }
 
 void alloc_unit(Bump& b, Unit& u, long n, int C, bool lean = false) {
@@ -416,6 +418,7 @@ size_t plan(gtcrn_trainer* t, int B, int T, float* base) {
         if (i > 0) t->tcn[i - 1].c3.deferred = fuse;
         k.c3.deferred = false;
         X = k.c3.a;
+        t->taps["tcn" + std::to_string(i)] = {X, {T, 33, 16}};
         if ((i & 3) == 3) t->taps["gtcn" + std::to_string(i / 4 + 1)] = {X, {T, 33, 16}};
     }
     // bf16 storage (the memory-lean variant): the decoder's sums x + skip (three block inputs, s3, s4) are not saved --
@@ -433,8 +436,8 @@ size_t plan(gtcrn_trainer* t, int B, int T, float* base) {
     if (t->fuse_sums) {
         t->tcn[7].c3.post = t->enc[2].out;              // dec[0].s = gtcn2 output + en_outs[4]
         t->tcn[7].c3.a = t->dec[0].s;
-        t->taps["gtcn2"] = {t->dec[0].s, {T, 33, 16}};
-        t->tap_minus["gtcn2"] = t->enc[2].out;
+        t->taps["gtcn2"] = t->taps["tcn7"] = {t->dec[0].s, {T, 33, 16}};
+        t->tap_minus["gtcn2"] = t->tap_minus["tcn7"] = t->enc[2].out;
     }
     for (int i = 0; i < 3; ++i) {
         GtBlock& k = t->dec[i];
@@ -466,6 +469,27 @@ size_t plan(gtcrn_trainer* t, int B, int T, float* base) {
     alloc_unit(b, t->de4, n129, 2);
     t->taps["de3"] = {t->de3.a, {T, 65, 16}};
     t->taps["de4"] = {t->de4.a, {T, 129, 2}};
+    // the stored decoder sums x + en_outs[4 - i], sum<i> the input of de_convs.<i>: what the next kernel read (a shared
+    // buffer holds only the last one after the forward; the exact chain sums in fp32 and stores no sum in the forward)
+    if (!t->exact) {
+        if (!t->share_sums) {
+            for (int i = 0; i < 3; ++i) t->taps["sum" + std::to_string(i)] = {t->dec[i].s, {T, 33, 16}};
+            t->taps["sum3"] = {t->s3, {T, 33, 16}};
+        }
+        t->taps["sum4"] = {t->s4, {T, 65, 16}};
+    }
+    {   // every unit's stored conv output y (bf16 storage: the centred copy, no shift added back), as "<bn prefix>.y"
+        Unit* all[4 + 6 * 3 + 8 * 3] = {&t->en0, &t->en1, &t->de3, &t->de4};
+        int n = 4;
+        for (int k = 0; k < 3; ++k)
+            for (GtBlock* g : {&t->enc[k], &t->dec[k]}) { all[n++] = &g->pc1; all[n++] = &g->depth; all[n++] = &g->pc2; }
+        for (int i = 0; i < 8; ++i) { all[n++] = &t->tcn[i].c1; all[n++] = &t->tcn[i].c2; all[n++] = &t->tcn[i].c3; }
+        for (int i = 0; i < n; ++i) {
+            const Unit& u = *all[i];
+            const int F = u.dw ? u.dg.F : u.cg.Fout, Ty = u.dw ? u.dg.Tout : u.cg.Tout;
+            t->taps[u.bn_name + ".y"] = {u.y, {Ty, F, u.C}};
+        }
+    }
     // ---- backward buffers
     const size_t bwd_begin = b.used;
     // (take_grad: the tensors handed from one unit's backward to the next are bf16 in storage mode 5; dy -- a unit's own

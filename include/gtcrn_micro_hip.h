@@ -379,9 +379,15 @@ long gtcrn_clip_adam_workspace_bytes(long n);
 int gtcrn_clip_adam_step(int device, float *d_params, float *d_grads, float *d_exp_avg, float *d_exp_avg_sq,
                          const float *d_mask, long n, float max_norm, double lr, double beta1, double beta2, double eps,
                          double weight_decay, long step, float *d_norm_out, void *d_workspace, void *stream);
-/* Test hook: train-mode activation of the most recent forward at a stage boundary (en0..en4, gtcn1,
- * gtcn2, de0..de4), channels-last (B, T, F, C) in the reference's channel order; shape4 receives
- * the four extents; d_out may be NULL to query the shape. */
+/* Test hook: a tensor the most recent forward stored, valid until the next backward: the stage boundaries
+ * en0..en4, tcn0..tcn7 (the output of each TCN block; tcn3 / tcn7 are gtcn1 / gtcn2), de0..de4; the
+ * decoder sums sum0..sum4 (the input x + skip of de_convs.0..4, as stored: in the 16-bit modes without
+ * fusion bit 11 one shared buffer holds them, so only sum4 is there; none in storage mode 4); and every
+ * unit's stored conv output y as "<its BatchNorm's parameter prefix>.y" (e.g. gtcn1.blocks.2.bn2.y,
+ * encoder.en_convs.3.point_bn1.y) -- in the bf16 modes the centred copy bf16(y - shift) exactly, with no
+ * shift added back.  Channels-last (B, T, F, C) in the reference's channel order; shape4 receives the four
+ * extents; d_out may be NULL to query the shape.  With fusion bit 11 a block output stored only inside a
+ * sum (gtcn2 / tcn7, de0..de3) is returned as sum - skip. */
 int gtcrn_train_tap(gtcrn_trainer *t, const char *name, float *d_out, long *shape4, void *stream);
 
 #ifdef __cplusplus

@@ -45,8 +45,21 @@ class _RoundSTE(torch.autograd.Function):
         return g
 
 
+class _GradRoundBF16(torch.autograd.Function):
+    """Identity forward; the gradient is rounded to bf16 on its way back: a gradient tensor the trainer hands from one
+    unit to the next in bf16 (storage "bf16_grads", csrc/train.cpp gtcrn_train_backward / unit_bwd `gbf`)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
 class TorchPort:
-    def __init__(self, blob, train=False, dtype=torch.float32, store=None):
+    def __init__(self, blob, train=False, dtype=torch.float32, store=None, pin=None, grad_round=False):
         """train=True: BatchNorm uses batch statistics and updates the running ones in place
         (nn.BatchNorm2d in .train() mode, momentum 0.1), and trainable tensors require grad.
         dtype=torch.float64 runs the same graph in double: the "truth" that fp32 results scatter around.
@@ -54,7 +67,18 @@ class TorchPort:
         trainer writes out (features, conv outputs centred on the running mean, activations, block outputs, decoder
         sums, the mask) is rounded to bf16 where it is produced and its consumers read the rounded value; arithmetic in
         `dtype`.  With dtype=float64 this is the truth for THAT network: bf16-activation training computes the
-        gradient of a slightly different function than the fp32 network (tests/reports/bf16_storage_ablation.py)."""
+        gradient of a slightly different function than the fp32 network (tests/reports/bf16_storage_ablation.py).
+        pin: {name: tensor (B,C,T,F)} -- at every point the trainer stores (the names of gtcrn_train_tap: the centred
+        conv output "<bn prefix>.y" of every unit inside _bn, the block outputs en0..en4 / tcn0..tcn7 / gtcn1, gtcn2 /
+        de0..de4, the decoder sums sum0..sum4) the value is replaced by the pinned one through a straight-through snap,
+        v + (pin - v).detach(): every unit then sees exactly the inputs the trainer's unit saw (no compounding of rounding
+        flips along the chain) and the gradient still flows through this graph.  `skips` keep the pinned values.
+        grad_round=True (with store="bf16"): the gradient is rounded to bf16 at every hand-off the trainer stores in bf16
+        in storage "bf16_grads" (activations, block outputs, decoder sums, the TCN residual; not the mask's or the SFE
+        output's gradient, which stay fp32)."""
+        self.pin = pin
+        self.grad_round = bool(grad_round)
+        self._taps = None
         self.p = {k: v.to(dtype) for k, v in blob_to_dict(blob).items()}
         self.dtype = dtype
         self.store = store
@@ -65,8 +89,22 @@ class TorchPort:
                     v.requires_grad_(True)
 
     # conv + BatchNorm + activation (ConvBlock.forward, models/gtcrn_micro.py:163-164)
-    def _r(self, x):
-        return _RoundSTE.apply(x) if self.store == "bf16" else x
+    def _r(self, x, grad=True):
+        if self.store != "bf16":
+            return x
+        x = _RoundSTE.apply(x)
+        return self._gr(x) if grad else x
+
+    def _gr(self, x):
+        return _GradRoundBF16.apply(x) if self.grad_round else x
+
+    def _pt(self, name, v):
+        """A stored tensor: recorded (its value BEFORE any pin) when taps are asked for, then snapped to the pin."""
+        if self._taps is not None:
+            self._taps[name] = v.detach().clone()
+        if self.pin is not None and name in self.pin:
+            v = v + (torch.as_tensor(self.pin[name]).to(v.dtype) - v).detach()
+        return v
 
     def _bn(self, x, pre):
         p = self.p
@@ -74,7 +112,9 @@ class TorchPort:
             # the conv output is stored centred on the channel's mean of the previous step (the running mean before the
             # first one, csrc/train.cpp unit_fwd); the batch statistics are taken from the stored values
             rm = p[pre + ".running_mean"].detach().clone().view(1, -1, 1, 1)
-            x = _RoundSTE.apply(x - rm) + rm
+            x = self._pt(pre + ".y", _RoundSTE.apply(x - rm)) + rm
+        else:
+            x = self._pt(pre + ".y", x)
         return F.batch_norm(x, p[pre + ".running_mean"], p[pre + ".running_var"], p[pre + ".weight"],
                             p[pre + ".bias"], self.train, 0.1, 1e-5)
 
@@ -112,7 +152,7 @@ class TorchPort:
                      dilation=(d, 1), groups=16)
         y = self._r(F.prelu(self._bn(y, pre + ".bn2"), p[pre + ".act2.weight"]))
         y = self._bn(F.conv2d(y, p[pre + ".conv3.weight"], p[pre + ".conv3.bias"]), pre + ".bn3")
-        return self._r(F.prelu(y + x, p[pre + ".act3.weight"]))
+        return self._r(F.prelu(y + self._gr(x), p[pre + ".act3.weight"]))      # (the residual's gradient: a hand-off)
 
     def forward(self, spec, taps=None):
         """GTCRNMicro.forward (models/gtcrn_micro.py:506-532): (B,257,T,2) -> (B,257,T,2)."""
@@ -122,42 +162,43 @@ class TorchPort:
             return self._forward(spec, taps)
 
     def _forward(self, spec, taps=None):
-        p = self.p
+        self._taps = taps
+        try:
+            return self._forward_body(spec)
+        finally:
+            self._taps = None
 
-        def tap(name, v):
-            if taps is not None:
-                taps[name] = v.detach().clone()
+    def _forward_body(self, spec):
+        p = self.p
+        tap = self._pt
         spec = torch.as_tensor(spec).to(self.dtype)
         re, im = spec[..., 0].permute(0, 2, 1), spec[..., 1].permute(0, 2, 1)
         feat = torch.stack([torch.sqrt(re * re + im * im + 1e-12), re, im], dim=1)
-        feat = self._r(torch.cat([feat[..., :65], F.linear(feat[..., 65:], p["erb.erb_fc.weight"])], dim=-1))
-        x = self._r(F.conv2d(feat, p["sfe.depth_conv.weight"], padding=(0, 1), groups=3))
+        feat = self._r(torch.cat([feat[..., :65], F.linear(feat[..., 65:], p["erb.erb_fc.weight"])], dim=-1), False)
+        x = self._r(F.conv2d(feat, p["sfe.depth_conv.weight"], padding=(0, 1), groups=3), False)   # (df0: fp32)
         skips = []
         for i in range(2):
             pre = f"encoder.en_convs.{i}"
             x = F.conv2d(x, p[pre + ".conv.weight"], p[pre + ".conv.bias"], stride=(1, 2), padding=(0, 2))
-            x = self._r(F.prelu(self._bn(x, pre + ".bn"), p[pre + ".act.weight"]))
+            x = tap(f"en{i}", self._r(F.prelu(self._bn(x, pre + ".bn"), p[pre + ".act.weight"])))
             skips.append(x)
-            tap(f"en{i}", x)
         for i in range(2, 5):
-            x = self._gtconv(x, f"encoder.en_convs.{i}", False)
+            x = tap(f"en{i}", self._gtconv(x, f"encoder.en_convs.{i}", False))
             skips.append(x)
-            tap(f"en{i}", x)
         for g in (1, 2):
             for k in range(4):
-                x = self._tcn(x, f"gtcn{g}.blocks.{k}", 1 << k)
-            tap(f"gtcn{g}", x)
+                x = tap(f"tcn{4 * g - 4 + k}", self._tcn(x, f"gtcn{g}.blocks.{k}", 1 << k))
+            x = tap(f"gtcn{g}", x)
         for i in range(3):
-            x = self._gtconv(self._r(x + skips[4 - i]), f"decoder.de_convs.{i}", True)
-            tap(f"de{i}", x)
+            x = tap(f"de{i}", self._gtconv(tap(f"sum{i}", self._r(x + skips[4 - i])), f"decoder.de_convs.{i}", True))
         pre = "decoder.de_convs.3"
-        x = F.conv_transpose2d(self._r(x + skips[1]), p[pre + ".conv.weight"], p[pre + ".conv.bias"], stride=(1, 2), padding=(0, 2))
-        x = self._r(F.prelu(self._bn(x, pre + ".bn"), p[pre + ".act.weight"]))
-        tap("de3", x)
+        x = F.conv_transpose2d(tap("sum3", self._r(x + skips[1])), p[pre + ".conv.weight"], p[pre + ".conv.bias"],
+                               stride=(1, 2), padding=(0, 2))
+        x = tap("de3", self._r(F.prelu(self._bn(x, pre + ".bn"), p[pre + ".act.weight"])))
         pre = "decoder.de_convs.4"
-        x = F.conv_transpose2d(self._r(x + skips[0]), p[pre + ".conv.weight"], p[pre + ".conv.bias"], stride=(1, 2), padding=(0, 2))
-        m = self._r(torch.tanh(self._bn(x, pre + ".bn")))
-        tap("de4", m)
+        x = F.conv_transpose2d(tap("sum4", self._r(x + skips[0])), p[pre + ".conv.weight"], p[pre + ".conv.bias"],
+                               stride=(1, 2), padding=(0, 2))
+        m = tap("de4", self._r(torch.tanh(self._bn(x, pre + ".bn")), False))      # (dm: fp32)
         m = torch.cat([m[..., :65], F.linear(m[..., 65:], p["erb.ierb_fc.weight"])], dim=-1)   # (B,2,T,257)
         out_re = re * m[:, 0] - im * m[:, 1]
         out_im = im * m[:, 0] + re * m[:, 1]
@@ -204,12 +245,13 @@ class TorchPort:
         loss.backward()
         return enh.detach().numpy(), float(loss), enh.grad.numpy(), self.grads_blob()
 
-    def backward_from(self, spec, grad_enh):
-        """Gradients for a given upstream gradient (the model's backward alone, without the loss)."""
+    def backward_from(self, spec, grad_enh, taps=None):
+        """Gradients for a given upstream gradient (the model's backward alone, without the loss).  taps: a dict that
+        receives every stored tensor of the forward by its gtcrn_train_tap name (values before any pin)."""
         assert self.train
         for v in self.p.values():
             v.grad = None
-        enh = self.forward(torch.as_tensor(spec).to(self.dtype))
+        enh = self.forward(torch.as_tensor(spec).to(self.dtype), taps)
         enh.backward(torch.as_tensor(grad_enh).to(self.dtype))
         return enh.detach().numpy(), self.grads_blob()
 
