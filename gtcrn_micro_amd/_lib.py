@@ -81,6 +81,25 @@ def lib():
         getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
     for fn in ("gtcrn_wave_stream_flush", "gtcrn_wave_stream_flush_pcm16"):
         getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, ci, _vp, cl, ci, _vp, _vp]
+    L.gtcrn_resampler_create.argtypes = [ctypes.POINTER(_vp), ci, ci, ci]
+    L.gtcrn_resampler_destroy.argtypes = [_vp]
+    L.gtcrn_resampler_destroy.restype = None
+    L.gtcrn_resample_taps.restype = cl
+    L.gtcrn_resample_taps.argtypes = [ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), _c_f32p, cl]
+    L.gtcrn_resample_out_len.restype = cl
+    L.gtcrn_resample_out_len.argtypes = [ci, ci, cl]
+    for fn in ("gtcrn_resample", "gtcrn_resample_pcm16_in", "gtcrn_resample_pcm16_out"):
+        getattr(L, fn).argtypes = [_vp, _vp, cl, _vp, cl, _vp, cl, ci, _vp]
+    L.gtcrn_rate_stream_hop.argtypes = [ci]
+    L.gtcrn_rate_stream_latency.argtypes = [ci]
+    L.gtcrn_rate_stream_state_bytes.restype = ctypes.c_size_t
+    L.gtcrn_rate_stream_state_bytes.argtypes = [ci]
+    L.gtcrn_rate_stream_reserve.argtypes = [_vp, _vp, _vp, ci, ci]
+    L.gtcrn_rate_stream_reset.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ci, _vp]
+    for fn in ("gtcrn_rate_stream_step", "gtcrn_rate_stream_step_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
+    L.gtcrn_rate_stream_debug_handoff.restype = cl
+    L.gtcrn_rate_stream_debug_handoff.argtypes = [_vp, ci, _vp, cl, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -566,6 +585,82 @@ class Engine:
                       _stream_ptr()))
         return out
 
+    # ---- other sample rates (contract: include/gtcrn_micro_hip.h, gtcrn_resample / gtcrn_rate_stream_*) -------------
+    def resampler(self, fs_in, fs_out):
+        """The Resampler fs_in -> fs_out on this model's device, made once per pair."""
+        cache = self.__dict__.setdefault("_resamplers", {})
+        key = (int(fs_in), int(fs_out))
+        if key not in cache:
+            cache[key] = Resampler(key[0], key[1], self.device)
+        return cache[key]
+
+    def forward_wave_rate(self, wave, fs, window, out_fs=None):
+        """wave (B,L) or (L,) at `fs` Hz -> the enhanced waveform at 16 kHz (out_fs None or 16000) or at `out_fs`: exactly
+        resampler(fs, 16000)(wave) -> forward_wave -> resampler(16000, out_fs), the three public calls composed."""
+        fs = int(fs)
+        x = wave if fs == 16000 else self.resampler(fs, 16000)(wave)
+        y = self.forward_wave(x, window)
+        if out_fs is None or int(out_fs) == 16000:
+            return y
+        return self.resampler(16000, int(out_fs))(y)
+
+    def new_rate_state(self, nstreams, window, fs):
+        """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
+        resamplers and their per-stream histories."""
+        import torch
+        fs = int(fs)
+        hop = _check(lib().gtcrn_rate_stream_hop(fs))
+        ws = self.new_wave_state(nstreams, window)
+        st = RateStreamState(ws.model, ws.wave, ws.window, fs, hop, self.resampler(fs, 16000), self.resampler(16000, fs),
+                             torch.empty((ws.n, rate_stream_state_bytes(fs) // 4), device=ws.wave.device, dtype=torch.float32))
+        self.rate_stream_reset(st)
+        return st
+
+    def rate_stream_reserve(self, state, nhops):
+        """Sizes every buffer a rate step of `nhops` hops needs: after it a step allocates nothing (capturable)."""
+        _check(lib().gtcrn_rate_stream_reserve(self._h, state.rs_in._h, state.rs_out._h, state.n, int(nhops)))
+
+    def rate_stream_reset(self, state, lo=0, hi=None):
+        """Resets streams lo..hi-1 (all three states) to the start of a new clip."""
+        hi = state.n if hi is None else int(hi)
+        lo = int(lo)
+        if not isinstance(state, RateStreamState):
+            raise GtcrnError("state must come from new_rate_state")
+        if not 0 <= lo < hi <= state.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        with self._dev():
+            _check(lib().gtcrn_rate_stream_reset(self._h, state.rs_in._h, state.rs_out._h, state.model[lo:hi].data_ptr(),
+                                                 state.wave[lo:hi].data_ptr(), state.rate[lo:hi].data_ptr(), hi - lo,
+                                                 _stream_ptr()))
+
+    def rate_stream_step(self, state, x, out=None):
+        """x (N, H*nhops) float32 or int16 at the state's rate (H = state.hop) -> the enhanced (N, H*nhops) at that rate,
+        same dtype, state.latency samples late.  Asynchronous on the current stream; no allocation when `out` is given
+        and rate_stream_reserve(state, nhops) was called."""
+        import torch
+        if not isinstance(state, RateStreamState):
+            raise GtcrnError("state must come from new_rate_state")
+        x = self._wave_rows(state, x, "x")
+        L = x.shape[1]
+        if L < state.hop or L % state.hop:
+            raise GtcrnError(f"x must hold a whole number of {state.hop}-sample hops per stream, got {L}")
+        out = self._wave_out(out, x, L)
+        fn = lib().gtcrn_rate_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_rate_stream_step
+        with self._dev():
+            _check(fn(self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
+                      state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n,
+                      L // state.hop, state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def rate_stream_handoff(self, state, nhops, which=0):
+        """Test hook: a copy of the 16 kHz hand-off of the most recent rate step of `nhops` hops, (N, 256*nhops): which = 0
+        what k_rate_in produced, 1 what the wave step produced."""
+        import torch
+        out = torch.empty((state.n, 256 * int(nhops)), device=state.wave.device, dtype=torch.float32)
+        with self._dev():
+            _check(lib().gtcrn_rate_stream_debug_handoff(self._h, int(which), out.data_ptr(), out.numel(), _stream_ptr()))
+        return out
+
     def _cache_ptrs(self, tcn_cache):
         flat = [tcn_cache[g][k] for g in range(2) for k in range(4)]
         for g in range(2):
@@ -667,6 +762,126 @@ class WaveStreamState:
     @property
     def n(self):
         return self.model.shape[0]
+
+
+class RateStreamState(WaveStreamState):
+    """WaveStreamState of live streams at ``fs`` Hz (Engine.new_rate_state): plus ``rate`` (N, rate_stream_state_bytes/4),
+    the two resamplers, the hop ``hop`` = 256 fs / 16000 and the end-to-end ``latency``, both in samples at fs."""
+
+    def __init__(self, model, wave, window, fs, hop, rs_in, rs_out, rate):
+        super().__init__(model, wave, window)
+        self.fs = fs
+        self.hop = hop
+        self.latency = rate_stream_latency(fs)
+        self.rs_in = rs_in
+        self.rs_out = rs_out
+        self.rate = rate
+
+
+SUPPORTED_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)
+LIVE_RATES = (8000, 16000, 24000, 32000, 48000)
+
+
+def resample_taps(fs_in, fs_out):
+    """(up, down, h): the lowest-terms ratio fs_out / fs_in and the 2 half + 1 float32 coefficients the kernels use
+    (host only; the filter's definition is in include/gtcrn_micro_hip.h)."""
+    up, down = ctypes.c_int(), ctypes.c_int()
+    n = _check(lib().gtcrn_resample_taps(int(fs_in), int(fs_out), ctypes.byref(up), ctypes.byref(down), None, 0))
+    h = np.empty(n, np.float32)
+    _check(lib().gtcrn_resample_taps(int(fs_in), int(fs_out), ctypes.byref(up), ctypes.byref(down),
+                                     h.ctypes.data_as(_c_f32p), n))
+    return up.value, down.value, h
+
+
+def resample_out_len(fs_in, fs_out, L):
+    return _check(lib().gtcrn_resample_out_len(int(fs_in), int(fs_out), int(L)))
+
+
+def rate_stream_hop(fs):
+    return _check(lib().gtcrn_rate_stream_hop(int(fs)))
+
+
+def rate_stream_latency(fs):
+    return _check(lib().gtcrn_rate_stream_latency(int(fs)))
+
+
+def rate_stream_state_bytes(fs):
+    n = int(lib().gtcrn_rate_stream_state_bytes(int(fs)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+class Resampler:
+    """One polyphase resampler fs_in -> fs_out on one device (gtcrn_resampler): 16 kHz to or from 8, 11.025, 22.05, 24,
+    32, 44.1 or 48 kHz.  Calling it resamples a (B,L) / (L,) float32 or int16 CUDA tensor."""
+
+    def __init__(self, fs_in, fs_out, device=0):
+        self.fs_in, self.fs_out, self.device = int(fs_in), int(fs_out), int(device)
+        h = ctypes.c_void_p()
+        _check(lib().gtcrn_resampler_create(ctypes.byref(h), self.fs_in, self.fs_out, self.device))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gtcrn_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_len(self, L):
+        return resample_out_len(self.fs_in, self.fs_out, L)
+
+    def __call__(self, x, lengths=None, out=None, out_dtype=None):
+        """x (B,L) or (L,): float32, or int16 PCM (then the output is float32).  lengths (optional, B ints, host or
+        device): row b holds lengths[b] <= L samples and receives out_len(lengths[b]); the rest of its output row is left
+        as it is.  out: a (B, >= out_len(L)) tensor with contiguous rows, float32 or (float32 input only) int16;
+        out_dtype=torch.int16 asks for a new int16 output.  Asynchronous on the current stream."""
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
+            raise GtcrnError("x must be a float32 or int16 CUDA (ROCm) tensor")
+        if x.device.index != self.device:
+            raise GtcrnError(f"x is on cuda:{x.device.index}, the resampler on cuda:{self.device}")
+        one = x.dim() == 1
+        x2 = x.reshape(1, -1) if one else x
+        if x2.dim() != 2 or x2.shape[1] < 1 or x2.shape[0] < 1:
+            raise GtcrnError(f"x must be (B,L) or (L,) with L >= 1, got {tuple(x.shape)}")
+        if x2.stride(1) != 1 and x2.shape[1] > 1:
+            x2 = x2.contiguous()
+        B, L = x2.shape
+        n = self.out_len(L)
+        if out is None:
+            out2 = torch.empty((B, n), device=x.device, dtype=out_dtype or torch.float32)
+        else:
+            out2 = out.reshape(1, -1) if (one and out.dim() == 1) else out
+            if (not isinstance(out2, torch.Tensor) or out2.device != x.device or out2.dim() != 2 or out2.shape[0] != B
+                    or out2.shape[1] < n or (out2.stride(1) != 1 and out2.shape[1] > 1)
+                    or out2.dtype not in (torch.float32, torch.int16)):
+                raise GtcrnError(f"out must be a float32 or int16 tensor of shape ({B}, >= {n}) with contiguous rows")
+        if x2.dtype == torch.int16 and out2.dtype == torch.int16:
+            raise GtcrnError("int16 -> int16 is not offered: one side is float32")
+        lens = None
+        if lengths is not None:
+            lens = torch.as_tensor(lengths).reshape(-1)
+            if lens.numel() != B:
+                raise GtcrnError(f"lengths must hold {B} entries, got {lens.numel()}")
+            if not lens.is_cuda:
+                if int(lens.min()) < 0 or int(lens.max()) > L:
+                    raise GtcrnError(f"every length must lie in [0, L={L}]")
+            lens = lens.to(device=x.device, dtype=torch.int32).contiguous()
+        fn = (lib().gtcrn_resample_pcm16_in if x2.dtype == torch.int16 else
+              lib().gtcrn_resample_pcm16_out if out2.dtype == torch.int16 else lib().gtcrn_resample)
+        with torch.cuda.device(x.device):
+            # (a one-row tensor may report any stride)
+            _check(fn(self._h, x2.data_ptr(), max(x2.stride(0), L), lens.data_ptr() if lens is not None else None, L,
+                      out2.data_ptr(), max(out2.stride(0), n), B, _stream_ptr()))
+        if out is not None:
+            return out
+        return out2[0] if one else out2
 
 
 def _pcm_pair(pcm, wave, who):

@@ -80,6 +80,9 @@ struct gtcrn_model {
     float* d_g2 = nullptr;   // gtcn2 output
     float* d_spec_a = nullptr;  // frame-major spectrograms for forward_wave (B,T,257,2)
     float* d_spec_b = nullptr;
+    float* d_rate_a = nullptr;  // 16 kHz hand-offs of gtcrn_rate_stream_step (nstreams x 256 nhops each): k_rate_in -> wave step,
+    float* d_rate_b = nullptr;  // wave step -> k_rate_out; sized by gtcrn_rate_stream_reserve
+    long cap_rate = 0;          // capacity of each in (streams * hops)
     bool debug = false;
     bool debug_keep_fused = false;   // gtcrn_debug_enable(m, 2): phase stamps only -- single-frame steps stay ONE launch
     float* d_dbg = nullptr;
@@ -377,6 +380,8 @@ void gtcrn_model_destroy(gtcrn_model* m) {
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
     free_workspace(m);
+    if (m->d_rate_a) (void)hipFree(m->d_rate_a);
+    if (m->d_rate_b) (void)hipFree(m->d_rate_b);
     if (m->d_dbg) (void)hipFree(m->d_dbg);
     if (m->d_stamps) (void)hipFree(m->d_stamps);
     if (m->d_pf) (void)hipFree(m->d_pf);
@@ -658,6 +663,283 @@ int gtcrn_wave_stream_flush_pcm16(gtcrn_model* m, void* d_state, void* d_wstate,
                                   short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
     return wave_stream_impl<short>("gtcrn_wave_stream_flush_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
                                    out_stride, nstreams, 1, true, r, d_win, stream);
+}
+
+// ---- sample-rate conversion ------------------------------------------------------------------------------------------
+// The filter of include/gtcrn_micro_hip.h, designed here in double and rounded once to float: the kernels, the tests and
+// gtcrn_resample_taps all see these coefficients.
+namespace {
+
+struct RsDesign {
+    int up = 1, down = 1, half = 0;
+    int nt = 1, ntp = 4;            // taps of the longest phase; the same rounded up to a multiple of 4 (the table's row)
+    std::vector<float> h;           // 2 half + 1 taps
+};
+
+bool rs_rate_ok(int fs) {
+    for (int r : {8000, 11025, 22050, 24000, 32000, 44100, 48000})
+        if (fs == r) return true;
+    return false;
+}
+bool rs_pair_ok(int fs_in, int fs_out) {
+    return (fs_in == 16000 && (fs_out == 16000 || rs_rate_ok(fs_out))) || (fs_out == 16000 && rs_rate_ok(fs_in));
+}
+double bessel_i0(double x) {        // sum over k of ((x / 2)^k / k!)^2: every term positive, converges for all x
+    const double y = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= y / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+void rs_ratio(int fs_in, int fs_out, int* up, int* down) {
+    int a = fs_out, b = fs_in;
+    while (b) { const int t = a % b; a = b; b = t; }
+    *up = fs_out / a;
+    *down = fs_in / a;
+}
+void rs_design(int fs_in, int fs_out, RsDesign* d, bool taps) {
+    rs_ratio(fs_in, fs_out, &d->up, &d->down);
+    if (fs_in == fs_out) {          // the no-op: one tap of 1
+        d->half = 0; d->nt = 1; d->ntp = 4;
+        if (taps) d->h.assign(1, 1.0f);
+        return;
+    }
+    const int q = d->up > d->down ? d->up : d->down;
+    d->half = 32 * q;
+    d->nt = 2 * d->half / d->up + 1;
+    d->ntp = (d->nt + 3) & ~3;
+    if (!taps) return;
+    const int n = 2 * d->half + 1;
+    const double kPi = 3.14159265358979323846, beta = 8.95926, fc = 0.9375 * 0.5 / q, i0b = bessel_i0(beta);
+    std::vector<double> h(n);
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int k = i - d->half;
+        const double x = 2.0 * fc * k, y = kPi * x, r = (double)k / (double)d->half;
+        const double w = bessel_i0(beta * std::sqrt(1.0 - r * r)) / i0b;
+        h[i] = (k == 0 ? 1.0 : std::sin(y) / y) * w;
+        sum += h[i];
+    }
+    d->h.resize(n);
+    for (int i = 0; i < n; ++i) d->h[i] = (float)(h[i] * ((double)d->up / sum));
+}
+// live rates: a hop of 256 samples at 16 kHz and the 32-period stage delay are whole numbers of samples at fs
+bool rs_live_ok(int fs) { return fs == 8000 || fs == 24000 || fs == 32000 || fs == 48000; }
+
+}  // namespace
+
+struct gtcrn_resampler {
+    int device = 0, fs_in = 0, fs_out = 0;
+    RsDesign d;                     // (taps dropped after the upload)
+    float* d_taps = nullptr;        // phase table: up rows of ntp floats, row k0 = h[k0], h[k0 + up], ... then +0.0f
+};
+
+long gtcrn_resample_taps(int fs_in, int fs_out, int* up, int* down, float* h_taps, long cap) {
+    if (!rs_pair_ok(fs_in, fs_out))
+        return fail(GTCRN_ERR_ARG, "gtcrn_resample_taps: supported rates are 8000, 11025, 22050, 24000, 32000, 44100, 48000 to / from 16000");
+    RsDesign d;
+    rs_design(fs_in, fs_out, &d, h_taps != nullptr);
+    if (up) *up = d.up;
+    if (down) *down = d.down;
+    const long n = 2L * d.half + 1;
+    if (h_taps) {
+        if (cap < n) return fail(GTCRN_ERR_ARG, "gtcrn_resample_taps: the buffer holds fewer than 2 half + 1 taps");
+        std::memcpy(h_taps, d.h.data(), sizeof(float) * n);
+    }
+    return n;
+}
+
+long gtcrn_resample_out_len(int fs_in, int fs_out, long L) {
+    if (!rs_pair_ok(fs_in, fs_out) || L < 0) return fail(GTCRN_ERR_ARG, "gtcrn_resample_out_len: unsupported rate pair or L < 0");
+    int up, down;
+    rs_ratio(fs_in, fs_out, &up, &down);
+    return (L * up + down - 1) / down;
+}
+
+int gtcrn_resampler_create(gtcrn_resampler** out, int fs_in, int fs_out, int device) {
+    if (!out) return fail(GTCRN_ERR_ARG, "gtcrn_resampler_create: null out pointer");
+    *out = nullptr;
+    if (!rs_pair_ok(fs_in, fs_out))
+        return fail(GTCRN_ERR_ARG, "gtcrn_resampler_create: supported rates are 8000, 11025, 22050, 24000, 32000, 44100, 48000 to / from 16000");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GTCRN_ERR_DEVICE, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(GTCRN_ERR_ARG, "gtcrn_resampler_create: no such device");
+    gtcrn_resampler* r = new gtcrn_resampler;
+    r->device = device; r->fs_in = fs_in; r->fs_out = fs_out;
+    rs_design(fs_in, fs_out, &r->d, true);
+    const RsDesign& d = r->d;
+    if (gtk::resample_tile_span(d.up, d.down, d.ntp) > gtk::RS_SPAN) {
+        delete r;
+        return fail(GTCRN_ERR_ARG, "gtcrn_resampler_create: the ratio's input span exceeds the kernel's tile");
+    }
+    std::vector<float> P((size_t)d.up * d.ntp, 0.0f);
+    for (int k0 = 0; k0 < d.up; ++k0)
+        for (int t = 0; k0 + (long)t * d.up <= 2L * d.half; ++t) P[(size_t)k0 * d.ntp + t] = d.h[k0 + (size_t)t * d.up];
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc(&r->d_taps, sizeof(float) * P.size());
+    if (e == hipSuccess) e = hipMemcpy(r->d_taps, P.data(), sizeof(float) * P.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (r->d_taps) (void)hipFree(r->d_taps);
+        delete r;
+        return hip_fail(e, "gtcrn_resampler_create");
+    }
+    r->d.h.clear();
+    *out = r;
+    return 0;
+}
+
+void gtcrn_resampler_destroy(gtcrn_resampler* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    (void)hipDeviceSynchronize();
+    if (r->d_taps) (void)hipFree(r->d_taps);
+    delete r;
+}
+
+extern "C++" template <typename SI, typename SO>
+static int resample_impl(const char* who, gtcrn_resampler* r, const SI* d_in, long in_stride, const int* d_lengths, long L,
+                         SO* d_out, long out_stride, int B, void* stream) {
+    const std::string w(who);
+    if (!r || !r->d_taps) return fail(GTCRN_ERR_ARG, w + ": null resampler");
+    if (!d_in || !d_out) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (B < 1 || L < 1) return fail(GTCRN_ERR_ARG, w + ": B and L must be >= 1");
+    const RsDesign& d = r->d;
+    const long nout = (L * d.up + d.down - 1) / d.down;
+    if (in_stride < L || out_stride < nout) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    HIP_TRY(hipSetDevice(r->device));
+    LAUNCH_TRY((gtk::launch_resample<SI, SO>(d_in, in_stride, d_lengths, L, d_out, out_stride, B, d.up, d.down, d.half, d.ntp,
+                                             r->d_taps, static_cast<hipStream_t>(stream))));
+    return 0;
+}
+int gtcrn_resample(gtcrn_resampler* r, const float* d_in, long in_stride, const int* d_lengths, long L, float* d_out,
+                   long out_stride, int B, void* stream) {
+    return resample_impl<float, float>("gtcrn_resample", r, d_in, in_stride, d_lengths, L, d_out, out_stride, B, stream);
+}
+int gtcrn_resample_pcm16_in(gtcrn_resampler* r, const short* d_in, long in_stride, const int* d_lengths, long L, float* d_out,
+                            long out_stride, int B, void* stream) {
+    return resample_impl<short, float>("gtcrn_resample_pcm16_in", r, d_in, in_stride, d_lengths, L, d_out, out_stride, B, stream);
+}
+int gtcrn_resample_pcm16_out(gtcrn_resampler* r, const float* d_in, long in_stride, const int* d_lengths, long L, short* d_out,
+                             long out_stride, int B, void* stream) {
+    return resample_impl<float, short>("gtcrn_resample_pcm16_out", r, d_in, in_stride, d_lengths, L, d_out, out_stride, B, stream);
+}
+
+// ---- hop-level streaming at the caller's rate: k_rate_in -> the three launches of the wave step -> k_rate_out
+int gtcrn_rate_stream_hop(int fs) {
+    if (!rs_live_ok(fs)) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_hop: live rates are 8000, 24000, 32000, 48000");
+    return (int)(256L * fs / 16000);
+}
+int gtcrn_rate_stream_latency(int fs) {
+    if (!rs_live_ok(fs)) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_latency: live rates are 8000, 24000, 32000, 48000");
+    RsDesign d;
+    rs_design(fs, 16000, &d, false);
+    return (int)(256L * fs / 16000) + 2 * (d.half / d.up);
+}
+size_t gtcrn_rate_stream_state_bytes(int fs) {
+    if (!rs_live_ok(fs)) { (void)fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_state_bytes: live rates are 8000, 24000, 32000, 48000"); return 0; }
+    RsDesign a, b;
+    rs_design(fs, 16000, &a, false);
+    rs_design(16000, fs, &b, false);
+    return sizeof(float) * (size_t)(a.ntp + b.ntp);
+}
+
+namespace {
+int rate_pair_check(const std::string& w, gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out) {
+    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
+    if (!in || !out || !in->d_taps || !out->d_taps) return fail(GTCRN_ERR_ARG, w + ": null resampler");
+    if (in->fs_out != 16000 || out->fs_in != 16000 || in->fs_in != out->fs_out || !rs_live_ok(in->fs_in))
+        return fail(GTCRN_ERR_ARG, w + ": the resamplers must be fs -> 16000 and 16000 -> fs, fs in {8000, 24000, 32000, 48000}");
+    if (in->device != m->device || out->device != m->device) return fail(GTCRN_ERR_ARG, w + ": resamplers and model on different devices");
+    return 0;
+}
+int ensure_rate_workspace(gtcrn_model* m, int nstreams, int nhops, hipStream_t s) {
+    const long need = (long)nstreams * nhops;
+    if (need <= m->cap_rate) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(GTCRN_ERR_STATE, "rate hand-off buffers too small during stream capture: call gtcrn_rate_stream_reserve first");
+    HIP_TRY(hipDeviceSynchronize());
+    if (m->d_rate_a) (void)hipFree(m->d_rate_a);
+    if (m->d_rate_b) (void)hipFree(m->d_rate_b);
+    m->d_rate_a = m->d_rate_b = nullptr;
+    m->cap_rate = 0;
+    HIP_TRY(hipMalloc(&m->d_rate_a, sizeof(float) * 256 * need));
+    HIP_TRY(hipMalloc(&m->d_rate_b, sizeof(float) * 256 * need));
+    m->cap_rate = need;
+    return 0;
+}
+}  // namespace
+
+int gtcrn_rate_stream_reserve(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, int nstreams, int nhops) {
+    if (int rc = rate_pair_check("gtcrn_rate_stream_reserve", m, in, out)) return rc;
+    if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_reserve: nstreams and nhops must be >= 1");
+    int rc = check_model(m);
+    if (rc) return rc;
+    if ((rc = ensure_workspace(m, nstreams, nhops, nullptr))) return rc;
+    return ensure_rate_workspace(m, nstreams, nhops, nullptr);
+}
+
+long gtcrn_rate_stream_debug_handoff(gtcrn_model* m, int which, float* d_dst, long n, void* stream) {
+    if (!m || !d_dst || (which != 0 && which != 1) || n < 1)
+        return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_debug_handoff: null pointer, n < 1 or which not 0 / 1");
+    if (n > 256 * m->cap_rate) return fail(GTCRN_ERR_STATE, "gtcrn_rate_stream_debug_handoff: no rate step of that size has run");
+    int rc = check_model(m);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_dst, which ? m->d_rate_b : m->d_rate_a, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return n;
+}
+
+int gtcrn_rate_stream_reset(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                            void* d_rstate, int nstreams, void* stream) {
+    if (int rc = rate_pair_check("gtcrn_rate_stream_reset", m, in, out)) return rc;
+    if (!d_rstate) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_reset: null state or nstreams < 1");
+    if (int rc = gtcrn_wave_stream_reset(m, d_state, d_wstate, nstreams, stream)) return rc;
+    HIP_TRY(hipMemsetAsync(d_rstate, 0, gtcrn_rate_stream_state_bytes(in->fs_in) * nstreams, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C++" template <typename S>
+static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state,
+                            void* d_wstate, void* d_rstate, const S* d_in, long in_stride, S* d_out, long out_stride,
+                            int nstreams, int nhops, const float* d_win, void* stream) {
+    const std::string w(who);
+    if (int rc = rate_pair_check(w, m, in, out)) return rc;
+    if (!d_state || !d_wstate || !d_rstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, w + ": nstreams and nhops must be >= 1");
+    const int H = (int)(256L * in->fs_in / 16000);
+    if (in_stride < (long)H * nhops || out_stride < (long)H * nhops) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate) | reinterpret_cast<uintptr_t>(d_rstate)) & 15)
+        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    int rc = check_model(m);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = ensure_workspace(m, nstreams, nhops, s))) return rc;
+    if ((rc = ensure_rate_workspace(m, nstreams, nhops, s))) return rc;
+    const RsDesign &di = in->d, &dout = out->d;
+    float* rs = static_cast<float*>(d_rstate);
+    const long rs_stride = di.ntp + dout.ntp, row = 256L * nhops;
+    LAUNCH_TRY(gtk::launch_rate_in<S>(d_in, in_stride, m->d_rate_a, row, rs, rs_stride, nstreams, nhops, H, di.up, di.down,
+                                      di.ntp, in->d_taps, s));
+    rc = gtcrn_wave_stream_step(m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams, nhops, d_win, stream);
+    if (rc) return rc;
+    LAUNCH_TRY(gtk::launch_rate_out<S>(m->d_rate_b, row, d_out, out_stride, rs + di.ntp, rs_stride, nstreams, nhops, H, dout.up,
+                                       dout.down, dout.ntp, out->d_taps, s));
+    return 0;
+}
+int gtcrn_rate_stream_step(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                           void* d_rstate, const float* d_in, long in_stride, float* d_out, long out_stride, int nstreams,
+                           int nhops, const float* d_win, void* stream) {
+    return rate_stream_impl<float>("gtcrn_rate_stream_step", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride, d_out,
+                                   out_stride, nstreams, nhops, d_win, stream);
+}
+int gtcrn_rate_stream_step_pcm16(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                                 void* d_rstate, const short* d_in, long in_stride, short* d_out, long out_stride,
+                                 int nstreams, int nhops, const float* d_win, void* stream) {
+    return rate_stream_impl<short>("gtcrn_rate_stream_step_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride,
+                                   d_out, out_stride, nstreams, nhops, d_win, stream);
 }
 
 static int state_convert(gtcrn_model* m, void* d_state, int nstreams, float* conv, float* tra,

@@ -69,6 +69,26 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, hipStream_t s);
+// sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
+// floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
+constexpr int RS_THREADS = 256;
+constexpr int RS_TILE = 1024;                    // outputs per k_resample workgroup
+constexpr int RS_SPAN = 3328;                    // floats of input one tile stages: 48 -> 16 kHz needs 3 * 1023 + 196 + slack
+constexpr int RS_LDS_TAPS = 1024;                // phase tables up to this many floats are staged in LDS
+constexpr int RATE_SPAN = 1024;                  // per-stream form: history (<= 196) + one hop at the caller's rate (<= 768)
+long resample_tile_span(int up, int down, int ntp);
+// batch form: row b holds lens[b] (nullptr: L) <= L samples; ceil(len * up / down) outputs per row
+template <typename SI, typename SO>
+int launch_resample(const SI* in, long in_stride, const int* lens, long L, SO* out, long out_stride, int B, int up, int down,
+                    int half, int ntp, const float* taps, hipStream_t s);
+// per-stream causal forms (the centred filter delayed by half / down outputs): nhops hops of hin -> 256 (in) or 256 -> hout
+// (out) samples per stream; rstate + n * rs_stride = the stream's ntp history floats, read and advanced
+template <typename S>
+int launch_rate_in(const S* in, long in_stride, float* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
+                   int hin, int up, int down, int ntp, const float* taps, hipStream_t s);
+template <typename S>
+int launch_rate_out(const float* in, long in_stride, S* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
+                    int hout, int up, int down, int ntp, const float* taps, hipStream_t s);
 // gspec += adjoint(iSTFT)(gwave): gwave (B, 256 (T-1)) is the gradient w.r.t. the iSTFT output ALREADY divided by
 // the window envelope; gspec (B,257,T,2 by strides) receives the gradient w.r.t. the spectrogram (accumulated).
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,

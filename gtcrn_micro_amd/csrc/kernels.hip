@@ -5086,4 +5086,181 @@ int launch_selftest(const float* A, const float* Bm, const float* C, float* D, h
     return 0;
 }
 
+// ===================================================================== sample-rate conversion (gtcrn_resample, gtcrn_rate_stream_*)
+// Polyphase FIR between 16 kHz and the caller's rate (include/gtcrn_micro_hip.h: the filter is designed on the host).  The
+// taps arrive as a phase table P[k0][t] = h[k0 + t * up] (k0 < up, t < ntp; ntp = the taps of the longest phase rounded up
+// to a multiple of 4, the rest +0.0f), so output j of  y[j] = sum_i x[i] h[j down - i up + half]  is the dot product of
+// row k0 = (j down + half) mod up with the samples x[ihi], x[ihi - 1], ..., ihi = (j down + half) div up.
+//
+// rs_dot is that dot product and the ONLY place a sample meets a tap: ntp products in the table's order into four fp32
+// accumulators (tap t into accumulator t mod 4) by fmaf, joined (a0 + a1) + (a2 + a3).  Samples outside the signal are
+// staged as +0.0f and multiplied like any other.  The batch kernel and the two per-stream causal kernels stage the same
+// sample values around the same expression, so a stream equals the batch call on the same signal bit for bit.
+__device__ __forceinline__ float rs_dot(const float* __restrict__ tp, int ntp, const float* __restrict__ xs) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int t = 0; t < ntp; t += 4) {
+        const f32x4 h = ld4(tp + t);
+        a0 = fmaf(h[0], xs[-t], a0);
+        a1 = fmaf(h[1], xs[-t - 1], a1);
+        a2 = fmaf(h[2], xs[-t - 2], a2);
+        a3 = fmaf(h[3], xs[-t - 3], a3);
+    }
+    return (a0 + a1) + (a2 + a3);
+}
+
+// phase tables of at most RS_LDS_TAPS floats are staged in LDS (every integer ratio and 2/3, 3/2: <= 196 floats); the
+// 147- to 640-phase tables of the 44.1 kHz family (57 - 164 KB) are read from global memory (L2)
+__device__ __forceinline__ const float* rs_stage_taps(const float* __restrict__ taps, int n, float* s_t, int tid, int nthr) {
+    if (n > RS_LDS_TAPS) return nullptr;
+    for (int i = tid; i < n; i += nthr) s_t[i] = taps[i];
+    return s_t;
+}
+
+// Batch form: a workgroup computes RS_TILE consecutive outputs of one row from the input span they read, staged once in
+// LDS as floats (16-byte loads where the row allows it; +0.0f outside [0, row length)).  Lane j reads the samples
+// around j * down / up: a stride of down / up <= 3 words between lanes -- 1 (up-sampling: neighbours share a word,
+// broadcast), 3 (48 -> 16 kHz: conflict free on the 32 banks of ds_read_b32) or 2 (32 -> 16 kHz: two-way).
+// Rows have their own lengths (lens, device; nullptr: all L); outputs beyond ceil(len * up / down) are not written.
+template <typename SI, typename SO>
+__global__ __launch_bounds__(RS_THREADS) void k_resample(const SI* __restrict__ in, long in_stride, const int* __restrict__ lens,
+                                                         long L, SO* __restrict__ out, long out_stride, int tiles, int up,
+                                                         int down, int half, int ntp, const float* __restrict__ taps, int vec) {
+    __shared__ __attribute__((aligned(16))) float s_x[RS_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const int row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    long len = lens ? (long)lens[row] : L;
+    len = len < 0 ? 0 : (len > L ? L : len);
+    const long nout = (len * up + down - 1) / down;
+    const long j0 = (long)tile * RS_TILE;
+    if (j0 >= nout) return;                                         // (workgroup uniform)
+    const long j1 = j0 + RS_TILE < nout ? j0 + RS_TILE : nout;
+    const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);
+    constexpr int V = std::is_same<SI, short>::value ? 8 : 4;        // samples per 16-byte load
+    const long lo = (j0 * down + half) / up - (ntp - 1), hi = ((j1 - 1) * down + half) / up;
+    const long a0 = lo - (((lo % V) + V) % V);                     // the span starts on a 16-byte boundary of the row
+    const int nv = (int)((hi - a0) / V) + 1;                       // nv * V <= RS_SPAN: launch_resample checks the worst tile
+    const SI* x = in + (long)row * in_stride;
+    for (int v = tid; v < nv; v += RS_THREADS) {
+        const long i = a0 + (long)v * V;
+        float f[V];
+        if (vec && i >= 0 && i + V <= len) {
+            if constexpr (V == 8) {
+                const i16x8 q = *reinterpret_cast<const i16x8*>(x + i);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const short qe = q[e]; f[e] = wave_ld<short>(&qe); }
+            } else {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[e] = q[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) f[e] = (i + e >= 0 && i + e < len) ? wave_ld<SI>(x + i + e) : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; e += 4) st4(s_x + v * V + e, f32x4{f[e], f[e + 1], f[e + 2], f[e + 3]});
+    }
+    __syncthreads();
+    SO* o = out + (long)row * out_stride;
+    for (long j = j0 + tid; j < j1; j += RS_THREADS) {
+        const long num = j * down + half, ih = num / up;
+        const int k0 = (int)(num - ih * up);
+        const float* xs = s_x + (ih - a0);
+        const float y = tp ? rs_dot(tp + k0 * ntp, ntp, xs) : rs_dot(taps + (long)k0 * ntp, ntp, xs);
+        wave_st<SO>(o + j, y);
+    }
+}
+
+// Per-stream causal form, one workgroup per stream: the stream's centred filter delayed by half / down output samples,
+// so output m of a hop reads inputs up to (m down) div up of the SAME hop (hin * up == hout * down: every hop starts at
+// phase 0) and back ntp - 1 samples, the first of which are the stream's history hist[0 .. ntp) (the last ntp input
+// samples as floats; zeros after a reset).  Hop by hop: [previous ntp samples ++ the hop] staged in LDS, hout outputs,
+// then the history advances to the call's last ntp input samples (ntp <= hin).
+template <typename SI, typename SO>
+__device__ __forceinline__ void rate_hops(const SI* __restrict__ x, SO* __restrict__ o, float* __restrict__ hist, int nhops,
+                                          int hin, int hout, int up, int down, int ntp, const float* __restrict__ taps) {
+    __shared__ __attribute__((aligned(16))) float s_x[RATE_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);      // (never nullptr: launch_rate checks)
+    for (int h = 0; h < nhops; ++h) {
+        for (int i = tid; i < ntp + hin; i += RS_THREADS) {
+            const long g = (long)h * hin + i - ntp;
+            s_x[i] = g >= 0 ? wave_ld<SI>(x + g) : hist[ntp + g];
+        }
+        __syncthreads();
+        for (int m = tid; m < hout; m += RS_THREADS) {
+            const int num = m * down, ih = num / up, k0 = num - ih * up;
+            wave_st<SO>(o + (long)h * hout + m, rs_dot(tp + k0 * ntp, ntp, s_x + ntp + ih));
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = wave_ld<SI>(x + (long)nhops * hin - ntp + i);
+}
+// caller's rate -> 16 kHz in front of the wave step: rstate row = [inbound history | outbound history]
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_rate_in(const S* __restrict__ in, long in_stride, float* __restrict__ out,
+                                                        long out_stride, float* __restrict__ rstate, long rs_stride, int nhops,
+                                                        int hin, int up, int down, int ntp, const float* __restrict__ taps) {
+    const long n = blockIdx.x;
+    rate_hops<S, float>(in + n * in_stride, out + n * out_stride, rstate + n * rs_stride, nhops, hin, 256, up, down, ntp, taps);
+}
+// 16 kHz -> caller's rate behind it, from the 256-sample blocks k_wave_synthesis emits
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_rate_out(const float* __restrict__ in, long in_stride, S* __restrict__ out,
+                                                         long out_stride, float* __restrict__ rstate, long rs_stride, int nhops,
+                                                         int hout, int up, int down, int ntp, const float* __restrict__ taps) {
+    const long n = blockIdx.x;
+    rate_hops<float, S>(in + n * in_stride, out + n * out_stride, rstate + n * rs_stride, nhops, 256, hout, up, down, ntp, taps);
+}
+
+// the widest input span one tile of RS_TILE outputs stages (with the alignment slack of the 16-byte loads)
+long resample_tile_span(int up, int down, int ntp) { return ((long)(RS_TILE - 1) * down + up - 1) / up + 1 + ntp + 8 + 8; }
+
+template <typename SI, typename SO>
+int launch_resample(const SI* in, long in_stride, const int* lens, long L, SO* out, long out_stride, int B, int up, int down,
+                    int half, int ntp, const float* taps, hipStream_t s) {
+    if (resample_tile_span(up, down, ntp) > RS_SPAN || (ntp & 3) || (reinterpret_cast<uintptr_t>(taps) & 15))
+        return (int)hipErrorInvalidValue;
+    const long nout = (L * up + down - 1) / down;
+    const long tiles = (nout + RS_TILE - 1) / RS_TILE;
+    if (tiles < 1 || tiles * B > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    constexpr int V = std::is_same<SI, short>::value ? 8 : 4;
+    const int vec = !(reinterpret_cast<uintptr_t>(in) & 15) && in_stride % V == 0;
+    hipLaunchKernelGGL((k_resample<SI, SO>), dim3((unsigned)(tiles * B)), dim3(RS_THREADS), 0, s, in, in_stride, lens, L, out,
+                       out_stride, (int)tiles, up, down, half, ntp, taps, vec);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_resample<float, float>(const float*, long, const int*, long, float*, long, int, int, int, int, int, const float*, hipStream_t);
+template int launch_resample<short, float>(const short*, long, const int*, long, float*, long, int, int, int, int, int, const float*, hipStream_t);
+template int launch_resample<float, short>(const float*, long, const int*, long, short*, long, int, int, int, int, int, const float*, hipStream_t);
+
+static bool rate_geometry_ok(int hin, int hout, int up, int down, int ntp) {
+    return (long)hin * up == (long)hout * down && ntp <= hin && !(ntp & 3) && ntp + hin <= RATE_SPAN && up * ntp <= RS_LDS_TAPS;
+}
+template <typename S>
+int launch_rate_in(const S* in, long in_stride, float* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
+                   int hin, int up, int down, int ntp, const float* taps, hipStream_t s) {
+    if (!rate_geometry_ok(hin, 256, up, down, ntp)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_rate_in<S>), dim3(N), dim3(RS_THREADS), 0, s, in, in_stride, out, out_stride, rstate, rs_stride, nhops,
+                       hin, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_rate_out(const float* in, long in_stride, S* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
+                    int hout, int up, int down, int ntp, const float* taps, hipStream_t s) {
+    if (!rate_geometry_ok(256, hout, up, down, ntp)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_rate_out<S>), dim3(N), dim3(RS_THREADS), 0, s, in, in_stride, out, out_stride, rstate, rs_stride, nhops,
+                       hout, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_rate_in<float>(const float*, long, float*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_rate_in<short>(const short*, long, float*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_rate_out<float>(const float*, long, float*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_rate_out<short>(const float*, long, short*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
+
 }  // namespace gtk

@@ -11,8 +11,12 @@ checkpoint, length-matched to its clean reference (zero-pad / crop, ``:98-102``)
   merges the per-rank lists into the single ``inf.scp`` / ``ref.scp`` the reference's eval expects;
 * a clip shorter than 257 samples cannot be reflect-padded by 256 (``torch.stft`` raises there too): it is skipped
   with a warning instead of aborting the folder;
-* WAV I/O uses ``scipy.io.wavfile`` (16-bit PCM out, what libsndfile writes for the reference); a file that
-  is not 16 kHz raises instead of being resampled (the reference needs librosa for that, ``:55-57``);
+* WAV I/O uses ``scipy.io.wavfile`` (16-bit PCM out, what libsndfile writes for the reference);
+* a clip at 8, 11.025, 22.05, 24, 32, 44.1 or 48 kHz is resampled to 16 kHz on the GPU (``gtcrn_resample``: the
+  library's own polyphase filter, stated in ``include/gtcrn_micro_hip.h`` -- not librosa's ``soxr_hq`` of ``:55-57``,
+  which is not reproducible to the sample), batched per rate with the clips' lengths, and then enhanced like any
+  other; the file is written at 16 kHz as the reference writes it, and a reference file at another rate counts
+  with its 16 kHz length (``:90-93``).  Any other rate raises;
 * configuration comes from command-line flags (the reference reads two OmegaConf YAML files, ``:27-28``).
 
     python -m gtcrn_micro_amd.infer --noisy-dir N --clean-dir C --enh-dir E --checkpoint best_model_dns3.tar
@@ -87,9 +91,52 @@ def _clip_info(noisy_dir, clean_dir, wav_name):
     if not os.path.exists(ref_path):
         raise FileNotFoundError(f"Clean file not found for clean_fileid_{fileid}.wav, fileid={fileid}:\n {ref_path}")
     fs_c, clean = wavfile.read(ref_path, mmap=True)
+    n_clean = int(clean.shape[0])
     if fs_c != 16000:
-        raise AssertionError(f"{ref_path}: sample rate {fs_c} != 16000")
-    return path, ref_path, int(clean.shape[0])
+        _check_rate(ref_path, fs_c)
+        from . import _lib
+        n_clean = _lib.resample_out_len(fs_c, 16000, n_clean)      # its length once resampled (infer.py:90-93)
+    return path, ref_path, n_clean
+
+
+def _check_rate(path, fs):
+    from ._lib import SUPPORTED_RATES
+    if fs not in SUPPORTED_RATES:
+        raise AssertionError(f"{path}: sample rate {fs} is not supported: the clips must be at one of "
+                             f"{', '.join(str(r) for r in SUPPORTED_RATES)} Hz (16000 is the model's rate, the others "
+                             "are resampled on the GPU); resample the file first")
+
+
+def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows):
+    """The clips that are not at 16 kHz (other: item index -> (rate, samples at that rate)): per rate one Resampler and
+    batches of similar lengths; a batch is resampled on the device with its lengths (gtcrn_resample), enhanced with
+    its 16 kHz lengths and finished like any other clip.  Returns (bytes up, bytes down)."""
+    import torch
+    up = down = 0
+    for fs in sorted({fs for fs, _ in other.values()}):
+        rs = eng.resampler(fs, 16000)
+        idx = sorted((i for i in other if other[i][0] == fs), key=lambda i: other[i][1])
+        for k in range(0, len(idx), max_batch):
+            sel = idx[k:k + max_batch]
+            waves = [read_wav_f32(items[i][1])[1] for i in sel]
+            lens = [len(w) for w in waves]
+            if lens != [other[i][1] for i in sel]:
+                raise RuntimeError(f"{items[sel[0]][1]}: a clip changed length while the folder was being enhanced")
+            host = np.zeros((len(sel), max(lens)), np.float32)
+            for j, w in enumerate(waves):
+                host[j, :len(w)] = w
+            lens16 = [items[i][4] for i in sel]
+            x16 = torch.zeros((len(sel), rs.out_len(max(lens))), device=dev)
+            rs(torch.from_numpy(host).to(dev), lengths=lens, out=x16)
+            if min(lens16) == x16.shape[1]:
+                y = eng.forward_wave(x16, win).cpu().numpy()
+            else:
+                y = eng.forward_wave_var(x16, lens16, win).cpu().numpy()
+            up += 4 * host.size
+            down += 4 * y.size
+            for j, i in enumerate(sel):
+                rows[i] = _finish_clip(y[j], items[i], enh_dir)
+    return up, down
 
 
 def merge_scp(enh_dir, world):
@@ -151,27 +198,34 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     from scipy.io import wavfile
     items = []
     fast = {}
+    other = {}                      # item index -> (rate, samples at that rate) of the clips that are not at 16 kHz
     for wav_name in names[lo:hi]:
         path, ref_path, n_clean = _clip_info(noisy_dir, clean_dir, wav_name)
         fs, x = wavfile.read(path, mmap=True)
+        n16 = int(x.shape[0])
         if fs != 16000:
-            raise AssertionError(f"{path}: sample rate {fs} != 16000 (resampling is not part of this path: the "
-                                 "reference resamples with librosa, infer.py:54-57; resample the folder first)")
-        if x.shape[0] < MIN_SAMPLES:
-            warnings.warn(f"{path}: {x.shape[0]} samples < {MIN_SAMPLES}, cannot be reflect-padded: skipped")
+            _check_rate(path, fs)
+            n16 = _lib.resample_out_len(fs, 16000, n16)
+        if n16 < MIN_SAMPLES:
+            warnings.warn(f"{path}: {n16} samples at 16 kHz < {MIN_SAMPLES}, cannot be reflect-padded: skipped")
             continue
-        items.append((wav_name, path, ref_path, n_clean, int(x.shape[0])))
+        items.append((wav_name, path, ref_path, n_clean, n16))
+        if fs != 16000:
+            other[len(items) - 1] = (fs, int(x.shape[0]))
+            continue
         # mono 16-bit PCM (what the reference's data are): pass 2 reads the samples straight from their byte offset
         fast[len(items) - 1] = int(x.offset) if (isinstance(x, np.memmap) and x.ndim == 1 and x.dtype == np.int16) else None
     # pass 2: batches of similar lengths, each through one launch sequence, written as soon as it is done
-    order = sorted(range(len(items)), key=lambda i: items[i][4])
+    order = sorted((i for i in range(len(items)) if i not in other), key=lambda i: items[i][4])
     batches = [order[k:k + max_batch] for k in range(0, len(order), max_batch)]
     rows = {}
     t_start = time.perf_counter()
-    frames = sum(1 + items[i][4] // 256 for i in order)
+    frames = sum(1 + it[4] // 256 for it in items)
     busy_ms = 0.0
     setup_s = 0.0
     nbytes = [0, 0]
+    if other:
+        nbytes[0], nbytes[1] = _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows)
 
     if not pipeline or not batches:
         for sel in batches:

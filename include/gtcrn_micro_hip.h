@@ -197,6 +197,84 @@ int gtcrn_wave_stream_flush(gtcrn_model *m, void *d_state, void *d_wstate, const
 int gtcrn_wave_stream_flush_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const short *d_tail, long tail_stride,
                                   int r, short *d_out, long out_stride, int nstreams, const float *d_win, void *stream);
 
+/* ---- sample-rate conversion: 8 / 11.025 / 22.05 / 24 / 32 / 44.1 / 48 kHz <-> 16 kHz ---------------------------
+ * Replaces `librosa.resample(noisy, orig_sr=sr, target_sr=16000)` in front of the STFT (infer.py:54-57, and the same
+ * call on the reference file, infer.py:90-93) and the stateful per-stream resamplers a live caller would otherwise
+ * write around gtcrn_wave_stream_step.  The model runs at 16 kHz; these calls are the only way another rate gets in
+ * or out.
+ *
+ * Contract: the filter is this library's own, stated here to the coefficient.  It is NOT librosa's: librosa.resample
+ * defaults to soxr_hq, whose filter is not documented to the coefficient, so bit parity with the reference's resampled
+ * waveform is neither claimed nor tested; the tests compare with an independent float64 implementation of the
+ * definition below (scipy.signal.resample_poly(x, up, down, window=h / up)).
+ *   up / down = fs_out / fs_in in lowest terms, q = max(up, down), half = 32 q, 2 half + 1 taps on the fs_in * up grid
+ *   h[n] ~ sinc(2 fc n) * kaiser(n; beta),  n = -half .. half,  fc = 0.9375 * 0.5 / q,  beta = 8.95926 (90 dB),
+ *          scaled so that sum(h) == up; computed in double on the host, rounded once to float
+ *   y[j] = sum over i of x[i] * h[j * down - i * up + half],  0 <= i < L,  0 <= index <= 2 half,
+ *          j = 0 .. ceil(L * up / down) - 1; samples outside x are zero (zero padding, centred: no delay)
+ * Within +0.0003 / -0.112 dB up to 0.875 of the lower Nyquist frequency, >= 96 dB down from 1.125 x it (whatever
+ * aliases lands in 7 - 8 kHz-equivalent only).  Audio above 8 kHz of a wide-band input never reaches the model, and the
+ * output at fs is band-limited to 8 kHz.  fs_in == fs_out == 16000 is a one-tap copy.  Any other pair of rates is
+ * GTCRN_ERR_ARG.  Arithmetic: fp32 fmaf, each output's products in a fixed order into four accumulators, so one signal
+ * gives the same bits in a batch of any shape and in the streaming form below.
+ *
+ * gtcrn_resample_taps (host only, no device): up, down and the 2 half + 1 coefficients exactly as the kernels use
+ * them; returns the tap count (h_taps may be NULL to query it; cap = capacity of h_taps in floats).
+ * gtcrn_resample_out_len (host only): ceil(L * up / down).
+ * gtcrn_resample: B rows; row b holds d_lengths[b] <= L samples (d_lengths: int32 on the device, or NULL = all L) at
+ * d_in + b * in_stride and receives ceil(d_lengths[b] * up / down) samples at d_out + b * out_stride; nothing beyond
+ * that is written.  Asynchronous on `stream`.  _pcm16_in reads int16 samples (s / 32768), _pcm16_out writes them
+ * (clip(rint(y * 32768))): equal to the float form between gtcrn_pcm16_to_f32 / gtcrn_f32_to_pcm16, bit for bit. */
+typedef struct gtcrn_resampler gtcrn_resampler;
+int gtcrn_resampler_create(gtcrn_resampler **out, int fs_in, int fs_out, int device);   /* designs the taps, uploads them */
+void gtcrn_resampler_destroy(gtcrn_resampler *r);
+long gtcrn_resample_taps(int fs_in, int fs_out, int *up, int *down, float *h_taps, long cap);
+long gtcrn_resample_out_len(int fs_in, int fs_out, long L);
+int gtcrn_resample(gtcrn_resampler *r, const float *d_in, long in_stride, const int *d_lengths, long L, float *d_out,
+                   long out_stride, int B, void *stream);
+int gtcrn_resample_pcm16_in(gtcrn_resampler *r, const short *d_in, long in_stride, const int *d_lengths, long L,
+                            float *d_out, long out_stride, int B, void *stream);
+int gtcrn_resample_pcm16_out(gtcrn_resampler *r, const float *d_in, long in_stride, const int *d_lengths, long L,
+                             short *d_out, long out_stride, int B, void *stream);
+
+/* ---- hop-level streaming at the caller's rate --------------------------------------------------------------------
+ * gtcrn_wave_stream_step for a live caller whose audio is not at 16 kHz: fs in {8000, 24000, 32000, 48000} (the rates
+ * at which a hop H = 256 fs / 16000 = 128 / 384 / 512 / 768 samples and the stage delay D below are whole numbers;
+ * 44.1 kHz and its family are offline only).  nhops hops of H samples in per stream and call, as many out.
+ *
+ * Contract.  `in` is a resampler fs -> 16000, `out` one 16000 -> fs on the model's device.  Each is run in its causal
+ * form: the centred filter above delayed by D = 32 q / up_in samples at fs (96 / 48 / 64 / 32 samples at 48 / 24 / 32 /
+ * 8 kHz: 2 ms, 4 ms at 8 kHz), with the stream's last samples kept in d_rstate.  With the one-hop delay of the wave step,
+ * after a reset, for K hops of input x and u = resample(16000 -> fs) of gtcrn_forward_wave of resample(fs -> 16000) of
+ * (D zeros followed by x):
+ *     out[n] = 0                  0 <= n < H
+ *     out[n] = u[n - H - D]       H + D <= n < H * K          bit for bit
+ * (the D samples in between are the interpolator's pre-ringing).  gtcrn_rate_stream_latency = H + 2 D samples at fs:
+ * 20 ms, 24 ms at 8 kHz.  There is no rate flush: a caller drains a stream by sending ceil(latency / H) hops of zeros.
+ *
+ * State.  d_state and d_wstate are those of gtcrn_wave_stream_step, unchanged; d_rstate holds
+ * gtcrn_rate_stream_state_bytes(fs) per stream (the two filters' histories as floats).  All 16-byte aligned; reset a
+ * sub-range of streams by offsetting the three pointers.  gtcrn_rate_stream_reset resets all three.
+ *
+ * Calls.  A step is five launches on `stream` (k_rate_in, the three of gtcrn_wave_stream_step, k_rate_out),
+ * asynchronous, and allocates nothing once gtcrn_rate_stream_reserve(m, in, out, nstreams, nhops) was called (it sizes
+ * the model workspace and the two 16 kHz hand-off buffers, which belong to the model handle): capturable into a HIP
+ * graph.  Rows: d_in + n * in_stride and d_out + n * out_stride, H * nhops samples each.  The _pcm16 form takes and
+ * returns int16 samples and equals the float form between the two PCM conversions.  Null pointers, counts < 1, short
+ * strides, an unsupported rate and a resampler pair that does not match return GTCRN_ERR_ARG before any launch. */
+int gtcrn_rate_stream_hop(int fs);              /* H */
+int gtcrn_rate_stream_latency(int fs);          /* H + 2 D samples at fs */
+size_t gtcrn_rate_stream_state_bytes(int fs);   /* per stream; 0 for an unsupported rate */
+int gtcrn_rate_stream_reserve(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, int nstreams, int nhops);
+int gtcrn_rate_stream_reset(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                            void *d_rstate, int nstreams, void *stream);
+int gtcrn_rate_stream_step(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                           void *d_rstate, const float *d_in, long in_stride, float *d_out, long out_stride, int nstreams,
+                           int nhops, const float *d_win, void *stream);
+int gtcrn_rate_stream_step_pcm16(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                                 void *d_rstate, const short *d_in, long in_stride, short *d_out, long out_stride,
+                                 int nstreams, int nhops, const float *d_win, void *stream);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
@@ -244,6 +322,10 @@ int gtcrn_stream_form(gtcrn_model *m, int form);
  * once the narrow one needs more rounds than it. */
 int gtcrn_stream_streams_per_workgroup(int nstreams);
 long gtcrn_debug_tap(gtcrn_model *m, const char *name, int b, float *h_dst, long cap);
+/* The 16 kHz hand-off of the most recent gtcrn_rate_stream_step, copied to d_dst (n floats: nstreams rows of
+ * 256 * nhops) on `stream`: which = 0 what k_rate_in handed to the wave step, 1 what the wave step handed to
+ * k_rate_out.  Returns n, or a negative status. */
+long gtcrn_rate_stream_debug_handoff(gtcrn_model *m, int which, float *d_dst, long n, void *stream);
 /* Diagnostic build only (libgtcrn_micro_hip_stamps.so, -DGT_STAMPS): per-workgroup sums of shader
  * cycles spent in each barrier-delimited phase of kernel 0 encoder, 1 gtcn1, 2 gtcn2, 3 decoder,
  * (B,16) values.  The product library returns zeros. */

@@ -6,6 +6,10 @@ out) per stream and step, timed with device events over `--iters` steps, warm-up
 bytes the two wave kernels add per stream-step (from shapes).  Writes profiles/wave_stream_bench.json.
 
 --trace-only N: just run wave steps at N streams (for `rocprofv3 --kernel-trace --stats -- python <this> --trace-only N`).
+
+--rate: the step at the caller's rate (gtcrn_rate_stream_step: k_rate_in, the wave step, k_rate_out) at 48 kHz and 8 kHz
+against the 16 kHz wave step of the SAME run, same warm-up, repetitions and medians; writes
+profiles/rate_stream_bench.json.  With --trace-only N: rate steps at --trace-fs (default 48000).
 """
 import argparse
 import json
@@ -67,6 +71,39 @@ def compare(eng, win, N, iters, reps):
             "spectral_reps_ms": ts, "wave_reps_ms": tw, "iters": iters}
 
 
+def compare_rate(eng, win, N, iters, reps, rates=(48000, 8000)):
+    """One hop per stream and step: the 16 kHz wave step and the rate step at each of `rates`, alternating."""
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    eng.reserve(N, 1)
+    wst = eng.new_wave_state(N, win)
+    fns = {16000: lambda: eng.wave_stream_step(wst, x, out=y)}
+    keep = [wst]
+    for fs in rates:
+        st = eng.new_rate_state(N, win, fs)
+        eng.rate_stream_reserve(st, 1)
+        xr = torch.randn(N, st.hop, device="cuda", generator=gen) * 0.1
+        yr = torch.empty_like(xr)
+        fns[fs] = lambda st=st, xr=xr, yr=yr: eng.rate_stream_step(st, xr, out=yr)
+        keep.append(st)
+    for f in fns.values():
+        timed(f, max(3, iters // 4))                              # warm-up
+    t = {fs: [] for fs in fns}
+    for _ in range(reps):
+        for fs, f in fns.items():
+            t[fs].append(timed(f, iters))
+    med = {fs: statistics.median(v) for fs, v in t.items()}
+    del keep, fns
+    torch.cuda.empty_cache()
+    r = {"N": N, "wave_step_16k_ms": med[16000], "wave_reps_16k_ms": t[16000], "iters": iters}
+    for fs in rates:
+        r[f"rate_step_{fs}_ms"] = med[fs]
+        r[f"ratio_{fs}"] = med[fs] / med[16000]
+        r[f"rate_reps_{fs}_ms"] = t[fs]
+    return r
+
+
 def latency_n1(eng, win, iters):
     eng.reserve(1, 1)
     x = torch.randn(1, 256, device="cuda") * 0.1
@@ -105,6 +142,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wave_stream_bench.json"))
     ap.add_argument("--trace-only", type=int, default=0)
+    ap.add_argument("--rate", action="store_true", help="the rate step at 48 / 8 kHz against the 16 kHz wave step")
+    ap.add_argument("--trace-fs", type=int, default=48000)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wave_stream_bench needs the GPU (nothing is measured on the CPU)")
@@ -112,6 +151,28 @@ def main():
     params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
     eng = Engine(params, 0)
     win = torch.hann_window(512).pow(0.5).cuda()
+    if a.trace_only and a.rate:
+        N = a.trace_only
+        st = eng.new_rate_state(N, win, a.trace_fs)
+        eng.rate_stream_reserve(st, 1)
+        x = torch.randn(N, st.hop, device="cuda") * 0.1
+        y = torch.empty_like(x)
+        for _ in range(a.iters):
+            eng.rate_stream_step(st, x, out=y)
+        torch.cuda.synchronize()
+        return
+    if a.rate:
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "rate_stream_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in [int(s) for s in a.sizes.split(",")]:
+            r = compare_rate(eng, win, N, a.iters, a.reps)
+            print(json.dumps({k: v for k, v in r.items() if "reps" not in k}), flush=True)
+            res["compare"].append(r)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
     if a.trace_only:
         N = a.trace_only
         eng.reserve(N, 1)
