@@ -100,6 +100,21 @@ def lib():
         getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
     L.gtcrn_rate_stream_debug_handoff.restype = cl
     L.gtcrn_rate_stream_debug_handoff.argtypes = [_vp, ci, _vp, cl, _vp]
+    L.gtcrn_packet_stream_n16.argtypes = [ci, ci]
+    L.gtcrn_packet_stream_latency16.argtypes = [ci, ci]
+    L.gtcrn_packet_stream_state_bytes.restype = ctypes.c_size_t
+    L.gtcrn_packet_stream_state_bytes.argtypes = [ci, ci]
+    L.gtcrn_packet_stream_schedule.argtypes = [ci, ci, ci, ctypes.POINTER(ci)]
+    L.gtcrn_packet_stream_create.argtypes = [ctypes.POINTER(_vp), _vp, _vp, _vp, ci, ci, ci]
+    L.gtcrn_packet_stream_destroy.argtypes = [_vp]
+    L.gtcrn_packet_stream_destroy.restype = None
+    L.gtcrn_packet_stream_phase.argtypes = [_vp]
+    L.gtcrn_packet_stream_next_hops.argtypes = [_vp]
+    L.gtcrn_packet_stream_reset.argtypes = [_vp, _vp, _vp, _vp, ci, _vp]
+    for fn in ("gtcrn_packet_stream_step", "gtcrn_packet_stream_step_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, _vp, _vp]
+    L.gtcrn_packet_stream_debug_handoff.restype = cl
+    L.gtcrn_packet_stream_debug_handoff.argtypes = [_vp, ci, _vp, cl, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -661,6 +676,72 @@ class Engine:
             _check(lib().gtcrn_rate_stream_debug_handoff(self._h, int(which), out.data_ptr(), out.numel(), _stream_ptr()))
         return out
 
+    # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
+    def new_packet_state(self, nstreams, window, packet, fs=16000):
+        """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
+        16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
+        the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
+        needs is reserved here."""
+        import torch
+        fs, packet = int(fs), int(packet)
+        n16 = packet_stream_n16(fs, packet)
+        nbytes = packet_stream_state_bytes(fs, packet)
+        ws = self.new_wave_state(nstreams, window)
+        rs_in = self.resampler(fs, 16000) if fs != 16000 else None
+        rs_out = self.resampler(16000, fs) if fs != 16000 else None
+        h = ctypes.c_void_p()
+        with self._dev():
+            _check(lib().gtcrn_packet_stream_create(ctypes.byref(h), self._h, rs_in._h if rs_in else None,
+                                                    rs_out._h if rs_out else None, fs, packet, ws.n))
+        st = PacketStreamState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
+                               torch.empty((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32))
+        self.packet_stream_reset(st)
+        return st
+
+    def packet_stream_reset(self, state, lo=0, hi=None):
+        """Resets streams lo..hi-1 (all three states).  They join the group at its current phase: state.phase zeros in
+        front of their input, the group's latency."""
+        hi = state.n if hi is None else int(hi)
+        lo = int(lo)
+        if not isinstance(state, PacketStreamState):
+            raise GtcrnError("state must come from new_packet_state")
+        if not 0 <= lo < hi <= state.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        with self._dev():
+            _check(lib().gtcrn_packet_stream_reset(state._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
+                                                   state.pkt[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
+
+    def packet_stream_step(self, state, x, out=None):
+        """x (N, state.packet) float32 or int16 at the state's rate -> the enhanced (N, state.packet), same dtype,
+        state.latency16 samples (counted at 16 kHz) late.  Steps state.next_hops hops of the model (possibly none) and
+        advances the group's phase.  Asynchronous on the current stream; no allocation when `out` is given."""
+        import torch
+        if not isinstance(state, PacketStreamState):
+            raise GtcrnError("state must come from new_packet_state")
+        x = self._wave_rows(state, x, "x")
+        if x.shape[1] != state.packet:
+            raise GtcrnError(f"x must hold one packet of {state.packet} samples per stream, got {x.shape[1]}")
+        out = self._wave_out(out, x, state.packet)
+        fn = lib().gtcrn_packet_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step
+        state.last_hops = state.next_hops
+        with self._dev():
+            # (a one-row tensor may report any stride)
+            _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
+                      max(x.stride(0), state.packet), out.data_ptr(), max(out.stride(0), state.packet), state.n,
+                      state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def packet_stream_handoff(self, state, which=0):
+        """Test hook: a copy of the 16 kHz hand-off of the most recent packet step, (N, 256 * hops of that step): which = 0
+        what k_packet_in produced, 1 what the wave step produced."""
+        import torch
+        out = torch.empty((state.n, 256 * state.last_hops), device=state.wave.device, dtype=torch.float32)
+        if out.numel():
+            with self._dev():
+                _check(lib().gtcrn_packet_stream_debug_handoff(state._h, int(which), out.data_ptr(), out.numel(),
+                                                               _stream_ptr()))
+        return out
+
     def _cache_ptrs(self, tcn_cache):
         flat = [tcn_cache[g][k] for g in range(2) for k in range(4)]
         for g in range(2):
@@ -778,8 +859,81 @@ class RateStreamState(WaveStreamState):
         self.rate = rate
 
 
+class PacketStreamState(WaveStreamState):
+    """WaveStreamState of a group of live streams fed in packets (Engine.new_packet_state): plus ``pkt``
+    (N, packet_stream_state_bytes / 4: two FIFOs and the two filter histories per stream), the rate ``fs``, the packet
+    ``packet`` in samples at fs and ``n16`` at 16 kHz, ``latency16`` (the end-to-end delay in 16 kHz samples; at fs it is
+    latency16 * fs / 16000, not a whole number in the 44.1 kHz family), and the host handle with the group's ``phase``."""
+
+    def __init__(self, engine, handle, model, wave, window, fs, packet, n16, rs_in, rs_out, pkt):
+        super().__init__(model, wave, window)
+        self._eng = engine          # the handle points into the engine's model and the resamplers: keep them alive
+        self._h = handle
+        self.fs = fs
+        self.packet = packet
+        self.n16 = n16
+        self.latency16 = packet_stream_latency16(fs, packet)
+        self.rs_in = rs_in
+        self.rs_out = rs_out
+        self.pkt = pkt
+        self.last_hops = 0
+
+    @property
+    def phase(self):
+        """(16 kHz samples the group has taken) mod 256."""
+        return _check(lib().gtcrn_packet_stream_phase(self._h))
+
+    @property
+    def next_hops(self):
+        """Hops of the model the next step runs (0 when the packet does not complete one)."""
+        return _check(lib().gtcrn_packet_stream_next_hops(self._h))
+
+    @property
+    def period(self):
+        """Calls after which the phase, and so the launch sequence, repeats: 256 / gcd(n16, 256)."""
+        from math import gcd
+        return 256 // gcd(self.n16, 256)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gtcrn_packet_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 SUPPORTED_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)
 LIVE_RATES = (8000, 16000, 24000, 32000, 48000)
+PACKET_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+
+
+def packet_stream_n16(fs, packet):
+    """`packet` samples at `fs` Hz in 16 kHz samples (host only; raises for a packet the packet form does not take)."""
+    return _check(lib().gtcrn_packet_stream_n16(int(fs), int(packet)))
+
+
+def packet_stream_latency16(fs, packet):
+    """End-to-end delay of the packet form in 16 kHz samples: 512 - gcd(n16, 256), plus the two filters' delays at
+    fs != 16000 (host only)."""
+    return _check(lib().gtcrn_packet_stream_latency16(int(fs), int(packet)))
+
+
+def packet_stream_state_bytes(fs, packet):
+    n = int(lib().gtcrn_packet_stream_state_bytes(int(fs), int(packet)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+def packet_stream_schedule(fs, packet, phase=0):
+    """(hops, next phase) of a packet step taken at `phase` (host only)."""
+    nxt = ctypes.c_int()
+    h = _check(lib().gtcrn_packet_stream_schedule(int(fs), int(packet), int(phase), ctypes.byref(nxt)))
+    return h, nxt.value
 
 
 def resample_taps(fs_in, fs_out):

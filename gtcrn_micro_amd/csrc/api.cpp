@@ -47,10 +47,11 @@ struct Timing {
 };
 // every timed launch records WHICH kernel it was (mixed offline / streaming calls keep their own rows)
 enum KernelId { K_STFT, K_ENCODER, K_GTCN1, K_GTCN2, K_DECODER, K_ISTFT, K_FRONT, K_ENCODER_GT, K_GTCN_MS, K_STREAM_MS, K_STREAM_WIDE,
-                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_COUNT };
+                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_PACKET_IN, K_PACKET_OUT, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_stft",  "k_encoder",    "k_gtcn1",   "k_gtcn2",    "k_decoder",
                                            "k_istft", "k_front",      "k_encoder_gt", "k_gtcn_ms", "k_stream_ms",
-                                           "k_stream_wide", "k_wave_analysis", "k_wave_synthesis"};
+                                           "k_stream_wide", "k_wave_analysis", "k_wave_synthesis", "k_packet_in",
+                                           "k_packet_out"};
 constexpr int kNumKernels = K_COUNT;
 
 }  // namespace
@@ -940,6 +941,206 @@ int gtcrn_rate_stream_step_pcm16(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resa
                                  int nstreams, int nhops, const float* d_win, void* stream) {
     return rate_stream_impl<short>("gtcrn_rate_stream_step_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride,
                                    d_out, out_stride, nstreams, nhops, d_win, stream);
+}
+
+// ---- packet-sized live streaming: k_packet_in -> the wave step for h hops (nothing when h == 0) -> k_packet_out.
+// All geometry is host arithmetic on (fs, n) and the group's phase; the kernels receive the numbers.
+namespace {
+
+struct PkGeom {
+    int n16 = 0, g = 0, hmax = 0;   // packet at 16 kHz; gcd(n16, 256); the most hops one call steps
+    int d_in = 0, d_out = 0;        // the two causal stages' delays in 16 kHz samples (0 at 16 kHz)
+    RsDesign in, out;               // (no taps) fs -> 16000 and 16000 -> fs; ntp = 0 at 16 kHz
+};
+
+bool pk_rate_ok(int fs) {
+    for (int r : {8000, 16000, 22050, 24000, 32000, 44100, 48000})
+        if (fs == r) return true;
+    return false;
+}
+// false: (fs, n) is not a packet this form takes
+bool pk_geometry(int fs, int n, PkGeom* p) {
+    if (!pk_rate_ok(fs) || n < 1 || n > gtk::PK_MAX16 * 3 || ((long)n * 16000) % fs) return false;
+    const long n16 = (long)n * 16000 / fs;
+    if (n16 < 1 || n16 > gtk::PK_MAX16) return false;
+    p->n16 = (int)n16;
+    int a = p->n16, b = 256;
+    while (b) { const int t = a % b; a = b; b = t; }
+    p->g = a;
+    p->hmax = (256 - p->g + p->n16) / 256;
+    p->in.ntp = p->out.ntp = 0;
+    p->d_in = p->d_out = 0;
+    if (fs == 16000) return true;
+    rs_design(fs, 16000, &p->in, false);
+    rs_design(16000, fs, &p->out, false);
+    p->d_in = p->in.half / p->in.down;
+    p->d_out = p->out.half / p->out.up;
+    // each stage's history comes out of ONE packet, and a staging round of the inbound stage fits its LDS span
+    return p->in.ntp <= n && p->out.ntp <= p->n16 && p->out.ntp <= gtk::PK_HIST &&
+           ((gtk::PK_TILE - 1) * p->in.down) / p->in.up + p->in.ntp + 1 <= gtk::PK_SPAN;
+}
+const char* const kPkBad = ": packets are n samples at fs in {8000, 16000, 22050, 24000, 32000, 44100, 48000} with n * 16000 / fs a "
+                           "whole number in 1..4096 and, at fs != 16000, no shorter than either filter's history";
+
+}  // namespace
+
+struct gtcrn_packet_stream {
+    gtcrn_model* m = nullptr;
+    gtcrn_resampler *in = nullptr, *out = nullptr;
+    int device = 0, fs = 0, n = 0, max_streams = 0;
+    PkGeom p;
+    int phase = 0;              // (16 kHz samples taken so far) mod 256, the same for every stream of the group
+    float* d_a = nullptr;       // hand-offs, max_streams rows of 256 hmax floats: k_packet_in -> wave step,
+    float* d_b = nullptr;       // wave step -> k_packet_out
+    int last_h = 0, last_n = 0; // hops and streams of the most recent step (gtcrn_packet_stream_debug_handoff)
+};
+
+int gtcrn_packet_stream_n16(int fs, int n) {
+    PkGeom p;
+    if (!pk_geometry(fs, n, &p)) return fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_n16") + kPkBad);
+    return p.n16;
+}
+int gtcrn_packet_stream_latency16(int fs, int n) {
+    PkGeom p;
+    if (!pk_geometry(fs, n, &p)) return fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_latency16") + kPkBad);
+    return 512 - p.g + p.d_in + p.d_out;
+}
+size_t gtcrn_packet_stream_state_bytes(int fs, int n) {
+    PkGeom p;
+    if (!pk_geometry(fs, n, &p)) { (void)fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_state_bytes") + kPkBad); return 0; }
+    return sizeof(float) * (size_t)(2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp);
+}
+int gtcrn_packet_stream_schedule(int fs, int n, int phase, int* next_phase) {
+    PkGeom p;
+    if (!pk_geometry(fs, n, &p)) return fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_schedule") + kPkBad);
+    if (phase < 0 || phase >= 256 || phase % p.g) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_schedule: the phase is a multiple of gcd(n16, 256) in 0..255");
+    if (next_phase) *next_phase = (phase + p.n16) % 256;
+    return (phase + p.n16) / 256;
+}
+
+int gtcrn_packet_stream_create(gtcrn_packet_stream** out, gtcrn_model* m, gtcrn_resampler* rs_in, gtcrn_resampler* rs_out, int fs,
+                               int n, int max_streams) {
+    const std::string w("gtcrn_packet_stream_create");
+    if (!out) return fail(GTCRN_ERR_ARG, w + ": null out pointer");
+    *out = nullptr;
+    PkGeom p;
+    if (!pk_geometry(fs, n, &p)) return fail(GTCRN_ERR_ARG, w + kPkBad);
+    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
+    if (max_streams < 1) return fail(GTCRN_ERR_ARG, w + ": max_streams must be >= 1");
+    if (fs == 16000) {
+        if (rs_in || rs_out) return fail(GTCRN_ERR_ARG, w + ": 16 kHz packets take no resamplers (pass NULL)");
+    } else {
+        if (!rs_in || !rs_out || !rs_in->d_taps || !rs_out->d_taps) return fail(GTCRN_ERR_ARG, w + ": null resampler");
+        if (rs_in->fs_in != fs || rs_in->fs_out != 16000 || rs_out->fs_in != 16000 || rs_out->fs_out != fs)
+            return fail(GTCRN_ERR_ARG, w + ": the resamplers must be fs -> 16000 and 16000 -> fs");
+        if (rs_in->device != m->device || rs_out->device != m->device)
+            return fail(GTCRN_ERR_ARG, w + ": resamplers and model on different devices");
+    }
+    int rc = check_model(m);
+    if (rc) return rc;
+    if ((rc = ensure_workspace(m, max_streams, p.hmax, nullptr))) return rc;
+    gtcrn_packet_stream* ps = new gtcrn_packet_stream;
+    ps->m = m; ps->device = m->device; ps->in = rs_in; ps->out = rs_out; ps->fs = fs; ps->n = n; ps->max_streams = max_streams; ps->p = p;
+    const size_t bytes = sizeof(float) * 256 * (size_t)p.hmax * (size_t)max_streams;
+    hipError_t e = hipMalloc(&ps->d_a, bytes);
+    if (e == hipSuccess) e = hipMalloc(&ps->d_b, bytes);
+    if (e != hipSuccess) {
+        if (ps->d_a) (void)hipFree(ps->d_a);
+        delete ps;
+        return hip_fail(e, "gtcrn_packet_stream_create");
+    }
+    *out = ps;
+    return 0;
+}
+
+void gtcrn_packet_stream_destroy(gtcrn_packet_stream* ps) {
+    if (!ps) return;
+    (void)hipSetDevice(ps->device);
+    (void)hipDeviceSynchronize();
+    if (ps->d_a) (void)hipFree(ps->d_a);
+    if (ps->d_b) (void)hipFree(ps->d_b);
+    delete ps;
+}
+
+int gtcrn_packet_stream_phase(const gtcrn_packet_stream* ps) {
+    if (!ps) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_phase: null handle");
+    return ps->phase;
+}
+int gtcrn_packet_stream_next_hops(const gtcrn_packet_stream* ps) {
+    if (!ps) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_next_hops: null handle");
+    return (ps->phase + ps->p.n16) / 256;
+}
+
+int gtcrn_packet_stream_reset(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int nstreams, void* stream) {
+    if (!ps) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_reset: null handle");
+    if (!d_pstate) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_reset: null state or nstreams < 1");
+    if (nstreams > ps->max_streams) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_reset: more streams than the handle was created for");
+    if (int rc = gtcrn_wave_stream_reset(ps->m, d_state, d_wstate, nstreams, stream)) return rc;
+    // zeros ARE the pre-roll: the FIFO levels follow from the handle's phase, so a stream reset at phase z holds z zeros
+    // inbound and 256 - g - z zeros outbound
+    HIP_TRY(hipMemsetAsync(d_pstate, 0, gtcrn_packet_stream_state_bytes(ps->fs, ps->n) * nstreams, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C++" template <typename S>
+static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
+                              const S* d_in, long in_stride, S* d_out, long out_stride, int nstreams, const float* d_win,
+                              void* stream) {
+    const std::string w(who);
+    if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
+    if (!d_state || !d_wstate || !d_pstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (nstreams < 1 || nstreams > ps->max_streams)
+        return fail(GTCRN_ERR_ARG, w + ": nstreams must be >= 1 and at most the handle's max_streams");
+    if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate) | reinterpret_cast<uintptr_t>(d_pstate)) & 15)
+        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    gtcrn_model* m = ps->m;
+    int rc = check_model(m);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const PkGeom& p = ps->p;
+    const int phi = ps->phase, h = (phi + p.n16) / 256, lvl = 256 - p.g - phi;
+    const long row = 256L * h, ps_stride = 2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp;
+    float* pst = static_cast<float*>(d_pstate);
+    if (h && (rc = ensure_workspace(m, nstreams, h, s))) return rc;       // (create reserved max_streams x hmax)
+    Timer tm(m, s);
+    tm.begin(K_PACKET_IN);
+    LAUNCH_TRY(gtk::launch_packet_in<S>(d_in, in_stride, ps->n, ps->d_a, row, pst, ps_stride, nstreams, phi, p.n16, h, p.in.up,
+                                        p.in.down, p.in.ntp, ps->in ? ps->in->d_taps : nullptr, s));
+    tm.end();
+    if (h) {
+        rc = gtcrn_wave_stream_step(m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h, d_win, stream);
+        if (rc) return rc;
+    }
+    tm.begin(K_PACKET_OUT);
+    LAUNCH_TRY(gtk::launch_packet_out<S>(ps->d_b, row, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
+                                         nstreams, lvl, p.n16, h, p.out.up, p.out.down, p.out.ntp,
+                                         ps->out ? ps->out->d_taps : nullptr, s));
+    tm.end();
+    ps->phase = (phi + p.n16) % 256;
+    ps->last_h = h;
+    ps->last_n = nstreams;
+    return 0;
+}
+int gtcrn_packet_stream_step(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const float* d_in,
+                             long in_stride, float* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return packet_stream_impl<float>("gtcrn_packet_stream_step", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
+                                     out_stride, nstreams, d_win, stream);
+}
+int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const short* d_in,
+                                   long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return packet_stream_impl<short>("gtcrn_packet_stream_step_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
+                                     out_stride, nstreams, d_win, stream);
+}
+
+long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream* ps, int which, float* d_dst, long n, void* stream) {
+    if (!ps || !d_dst || (which != 0 && which != 1) || n < 1)
+        return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_debug_handoff: null pointer, n < 1 or which not 0 / 1");
+    if (n > 256L * ps->last_h * ps->last_n) return fail(GTCRN_ERR_STATE, "gtcrn_packet_stream_debug_handoff: the last step handed over fewer samples");
+    int rc = check_model(ps->m);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_dst, which ? ps->d_b : ps->d_a, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return n;
 }
 
 static int state_convert(gtcrn_model* m, void* d_state, int nstreams, float* conv, float* tra,

@@ -89,6 +89,26 @@ int launch_rate_in(const S* in, long in_stride, float* out, long out_stride, flo
 template <typename S>
 int launch_rate_out(const float* in, long in_stride, S* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
                     int hout, int up, int down, int ntp, const float* taps, hipStream_t s);
+// packet-sized live streaming (gtcrn_packet_stream_*): packets of n samples at the caller's rate = n16 samples at 16 kHz,
+// re-blocked on the device to the 256-sample hops of the wave step and back.  Per-stream state row (floats):
+// [inbound FIFO PK_FIFO | outbound FIFO PK_FIFO | inbound stage history ntp_in | outbound stage history ntp_out]; both FIFO
+// levels are functions of the group's phase (host arithmetic) and are not stored.
+constexpr int PK_MAX16 = 4096;                   // longest packet, in 16 kHz samples
+constexpr int PK_FIFO = 256;                     // floats of each FIFO between calls (both levels stay below one hop)
+constexpr int PK_SEQ = PK_FIFO + PK_MAX16;       // LDS: a FIFO's content ++ what one call appends
+constexpr int PK_HIST = 256;                     // LDS in front of the outbound sequence: the outbound stage's history (<= 132)
+constexpr int PK_TILE = 256;                     // outputs per staging round of the inbound stage
+constexpr int PK_SPAN = 1024;                    // floats of input one round stages: 48 -> 16 kHz needs 3 * 255 + 196 + 1
+// in: N packets (n samples, S) + the inbound FIFOs (phi samples each) -> h = (phi + n16) / 256 hops per stream in `hand`
+// (row stride hand_stride >= 256 h), the remainder back in the FIFO.  ntp == 0: no stage (16 kHz, n == n16).
+template <typename S>
+int launch_packet_in(const S* in, long in_stride, int n, float* hand, long hand_stride, float* pstate, long ps_stride, int N,
+                     int phi, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s);
+// out: the outbound FIFOs (lvl samples each) ++ the 256 h samples of the wave step -> n16 popped, resampled to n samples
+// (S) per stream, the remainder back in the FIFO.  hist_off: floats from the row's start to the outbound stage's history.
+template <typename S>
+int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stride, int n, float* pstate, long ps_stride,
+                      int hist_off, int N, int lvl, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s);
 // gspec += adjoint(iSTFT)(gwave): gwave (B, 256 (T-1)) is the gradient w.r.t. the iSTFT output ALREADY divided by
 // the window envelope; gspec (B,257,T,2 by strides) receives the gradient w.r.t. the spectrogram (accumulated).
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,

@@ -5263,4 +5263,132 @@ template int launch_rate_in<short>(const short*, long, float*, long, float*, lon
 template int launch_rate_out<float>(const float*, long, float*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_rate_out<short>(const float*, long, short*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
 
+// ===================================================================== packet-sized live streaming (gtcrn_packet_stream_*)
+// A caller's packet of n samples at fs (n16 = n 16000 / fs samples at 16 kHz, a whole number) in, n enhanced samples out,
+// around the UNCHANGED wave step: k_packet_in cuts the group's 16 kHz sample sequence into 256-sample hops, k_packet_out
+// cuts the hops the wave step emits back into packets.  The group's phase phi = (16 kHz samples taken so far) mod 256
+// lives on the host and is the same for every stream, and so are both FIFO levels: the inbound FIFO holds phi samples
+// between calls, the outbound one lvl = 256 - gcd(n16, 256) - phi.  A call steps h = (phi + n16) div 256 hops (host
+// arithmetic, possibly 0).  Neither level is stored: a reset is a memset, and a stream reset at phase z thereby holds z
+// zeros inbound and 256 - g - z zeros outbound, which is its pre-roll.  Per-stream state row (floats):
+// [inbound FIFO PK_FIFO | outbound FIFO PK_FIFO | inbound stage history ntp_in | outbound stage history ntp_out].
+//
+// The resampling stages (fs != 16000) are the causal forms of rate_hops on the same values through the same rs_dot: output
+// m of a packet reads the packet's inputs up to (m down) div up (n up == n16 down: every packet starts at filter phase 0)
+// and back ntp - 1 samples, into the stream's history.  The inbound stage walks the packet in rounds of PK_TILE outputs
+// whose input span it stages in LDS (a packet at 48 kHz may hold 12 288 samples); the outbound stage reads the popped 16 kHz
+// packet where it already sits in LDS, its history in front of it.  Phase tables above RS_LDS_TAPS floats (44.1 / 22.05
+// kHz) are read from global memory, as k_resample does.
+// One workgroup per stream.  Every global word of the state row is read into LDS before the barrier and written after it
+// by the thread that owns its index; nothing is read back.
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_in(const S* __restrict__ in, long in_stride, int n, float* __restrict__ hand,
+                                                          long hand_stride, float* __restrict__ pstate, long ps_stride, int phi,
+                                                          int n16, int h, int up, int down, int ntp,
+                                                          const float* __restrict__ taps) {
+    __shared__ __attribute__((aligned(16))) float s_a[PK_SEQ];       // the FIFO's phi samples ++ this packet at 16 kHz
+    __shared__ __attribute__((aligned(16))) float s_x[PK_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const S* x = in + row * in_stride;
+    float* ps = pstate + row * ps_stride;
+    for (int i = tid; i < phi; i += RS_THREADS) s_a[i] = ps[i];
+    if (ntp == 0) {                                                  // 16 kHz: the packet as it is
+        for (int m = tid; m < n16; m += RS_THREADS) s_a[phi + m] = wave_ld<S>(x + m);
+        __syncthreads();
+    } else {
+        float* hist = ps + 2 * PK_FIFO;
+        const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);
+        for (int m0 = 0; m0 < n16; m0 += PK_TILE) {
+            const int m1 = m0 + PK_TILE < n16 ? m0 + PK_TILE : n16;
+            const int lo = (m0 * down) / up - (ntp - 1), cnt = ((m1 - 1) * down) / up - lo + 1;   // <= PK_SPAN (launch check)
+            for (int i = tid; i < cnt; i += RS_THREADS) {
+                const int g = lo + i;                                // >= 1 - ntp; < n
+                s_x[i] = g >= 0 ? wave_ld<S>(x + g) : hist[ntp + g];
+            }
+            __syncthreads();
+            for (int m = m0 + tid; m < m1; m += RS_THREADS) {
+                const int num = m * down, ih = num / up, k0 = num - ih * up;
+                const float* xs = s_x + (ih - lo);
+                s_a[phi + m] = tp ? rs_dot(tp + k0 * ntp, ntp, xs) : rs_dot(taps + (long)k0 * ntp, ntp, xs);
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = wave_ld<S>(x + n - ntp + i);        // (ntp <= n)
+    }
+    float* o = hand + row * hand_stride;
+    const int whole = 256 * h, rem = phi + n16 - whole;              // rem < 256: the next call's phi
+    for (int i = tid; i < whole; i += RS_THREADS) o[i] = s_a[i];
+    for (int i = tid; i < rem; i += RS_THREADS) ps[i] = s_a[whole + i];
+}
+
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_out(const float* __restrict__ hand, long hand_stride, S* __restrict__ out,
+                                                           long out_stride, int n, float* __restrict__ pstate, long ps_stride,
+                                                           int hist_off, int lvl, int n16, int h, int up, int down, int ntp,
+                                                           const float* __restrict__ taps) {
+    __shared__ __attribute__((aligned(16))) float s_q[PK_HIST + PK_SEQ];   // [stage history | the FIFO's lvl samples ++ 256 h new]
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    float* ps = pstate + row * ps_stride;
+    float* fo = ps + PK_FIFO;
+    float* hist = ps + hist_off;
+    float* q = s_q + PK_HIST;
+    const float* hb = hand + row * hand_stride;
+    const int whole = 256 * h;
+    for (int i = tid; i < lvl; i += RS_THREADS) q[i] = fo[i];
+    for (int i = tid; i < whole; i += RS_THREADS) q[lvl + i] = hb[i];
+    for (int i = tid; i < ntp; i += RS_THREADS) q[i - ntp] = hist[i];
+    const float* tp = ntp ? rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS) : nullptr;
+    __syncthreads();
+    S* o = out + row * out_stride;
+    if (ntp == 0) {
+        for (int m = tid; m < n; m += RS_THREADS) wave_st<S>(o + m, q[m]);
+    } else {
+        for (int m = tid; m < n; m += RS_THREADS) {
+            const int num = m * down, ih = num / up, k0 = num - ih * up;       // ih < n16
+            wave_st<S>(o + m, tp ? rs_dot(tp + k0 * ntp, ntp, q + ih) : rs_dot(taps + (long)k0 * ntp, ntp, q + ih));
+        }
+        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = q[n16 - ntp + i];
+    }
+    const int rem = lvl + whole - n16;                               // < 256: the next call's lvl
+    for (int i = tid; i < rem; i += RS_THREADS) fo[i] = q[n16 + i];
+}
+
+static bool packet_stage_ok(int n_in, int n_out, int up, int down, int ntp, const float* taps) {
+    if (ntp == 0) return n_in == n_out;
+    return taps && !(reinterpret_cast<uintptr_t>(taps) & 15) && up >= 1 && down >= 1 && (long)n_in * up == (long)n_out * down &&
+           !(ntp & 3) && ntp <= n_in;
+}
+template <typename S>
+int launch_packet_in(const S* in, long in_stride, int n, float* hand, long hand_stride, float* pstate, long ps_stride, int N,
+                     int phi, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s) {
+    if (phi < 0 || phi >= 256 || n16 < 1 || n16 > PK_MAX16 || h != (phi + n16) / 256 || hand_stride < 256L * h ||
+        ps_stride < 2 * PK_FIFO + ntp || !packet_stage_ok(n, n16, up, down, ntp, taps) ||
+        (ntp && ((PK_TILE - 1) * down) / up + ntp + 1 > PK_SPAN))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_in<S>), dim3(N), dim3(RS_THREADS), 0, s, in, in_stride, n, hand, hand_stride, pstate, ps_stride,
+                       phi, n16, h, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stride, int n, float* pstate, long ps_stride,
+                      int hist_off, int N, int lvl, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s) {
+    const int rem = lvl + 256 * h - n16;
+    if (lvl < 0 || lvl >= 256 || n16 < 1 || n16 > PK_MAX16 || h < 0 || rem < 0 || rem >= 256 || hand_stride < 256L * h ||
+        hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST || !packet_stage_ok(n16, n, up, down, ntp, taps))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_out<S>), dim3(N), dim3(RS_THREADS), 0, s, hand, hand_stride, out, out_stride, n, pstate,
+                       ps_stride, hist_off, lvl, n16, h, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_packet_in<float>(const float*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in<short>(const short*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out<float>(const float*, long, float*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out<short>(const float*, long, short*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+
 }  // namespace gtk

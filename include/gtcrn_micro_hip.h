@@ -240,7 +240,7 @@ int gtcrn_resample_pcm16_out(gtcrn_resampler *r, const float *d_in, long in_stri
 /* ---- hop-level streaming at the caller's rate --------------------------------------------------------------------
  * gtcrn_wave_stream_step for a live caller whose audio is not at 16 kHz: fs in {8000, 24000, 32000, 48000} (the rates
  * at which a hop H = 256 fs / 16000 = 128 / 384 / 512 / 768 samples and the stage delay D below are whole numbers;
- * 44.1 kHz and its family are offline only).  nhops hops of H samples in per stream and call, as many out.
+ * 44.1 kHz and its family have no hop form; 44.1 and 22.05 kHz are live through packets, below).  nhops hops of H samples in per stream and call, as many out.
  *
  * Contract.  `in` is a resampler fs -> 16000, `out` one 16000 -> fs on the model's device.  Each is run in its causal
  * form: the centred filter above delayed by D = 32 q / up_in samples at fs (96 / 48 / 64 / 32 samples at 48 / 24 / 32 /
@@ -274,6 +274,77 @@ int gtcrn_rate_stream_step(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler 
 int gtcrn_rate_stream_step_pcm16(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
                                  void *d_rstate, const short *d_in, long in_stride, short *d_out, long out_stride,
                                  int nstreams, int nhops, const float *d_win, void *stream);
+
+/* ---- packet-sized live streaming -----------------------------------------------------------------------------------
+ * gtcrn_wave_stream_step / gtcrn_rate_stream_step for a live caller whose audio arrives in blocks that are not the model's
+ * hop: RTP / WebRTC packets of 10 or 20 ms (160 / 320 samples at 16 kHz, 480 / 960 at 48 kHz), sound-card blocks of 441
+ * samples at 44.1 kHz.  For a GROUP of streams every call takes one packet of n samples per stream at fs and returns n
+ * enhanced samples per stream, at a constant latency.  The re-blocking to 256-sample hops, both FIFOs and the two
+ * resampling stages run on the device (k_packet_in, k_packet_out); the model step in between is gtcrn_wave_stream_step.
+ *
+ * Geometry (host arithmetic).  fs in {8000, 16000, 22050, 24000, 32000, 44100, 48000} (11025: offline only, its stage
+ * delays are not whole samples at 16 kHz).  n16 = n * 16000 / fs must be a whole number in 1..4096, and at fs != 16000 the
+ * packet must hold each stage's filter history (ntp_in <= n, ntp_out <= n16; ntp = the taps of the filter's longest phase
+ * rounded up to a multiple of 4): 10 ms packets pass at every rate but 22050 (220.5 samples), which takes 20 ms (441).
+ * The group has ONE phase phi = (16 kHz samples taken so far) mod 256, kept in the host handle.  A call steps
+ * h = (phi + n16) div 256 hops -- the same for every stream, possibly 0 -- then phi <- (phi + n16) mod 256.  With
+ * g = gcd(n16, 256) the outbound FIFO starts with 256 - g zeros, the smallest pre-fill that never underflows (its level is
+ * 256 - g - phi between calls), so the latency at 16 kHz is L16 = 512 - g samples: 256 at n16 = 256, 480 (30 ms) at 160,
+ * 448 (28 ms) at 320.  At fs != 16000 the two causal stages of the rate form add d_in + d_out 16 kHz samples (32 + 32; 64 + 64
+ * at 8 kHz).  gtcrn_packet_stream_latency16 returns L16 + d_in + d_out IN 16 kHz SAMPLES: at fs that is
+ * latency16 * fs / 16000, a whole number except in the 44.1 kHz family (1499.4 samples for 10 ms packets at 44.1 kHz).
+ * A stream that is reset while the group is at phase z joins with z zeros in front of its input (its FIFOs are zeroed and
+ * the levels are the group's) and runs in lockstep with the others at the same latency.
+ *
+ * Contract, bit for bit.  At 16 kHz: for a stream reset at group phase z whose input since then is x, with
+ * Y = gtcrn_forward_wave(zeros(z) ++ x, win):
+ *     out[k] = 0                    0 <= k < L16 - z
+ *     out[k] = Y[k + z - L16]       L16 - z <= k < samples emitted so far
+ * (n = 256, z = 0: the calls equal gtcrn_wave_stream_step call by call, outputs and both states.)  At another rate,
+ * stage by stage through the public batch calls, with R = gtcrn_resample(fs -> 16000), up / down its ratio,
+ * c = ceil(d_in / up) and x the stream's input since its reset:
+ *     a16 = R(zeros(c * down) ++ x)[c * up - d_in ...]   -- R(x) delayed by d_in samples; a16[k] == R(x)[k - d_in] for
+ *           k >= d_in, and the d_in samples in front are the decimator's pre-ringing, NOT zeros: the stage is the causal
+ *           form of k_rate_in (where d_in * fs / 16000 is whole, a16 = R(zeros(D) ++ x) as in the rate form above)
+ *     b16 = the 16 kHz contract above applied to a16
+ *     out = gtcrn_resample(16000 -> fs)(zeros(d_out) ++ b16), cut to n * calls
+ * At 48 kHz with n = 768, z = 0 the calls equal gtcrn_rate_stream_step (960 = H + 2 D).  There is no flush: a caller
+ * drains a stream with ceil(latency / packet) packets of zeros.
+ *
+ * State.  d_state and d_wstate are those of gtcrn_wave_stream_step; d_pstate holds gtcrn_packet_stream_state_bytes(fs, n)
+ * per stream: two FIFOs of 256 floats (neither ever holds a whole hop between calls) and the two filter histories.
+ * All 16-byte aligned; reset a sub-range of streams by offsetting the three pointers.
+ *
+ * Calls.  gtcrn_packet_stream_create checks (fs, n) and the resamplers (fs -> 16000 and 16000 -> fs on the model's device;
+ * both NULL at 16 kHz), reserves the model workspace for max_streams streams and allocates the hand-off buffers: after it
+ * a step allocates nothing.  The handle keeps the model and the resamplers by pointer; destroy it before them.  A step is
+ * TWO launches plus those of gtcrn_wave_stream_step for h hops; with h == 0 it is the two alone, no model kernel runs.
+ * Asynchronous on `stream`.  Rows: d_in + s * in_stride and d_out + s * out_stride, n samples each.  The _pcm16 form takes
+ * and returns int16 samples and equals the float form between the two PCM conversions.  The launch sequence of a call
+ * depends only on (n16, phi) and the step advances phi on the HOST, so phi returns to its start after 256 / g calls: a
+ * caller who wants a HIP graph captures ONE WHOLE PERIOD of 256 / g steps (each with its own packet buffers) and replays
+ * it; streams then join (gtcrn_packet_stream_reset) between replays.  gtcrn_packet_stream_schedule (host only) returns h
+ * for a phase and the phase after it; _phase and _next_hops read the handle.  A call's cost varies with h (n16 = 160:
+ * 0,1,0,1,1,0,1,1 over a period); a server evens it out with two groups created at different points of their periods.
+ * Null pointers, counts < 1 or above max_streams, short strides and an unsupported (fs, n) or resampler pair return
+ * GTCRN_ERR_ARG before any launch. */
+typedef struct gtcrn_packet_stream gtcrn_packet_stream;
+int gtcrn_packet_stream_n16(int fs, int n);             /* n * 16000 / fs, or GTCRN_ERR_ARG */
+int gtcrn_packet_stream_latency16(int fs, int n);       /* 512 - g + d_in + d_out, in 16 kHz samples */
+size_t gtcrn_packet_stream_state_bytes(int fs, int n);  /* per stream; 0 for an unsupported (fs, n) */
+int gtcrn_packet_stream_schedule(int fs, int n, int phase, int *next_phase);   /* h of a call at `phase` */
+int gtcrn_packet_stream_create(gtcrn_packet_stream **out, gtcrn_model *m, gtcrn_resampler *rs_in, gtcrn_resampler *rs_out,
+                               int fs, int n, int max_streams);
+void gtcrn_packet_stream_destroy(gtcrn_packet_stream *ps);
+int gtcrn_packet_stream_phase(const gtcrn_packet_stream *ps);
+int gtcrn_packet_stream_next_hops(const gtcrn_packet_stream *ps);
+int gtcrn_packet_stream_reset(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, int nstreams,
+                              void *stream);
+int gtcrn_packet_stream_step(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, const float *d_in,
+                             long in_stride, float *d_out, long out_stride, int nstreams, const float *d_win, void *stream);
+int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                   const short *d_in, long in_stride, short *d_out, long out_stride, int nstreams,
+                                   const float *d_win, void *stream);
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
@@ -326,6 +397,10 @@ long gtcrn_debug_tap(gtcrn_model *m, const char *name, int b, float *h_dst, long
  * 256 * nhops) on `stream`: which = 0 what k_rate_in handed to the wave step, 1 what the wave step handed to
  * k_rate_out.  Returns n, or a negative status. */
 long gtcrn_rate_stream_debug_handoff(gtcrn_model *m, int which, float *d_dst, long n, void *stream);
+/* The same for the most recent gtcrn_packet_stream_step: nstreams rows of 256 h floats, h the hops that step ran (n at
+ * most nstreams * 256 * h; GTCRN_ERR_STATE when the step ran no hop): which = 0 what k_packet_in handed to the wave
+ * step, 1 what the wave step handed to k_packet_out. */
+long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream *ps, int which, float *d_dst, long n, void *stream);
 /* Diagnostic build only (libgtcrn_micro_hip_stamps.so, -DGT_STAMPS): per-workgroup sums of shader
  * cycles spent in each barrier-delimited phase of kernel 0 encoder, 1 gtcn1, 2 gtcn2, 3 decoder,
  * (B,16) values.  The product library returns zeros. */

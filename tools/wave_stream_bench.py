@@ -10,6 +10,12 @@ bytes the two wave kernels add per stream-step (from shapes).  Writes profiles/w
 --rate: the step at the caller's rate (gtcrn_rate_stream_step: k_rate_in, the wave step, k_rate_out) at 48 kHz and 8 kHz
 against the 16 kHz wave step of the SAME run, same warm-up, repetitions and medians; writes
 profiles/rate_stream_bench.json.  With --trace-only N: rate steps at --trace-fs (default 48000).
+
+--packet: the packet form (gtcrn_packet_stream_step) at 16 384 and 65 536 streams (or --sizes): 16 kHz / 160 and 320,
+48 kHz / 480, 44.1 kHz / 441.  The timed unit is one whole period of calls, divided by the hops it steps, next to the
+per-hop time of the 16 kHz wave step and the 48 kHz rate step of the SAME run; plus every call of a period on its own
+(the cost follows the hops of the call) and the library's per-kernel event times over one period.  Writes
+profiles/packet_stream_bench.json.  With --trace-only N: packet steps at --trace-fs / --trace-packet.
 """
 import argparse
 import json
@@ -104,6 +110,84 @@ def compare_rate(eng, win, N, iters, reps, rates=(48000, 8000)):
     return r
 
 
+PACKET_CASES = ((16000, 160), (16000, 320), (48000, 480), (44100, 441))
+
+
+def compare_packet(eng, win, N, iters, reps, cases=PACKET_CASES):
+    """The packet form (gtcrn_packet_stream_step) at N streams: for each (fs, packet) one WHOLE PERIOD of calls is the
+    timed unit (its launch sequence repeats from there), divided by the hops it steps; next to it the per-hop time of
+    the 16 kHz wave step and of the 48 kHz rate step, alternating in the same run.  Then, per case: every call of a
+    period timed on its own (the cost follows the hops h of the call) and the library's per-kernel event times."""
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    eng.reserve(N, 1)
+    x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    wst = eng.new_wave_state(N, win)
+    rst = eng.new_rate_state(N, win, 48000)
+    eng.rate_stream_reserve(rst, 1)
+    xr = torch.randn(N, rst.hop, device="cuda", generator=gen) * 0.1
+    yr = torch.empty_like(xr)
+    wave = lambda: eng.wave_stream_step(wst, x, out=y)             # noqa: E731
+    rate = lambda: eng.rate_stream_step(rst, xr, out=yr)           # noqa: E731
+    res = {"N": N, "iters": iters, "cases": []}
+    tw, tr = [], []
+    for fs, n in cases:
+        st = eng.new_packet_state(N, win, n, fs)
+        P = st.period
+        xp = torch.randn(N, n, device="cuda", generator=gen) * 0.1
+        yp = torch.empty_like(xp)
+        hops = []
+
+        def period():
+            for _ in range(P):
+                eng.packet_stream_step(st, xp, out=yp)
+
+        for _ in range(P):
+            hops.append(st.next_hops)
+            eng.packet_stream_step(st, xp, out=yp)
+        nper = max(2, iters // P)
+        for f in (wave, rate):
+            timed(f, max(3, iters // 4))                           # warm-up (every h of the period ran above)
+        timed(period, 2)
+        tp, w, r = [], [], []
+        for _ in range(reps):
+            w.append(timed(wave, iters))
+            r.append(timed(rate, iters))
+            tp.append(timed(period, nper))
+        tw += w
+        tr += r
+        # every call of a period on its own
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(P + 1)] for _ in range(nper)]
+        for k in range(nper):
+            ev[k][0].record()
+            for p in range(P):
+                eng.packet_stream_step(st, xp, out=yp)
+                ev[k][p + 1].record()
+        torch.cuda.synchronize()
+        per_call = [statistics.median(ev[k][p].elapsed_time(ev[k][p + 1]) for k in range(nper)) for p in range(P)]
+        eng.timing_enable(True)
+        period()
+        torch.cuda.synchronize()
+        kern = {k: {"avg_ms": v[0], "launches": v[1]} for k, v in eng.timing_read().items()}
+        eng.timing_enable(False)
+        ms_period = statistics.median(tp)
+        c = {"fs": fs, "packet": n, "n16": st.n16, "period_calls": P, "hops_per_period": sum(hops), "hops_by_call": hops,
+             "latency16": st.latency16, "period_ms": ms_period, "per_hop_ms": ms_period / sum(hops),
+             "per_call_ms": ms_period / P, "period_reps_ms": tp, "wave_per_hop_ms": statistics.median(w),
+             "rate48k_per_hop_ms": statistics.median(r), "call_ms_by_position": per_call, "kernels_one_period": kern,
+             "packet_kernel_bytes_per_stream_call": 8 * (st.n16 + 256 * sum(hops) / P)}
+        c["per_hop_vs_wave"] = c["per_hop_ms"] / c["wave_per_hop_ms"]
+        c["per_hop_vs_rate48k"] = c["per_hop_ms"] / c["rate48k_per_hop_ms"]
+        res["cases"].append(c)
+        del st
+        torch.cuda.empty_cache()
+    res["wave_step_16k_ms"] = statistics.median(tw)
+    res["rate_step_48000_ms"] = statistics.median(tr)
+    del wst, rst
+    torch.cuda.empty_cache()
+    return res
+
+
 def latency_n1(eng, win, iters):
     eng.reserve(1, 1)
     x = torch.randn(1, 256, device="cuda") * 0.1
@@ -144,6 +228,9 @@ def main():
     ap.add_argument("--trace-only", type=int, default=0)
     ap.add_argument("--rate", action="store_true", help="the rate step at 48 / 8 kHz against the 16 kHz wave step")
     ap.add_argument("--trace-fs", type=int, default=48000)
+    ap.add_argument("--packet", action="store_true",
+                    help="the packet form at 16 kHz / 160, 320, 48 kHz / 480 and 44.1 kHz / 441 against the wave and rate steps")
+    ap.add_argument("--trace-packet", type=int, default=480, help="--packet --trace-only: the packet, in samples at --trace-fs")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wave_stream_bench needs the GPU (nothing is measured on the CPU)")
@@ -151,6 +238,29 @@ def main():
     params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
     eng = Engine(params, 0)
     win = torch.hann_window(512).pow(0.5).cuda()
+    if a.packet:
+        sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
+        if a.trace_only:
+            st = eng.new_packet_state(a.trace_only, win, a.trace_packet, a.trace_fs)
+            x = torch.randn(a.trace_only, a.trace_packet, device="cuda") * 0.1
+            y = torch.empty_like(x)
+            for _ in range(a.iters * st.period):
+                eng.packet_stream_step(st, x, out=y)
+            torch.cuda.synchronize()
+            return
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "packet_stream_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in sizes:
+            r = compare_packet(eng, win, N, a.iters, a.reps)
+            for c in r["cases"]:
+                print(json.dumps({"N": N, **{k: v for k, v in c.items() if "reps" not in k and k != "kernels_one_period"}}),
+                      flush=True)
+            res["compare"].append(r)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
     if a.trace_only and a.rate:
         N = a.trace_only
         st = eng.new_rate_state(N, win, a.trace_fs)
