@@ -115,6 +115,15 @@ def lib():
         getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, _vp, _vp]
     L.gtcrn_packet_stream_debug_handoff.restype = cl
     L.gtcrn_packet_stream_debug_handoff.argtypes = [_vp, ci, _vp, cl, _vp]
+    # the attenuation-limited forms: the plain argument lists with d_gain in front of d_win
+    L.gtcrn_forward_wave_limited.argtypes = [_vp, _vp, _vp, ci, cl, _vp, _vp, _vp, _vp]
+    for fn in ("gtcrn_wave_stream_step_limited", "gtcrn_wave_stream_step_limited_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp]
+    for fn in ("gtcrn_wave_stream_flush_limited", "gtcrn_wave_stream_flush_limited_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, cl, ci, _vp, cl, ci, _vp, _vp, _vp]
+    for fn in ("gtcrn_rate_stream_step_limited", "gtcrn_rate_stream_step_limited_pcm16"):
+        getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp]
+    L.gtcrn_packet_stream_set_dry_gain.argtypes = [_vp, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -206,6 +215,29 @@ def pack_params_host(params, quant=False):
 def round_to_half(x):
     """float -> IEEE binary16 (round to nearest even) -> float, the host twin of the kernels' v_cvt_f16_f32."""
     return float(lib().gtcrn_round_to_half(float(x)))
+
+
+def atten_lim_to_gain(db):
+    """Attenuation limit in dB -> the dry gain beta = 10^(-db / 20) of the limited calls (include/gtcrn_micro_hip.h,
+    "attenuation limit"): None or inf = no limit = 0.0; 0 dB = bypass = 1.0; negative or NaN raises ValueError."""
+    if db is None:
+        return 0.0
+    db = float(db)
+    if db != db or db < 0.0:
+        raise ValueError(f"the attenuation limit must be >= 0 dB (None or inf: no limit), got {db!r}")
+    if db == float("inf"):
+        return 0.0
+    return float(10.0 ** (-db / 20.0))
+
+
+def _gains_of(db, n):
+    """db: None, a number, or a sequence of n of them -> a float (one gain for all) or a float32 array of n gains."""
+    if db is None or np.isscalar(db):
+        return atten_lim_to_gain(db)
+    seq = list(db)
+    if len(seq) != n:
+        raise GtcrnError(f"expected one attenuation limit or {n} of them, got {len(seq)}")
+    return np.asarray([atten_lim_to_gain(v) for v in seq], np.float32)
 
 
 def _stream_ptr(stream=None):
@@ -389,7 +421,30 @@ class Engine:
             raise GtcrnError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)}, got "
                              f"{tuple(t.shape)} (contiguous: {t.is_contiguous()})")
 
-    def forward_wave(self, wave, window, out=None):
+    def _dry_gain(self, dry_gain, B, device):
+        """None, a float in [0, 1] or a (B,) float32 CUDA tensor of them -> None or the (B,) device tensor.  The kernels
+        take 0 <= beta <= 1 as a precondition; it is checked here (a tensor's check reads it back: one synchronisation)."""
+        import torch
+        if dry_gain is None:
+            return None
+        if isinstance(dry_gain, torch.Tensor):
+            g = dry_gain
+            if not g.is_cuda or g.dtype != torch.float32 or g.device != device or tuple(g.shape) != (B,) or not g.is_contiguous():
+                raise GtcrnError(f"dry_gain must be a float or a contiguous ({B},) float32 tensor on {device}, got "
+                                 f"{tuple(g.shape)} {g.dtype} on {g.device}")
+            lo, hi = (float(v) for v in torch.aminmax(g))
+            if not (0.0 <= lo and hi <= 1.0):
+                raise GtcrnError(f"every dry gain must lie in [0, 1], got min {lo} max {hi}")
+            return g
+        v = float(dry_gain)
+        if not 0.0 <= v <= 1.0:
+            raise GtcrnError(f"the dry gain must lie in [0, 1], got {v!r}")
+        return torch.full((B,), v, device=device, dtype=torch.float32)
+
+    def forward_wave(self, wave, window, out=None, dry_gain=None):
+        """dry_gain (None, a float or a (B,) CUDA float tensor, each in [0, 1]): the attenuation limit, beta =
+        atten_lim_to_gain(dB); row b becomes fl(fl(beta_b x) + fl(fl(1 - beta_b) y)), x the input cut to the output's
+        length (gtcrn_forward_wave_limited).  None: the plain call."""
         import torch
         self._check_on_device(wave, "wave")
         w2 = (wave.reshape(1, -1) if wave.dim() == 1 else wave).contiguous()
@@ -402,9 +457,14 @@ class Engine:
             out = torch.empty((B, 256 * (T - 1)), device=wave.device, dtype=torch.float32)
         else:
             self._check_on_device(out, "out", (B, 256 * (T - 1)))
+        gain = self._dry_gain(dry_gain, B, w2.device)
         with self._dev():
-            _check(lib().gtcrn_forward_wave(self._h, w2.data_ptr(), out.data_ptr(), B, L, win.data_ptr(),
-                                            _stream_ptr()))
+            if gain is None:
+                _check(lib().gtcrn_forward_wave(self._h, w2.data_ptr(), out.data_ptr(), B, L, win.data_ptr(),
+                                                _stream_ptr()))
+            else:
+                _check(lib().gtcrn_forward_wave_limited(self._h, w2.data_ptr(), out.data_ptr(), B, L, None, gain.data_ptr(),
+                                                        win.data_ptr(), _stream_ptr()))
         return out[0] if wave.dim() == 1 else out
 
     # ---- int8-weight / fp16-activation variant (BASELINE configs[4]; contract in include/gtcrn_micro_hip.h) ------
@@ -447,11 +507,11 @@ class Engine:
                                                   float(in_scale), float(out_scale), _stream_ptr()))
         return out[0] if wave.dim() == 1 else out
 
-    def forward_wave_var(self, wave, lengths, window, out=None):
+    def forward_wave_var(self, wave, lengths, window, out=None, dry_gain=None):
         """Clips of different lengths through ONE launch sequence: ``wave`` (B,Lmax) holds clip b in its first
         ``lengths[b]`` samples (257 <= lengths[b] <= Lmax).  Returns (B, 256*(Lmax//256)); row b carries its
         256*(lengths[b]//256) enhanced samples (bit-identical to forward_wave on that clip alone), the rest of the
-        row is unspecified."""
+        row is unspecified (not written).  dry_gain: as in forward_wave, one gain per clip."""
         import torch
         self._check_on_device(wave, "wave")
         if wave.dim() != 2 or not wave.is_contiguous():
@@ -470,9 +530,14 @@ class Engine:
             out = torch.empty((B, 256 * (T - 1)), device=wave.device, dtype=torch.float32)
         else:
             self._check_on_device(out, "out", (B, 256 * (T - 1)))
+        gain = self._dry_gain(dry_gain, B, wave.device)
         with self._dev():
-            _check(lib().gtcrn_forward_wave_var(self._h, wave.data_ptr(), out.data_ptr(), B, L, lens.data_ptr(),
-                                                win.data_ptr(), _stream_ptr()))
+            if gain is None:
+                _check(lib().gtcrn_forward_wave_var(self._h, wave.data_ptr(), out.data_ptr(), B, L, lens.data_ptr(),
+                                                    win.data_ptr(), _stream_ptr()))
+            else:
+                _check(lib().gtcrn_forward_wave_limited(self._h, wave.data_ptr(), out.data_ptr(), B, L, lens.data_ptr(),
+                                                        gain.data_ptr(), win.data_ptr(), _stream_ptr()))
         return out
 
     # ---- streaming -----------------------------------------------------------------------
@@ -514,10 +579,12 @@ class Engine:
     def wave_state_bytes():
         return int(lib().gtcrn_wave_stream_state_bytes())
 
-    def new_wave_state(self, nstreams, window):
+    def new_wave_state(self, nstreams, window, atten_lim_db=None):
         """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
         counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
-        one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it)."""
+        one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it).  atten_lim_db (a
+        number or one per stream; None: off): the attenuation limit, kept as the per-stream gains ``state.dry_gain``
+        that every step and flush of the state then applies (WaveStreamState.set_atten_lim_db rewrites them)."""
         import torch
         n = int(nstreams)
         if n < 1:
@@ -532,6 +599,8 @@ class Engine:
         st = WaveStreamState(self.new_state(n),
                              torch.empty((n, self.wave_state_bytes() // 4), device=win.device, dtype=torch.float32), win)
         self.wave_stream_reset(st)
+        if atten_lim_db is not None:
+            st.set_atten_lim_db(atten_lim_db)
         return st
 
     def wave_stream_reset(self, state, lo=0, hi=None):
@@ -578,10 +647,16 @@ class Engine:
         if L < 256 or L % 256:
             raise GtcrnError(f"x must hold a whole number of 256-sample hops per stream, got {L}")
         out = self._wave_out(out, x, L)
-        fn = lib().gtcrn_wave_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step
+        pcm = x.dtype == torch.int16
+        args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
+                out.stride(0), state.n, L // 256)
         with self._dev():
-            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
-                      out.stride(0), state.n, L // 256, state.window.data_ptr(), _stream_ptr()))
+            if state.dry_gain is None:
+                fn = lib().gtcrn_wave_stream_step_pcm16 if pcm else lib().gtcrn_wave_stream_step
+                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
+            else:
+                fn = lib().gtcrn_wave_stream_step_limited_pcm16 if pcm else lib().gtcrn_wave_stream_step_limited
+                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
         return out
 
     def wave_stream_flush(self, state, tail, out=None):
@@ -593,11 +668,16 @@ class Engine:
         if r > 255:
             raise GtcrnError(f"the tail holds 0..255 samples, got {r}: push whole hops with wave_stream_step first")
         out = self._wave_out(out, tail, 256)
-        fn = lib().gtcrn_wave_stream_flush_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush
+        pcm = tail.dtype == torch.int16
+        args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
+                tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n)
         with self._dev():
-            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
-                      tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n, state.window.data_ptr(),
-                      _stream_ptr()))
+            if state.dry_gain is None:
+                fn = lib().gtcrn_wave_stream_flush_pcm16 if pcm else lib().gtcrn_wave_stream_flush
+                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
+            else:
+                fn = lib().gtcrn_wave_stream_flush_limited_pcm16 if pcm else lib().gtcrn_wave_stream_flush_limited
+                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
         return out
 
     # ---- other sample rates (contract: include/gtcrn_micro_hip.h, gtcrn_resample / gtcrn_rate_stream_*) -------------
@@ -609,19 +689,20 @@ class Engine:
             cache[key] = Resampler(key[0], key[1], self.device)
         return cache[key]
 
-    def forward_wave_rate(self, wave, fs, window, out_fs=None):
+    def forward_wave_rate(self, wave, fs, window, out_fs=None, dry_gain=None):
         """wave (B,L) or (L,) at `fs` Hz -> the enhanced waveform at 16 kHz (out_fs None or 16000) or at `out_fs`: exactly
-        resampler(fs, 16000)(wave) -> forward_wave -> resampler(16000, out_fs), the three public calls composed."""
+        resampler(fs, 16000)(wave) -> forward_wave -> resampler(16000, out_fs), the three public calls composed.
+        dry_gain goes to forward_wave: the attenuation limit is mixed at 16 kHz."""
         fs = int(fs)
         x = wave if fs == 16000 else self.resampler(fs, 16000)(wave)
-        y = self.forward_wave(x, window)
+        y = self.forward_wave(x, window, dry_gain=dry_gain)
         if out_fs is None or int(out_fs) == 16000:
             return y
         return self.resampler(16000, int(out_fs))(y)
 
-    def new_rate_state(self, nstreams, window, fs):
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
-        resamplers and their per-stream histories."""
+        resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz)."""
         import torch
         fs = int(fs)
         hop = _check(lib().gtcrn_rate_stream_hop(fs))
@@ -629,6 +710,8 @@ class Engine:
         st = RateStreamState(ws.model, ws.wave, ws.window, fs, hop, self.resampler(fs, 16000), self.resampler(16000, fs),
                              torch.empty((ws.n, rate_stream_state_bytes(fs) // 4), device=ws.wave.device, dtype=torch.float32))
         self.rate_stream_reset(st)
+        if atten_lim_db is not None:
+            st.set_atten_lim_db(atten_lim_db)
         return st
 
     def rate_stream_reserve(self, state, nhops):
@@ -660,11 +743,16 @@ class Engine:
         if L < state.hop or L % state.hop:
             raise GtcrnError(f"x must hold a whole number of {state.hop}-sample hops per stream, got {L}")
         out = self._wave_out(out, x, L)
-        fn = lib().gtcrn_rate_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_rate_stream_step
+        pcm = x.dtype == torch.int16
+        args = (self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
+                state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
         with self._dev():
-            _check(fn(self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
-                      state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n,
-                      L // state.hop, state.window.data_ptr(), _stream_ptr()))
+            if state.dry_gain is None:
+                fn = lib().gtcrn_rate_stream_step_pcm16 if pcm else lib().gtcrn_rate_stream_step
+                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
+            else:
+                fn = lib().gtcrn_rate_stream_step_limited_pcm16 if pcm else lib().gtcrn_rate_stream_step_limited
+                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
         return out
 
     def rate_stream_handoff(self, state, nhops, which=0):
@@ -677,11 +765,12 @@ class Engine:
         return out
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
-    def new_packet_state(self, nstreams, window, packet, fs=16000):
+    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
-        needs is reserved here."""
+        needs is reserved here.  atten_lim_db: as in new_wave_state; the handle keeps the gains' address
+        (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains."""
         import torch
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
@@ -696,6 +785,8 @@ class Engine:
         st = PacketStreamState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
                                torch.empty((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32))
         self.packet_stream_reset(st)
+        if atten_lim_db is not None:
+            st.set_atten_lim_db(atten_lim_db)
         return st
 
     def packet_stream_reset(self, state, lo=0, hi=None):
@@ -839,10 +930,39 @@ class WaveStreamState:
         self.model = model
         self.wave = wave
         self.window = window
+        self.dry_gain = None        # (N,) float32 on the device: the attenuation limit's dry gains; None: limit off
 
     @property
     def n(self):
         return self.model.shape[0]
+
+    def set_dry_gain(self, gain):
+        """Installs `gain`, a contiguous (N,) float32 tensor on the state's device holding every stream's dry gain in
+        [0, 1] (the caller's precondition: it is not read back), or None: the limit off, the plain kernels again.  The
+        steps read the tensor on the device at every call, so it may be rewritten in place at any time."""
+        import torch
+        if gain is not None and (not isinstance(gain, torch.Tensor) or gain.dtype != torch.float32 or gain.device != self.model.device
+                                 or tuple(gain.shape) != (self.n,) or not gain.is_contiguous()):
+            raise GtcrnError(f"the dry gains must be a contiguous ({self.n},) float32 tensor on {self.model.device}")
+        self.dry_gain = gain
+
+    def set_atten_lim_db(self, db, lo=0, hi=None):
+        """Sets the attenuation limit of streams lo..hi-1 to `db` dB (None or inf: no limit, 0: bypass; a sequence gives
+        one limit per stream of the range): rewrites state.dry_gain[lo:hi] on the device, asynchronously on the current
+        stream and, for one value, without any allocation; takes effect at the next emitted block, also under the replay of
+        a captured graph.  A state created without a limit gets its gains (zeros: no limit) at the first call here."""
+        import torch
+        hi = self.n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        g = _gains_of(db, hi - lo)
+        if self.dry_gain is None:
+            self.set_dry_gain(torch.zeros((self.n,), device=self.model.device, dtype=torch.float32))
+        if isinstance(g, float):
+            self.dry_gain[lo:hi].fill_(g)
+        else:
+            self.dry_gain[lo:hi].copy_(torch.from_numpy(g), non_blocking=True)
 
 
 class RateStreamState(WaveStreamState):
@@ -877,6 +997,10 @@ class PacketStreamState(WaveStreamState):
         self.rs_out = rs_out
         self.pkt = pkt
         self.last_hops = 0
+
+    def set_dry_gain(self, gain):
+        super().set_dry_gain(gain)
+        _check(lib().gtcrn_packet_stream_set_dry_gain(self._h, None if gain is None else gain.data_ptr()))
 
     @property
     def phase(self):

@@ -47,11 +47,11 @@ struct Timing {
 };
 // every timed launch records WHICH kernel it was (mixed offline / streaming calls keep their own rows)
 enum KernelId { K_STFT, K_ENCODER, K_GTCN1, K_GTCN2, K_DECODER, K_ISTFT, K_FRONT, K_ENCODER_GT, K_GTCN_MS, K_STREAM_MS, K_STREAM_WIDE,
-                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_PACKET_IN, K_PACKET_OUT, K_COUNT };
+                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_PACKET_IN, K_PACKET_OUT, K_WAVE_SYNTHESIS_MIX, K_ISTFT_MIX, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_stft",  "k_encoder",    "k_gtcn1",   "k_gtcn2",    "k_decoder",
                                            "k_istft", "k_front",      "k_encoder_gt", "k_gtcn_ms", "k_stream_ms",
                                            "k_stream_wide", "k_wave_analysis", "k_wave_synthesis", "k_packet_in",
-                                           "k_packet_out"};
+                                           "k_packet_out", "k_wave_synthesis_mix", "k_istft_mix"};
 constexpr int kNumKernels = K_COUNT;
 
 }  // namespace
@@ -504,9 +504,10 @@ int gtcrn_forward_spec(gtcrn_model* m, const float* d_spec_in, long isb, long is
     return run_model(m, d_spec_in, isb, isf, ist, d_spec_out, osb, osf, ost, B, T, nullptr, s);
 }
 
+// d_gain (optional): the attenuation limit, mixed by the iSTFT launch (k_istft_mix)
 static int forward_wave_impl(gtcrn_model* m, const float* d_wave, float* d_wave_out, int B, long L,
                              const int* d_lengths, const float* d_win, void* stream,
-                             const gtk::Quant* q = nullptr) {
+                             const gtk::Quant* q = nullptr, const float* d_gain = nullptr) {
     int rc = check_model(m);
     if (rc) return rc;
     if (!d_wave || !d_wave_out || !d_win) return fail(GTCRN_ERR_ARG, "null pointer");
@@ -525,8 +526,8 @@ static int forward_wave_impl(gtcrn_model* m, const float* d_wave, float* d_wave_
     tm.end();
     rc = run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, B, T, nullptr, s, d_lengths, q, true);
     if (rc) return rc;
-    tm.begin(K_ISTFT);
-    LAUNCH_TRY(gtk::launch_istft(m->d_spec_b, sb, sf, st, B, T, d_lengths, d_win, m->d_twid, d_wave_out, s));
+    tm.begin(d_gain ? K_ISTFT_MIX : K_ISTFT);
+    LAUNCH_TRY(gtk::launch_istft(m->d_spec_b, sb, sf, st, B, T, d_lengths, d_win, m->d_twid, d_wave_out, s, d_wave, L, d_gain));
     tm.end();
     return 0;
 }
@@ -540,6 +541,11 @@ int gtcrn_forward_wave_var(gtcrn_model* m, const float* d_wave, float* d_wave_ou
                            const int* d_lengths, const float* d_win, void* stream) {
     if (!d_lengths) return fail(GTCRN_ERR_ARG, "gtcrn_forward_wave_var: null lengths");
     return forward_wave_impl(m, d_wave, d_wave_out, B, Lmax, d_lengths, d_win, stream);
+}
+
+int gtcrn_forward_wave_limited(gtcrn_model* m, const float* d_wave, float* d_wave_out, int B, long Lmax, const int* d_lengths,
+                               const float* d_gain, const float* d_win, void* stream) {
+    return forward_wave_impl(m, d_wave, d_wave_out, B, Lmax, d_lengths, d_win, stream, nullptr, d_gain);
 }
 
 static int quant_opts(float in_scale, float out_scale, gtk::Quant* q) {
@@ -614,7 +620,7 @@ int gtcrn_wave_stream_reset(gtcrn_model* m, void* d_state, void* d_wstate, int n
 extern "C++" template <typename S>
 static int wave_stream_impl(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const S* d_in, long in_stride,
                             S* d_out, long out_stride, int nstreams, int nhops, bool flush, int r, const float* d_win,
-                            void* stream) {
+                            void* stream, const float* d_gain = nullptr) {
     const std::string w(who);
     if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
     if (!d_state || !d_wstate || !d_out || !d_win || (!d_in && !(flush && r == 0)))
@@ -638,9 +644,9 @@ static int wave_stream_impl(const char* who, gtcrn_model* m, void* d_state, void
     tm.end();
     rc = run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, nstreams, nhops, static_cast<float*>(d_state), s);
     if (rc) return rc;
-    tm.begin(K_WAVE_SYNTHESIS);
+    tm.begin(d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
     LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, nstreams, nhops, r, flush, ws,
-                                             d_win, m->d_twid, s));
+                                             d_win, m->d_twid, s, d_gain));
     tm.end();
     return 0;
 }
@@ -664,6 +670,32 @@ int gtcrn_wave_stream_flush_pcm16(gtcrn_model* m, void* d_state, void* d_wstate,
                                   short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
     return wave_stream_impl<short>("gtcrn_wave_stream_flush_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
                                    out_stride, nstreams, 1, true, r, d_win, stream);
+}
+
+// the attenuation-limited forms: d_gain holds one dry gain per stream (NULL: the plain call)
+int gtcrn_wave_stream_step_limited(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_in, long in_stride,
+                                   float* d_out, long out_stride, int nstreams, int nhops, const float* d_gain,
+                                   const float* d_win, void* stream) {
+    return wave_stream_impl<float>("gtcrn_wave_stream_step_limited", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                                   nstreams, nhops, false, 0, d_win, stream, d_gain);
+}
+int gtcrn_wave_stream_step_limited_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_in, long in_stride,
+                                         short* d_out, long out_stride, int nstreams, int nhops, const float* d_gain,
+                                         const float* d_win, void* stream) {
+    return wave_stream_impl<short>("gtcrn_wave_stream_step_limited_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out,
+                                   out_stride, nstreams, nhops, false, 0, d_win, stream, d_gain);
+}
+int gtcrn_wave_stream_flush_limited(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_tail, long tail_stride,
+                                    int r, float* d_out, long out_stride, int nstreams, const float* d_gain,
+                                    const float* d_win, void* stream) {
+    return wave_stream_impl<float>("gtcrn_wave_stream_flush_limited", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                                   out_stride, nstreams, 1, true, r, d_win, stream, d_gain);
+}
+int gtcrn_wave_stream_flush_limited_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_tail, long tail_stride,
+                                          int r, short* d_out, long out_stride, int nstreams, const float* d_gain,
+                                          const float* d_win, void* stream) {
+    return wave_stream_impl<short>("gtcrn_wave_stream_flush_limited_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                                   out_stride, nstreams, 1, true, r, d_win, stream, d_gain);
 }
 
 // ---- sample-rate conversion ------------------------------------------------------------------------------------------
@@ -905,7 +937,7 @@ int gtcrn_rate_stream_reset(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler
 extern "C++" template <typename S>
 static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state,
                             void* d_wstate, void* d_rstate, const S* d_in, long in_stride, S* d_out, long out_stride,
-                            int nstreams, int nhops, const float* d_win, void* stream) {
+                            int nstreams, int nhops, const float* d_win, void* stream, const float* d_gain = nullptr) {
     const std::string w(who);
     if (int rc = rate_pair_check(w, m, in, out)) return rc;
     if (!d_state || !d_wstate || !d_rstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
@@ -924,7 +956,8 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
     const long rs_stride = di.ntp + dout.ntp, row = 256L * nhops;
     LAUNCH_TRY(gtk::launch_rate_in<S>(d_in, in_stride, m->d_rate_a, row, rs, rs_stride, nstreams, nhops, H, di.up, di.down,
                                       di.ntp, in->d_taps, s));
-    rc = gtcrn_wave_stream_step(m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams, nhops, d_win, stream);
+    rc = wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams,
+                                 nhops, false, 0, d_win, stream, d_gain);      // (the limit is mixed at 16 kHz)
     if (rc) return rc;
     LAUNCH_TRY(gtk::launch_rate_out<S>(m->d_rate_b, row, d_out, out_stride, rs + di.ntp, rs_stride, nstreams, nhops, H, dout.up,
                                        dout.down, dout.ntp, out->d_taps, s));
@@ -941,6 +974,20 @@ int gtcrn_rate_stream_step_pcm16(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resa
                                  int nstreams, int nhops, const float* d_win, void* stream) {
     return rate_stream_impl<short>("gtcrn_rate_stream_step_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride,
                                    d_out, out_stride, nstreams, nhops, d_win, stream);
+}
+
+int gtcrn_rate_stream_step_limited(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                                   void* d_rstate, const float* d_in, long in_stride, float* d_out, long out_stride,
+                                   int nstreams, int nhops, const float* d_gain, const float* d_win, void* stream) {
+    return rate_stream_impl<float>("gtcrn_rate_stream_step_limited", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride,
+                                   d_out, out_stride, nstreams, nhops, d_win, stream, d_gain);
+}
+int gtcrn_rate_stream_step_limited_pcm16(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state,
+                                         void* d_wstate, void* d_rstate, const short* d_in, long in_stride, short* d_out,
+                                         long out_stride, int nstreams, int nhops, const float* d_gain, const float* d_win,
+                                         void* stream) {
+    return rate_stream_impl<short>("gtcrn_rate_stream_step_limited_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in,
+                                   in_stride, d_out, out_stride, nstreams, nhops, d_win, stream, d_gain);
 }
 
 // ---- packet-sized live streaming: k_packet_in -> the wave step for h hops (nothing when h == 0) -> k_packet_out.
@@ -993,6 +1040,7 @@ struct gtcrn_packet_stream {
     float* d_a = nullptr;       // hand-offs, max_streams rows of 256 hmax floats: k_packet_in -> wave step,
     float* d_b = nullptr;       // wave step -> k_packet_out
     int last_h = 0, last_n = 0; // hops and streams of the most recent step (gtcrn_packet_stream_debug_handoff)
+    const float* d_gain = nullptr;   // the caller's dry gains, max_streams floats (gtcrn_packet_stream_set_dry_gain); NULL: no limit
 };
 
 int gtcrn_packet_stream_n16(int fs, int n) {
@@ -1071,6 +1119,12 @@ int gtcrn_packet_stream_next_hops(const gtcrn_packet_stream* ps) {
     return (ps->phase + ps->p.n16) / 256;
 }
 
+int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream* ps, const float* d_gain) {
+    if (!ps) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_set_dry_gain: null handle");
+    ps->d_gain = d_gain;
+    return 0;
+}
+
 int gtcrn_packet_stream_reset(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int nstreams, void* stream) {
     if (!ps) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_reset: null handle");
     if (!d_pstate) return fail(GTCRN_ERR_ARG, "gtcrn_packet_stream_reset: null state or nstreams < 1");
@@ -1109,7 +1163,8 @@ static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_
                                         p.in.down, p.in.ntp, ps->in ? ps->in->d_taps : nullptr, s));
     tm.end();
     if (h) {
-        rc = gtcrn_wave_stream_step(m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h, d_win, stream);
+        rc = wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h,
+                                     false, 0, d_win, stream, ps->d_gain);
         if (rc) return rc;
     }
     tm.begin(K_PACKET_OUT);

@@ -57,18 +57,23 @@ int launch_stft(const float* wave, int B, long L, int T, const int* lens, const 
                 float* spec, long sb, long sf, long st, float* frames, hipStream_t s);
 // 16-bit PCM <-> float32 at the host boundary (n samples, a multiple of 8; dir 0: int16 / 32768, 1: clip(rint(y * 32768)))
 int launch_pcm16_convert(const void* src, void* dst, long n, int dir, hipStream_t s);
+// gain (optional, device, float[B]): the attenuation limit -- sample n of row b becomes the mix of dry[b * dry_stride + n]
+// and the iSTFT's sample with dry gain gain[b] (k_istft_mix); nullptr: the plain kernel
 int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, const int* lens, const float* win,
-                 const float* twid, float* wave, hipStream_t s);
+                 const float* twid, float* wave, hipStream_t s, const float* dry = nullptr, long dry_stride = 0,
+                 const float* gain = nullptr);
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
-// wstate (not on flush).  flush = the end-reflected last frame.
+// wstate (not on flush).  flush = the end-reflected last frame.  gain (optional, device, float[N]): the attenuation limit,
+// mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
                          const float* win, const float* twid, float* spec, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s);
+                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s,
+                          const float* gain = nullptr);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;

@@ -528,14 +528,26 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_stft(const float* __restrict
     }
 }
 
+// Attenuation limit (include/gtcrn_micro_hip.h, "attenuation limit"): dry gain g, dry sample x, wet sample w ->
+// fl(fl(g x) + fl(fl(1 - g) w)).  Four fp32 roundings, each in a call of its own: -ffp-contract=on fuses inside one source
+// expression only, so no fma is formed and numpy float32 reproduces the value bit for bit.  g = 0 gives w, g = 1 gives x.
+__device__ __forceinline__ float wave_mix(float g, float x, float w) {
+    return __fadd_rn(__fmul_rn(g, x), __fmul_rn(__fsub_rn(1.0f, g), w));
+}
+
 // torch.istft(view_as_complex(y),512,256,512,win) (infer.py:73-76): irfft (1/512), * win,
 // overlap-add, / sum(win^2), trim 256 samples at both ends -> 256*(T-1) samples.  The 512-point
 // c2r runs as a 256-point complex inverse FFT of the merged spectrum (scale 1/256).
 // One workgroup produces ISTFT_BLOCKS hop blocks of one utterance from ISTFT_BLOCKS+1 frames.
-__global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restrict__ spec, long sb, long sf, long st,
-                                                         int B, int T, const int* __restrict__ lens,
-                                                         const float* __restrict__ win,
-                                                         const float2* __restrict__ twid, float* __restrict__ wave) {
+// The body of k_istft and of its sibling k_istft_mix (MIX: the attenuation limit of the offline calls -- the stored sample
+// becomes wave_mix(gain[b], dry[b][n], sample), dry = the call's input wave in rows of dry_stride samples, sample n of the
+// output aligned with sample n of the input; a thread's dry samples, one per hop block, are fetched with the first frame,
+// ahead of the transforms).
+template <bool MIX>
+__device__ __forceinline__ void istft_body(const float* __restrict__ spec, long sb, long sf, long st, int B, int T,
+                                           const int* __restrict__ lens, const float* __restrict__ win,
+                                           const float2* __restrict__ twid, float* __restrict__ wave,
+                                           const float* __restrict__ dry, long dry_stride, const float* __restrict__ gain) {
     __shared__ float2 s_tw[256];
     __shared__ float2 s_tw512[256];
     __shared__ float s_win[512];
@@ -571,6 +583,13 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restric
     };
     float2 ck[4], cm[4], nk[4], nm[4];
     fetch(0, ck, cm);
+    static_assert(FFT_WAVES * 64 == 256, "the overlap-add below: one hop block per pass, thread = sample");
+    float dv[ISTFT_BLOCKS];
+    if constexpr (MIX) {
+        const float* x = dry + (long)b * dry_stride + (long)j0 * 256 + tid;
+#pragma unroll
+        for (int jb = 0; jb < ISTFT_BLOCKS; ++jb) dv[jb] = jb < nfr - 1 ? x[jb * 256] : 0.f;
+    }
     for (int it = 0; it < ROUNDS; ++it) {
         const int fi = it * FFT_WAVES + wv;
         const bool live = fi < nfr;
@@ -610,12 +629,37 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restric
     __syncthreads();   // the windowed frames of all four waves are overlap-added below
     // overlap-add: output block j = frame j second half + frame j+1 first half
     float* o = wave + (long)b * 256 * (T - 1);                // rows of 256 (T - 1) samples
+    if constexpr (MIX) {
+        const float g = gain[b];
+        const float env = s_win[256 + tid] * s_win[256 + tid] + s_win[tid] * s_win[tid];
+#pragma unroll
+        for (int jb = 0; jb < ISTFT_BLOCKS; ++jb) {
+            if (jb >= nfr - 1) break;
+            const float acc = s_fr[jb][256 + tid] + s_fr[jb + 1][tid];
+            o[(long)(j0 + jb) * 256 + tid] = wave_mix(g, dv[jb], env > 1e-11f ? acc / env : acc);
+        }
+        return;
+    }
     for (int idx = tid; idx < (nfr - 1) * 256; idx += FFT_WAVES * 64) {
         const int jb = idx >> 8, i = idx & 255;
         const float acc = s_fr[jb][256 + i] + s_fr[jb + 1][i];
         const float env = s_win[256 + i] * s_win[256 + i] + s_win[i] * s_win[i];
         o[(long)(j0 + jb) * 256 + i] = env > 1e-11f ? acc / env : acc;
     }
+}
+__global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restrict__ spec, long sb, long sf, long st,
+                                                         int B, int T, const int* __restrict__ lens,
+                                                         const float* __restrict__ win,
+                                                         const float2* __restrict__ twid, float* __restrict__ wave) {
+    istft_body<false>(spec, sb, sf, st, B, T, lens, win, twid, wave, nullptr, 0, nullptr);
+}
+__global__ __launch_bounds__(FFT_WAVES * 64) void k_istft_mix(const float* __restrict__ spec, long sb, long sf, long st,
+                                                             int B, int T, const int* __restrict__ lens,
+                                                             const float* __restrict__ win,
+                                                             const float2* __restrict__ twid, float* __restrict__ wave,
+                                                             const float* __restrict__ dry, long dry_stride,
+                                                             const float* __restrict__ gain) {
+    istft_body<true>(spec, sb, sf, st, B, T, lens, win, twid, wave, dry, dry_stride, gain);
 }
 
 // ===================================================================== hop-level waveform streaming
@@ -722,12 +766,17 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 // registers (lane's first-half samples 2m, 2m+1, m = lane + 64 q, q < 2, meet the previous frame's 256 + 2m, 256 + 2m + 1,
 // which the same lane holds at q + 2).  Then the state advances: tail, input ring (last 512 samples), hop counter.
 // FLUSH emits the stream's last block and leaves the wave state as it is (the stream has ended).
-template <typename S, bool FLUSH>
+// MIX: the attenuation limit -- every emitted sample becomes wave_mix(gain[n], dry, sample), in float, before the one
+// rounding of the int16 form; the zeros of a stream's first call and of an empty flush stay zeros.  The block of hop h is
+// block c0 + h - 1, so its dry samples are the ring's newest 256 (h == 0: the float2 pairs this lane loads for the ring
+// shift at nhops == 1 anyway) or hop h - 1 of this call's input rows.
+template <typename S, bool FLUSH, bool MIX = false>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
                                                                   int N, int nhops, int r, float* __restrict__ wstate,
                                                                   const float* __restrict__ win,
-                                                                  const float2* __restrict__ twid) {
+                                                                  const float2* __restrict__ twid,
+                                                                  const float* __restrict__ gain) {
     __shared__ float2 s_tw[256];
     __shared__ float2 s_tw512[256];
     __shared__ float s_win[512];
@@ -756,6 +805,13 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     float2* A = s_buf[wv][0];
     float2* Bf = s_buf[wv][1];
     S* o = out + (long)n * out_stride;
+    float g = 0.f;
+    float2 dry0[2];      // MIX: the ring's newest 256 samples, this lane's pairs
+    if constexpr (MIX) {
+        g = gain[n];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
+    }
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
         // merge: Z[k] = Xe + i Xo (k_istft); the imaginary parts of DC and Nyquist are ignored
@@ -788,8 +844,18 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
         for (int q = 0; q < 2; ++q) {
             const int m = lane + 64 * q;
             const float a0 = prev[q].x + f[q].x, a1 = prev[q].y + f[q].y;
-            wave_st(o + 256L * h + 2 * m, zero ? 0.f : (env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
-            wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : (env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
+            if constexpr (MIX) {
+                float2 d = dry0[q];
+                if (h > 0) {
+                    const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
+                    d = make_float2(wave_ld(xd), wave_ld(xd + 1));
+                }
+                wave_st(o + 256L * h + 2 * m, zero ? 0.f : wave_mix(g, d.x, env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
+                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : wave_mix(g, d.y, env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
+            } else {
+                wave_st(o + 256L * h + 2 * m, zero ? 0.f : (env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
+                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : (env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
+            }
             prev[q] = f[q + 2];
         }
     }
@@ -802,8 +868,10 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int j = 2 * (lane + 64 * q);
-        if (q < 2 && nhops == 1) ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);   // (this lane's own q + 2)
-        else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
+        if (q < 2 && nhops == 1) {      // (this lane's own q + 2; MIX holds the pair already)
+            if constexpr (MIX) ring[q] = dry0[q];
+            else ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);
+        } else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) *reinterpret_cast<float2*>(ws + WS_RING + 2 * (lane + 64 * q)) = ring[q];
@@ -4723,18 +4791,23 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 }
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s) {
+                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s, const float* gain) {
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
-    if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw);
-    else hipLaunchKernelGGL((k_wave_synthesis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw);
+    const float* none = nullptr;
+    if (gain) {
+        // a flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
+        if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw, gain);
+        else hipLaunchKernelGGL((k_wave_synthesis<S, false, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw, gain);
+    } else if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw, none);
+    else hipLaunchKernelGGL((k_wave_synthesis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw, none);
     GT_LAUNCH_CHECK();
     return 0;
 }
 template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
 template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t, const float*);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t, const float*);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {
@@ -4749,10 +4822,12 @@ int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, con
 }
 
 int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, const int* lens, const float* win,
-                 const float* twid, float* wave, hipStream_t s) {
+                 const float* twid, float* wave, hipStream_t s, const float* dry, long dry_stride, const float* gain) {
     const int groups = (T - 1 + ISTFT_BLOCKS - 1) / ISTFT_BLOCKS;
-    hipLaunchKernelGGL(k_istft, dim3(B * groups), dim3(FFT_WAVES * 64), 0, s, spec, sb, sf, st, B, T, lens, win,
-                       reinterpret_cast<const float2*>(twid), wave);
+    if (gain) hipLaunchKernelGGL(k_istft_mix, dim3(B * groups), dim3(FFT_WAVES * 64), 0, s, spec, sb, sf, st, B, T, lens, win,
+                                 reinterpret_cast<const float2*>(twid), wave, dry, dry_stride, gain);
+    else hipLaunchKernelGGL(k_istft, dim3(B * groups), dim3(FFT_WAVES * 64), 0, s, spec, sb, sf, st, B, T, lens, win,
+                            reinterpret_cast<const float2*>(twid), wave);
     GT_LAUNCH_CHECK();
     return 0;
 }

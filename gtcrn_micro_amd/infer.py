@@ -107,10 +107,11 @@ def _check_rate(path, fs):
                              "are resampled on the GPU); resample the file first")
 
 
-def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows):
+def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta=None):
     """The clips that are not at 16 kHz (other: item index -> (rate, samples at that rate)): per rate one Resampler and
     batches of similar lengths; a batch is resampled on the device with its lengths (gtcrn_resample), enhanced with
-    its 16 kHz lengths and finished like any other clip.  Returns (bytes up, bytes down)."""
+    its 16 kHz lengths and finished like any other clip.  beta: the attenuation limit's dry gain (mixed at 16 kHz).
+    Returns (bytes up, bytes down)."""
     import torch
     up = down = 0
     for fs in sorted({fs for fs, _ in other.values()}):
@@ -129,9 +130,9 @@ def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows):
             x16 = torch.zeros((len(sel), rs.out_len(max(lens))), device=dev)
             rs(torch.from_numpy(host).to(dev), lengths=lens, out=x16)
             if min(lens16) == x16.shape[1]:
-                y = eng.forward_wave(x16, win).cpu().numpy()
+                y = eng.forward_wave(x16, win, dry_gain=beta).cpu().numpy()
             else:
-                y = eng.forward_wave_var(x16, lens16, win).cpu().numpy()
+                y = eng.forward_wave_var(x16, lens16, win, dry_gain=beta).cpu().numpy()
             up += 4 * host.size
             down += 4 * y.size
             for j, i in enumerate(sel):
@@ -163,7 +164,7 @@ def _finish_clip(y_row, item, enh_dir):
 
 
 def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1,
-                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4):
+                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4, atten_lim_db=None):
     """barrier: a callable all ranks call once their lists are written (multi-GPU runs; main() passes
     torch.distributed.barrier); rank 0 then merges the per-rank scp files.
 
@@ -177,6 +178,8 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     so disk reads, PCIe both ways, the kernels and disk writes of different batches overlap.  The batches and the
     kernels are the ones of the serial form (pipeline=False: read -> pageable copy -> kernels -> copy back -> write, one
     batch after the other, what round 4 shipped), so every output file is bit-identical between the two.
+    atten_lim_db: the attenuation limit in dB for every clip (None: off), applied by the iSTFT launch of the same calls
+    (Engine.forward_wave's dry_gain) on the 16 kHz path and the other-rate path alike.
     stats (optional dict) receives: clips, frames, wall_s, frames_per_s, gpu_busy_frac (device time of the kernel
     sequences / wall time, from events), h2d_bytes, d2h_bytes."""
     import queue
@@ -191,6 +194,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     os.makedirs(enh_dir, exist_ok=True)
     eng = Engine(load_params(checkpoint), device)
     dev = f"cuda:{device}"
+    beta = None if atten_lim_db is None else _lib.atten_lim_to_gain(atten_lim_db)
     win = torch.hann_window(512).pow(0.5).to(dev)                   # infer.py:65
     names = sorted(f for f in os.listdir(noisy_dir) if f.endswith("wav"))
     lo, hi = shard_range(len(names), world, rank)
@@ -225,7 +229,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     setup_s = 0.0
     nbytes = [0, 0]
     if other:
-        nbytes[0], nbytes[1] = _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows)
+        nbytes[0], nbytes[1] = _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta)
 
     if not pipeline or not batches:
         for sel in batches:
@@ -233,12 +237,12 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
             lens = [len(w) for w in waves]
             Lmax = max(lens)
             if min(lens) == Lmax:
-                y = eng.forward_wave(torch.from_numpy(np.stack(waves)).to(dev), win).cpu().numpy()
+                y = eng.forward_wave(torch.from_numpy(np.stack(waves)).to(dev), win, dry_gain=beta).cpu().numpy()
             else:
                 host = np.zeros((len(sel), Lmax), np.float32)
                 for j, w in enumerate(waves):
                     host[j, :len(w)] = w
-                y = eng.forward_wave_var(torch.from_numpy(host).to(dev), lens, win).cpu().numpy()
+                y = eng.forward_wave_var(torch.from_numpy(host).to(dev), lens, win, dry_gain=beta).cpu().numpy()
             nbytes[0] += 4 * len(sel) * Lmax
             nbytes[1] += 4 * y.size
             for j, i in enumerate(sel):
@@ -379,9 +383,9 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
                         else:
                             x.copy_(sl["din"][:nb].view(torch.float32).view(n, Lmax))
                         if min(lens) == Lmax:
-                            eng.forward_wave(x, win, out=y)
+                            eng.forward_wave(x, win, out=y, dry_gain=beta)
                         else:
-                            eng.forward_wave_var(x, lens, win, out=y)
+                            eng.forward_wave_var(x, lens, win, out=y, dry_gain=beta)
                         # write_wav_pcm16's conversion on the device: rint(y * 32768) clipped to the int16 range, one pass
                         # (gtcrn_f32_to_pcm16; n * Lout is a multiple of 256)
                         _lib.f32_to_pcm16(yf[:n * Lout], out=sl["dout"][:n * Lout])
@@ -427,7 +431,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
 
 
 def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1, barrier=None,
-                   agree=None, pipeline=True, stats=None, io_threads=4):
+                   agree=None, pipeline=True, stats=None, io_threads=4, atten_lim_db=None):
     """Counterpart of infer.py:26-119 for a folder (see ``_enhance_shard``): every rank enhances its contiguous shard of
     the sorted file list, then rank 0 merges the per-rank scp lists.
 
@@ -440,7 +444,7 @@ def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     result = None
     try:
         result = _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device, max_batch, rank, world, barrier,
-                                pipeline=pipeline, stats=stats, io_threads=io_threads)
+                                pipeline=pipeline, stats=stats, io_threads=io_threads, atten_lim_db=atten_lim_db)
     except Exception as e:           # re-raised below, after the exchange.  NOT BaseException: a KeyboardInterrupt or
         err = e                      # SystemExit must leave at once instead of waiting in a collective first
     all_ok = err is None
@@ -468,6 +472,8 @@ def main(argv=None):
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--serial", action="store_true",
                     help="one batch after the other with pageable copies (the A/B of the pipelined default)")
+    ap.add_argument("--atten-lim-db", type=float, default=None,
+                    help="attenuation limit: remove at most this many dB of noise (0 = bypass; default: no limit)")
     ap.add_argument("--stats", action="store_true", help="print this rank's throughput / GPU-busy figures as JSON")
     a = ap.parse_args(argv)
     from .sharding import rank_world
@@ -493,7 +499,7 @@ def main(argv=None):
     try:
         st = {} if a.stats else None
         enhance_folder(a.noisy_dir, a.clean_dir, a.enh_dir, a.checkpoint, dev, a.max_batch, rank, world, barrier, agree,
-                       pipeline=not a.serial, stats=st)
+                       pipeline=not a.serial, stats=st, atten_lim_db=a.atten_lim_db)
         if st is not None:
             import json
             print(json.dumps({"rank": rank, **st}), flush=True)

@@ -228,18 +228,20 @@ class StreamGTCRNMicro(GTCRNMicro):
         """spec_t (N,257,n,2), n >= 1 new frames per stream; state from init_state (updated in place)."""
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
-    def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None):
+    def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
         packet: the caller's block size in samples at fs (e.g. 160 = 10 ms at 16 kHz, 441 at 44.1 kHz) gives the packet
-        form (Engine.new_packet_state: one packet in, one out per call, at 8 / 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz)."""
+        form (Engine.new_packet_state: one packet in, one out per call, at 8 / 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz).
+        atten_lim_db: the attenuation limit in dB, one value or one per stream (None: off; 0: bypass at the form's
+        latency); state.set_atten_lim_db changes it while the streams run."""
         eng = self.engine(torch.device(device))
         if packet is not None:
-            return eng.new_packet_state(nstreams, window, int(packet), int(fs))
+            return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db)
         if int(fs) != 16000:
-            return eng.new_rate_state(nstreams, window, int(fs))
-        return eng.new_wave_state(nstreams, window)
+            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db)
+        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db)
 
     def step_wave(self, x, state):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a

@@ -346,6 +346,66 @@ int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream *ps, void *d_state, void 
                                    const short *d_in, long in_stride, short *d_out, long out_stride, int nstreams,
                                    const float *d_win, void *stream);
 
+/* ---- attenuation limit: a per-stream dry / wet mix on every waveform path ------------------------------------------
+ * The "suppression level" / "attenuation limit" / "dry-wet" control of a deployed enhancer: an operator caps the noise
+ * reduction at limit_dB, a client switches the enhancer off for an A/B comparison without changing the call's latency.
+ * The library holds the dry signal where the output is written, so the control costs no launch, no delay line and, in the
+ * PCM16 forms, no second rounding.
+ *
+ * Contract.  A DRY GAIN beta in [0, 1] per stream or clip, beta = 10^(-limit_dB / 20): beta = 0 is no limit (the plain
+ * call's output), beta = 1 is bypass (the input comes out at the form's latency).  The calls take beta itself: d_gain, a
+ * device array of floats, one per stream / row.  d_gain == NULL means no limit and runs the plain call's kernels.  With w
+ * the sample the plain call emits and x the input sample aligned with it,
+ *     y = fl( fl(beta * x) + fl( fl(1 - beta) * w ) )        every fl() ONE fp32 rounding, no fused multiply-add
+ * so a numpy float32 expression reproduces y bit for bit.  Hence beta = 0 gives w and beta = 1 gives x, exactly, for finite
+ * inputs (as values: a zero may change its sign).  The mix is made in float BEFORE the one rounding to int16 of the _pcm16
+ * forms.  Samples a form emits as structural zeros stay zeros: the first block of a hop stream, the FIFO pre-fill of the
+ * packet form, the flush of a stream that holds fewer than 257 samples.  The limit changes no state: model state and wave
+ * state after a limited call equal those after the plain call, and no state layout or *_state_bytes differs.
+ *
+ * Alignment (it follows from the contracts above).
+ *   offline   gtcrn_forward_wave_limited: x = d_wave[b][n] for n < 256 * (L / 256); with d_lengths, n < 256 * (len_b / 256)
+ *             per row and nothing beyond is written, as in gtcrn_forward_wave_var.  d_lengths == NULL: all rows hold Lmax.
+ *   hop form  the block emitted for hop k is block k - 1, its dry samples are input hop k - 1: the ring's newest 256
+ *             samples for the first hop of a call (and for the flush's block), hop h - 1 of the call's input rows for
+ *             the later hops.  The stream equals gtcrn_forward_wave_limited one hop late, bit for bit.
+ *   rate and packet forms: the mix is made at 16 kHz inside the wave step they run.  Their stage-by-stage contracts hold
+ *             word for word with gtcrn_forward_wave replaced by gtcrn_forward_wave_limited (on a16, the 16 kHz hand-off);
+ *             the dry signal passes the same outbound stage as the wet one, band-limited and delayed identically.
+ *
+ * d_gain is read from device memory by the kernel at every call: a caller may rewrite it between calls, also between the
+ * replays of a captured HIP graph, and the change takes effect at the next emitted block.  The library cannot read device
+ * memory without a synchronisation: 0 <= beta <= 1 is the caller's precondition (as win[0] == 0 is).  A limited call makes
+ * the launches of its plain form, one for one (the mixing kernels are timed as k_wave_synthesis_mix / k_istft_mix), and
+ * checks its arguments as the plain form does.  gtcrn_packet_stream_set_dry_gain stores the pointer in the handle (it must
+ * cover max_streams floats and stay valid; NULL switches the limit off), so the packet steps keep their signatures and a
+ * captured period keeps replaying while gains change.
+ * Out of scope: ramping a change of beta inside a block (it would need a per-stream "previous gain" word in the state);
+ * the _quant entry points; the spectrogram-level calls (a caller holding spectra mixes them itself: by linearity
+ * beta * X + (1 - beta) * forward_spec(X) is this control up to the rounding of an STFT -> iSTFT round trip). */
+int gtcrn_forward_wave_limited(gtcrn_model *m, const float *d_wave, float *d_wave_out, int B, long Lmax,
+                               const int *d_lengths, const float *d_gain, const float *d_win, void *stream);
+int gtcrn_wave_stream_step_limited(gtcrn_model *m, void *d_state, void *d_wstate, const float *d_in, long in_stride,
+                                   float *d_out, long out_stride, int nstreams, int nhops, const float *d_gain,
+                                   const float *d_win, void *stream);
+int gtcrn_wave_stream_step_limited_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const short *d_in, long in_stride,
+                                         short *d_out, long out_stride, int nstreams, int nhops, const float *d_gain,
+                                         const float *d_win, void *stream);
+int gtcrn_wave_stream_flush_limited(gtcrn_model *m, void *d_state, void *d_wstate, const float *d_tail, long tail_stride,
+                                    int r, float *d_out, long out_stride, int nstreams, const float *d_gain,
+                                    const float *d_win, void *stream);
+int gtcrn_wave_stream_flush_limited_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const short *d_tail,
+                                          long tail_stride, int r, short *d_out, long out_stride, int nstreams,
+                                          const float *d_gain, const float *d_win, void *stream);
+int gtcrn_rate_stream_step_limited(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                                   void *d_rstate, const float *d_in, long in_stride, float *d_out, long out_stride,
+                                   int nstreams, int nhops, const float *d_gain, const float *d_win, void *stream);
+int gtcrn_rate_stream_step_limited_pcm16(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state,
+                                         void *d_wstate, void *d_rstate, const short *d_in, long in_stride, short *d_out,
+                                         long out_stride, int nstreams, int nhops, const float *d_gain, const float *d_win,
+                                         void *stream);
+int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream *ps, const float *d_gain);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),

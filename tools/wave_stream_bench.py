@@ -16,6 +16,13 @@ profiles/rate_stream_bench.json.  With --trace-only N: rate steps at --trace-fs 
 per-hop time of the 16 kHz wave step and the 48 kHz rate step of the SAME run; plus every call of a period on its own
 (the cost follows the hops of the call) and the library's per-kernel event times over one period.  Writes
 profiles/packet_stream_bench.json.  With --trace-only N: packet steps at --trace-fs / --trace-packet.
+
+--dry-gain: the attenuation limit.  At 16 384 and 65 536 streams (or --sizes) the plain and the limited 16 kHz wave step
+(12 dB on every stream) alternate in one run, then one period of the plain and the limited packet form at 16 kHz / 160;
+offline, the library's event times of k_istft and k_istft_mix at B = 256 x 4 s.  Each limited figure stands next to the
+plain one of the SAME run and that run's own repetition spread.  Writes profiles/dry_gain_bench.json.  With
+--trace-only N: plain and limited wave steps alternating, then plain and limited offline calls (for one rocprofv3
+--kernel-trace --stats run that holds k_wave_synthesis and k_istft in both forms).
 """
 import argparse
 import json
@@ -188,6 +195,88 @@ def compare_packet(eng, win, N, iters, reps, cases=PACKET_CASES):
     return res
 
 
+def spread(v):
+    """(max - min) / median of the repetitions of one side: the run's own noise."""
+    return (max(v) - min(v)) / statistics.median(v)
+
+
+def compare_dry_gain(eng, win, N, iters, reps, db=12.0, packet=160):
+    """Plain against limited at N streams, alternating in one run: the one-hop 16 kHz wave step, then one whole period of
+    the packet form at 16 kHz / `packet`."""
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    eng.reserve(N, 1)
+    x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    sp, sl = eng.new_wave_state(N, win), eng.new_wave_state(N, win, atten_lim_db=db)
+    plain = lambda: eng.wave_stream_step(sp, x, out=y)             # noqa: E731
+    lim = lambda: eng.wave_stream_step(sl, x, out=y)               # noqa: E731
+    for f in (plain, lim):
+        timed(f, max(3, iters // 4))
+    tp, tl = [], []
+    for _ in range(reps):
+        tp.append(timed(plain, iters))
+        tl.append(timed(lim, iters))
+    eng.timing_enable(True)
+    for _ in range(iters):
+        plain()
+        lim()
+    torch.cuda.synchronize()
+    kern = {k: {"avg_ms": v[0], "launches": v[1]} for k, v in eng.timing_read().items()}
+    eng.timing_enable(False)
+    r = {"N": N, "iters": iters, "atten_lim_db": db, "wave_step_plain_ms": statistics.median(tp),
+         "wave_step_limited_ms": statistics.median(tl), "wave_step_plain_reps_ms": tp, "wave_step_limited_reps_ms": tl,
+         "wave_step_plain_spread": spread(tp), "wave_step_limited_spread": spread(tl), "kernels_event_timed": kern}
+    r["wave_step_ratio"] = r["wave_step_limited_ms"] / r["wave_step_plain_ms"]
+    del sp, sl
+    torch.cuda.empty_cache()
+    pp, pl = eng.new_packet_state(N, win, packet), eng.new_packet_state(N, win, packet, atten_lim_db=db)
+    P = pp.period
+    xp = torch.randn(N, packet, device="cuda", generator=gen) * 0.1
+    yp = torch.empty_like(xp)
+
+    def period(st):
+        for _ in range(P):
+            eng.packet_stream_step(st, xp, out=yp)
+
+    nper = max(2, iters // P)
+    for st in (pp, pl):
+        timed(lambda: period(st), 2)
+    qp, ql = [], []
+    for _ in range(reps):
+        qp.append(timed(lambda: period(pp), nper))
+        ql.append(timed(lambda: period(pl), nper))
+    r.update({"packet": packet, "period_calls": P, "packet_period_plain_ms": statistics.median(qp),
+              "packet_period_limited_ms": statistics.median(ql), "packet_period_plain_reps_ms": qp,
+              "packet_period_limited_reps_ms": ql, "packet_period_plain_spread": spread(qp),
+              "packet_period_limited_spread": spread(ql)})
+    r["packet_period_ratio"] = r["packet_period_limited_ms"] / r["packet_period_plain_ms"]
+    del pp, pl
+    torch.cuda.empty_cache()
+    return r
+
+
+def offline_dry_gain(eng, win, B=256, seconds=4, reps=7, db=12.0):
+    """k_istft against k_istft_mix at B clips of `seconds` s, from the library's launch records (alternating calls)."""
+    from gtcrn_micro_amd import atten_lim_to_gain
+    L = 16000 * seconds
+    x = torch.randn(B, L, device="cuda") * 0.1
+    y = torch.empty(B, 256 * (L // 256), device="cuda")
+    g = torch.full((B,), atten_lim_to_gain(db), device="cuda")
+    for _ in range(2):
+        eng.forward_wave(x, win, out=y)
+        eng.forward_wave(x, win, out=y, dry_gain=g)
+    eng.timing_enable(True)
+    for _ in range(reps):
+        eng.forward_wave(x, win, out=y)
+        eng.forward_wave(x, win, out=y, dry_gain=g)
+    torch.cuda.synchronize()
+    kern = {k: {"avg_ms": v[0], "launches": v[1]} for k, v in eng.timing_read().items()}
+    eng.timing_enable(False)
+    return {"B": B, "seconds": seconds, "frames": 1 + L // 256, "k_istft_ms": kern["k_istft"]["avg_ms"],
+            "k_istft_mix_ms": kern["k_istft_mix"]["avg_ms"],
+            "ratio": kern["k_istft_mix"]["avg_ms"] / kern["k_istft"]["avg_ms"], "kernels_event_timed": kern}
+
+
 def latency_n1(eng, win, iters):
     eng.reserve(1, 1)
     x = torch.randn(1, 256, device="cuda") * 0.1
@@ -231,6 +320,8 @@ def main():
     ap.add_argument("--packet", action="store_true",
                     help="the packet form at 16 kHz / 160, 320, 48 kHz / 480 and 44.1 kHz / 441 against the wave and rate steps")
     ap.add_argument("--trace-packet", type=int, default=480, help="--packet --trace-only: the packet, in samples at --trace-fs")
+    ap.add_argument("--dry-gain", action="store_true",
+                    help="the attenuation limit: plain against limited wave step, packet period (16 kHz / 160) and k_istft")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wave_stream_bench needs the GPU (nothing is measured on the CPU)")
@@ -238,6 +329,35 @@ def main():
     params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
     eng = Engine(params, 0)
     win = torch.hann_window(512).pow(0.5).cuda()
+    if a.dry_gain:
+        sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
+        if a.trace_only:
+            N = a.trace_only
+            eng.reserve(N, 1)
+            sp, sl = eng.new_wave_state(N, win), eng.new_wave_state(N, win, atten_lim_db=12)
+            x = torch.randn(N, 256, device="cuda") * 0.1
+            y = torch.empty_like(x)
+            for _ in range(a.iters):
+                eng.wave_stream_step(sp, x, out=y)
+                eng.wave_stream_step(sl, x, out=y)
+            torch.cuda.synchronize()
+            del sp, sl
+            torch.cuda.empty_cache()
+            offline_dry_gain(eng, win, reps=5)
+            return
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "dry_gain_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in sizes:
+            r = compare_dry_gain(eng, win, N, a.iters, a.reps)
+            print(json.dumps({k: v for k, v in r.items() if "reps" not in k and k != "kernels_event_timed"}), flush=True)
+            res["compare"].append(r)
+        res["offline"] = offline_dry_gain(eng, win, reps=a.reps)
+        print(json.dumps({k: v for k, v in res["offline"].items() if k != "kernels_event_timed"}), flush=True)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
     if a.packet:
         sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
         if a.trace_only:
