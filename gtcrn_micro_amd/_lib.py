@@ -124,6 +124,16 @@ def lib():
     for fn in ("gtcrn_rate_stream_step_limited", "gtcrn_rate_stream_step_limited_pcm16"):
         getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp]
     L.gtcrn_packet_stream_set_dry_gain.argtypes = [_vp, _vp]
+    # stream slots: (model, state[, wstate], slots, count, max_active, ...).  A library of an earlier commit, loaded through
+    # LIB_PATH for a same-GPU comparison of the contiguous calls (tools/slot_stream_bench.py --lib), has none of these
+    # symbols: it loads, and a slot call on it fails with ctypes' AttributeError at the call.
+    if hasattr(L, "gtcrn_stream_step_slots"):
+        L.gtcrn_stream_step_slots.argtypes = [_vp, _vp, _vp, _vp, ci, _vp, cl, cl, cl, _vp, cl, cl, cl, _vp]
+        L.gtcrn_stream_reset_slots.argtypes = [_vp, _vp, _vp, _vp, _vp, ci, _vp]
+        for fn in ("gtcrn_wave_stream_step_slots", "gtcrn_wave_stream_step_slots_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, _vp, _vp, _vp]
+        for fn in ("gtcrn_wave_stream_flush_slots", "gtcrn_wave_stream_flush_slots_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, ci, _vp, cl, ci, _vp, cl, _vp, _vp, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -679,6 +689,125 @@ class Engine:
                 fn = lib().gtcrn_wave_stream_flush_limited_pcm16 if pcm else lib().gtcrn_wave_stream_flush_limited
                 _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
         return out
+
+    # ---- stream slots (contract: include/gtcrn_micro_hip.h, "stream slots") ------------------------------------------
+    def _slot_args(self, slots, count, max_active):
+        """Checks the slot table of a call: `slots` int32 (M,) on the model's device, `count` None or a one-element int32
+        tensor there, max_active None (all M rows) or 1..M.  Nothing is read back: ids in range and distinct are the
+        caller's precondition (check_slots verifies a list, synchronously)."""
+        import torch
+        if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or not slots.is_cuda or slots.device.index != self.device:
+            raise GtcrnError(f"slots must be an int32 tensor on cuda:{self.device}")
+        if slots.dim() != 1 or slots.numel() < 1 or not slots.is_contiguous():
+            raise GtcrnError(f"slots must be a contiguous 1-D tensor, got shape {tuple(slots.shape)}")
+        m = slots.numel() if max_active is None else int(max_active)
+        if not 1 <= m <= slots.numel():
+            raise GtcrnError(f"max_active must be 1..{slots.numel()} (the rows of slots), got {m}")
+        if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() != 1
+                                  or not count.is_cuda or count.device.index != self.device):
+            raise GtcrnError(f"count must be a one-element int32 tensor on cuda:{self.device}")
+        return m, (count.data_ptr() if count is not None else None)
+
+    def check_slots(self, state, slots, count=None):
+        """SYNCHRONOUS debugging validator: copies `slots` (and `count`) to the host and raises GtcrnError on an id outside
+        0..n-1 or a repeated one among the rows that would step.  Launches nothing."""
+        n = state.n if isinstance(state, WaveStreamState) else int(state.shape[0])
+        self._slot_args(slots, count, None)
+        ids = slots.detach().cpu().numpy()
+        k = len(ids) if count is None else min(max(int(count.detach().cpu().reshape(-1)[0]), 0), len(ids))
+        ids = ids[:k]
+        bad = ids[(ids < 0) | (ids >= n)]
+        if bad.size:
+            raise GtcrnError(f"slot id {int(bad[0])} outside [0, {n})")
+        uniq, cnt = np.unique(ids, return_counts=True)
+        if (cnt > 1).any():
+            raise GtcrnError(f"slot id {int(uniq[cnt > 1][0])} is named more than once")
+        return k
+
+    def stream_step_slots(self, state, slots, spec_t, count=None, out=None, max_active=None):
+        """One frame for the rows a call names: spec_t (M,257,1,2), row i = the stream in slot slots[i] of `state`
+        (new_state); `count` (device int32, None: all) rows step.  Returns (M,257,1,2); rows at or beyond count are not
+        written."""
+        import torch
+        self._check_on_device(spec_t, "spec")
+        if spec_t.dim() != 4 or spec_t.shape[1] != NBINS or spec_t.shape[2] != 1 or spec_t.shape[3] != 2:
+            raise GtcrnError(f"spec must be (M,257,1,2), got {tuple(spec_t.shape)}")
+        m, cnt = self._slot_args(slots, count, max_active)
+        if spec_t.shape[0] != m:
+            raise GtcrnError(f"spec must hold max_active = {m} rows, got {spec_t.shape[0]}")
+        if spec_t.stride(3) != 1:
+            spec_t = spec_t.contiguous()
+        self._check_on_device(state, "state", (state.shape[0], self.state_bytes() // 4))
+        if out is None:
+            out = torch.empty((m, NBINS, 1, 2), device=spec_t.device, dtype=torch.float32)
+        else:
+            self._check_on_device(out, "out")
+            if tuple(out.shape) != (m, NBINS, 1, 2) or out.stride(3) != 1:
+                raise GtcrnError(f"out must be ({m},257,1,2) with contiguous re/im pairs, got {tuple(out.shape)}")
+        isb, isf, ist = _spec_strides(spec_t)
+        osb, osf, ost = _spec_strides(out)
+        with self._dev():
+            _check(lib().gtcrn_stream_step_slots(self._h, state.data_ptr(), slots.data_ptr(), cnt, m, spec_t.data_ptr(), isb, isf,
+                                                 ist, out.data_ptr(), osb, osf, ost, _stream_ptr()))
+        return out
+
+    def _slot_rows(self, state, slots, x, count, max_active, what, cols=None):
+        import torch
+        if type(state) is not WaveStreamState:
+            raise GtcrnError("slots= needs a state of new_wave_state: rate and packet streams share a group phase and "
+                             "cannot be stepped by slot")
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
+            raise GtcrnError(f"{what} must be a float32 or int16 CUDA (ROCm) tensor")
+        if x.device.index != self.device or state.model.device != x.device:
+            raise GtcrnError(f"{what} and the state must be on cuda:{self.device}")
+        m, cnt = self._slot_args(slots, count, max_active)
+        if x.dim() != 2 or x.shape[0] != m:
+            raise GtcrnError(f"{what} must hold max_active = {m} rows, got {tuple(x.shape)}")
+        if cols is not None and x.shape[1] != cols:
+            raise GtcrnError(f"{what} must hold {cols} samples per row (one hop per call), got {x.shape[1]}")
+        if x.stride(1) != 1 and x.shape[1] > 1:
+            x = x.contiguous()
+        return x, m, cnt
+
+    def wave_stream_step_slots(self, state, slots, x, count=None, out=None, max_active=None):
+        """One hop for the rows a call names: x (M, 256) float32 or int16, row i = the stream in slot slots[i] of `state`
+        -> (M, 256), same dtype, each stream one hop late.  Applies state.dry_gain (per slot) when set.  Asynchronous; no
+        allocation when `out` is given and reserve(M, 1) was called (capturable)."""
+        import torch
+        x, m, cnt = self._slot_rows(state, slots, x, count, max_active, "x", 256)
+        out = self._wave_out(out, x, 256)
+        fn = lib().gtcrn_wave_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step_slots
+        gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
+        with self._dev():
+            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m, x.data_ptr(), x.stride(0),
+                      out.data_ptr(), out.stride(0), gain, state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def wave_stream_flush_slots(self, state, slots, tail, count=None, out=None, max_active=None):
+        """tail (M, r), r = 0..255: the samples after the last whole hop of the named streams -> their last 256 enhanced
+        samples.  Ends those streams (wave_stream_reset_slots before a slot is reused); the others are not touched."""
+        import torch
+        tail, m, cnt = self._slot_rows(state, slots, tail, count, max_active, "tail")
+        r = tail.shape[1]
+        if r > 255:
+            raise GtcrnError(f"the tail holds 0..255 samples, got {r}: push whole hops with wave_stream_step_slots first")
+        out = self._wave_out(out, tail, 256)
+        fn = lib().gtcrn_wave_stream_flush_slots_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush_slots
+        gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
+        with self._dev():
+            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
+                      tail.data_ptr() if r else None, tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), gain,
+                      state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def wave_stream_reset_slots(self, state, slots, count=None, max_active=None):
+        """Resets the named slots (both states) to the start of a new clip, with a kernel: asynchronous and capturable."""
+        if type(state) is not WaveStreamState:
+            raise GtcrnError("slots= needs a state of new_wave_state")
+        m, cnt = self._slot_args(slots, count, max_active)
+        with self._dev():
+            _check(lib().gtcrn_stream_reset_slots(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
+                                                  _stream_ptr()))
 
     # ---- other sample rates (contract: include/gtcrn_micro_hip.h, gtcrn_resample / gtcrn_rate_stream_*) -------------
     def resampler(self, fs_in, fs_out):

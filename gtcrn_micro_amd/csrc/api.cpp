@@ -698,6 +698,127 @@ int gtcrn_wave_stream_flush_limited_pcm16(gtcrn_model* m, void* d_state, void* d
                                    out_stride, nstreams, 1, true, r, d_win, stream, d_gain);
 }
 
+// ---- stream slots: the same steps for the rows a call names (contract: include/gtcrn_micro_hip.h) ---------------------------
+// Row i of a call is the stream whose states sit in slot d_slots[i]; *d_count rows (clamped to 0..max_active on the device)
+// step.  The host sizes the grid, the workspace and the form from max_active alone, so one captured graph serves any active set.
+namespace {
+int slots_args(const std::string& w, gtcrn_model* m, const void* d_state, const int* d_slots, int max_active) {
+    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
+    if (!d_state || !d_slots) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (max_active < 1) return fail(GTCRN_ERR_ARG, w + ": max_active must be >= 1");
+    if (reinterpret_cast<uintptr_t>(d_state) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    return 0;
+}
+// the single-launch model step of the named rows (spectra compact: row i of the call)
+int run_model_slots(const std::string& w, gtcrn_model* m, const float* spec_in, long isb, long isf, float* spec_out, long osb,
+                    long osf, int max_active, float* state, const int* slots, const int* cnt, hipStream_t s) {
+    if (m->stream_form == 1 || (m->debug && !m->debug_keep_fused))
+        return fail(GTCRN_ERR_STATE, w + ": the three-launch form (gtcrn_stream_form 1, gtcrn_debug_enable 1) has no indexed step");
+    if (!gtk::stream_ms_usable(isb, osb)) return fail(GTCRN_ERR_ARG, w + ": spectrogram row strides too large");
+    Timer tm(m, s);
+    const bool wide = m->stream_form == 3 || (m->stream_form == 0 && stream_wide_pays(max_active));
+    unsigned long long* stamps = (m->debug && m->d_stamps) ? m->d_stamps : nullptr;
+    m->last_quant = false;
+    tm.begin(wide ? K_STREAM_WIDE : K_STREAM_MS);
+    if (wide) LAUNCH_TRY(gtk::launch_stream_wide_slots(spec_in, isb, isf, spec_out, osb, osf, max_active, m->d_pf, m->d_pi, state,
+                                                       stamps, slots, cnt, s));
+    else LAUNCH_TRY(gtk::launch_stream_ms_slots(spec_in, isb, isf, spec_out, osb, osf, max_active, m->d_pf, m->d_pi, state, stamps,
+                                                slots, cnt, s));
+    tm.end();
+    m->last_fused_stream = true;
+    m->last_B = max_active;
+    m->last_T = 1;
+    return 0;
+}
+}  // namespace
+
+int gtcrn_stream_step_slots(gtcrn_model* m, void* d_state, const int* d_slots, const int* d_count, int max_active,
+                            const float* d_spec_t, long isb, long isf, long ist, float* d_spec_out_t, long osb, long osf,
+                            long ost, void* stream) {
+    const std::string w("gtcrn_stream_step_slots");
+    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
+    if (!d_spec_t || !d_spec_out_t) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (int rc0 = check_spec_layout(d_spec_t, isb, isf, ist)) return rc0;
+    if (int rc0 = check_spec_layout(d_spec_out_t, osb, osf, ost)) return rc0;
+    int rc = check_model(m);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = ensure_workspace(m, max_active, 1, s);
+    if (rc) return rc;
+    return run_model_slots(w, m, d_spec_t, isb, isf, d_spec_out_t, osb, osf, max_active, static_cast<float*>(d_state), d_slots,
+                           d_count, s);
+}
+
+int gtcrn_stream_reset_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
+                             int max_active, void* stream) {
+    const std::string w("gtcrn_stream_reset_slots");
+    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
+    if (reinterpret_cast<uintptr_t>(d_wstate) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    int rc = check_model(m);
+    if (rc) return rc;
+    LAUNCH_TRY(gtk::launch_reset_slots(static_cast<float*>(d_state), static_cast<float*>(d_wstate), d_slots, d_count, max_active,
+                                       (hipStream_t)stream));
+    return 0;
+}
+
+extern "C++" template <typename S>
+static int wave_stream_slots_impl(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots,
+                                  const int* d_count, int max_active, const S* d_in, long in_stride, S* d_out, long out_stride,
+                                  bool flush, int r, const float* d_gain, const float* d_win, void* stream) {
+    const std::string w(who);
+    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
+    if (!d_wstate || !d_out || !d_win || (!d_in && !(flush && r == 0))) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (flush && (r < 0 || r > 255)) return fail(GTCRN_ERR_ARG, w + ": the tail holds r = 0..255 samples");
+    if (in_stride < (flush ? r : 256L) || out_stride < 256L) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if (reinterpret_cast<uintptr_t>(d_wstate) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    int rc = check_model(m);
+    if (rc) return rc;
+    if (m->stream_form == 1 || (m->debug && !m->debug_keep_fused))      // (before the analysis launch: nothing runs on a refusal)
+        return fail(GTCRN_ERR_STATE, w + ": the three-launch form (gtcrn_stream_form 1, gtcrn_debug_enable 1) has no indexed step");
+    hipStream_t s = (hipStream_t)stream;
+    rc = ensure_workspace(m, max_active, 1, s);
+    if (rc) return rc;
+    const long sb = 514, sf = 2;                               // frame-major (max_active, 1, 257, 2), compact rows
+    float* ws = static_cast<float*>(d_wstate);
+    Timer tm(m, s);
+    tm.begin(K_WAVE_ANALYSIS);
+    LAUNCH_TRY(gtk::launch_wave_analysis_slots<S>(d_in, in_stride, max_active, r, flush, ws, d_win, m->d_twid, m->d_spec_a, d_slots,
+                                                  d_count, s));
+    tm.end();
+    rc = run_model_slots(w, m, m->d_spec_a, sb, sf, m->d_spec_b, sb, sf, max_active, static_cast<float*>(d_state), d_slots, d_count, s);
+    if (rc) return rc;
+    tm.begin(d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
+    LAUNCH_TRY(gtk::launch_wave_synthesis_slots<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, max_active, r, flush, ws, d_win,
+                                                   m->d_twid, d_slots, d_count, s, d_gain));
+    tm.end();
+    return 0;
+}
+
+int gtcrn_wave_stream_step_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
+                                 int max_active, const float* d_in, long in_stride, float* d_out, long out_stride,
+                                 const float* d_gain, const float* d_win, void* stream) {
+    return wave_stream_slots_impl<float>("gtcrn_wave_stream_step_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_in,
+                                         in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
+}
+int gtcrn_wave_stream_step_slots_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
+                                       int max_active, const short* d_in, long in_stride, short* d_out, long out_stride,
+                                       const float* d_gain, const float* d_win, void* stream) {
+    return wave_stream_slots_impl<short>("gtcrn_wave_stream_step_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
+                                         d_in, in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
+}
+int gtcrn_wave_stream_flush_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
+                                  int max_active, const float* d_tail, long tail_stride, int r, float* d_out, long out_stride,
+                                  const float* d_gain, const float* d_win, void* stream) {
+    return wave_stream_slots_impl<float>("gtcrn_wave_stream_flush_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_tail,
+                                         tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
+}
+int gtcrn_wave_stream_flush_slots_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
+                                        int max_active, const short* d_tail, long tail_stride, int r, short* d_out,
+                                        long out_stride, const float* d_gain, const float* d_win, void* stream) {
+    return wave_stream_slots_impl<short>("gtcrn_wave_stream_flush_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
+                                         d_tail, tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
+}
+
 // ---- sample-rate conversion ------------------------------------------------------------------------------------------
 // The filter of include/gtcrn_micro_hip.h, designed here in double and rounded once to float: the kernels, the tests and
 // gtcrn_resample_taps all see these coefficients.

@@ -147,6 +147,26 @@ int launch_stream_ms(const float* spec, long sb, long sf, float* out, long osb, 
 // for stream counts that fill the chip more than once
 int launch_stream_wide(const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
                        const int* PI, float* state, unsigned long long* stamps, hipStream_t s);
+// stream slots (gtcrn_*_slots): the same steps for the rows a call names -- row i is the stream whose state sits in slot
+// slots[i] (device, int32[max_active], in range and distinct); cnt (device int32, may be nullptr: max_active) is clamped to
+// 0..max_active on the device and rows at or beyond it are neither read nor written.  Spectrum / sample rows are compact
+// (row i of the call); gain is per SLOT.  One hop / frame per call.
+int launch_stream_ms_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active, const float* PF,
+                           const int* PI, float* state, unsigned long long* stamps, const int* slots, const int* cnt,
+                           hipStream_t s);
+int launch_stream_wide_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active,
+                             const float* PF, const int* PI, float* state, unsigned long long* stamps, const int* slots,
+                             const int* cnt, hipStream_t s);
+template <typename S>
+int launch_wave_analysis_slots(const S* in, long in_stride, int max_active, int r, bool flush, const float* wstate,
+                               const float* win, const float* twid, float* spec, const int* slots, const int* cnt,
+                               hipStream_t s);
+template <typename S>
+int launch_wave_synthesis_slots(const float* spec, const S* in, long in_stride, S* out, long out_stride, int max_active, int r,
+                                bool flush, float* wstate, const float* win, const float* twid, const int* slots,
+                                const int* cnt, hipStream_t s, const float* gain = nullptr);
+// zeroes the model state and (wstate != nullptr) the wave state of the listed slots (k_reset_slots)
+int launch_reset_slots(float* state, float* wstate, const int* slots, const int* cnt, int max_active, hipStream_t s);
 int stream_wide_streams();
 bool stream_ms_usable(long sb, long osb);
 int launch_state_convert(float* state, int N, float* conv, float* tra, float* const* tcn8, const int* PI, int dir,

@@ -228,31 +228,49 @@ class StreamGTCRNMicro(GTCRNMicro):
         """spec_t (N,257,n,2), n >= 1 new frames per stream; state from init_state (updated in place)."""
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
-    def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None):
+    def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
+                        count=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
         packet: the caller's block size in samples at fs (e.g. 160 = 10 ms at 16 kHz, 441 at 44.1 kHz) gives the packet
         form (Engine.new_packet_state: one packet in, one out per call, at 8 / 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz).
         atten_lim_db: the attenuation limit in dB, one value or one per stream (None: off; 0: bypass at the form's
-        latency); state.set_atten_lim_db changes it while the streams run."""
+        latency); state.set_atten_lim_db changes it while the streams run.
+        state=, slots= (int32 device tensor), count= (device int32, optional): a stream JOINS -- the named slots of the
+        existing 16 kHz `state` are reset to the start of a clip (Engine.wave_stream_reset_slots, a capturable kernel) and
+        `state` is returned; the other slots are not touched.  Rate and packet states cannot be addressed by slot (their
+        streams share a group phase)."""
         eng = self.engine(torch.device(device))
+        if slots is not None:
+            if state is None or packet is not None or int(fs) != 16000:
+                raise _lib.GtcrnError("slots= resets slots of an existing 16 kHz wave state: pass state=, no fs / packet")
+            eng.wave_stream_reset_slots(state, slots, count=count)
+            return state
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db)
         if int(fs) != 16000:
             return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db)
         return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db)
 
-    def step_wave(self, x, state):
+    def step_wave(self, x, state, slots=None, count=None):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a
         state made for another rate: hops of state.hop samples at that rate, state.latency samples late.  With a packet
-        state: exactly one packet of state.packet samples per stream, state.latency16 samples (at 16 kHz) late."""
+        state: exactly one packet of state.packet samples per stream, state.latency16 samples (at 16 kHz) late.
+        slots= (int32 device tensor, M ids), count= (device int32, optional): the live tick of a server -- x (M, 256), row i
+        is the stream in slot slots[i] of the 16 kHz `state`, `count` rows step, no other slot is touched
+        (Engine.wave_stream_step_slots).  Rate and packet states raise: their streams share a group phase."""
+        if slots is not None:
+            return self.engine(x.device).wave_stream_step_slots(state, slots, x, count=count)
         if isinstance(state, _lib.PacketStreamState):
             return self.engine(x.device).packet_stream_step(state, x)
         if isinstance(state, _lib.RateStreamState):
             return self.engine(x.device).rate_stream_step(state, x)
         return self.engine(x.device).wave_stream_step(state, x)
 
-    def flush_wave(self, tail, state):
-        """tail (N, r), r = 0..255 samples after the last whole hop -> the last 256 enhanced samples per stream."""
+    def flush_wave(self, tail, state, slots=None, count=None):
+        """tail (N, r), r = 0..255 samples after the last whole hop -> the last 256 enhanced samples per stream.
+        slots=, count=: the named streams of a 16 kHz state leave (Engine.wave_stream_flush_slots); tail is (M, r)."""
+        if slots is not None:
+            return self.engine(tail.device).wave_stream_flush_slots(state, slots, tail, count=count)
         return self.engine(tail.device).wave_stream_flush(state, tail)

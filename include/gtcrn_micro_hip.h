@@ -406,6 +406,56 @@ int gtcrn_rate_stream_step_limited_pcm16(gtcrn_model *m, gtcrn_resampler *in, gt
                                          void *stream);
 int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream *ps, const float *d_gain);
 
+/* ---- stream slots: step any subset of the resident live streams per call -----------------------------------------------
+ * The contiguous live calls step every stream of a state range.  In a server some streams have no packet this tick and
+ * streams join and leave all the time; the _slots calls leave every state where it is and take, per call, a device array
+ * naming the slots that step and a device word saying how many:
+ *   d_slots     int32[max_active] on the device: row i of the call is the stream whose model state sits at
+ *               d_state + d_slots[i] * gtcrn_stream_state_bytes() and whose wave state at
+ *               d_wstate + d_slots[i] * gtcrn_wave_stream_state_bytes();
+ *   d_count     one int32 on the device, clamped on the device to 0 .. max_active: rows at or beyond it are neither read
+ *               nor written (their slots, input and output rows alike).  NULL: max_active rows step;
+ *   max_active  >= 1: the host sizes the grid, the workspace (gtcrn_model_reserve(m, max_active, 1)) and the kernel form
+ *               from it alone, so ONE captured graph serves a changing active set: rewrite d_slots, d_count and the input
+ *               rows between replays.
+ * Sample and spectrum rows are COMPACT: row i of d_in / d_out / d_spec_t belongs to slot d_slots[i].  d_gain (may be NULL:
+ * no limit) is indexed BY SLOT, d_gain[d_slots[i]]: gains belong to the stream, not to the call.
+ * Contract:
+ *   - per slot, the sequence of calls that name it IS the contiguous stream of the same inputs: the outputs are those of
+ *     gtcrn_wave_stream_step (gtcrn_stream_step) on a state holding that one stream, bit for bit, i.e.
+ *     gtcrn_forward_wave (gtcrn_forward_wave_limited with a gain) one hop late;
+ *   - a slot not named in a call is not touched, byte for byte;
+ *   - the ids are in range and distinct within a call: the caller's precondition, as win[0] == 0 is (the library cannot
+ *     read device memory without a synchronisation).  A repeated id gives undefined results for that slot, an id out of
+ *     range is a memory error.  Sorted ids are recommended for locality and are not required.
+ * gtcrn_stream_reset_slots zeroes the model state and, when d_wstate is given, the wave state of the listed slots with a
+ * kernel (gtcrn_stream_reset / gtcrn_wave_stream_reset use a memset on a contiguous range), so a captured graph can admit
+ * a stream at any slot.  The flush emits the named streams' last 256 samples (r = 0..255 tail samples per row) and leaves
+ * their states as they are: reset a slot before it is reused.
+ * All calls are asynchronous on `stream`, allocate nothing once gtcrn_model_reserve(m, max_active, 1) was called, and can
+ * be captured.  One hop (frame) per call: this is the live tick.  Only the single-launch forms exist indexed: after
+ * gtcrn_stream_form(m, 1), or with gtcrn_debug_enable(m, 1), the step calls return GTCRN_ERR_STATE.  Argument errors
+ * (null pointers, max_active < 1, short strides, misaligned states, r outside 0..255) return GTCRN_ERR_ARG before any
+ * launch.  Out of scope: the rate and packet forms (their streams share a group phase), several hops per call. */
+int gtcrn_stream_step_slots(gtcrn_model *m, void *d_state, const int *d_slots, const int *d_count, int max_active,
+                            const float *d_spec_t, long isb, long isf, long ist, float *d_spec_out_t, long osb, long osf,
+                            long ost, void *stream);   /* one frame per row: (max_active,257,1,2) by strides */
+int gtcrn_stream_reset_slots(gtcrn_model *m, void *d_state, void *d_wstate /* may be NULL */, const int *d_slots,
+                             const int *d_count, int max_active, void *stream);
+int gtcrn_wave_stream_step_slots(gtcrn_model *m, void *d_state, void *d_wstate, const int *d_slots, const int *d_count,
+                                 int max_active, const float *d_in, long in_stride, float *d_out, long out_stride,
+                                 const float *d_gain /* per SLOT, may be NULL */, const float *d_win, void *stream);
+int gtcrn_wave_stream_step_slots_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const int *d_slots,
+                                       const int *d_count, int max_active, const short *d_in, long in_stride, short *d_out,
+                                       long out_stride, const float *d_gain, const float *d_win, void *stream);
+int gtcrn_wave_stream_flush_slots(gtcrn_model *m, void *d_state, void *d_wstate, const int *d_slots, const int *d_count,
+                                  int max_active, const float *d_tail, long tail_stride, int r, float *d_out,
+                                  long out_stride, const float *d_gain, const float *d_win, void *stream);
+int gtcrn_wave_stream_flush_slots_pcm16(gtcrn_model *m, void *d_state, void *d_wstate, const int *d_slots,
+                                        const int *d_count, int max_active, const short *d_tail, long tail_stride, int r,
+                                        short *d_out, long out_stride, const float *d_gain, const float *d_win,
+                                        void *stream);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),

@@ -1,0 +1,70 @@
+"""Compares the gfx950 device assembly of kernels.hip between two source trees, kernel by kernel.
+
+    hipcc --offload-arch=gfx950 <the flags of gtcrn_micro_amd/build.py for kernels.hip> --cuda-device-only -S \
+          OLD/gtcrn_micro_amd/csrc/kernels.hip -o old.s        (and the same for the new tree -> new.s)
+    python tools/asm_compare.py old.s new.s [--drop-arg false]
+
+A kernel is its instruction lines in order: comments and assembler directives dropped, branch labels renumbered by
+position.  Kernels pair up by demangled name without the argument list.  --drop-arg VALUE: a kernel template of the
+new file that gained one trailing template argument pairs with the old kernel when that argument is VALUE (only where
+the old file has no kernel of the full name).  Kernels only the new file has are counted, not compared.
+Prints one row per kernel of the old file and a summary line; exit status 1 if any kernel differs or is missing.
+Needs c++filt on the PATH and no GPU.
+"""
+import argparse
+import re
+import subprocess
+import sys
+
+
+def kernels(path):
+    out = {}
+    for m in re.finditer(r"^(\S+):\s*; @\S+\n(.*?)^\.Lfunc_end\d+:", open(path).read(), re.S | re.M):
+        lines, labels = [], {}
+        for ln in m.group(2).splitlines():
+            ln = ln.split(";")[0].strip()
+            if not ln or (ln.startswith(".") and not ln.startswith(".LBB")):
+                continue
+            ln = re.sub(r"\.LBB\d+_\d+", lambda t: labels.setdefault(t.group(0), f".L{len(labels)}"), ln)
+            lines.append(ln)
+        out[m.group(1)] = lines
+    return out
+
+
+def demangled(names):
+    r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
+    return [re.sub(r"\(.*$", "", d) for d in r.stdout.splitlines()]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--drop-arg", default=None)
+    a = ap.parse_args()
+    old, new = kernels(a.old), kernels(a.new)
+    old = dict(zip(demangled(list(old)), old.values()))
+    new = dict(zip(demangled(list(new)), new.values()))
+    if a.drop_arg:
+        for k in list(new):
+            short = re.sub(r", %s>$" % re.escape(a.drop_arg), ">", k)
+            if short != k and k not in old and short in old and short not in new:
+                new[short] = new.pop(k)
+    same = bad = 0
+    for k in sorted(old):
+        if k not in new:
+            bad += 1
+            print(f"MISSING {len(old[k]):6d}            {k}")
+        elif old[k] == new[k]:
+            same += 1
+            print(f"same    {len(old[k]):6d}            {k}")
+        else:
+            bad += 1
+            print(f"DIFFER  {len(old[k]):6d} -> {len(new[k]):6d}  {k}")
+    print(f"{same} of {len(old)} kernels compile to the same instructions ({sum(map(len, old.values()))} lines); "
+          f"{bad} differ or are missing; {len(set(new) - set(old))} kernels are new")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

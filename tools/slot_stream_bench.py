@@ -1,0 +1,130 @@
+"""Stream slots (gtcrn_wave_stream_step_slots) against the contiguous wave step, at N resident wave streams (default 65 536).
+
+Same process, same GPU, one hop per stream and step, device events over `--iters` steps, warm-up first, the four cases
+alternating for `--reps` repetitions; medians:
+  (a) the contiguous step of all N streams;
+  (b) the indexed step of all N streams, ids in identity order;
+  (c) the indexed step of a sorted random half;
+  (d) the contiguous step of N / 2 compact streams -- what a caller gets today after paying for compaction.
+(b)/(a) is what the indirection costs, (c)/(d) what stepping a subset in place costs against stepping it compacted.
+
+--parent-lib PATH: the regression check of case (a) against the parent commit's library on the same GPU: fresh child
+processes, new and parent library alternating, `--reps` each; both medians go into the JSON.
+--contiguous-only [--lib PATH]: what such a child runs (case (a) alone, one JSON line).
+Writes profiles/slot_stream_bench.json.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def spread(v):
+    return (max(v) - min(v)) / statistics.median(v)
+
+
+def engine(lib_path=None):
+    from gtcrn_micro_amd import _lib
+    if lib_path:
+        _lib.LIB_PATH = os.path.abspath(lib_path)
+    params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
+    return _lib.Engine(params, 0), torch.hann_window(512).pow(0.5).cuda()
+
+
+def contiguous_only(a):
+    eng, win = engine(a.lib)
+    N = a.streams
+    eng.reserve(N, 1)
+    x = torch.randn(N, 256, device="cuda") * 0.1
+    y = torch.empty_like(x)
+    st = eng.new_wave_state(N, win)
+    step = lambda: eng.wave_stream_step(st, x, out=y)              # noqa: E731
+    timed(step, max(3, a.iters // 4))
+    t = [timed(step, a.iters) for _ in range(a.reps)]
+    print(json.dumps({"lib": a.lib or "default", "N": N, "contiguous_ms": statistics.median(t), "reps_ms": t}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=65536)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "slot_stream_bench.json"))
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--contiguous-only", action="store_true")
+    ap.add_argument("--lib", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("slot_stream_bench needs the GPU (nothing is measured on the CPU)")
+    if a.contiguous_only:
+        return contiguous_only(a)
+    eng, win = engine()
+    N, H = a.streams, a.streams // 2
+    eng.reserve(N, 1)
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    st = eng.new_wave_state(N, win)
+    half = eng.new_wave_state(H, win)
+    ident = torch.arange(N, dtype=torch.int32, device="cuda")
+    pick = torch.sort(torch.randperm(N, device="cuda", generator=gen)[:H]).values.to(torch.int32)
+    cnt_all, cnt_half = torch.tensor([N], dtype=torch.int32, device="cuda"), torch.tensor([H], dtype=torch.int32, device="cuda")
+    xh, yh = x[:H], y[:H]
+    cases = {
+        "a_contiguous_all": lambda: eng.wave_stream_step(st, x, out=y),
+        "b_indexed_all_identity": lambda: eng.wave_stream_step_slots(st, ident, x, count=cnt_all, out=y),
+        "c_indexed_sorted_half": lambda: eng.wave_stream_step_slots(st, pick, xh, count=cnt_half, out=yh),
+        "d_contiguous_half_compact": lambda: eng.wave_stream_step(half, xh, out=yh),
+    }
+    for f in cases.values():
+        timed(f, max(3, a.iters // 4))                             # warm-up
+    t = {k: [] for k in cases}
+    for _ in range(a.reps):
+        for k, f in cases.items():
+            t[k].append(timed(f, a.iters))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    res = {"device": torch.cuda.get_device_name(0), "N": N, "half": H, "iters": a.iters, "reps": a.reps,
+           "ms": med, "reps_ms": t, "spread": {k: spread(v) for k, v in t.items()},
+           "b_over_a": med["b_indexed_all_identity"] / med["a_contiguous_all"],
+           "c_over_d": med["c_indexed_sorted_half"] / med["d_contiguous_half_compact"]}
+    print(json.dumps({k: v for k, v in res.items() if k != "reps_ms"}), flush=True)
+    del st, half, cases
+    torch.cuda.empty_cache()
+    if a.parent_lib:
+        runs = {"new": [], "parent": []}
+        for _ in range(2):
+            for tag, lib in (("new", None), ("parent", a.parent_lib)):
+                cmd = [sys.executable, os.path.abspath(__file__), "--contiguous-only", "--streams", str(N), "--iters", str(a.iters),
+                       "--reps", str(a.reps)] + (["--lib", lib] if lib else [])
+                out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300).stdout
+                runs[tag].append(json.loads(out.strip().splitlines()[-1])["contiguous_ms"])
+        res["parent_check"] = {"new_ms": statistics.median(runs["new"]), "parent_ms": statistics.median(runs["parent"]),
+                               "new_runs_ms": runs["new"], "parent_runs_ms": runs["parent"]}
+        res["parent_check"]["new_over_parent"] = res["parent_check"]["new_ms"] / res["parent_check"]["parent_ms"]
+        print(json.dumps(res["parent_check"]), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
