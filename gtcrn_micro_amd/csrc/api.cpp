@@ -45,13 +45,18 @@ struct Timing {
     int kernel = 0;  // index into kKernelNames
     hipEvent_t a = nullptr, b = nullptr;
 };
-// every timed launch records WHICH kernel it was (mixed offline / streaming calls keep their own rows)
-enum KernelId { K_STFT, K_ENCODER, K_GTCN1, K_GTCN2, K_DECODER, K_ISTFT, K_FRONT, K_ENCODER_GT, K_GTCN_MS, K_STREAM_MS, K_STREAM_WIDE,
-                K_WAVE_ANALYSIS, K_WAVE_SYNTHESIS, K_PACKET_IN, K_PACKET_OUT, K_WAVE_SYNTHESIS_MIX, K_ISTFT_MIX, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"k_stft",  "k_encoder",    "k_gtcn1",   "k_gtcn2",    "k_decoder",
-                                           "k_istft", "k_front",      "k_encoder_gt", "k_gtcn_ms", "k_stream_ms",
-                                           "k_stream_wide", "k_wave_analysis", "k_wave_synthesis", "k_packet_in",
-                                           "k_packet_out", "k_wave_synthesis_mix", "k_istft_mix"};
+// every timed launch records WHICH kernel it was (mixed offline / streaming calls keep their own rows).  The order is ABI:
+// gtcrn_timing_enable(m, 2 + k) and gtcrn_timing_read address a kernel by its index, so new rows go at the end.
+#define GT_KERNELS(X)                                                                                                     \
+    X(K_STFT, "k_stft") X(K_ENCODER, "k_encoder") X(K_GTCN1, "k_gtcn1") X(K_GTCN2, "k_gtcn2") X(K_DECODER, "k_decoder")   \
+    X(K_ISTFT, "k_istft") X(K_FRONT, "k_front") X(K_ENCODER_GT, "k_encoder_gt") X(K_GTCN_MS, "k_gtcn_ms")                 \
+    X(K_STREAM_MS, "k_stream_ms") X(K_STREAM_WIDE, "k_stream_wide") X(K_WAVE_ANALYSIS, "k_wave_analysis")                 \
+    X(K_WAVE_SYNTHESIS, "k_wave_synthesis") X(K_PACKET_IN, "k_packet_in") X(K_PACKET_OUT, "k_packet_out")                 \
+    X(K_WAVE_SYNTHESIS_MIX, "k_wave_synthesis_mix") X(K_ISTFT_MIX, "k_istft_mix")
+#define GT_KERNEL_ID(id, name) id,
+#define GT_KERNEL_NAME(id, name) name,
+enum KernelId { GT_KERNELS(GT_KERNEL_ID) K_COUNT };
+const char* const kKernelNames[K_COUNT] = {GT_KERNELS(GT_KERNEL_NAME)};
 constexpr int kNumKernels = K_COUNT;
 
 }  // namespace
@@ -111,13 +116,27 @@ void free_workspace(gtcrn_model* m) {
     m->cap_bt = 0;
 }
 
+// A buffer has to grow: refused while `s` is being captured (`what` says which reserve call was missing), otherwise the
+// device is drained so that the caller may free and allocate.
+int before_growing(hipStream_t s, const char* what) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return fail(GTCRN_ERR_STATE, what);
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
+// every state buffer of the live calls is read and written with 16-byte accesses
+int check_state_alignment(const std::string& w, std::initializer_list<const void*> states) {
+    uintptr_t bits = 0;
+    for (const void* p : states) bits |= reinterpret_cast<uintptr_t>(p);
+    if (bits & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    return 0;
+}
+
 int ensure_workspace(gtcrn_model* m, int B, int T, hipStream_t s) {
     const long bt = (long)B * T;
     if (bt > m->cap_bt) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return fail(GTCRN_ERR_STATE, "workspace too small during stream capture: call gtcrn_model_reserve first");
-        HIP_TRY(hipDeviceSynchronize());
+        if (int rc = before_growing(s, "workspace too small during stream capture: call gtcrn_model_reserve first")) return rc;
         free_workspace(m);
         HIP_TRY(hipMalloc(&m->d_en0, sizeof(float) * bt * 65 * 16));
         for (int i = 0; i < 4; ++i) HIP_TRY(hipMalloc(&m->d_en[i], sizeof(float) * bt * 528));
@@ -181,29 +200,39 @@ static bool stream_wide_pays(int B) {
     return (double)r7 * WIDE_COST < (double)r4;
 }
 
+// Single-frame steps run as ONE launch, nothing handed over through HBM, unless the three-launch form is asked for
+// (gtcrn_stream_form 1, or the stage taps of the parity tests, which read the hand-off tensors).
+bool fused_stream_allowed(const gtcrn_model* m) { return (!m->debug || m->debug_keep_fused) && m->stream_form != 1; }
+
+// The single-launch step of B streams (rows.slots: of the max_active = B rows the table names): picks the form, brackets the
+// launch for the timing rows and records what the last forward was.  The caller has checked fused_stream_allowed and
+// gtk::stream_ms_usable.
+int fused_stream_step(gtcrn_model* m, const float* spec_in, long isb, long isf, float* spec_out, long osb, long osf, int B,
+                      float* state, gtk::Rows rows, hipStream_t s) {
+    const bool wide = m->stream_form == 3 || (m->stream_form == 0 && stream_wide_pays(B));
+    unsigned long long* stamps = (m->debug && m->d_stamps) ? m->d_stamps : nullptr;
+    Timer tm(m, s);
+    tm.begin(wide ? K_STREAM_WIDE : K_STREAM_MS);
+    LAUNCH_TRY(gtk::launch_stream_step(wide, spec_in, isb, isf, spec_out, osb, osf, B, m->d_pf, m->d_pi, state, stamps, rows, s));
+    tm.end();
+    m->last_quant = false;
+    m->last_fused_stream = true;
+    m->last_B = B;
+    m->last_T = 1;
+    return 0;
+}
+
 // the five model kernels on one stream; state == nullptr for offline
 int run_model(gtcrn_model* m, const float* spec_in, long isb, long isf, long ist, float* spec_out, long osb, long osf,
               long ost, int B, int T, float* state, hipStream_t s, const int* lens = nullptr,
               const gtk::Quant* q = nullptr, bool front_done = false) {
+    if (state && T == 1 && !q && fused_stream_allowed(m) && gtk::stream_ms_usable(isb, osb))
+        return fused_stream_step(m, spec_in, isb, isf, spec_out, osb, osf, B, state, gtk::Rows{}, s);
     Timer tm(m, s);
     const float* pf = q ? m->d_pfq : m->d_pf;
     const bool offline = !state;
     m->last_quant = q != nullptr;
     m->last_fused_stream = false;
-    // single-frame streaming step: ONE launch, nothing handed over through HBM (the three-launch form below remains
-    // for the stage taps of the parity tests, which read the hand-off tensors)
-    if (state && T == 1 && !q && (!m->debug || m->debug_keep_fused) && m->stream_form != 1 && gtk::stream_ms_usable(isb, osb)) {
-        const bool wide = m->stream_form == 3 || (m->stream_form == 0 && stream_wide_pays(B));
-        unsigned long long* stamps = (m->debug && m->d_stamps) ? m->d_stamps : nullptr;
-        tm.begin(wide ? K_STREAM_WIDE : K_STREAM_MS);
-        if (wide) LAUNCH_TRY(gtk::launch_stream_wide(spec_in, isb, isf, spec_out, osb, osf, B, pf, m->d_pi, state, stamps, s));
-        else LAUNCH_TRY(gtk::launch_stream_ms(spec_in, isb, isf, spec_out, osb, osf, B, pf, m->d_pi, state, stamps, s));
-        tm.end();
-        m->last_fused_stream = true;
-        m->last_B = B;
-        m->last_T = T;
-        return 0;
-    }
     if (offline) {
         // offline: the frame-independent front end runs as a throughput kernel (fused with the STFT by
         // forward_wave_impl, which passes front_done), the per-utterance kernel keeps the three GTConv blocks
@@ -260,6 +289,17 @@ int run_model(gtcrn_model* m, const float* spec_in, long isb, long isf, long ist
     m->last_B = B;
     m->last_T = T;
     return 0;
+}
+
+// 256 complex twiddles of the 256-point FFT, then 256 of the real split's 512-point ones
+void make_twiddles(std::vector<float>& tw) {
+    tw.resize(1024);
+    for (int k = 0; k < 256; ++k) {
+        tw[2 * k] = (float)std::cos(-2.0 * M_PI * k / 256.0);
+        tw[2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 256.0);
+        tw[512 + 2 * k] = (float)std::cos(-2.0 * M_PI * k / 512.0);
+        tw[512 + 2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 512.0);
+    }
 }
 
 int check_model(gtcrn_model* m) {
@@ -344,13 +384,8 @@ int gtcrn_model_create(gtcrn_model** out, const float* h_params, long n_floats, 
         gtcrn_model_destroy(m);
         return hip_fail(e, "hipMalloc(params)");
     }
-    std::vector<float> tw(1024);
-    for (int k = 0; k < 256; ++k) {
-        tw[2 * k] = (float)std::cos(-2.0 * M_PI * k / 256.0);
-        tw[2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 256.0);
-        tw[512 + 2 * k] = (float)std::cos(-2.0 * M_PI * k / 512.0);
-        tw[512 + 2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 512.0);
-    }
+    std::vector<float> tw;
+    make_twiddles(tw);
     e = hipMemcpy(m->d_twid, tw.data(), sizeof(float) * 1024, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         gtcrn_model_destroy(m);
@@ -425,13 +460,8 @@ int device_twiddles(float** out) {
     if (dev < 0 || dev >= 16) return fail(GTCRN_ERR_DEVICE, "device ordinal >= 16");
     std::lock_guard<std::mutex> lock(g_twid_mu);
     if (!g_twid[dev]) {
-        std::vector<float> tw(1024);
-        for (int k = 0; k < 256; ++k) {
-            tw[2 * k] = (float)std::cos(-2.0 * M_PI * k / 256.0);
-            tw[2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 256.0);
-            tw[512 + 2 * k] = (float)std::cos(-2.0 * M_PI * k / 512.0);
-            tw[512 + 2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / 512.0);
-        }
+        std::vector<float> tw;
+        make_twiddles(tw);
         float* d = nullptr;
         HIP_TRY(hipMalloc(&d, sizeof(float) * 1024));
         HIP_TRY(hipMemcpy(d, tw.data(), sizeof(float) * 1024, hipMemcpyHostToDevice));
@@ -617,126 +647,126 @@ int gtcrn_wave_stream_reset(gtcrn_model* m, void* d_state, void* d_wstate, int n
     return 0;
 }
 
+// Stream slots (contract: include/gtcrn_micro_hip.h): row i of a call is the stream whose states sit in slot d_slots[i];
+// *d_count rows (clamped to 0..max_active on the device) step.  The host sizes the grid, the workspace and the form from
+// max_active alone, so one captured graph serves any active set.  Only the single-launch step exists indexed.
+namespace {
+int slots_args(const std::string& w, gtcrn_model* m, const void* d_state, const void* d_wstate, const int* d_slots,
+               int max_active) {
+    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
+    if (!d_state || !d_slots) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (max_active < 1) return fail(GTCRN_ERR_ARG, w + ": max_active must be >= 1");
+    return check_state_alignment(w, {d_state, d_wstate});
+}
+int refuse_three_launch_form(const std::string& w, const gtcrn_model* m) {
+    if (fused_stream_allowed(m)) return 0;
+    return fail(GTCRN_ERR_STATE, w + ": the three-launch form (gtcrn_stream_form 1, gtcrn_debug_enable 1) has no indexed step");
+}
+}  // namespace
+
+// Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given) of n rows.
+// Without a table the rows are the n streams of a contiguous state range, nhops hops each; with one (the _slots calls)
+// they are the n = max_active rows it names, one hop.
 extern "C++" template <typename S>
-static int wave_stream_impl(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const S* d_in, long in_stride,
-                            S* d_out, long out_stride, int nstreams, int nhops, bool flush, int r, const float* d_win,
-                            void* stream, const float* d_gain = nullptr) {
+static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const S* d_in, long in_stride, S* d_out,
+                     long out_stride, int n, int nhops, bool flush, int r, const float* d_gain, const float* d_win,
+                     gtk::Rows rows, void* stream) {
     const std::string w(who);
+    const bool indexed = rows.slots != nullptr;
     if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
     if (!d_state || !d_wstate || !d_out || !d_win || (!d_in && !(flush && r == 0)))
         return fail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, w + ": nstreams and nhops must be >= 1");
+    if (n < 1 || nhops < 1)
+        return fail(GTCRN_ERR_ARG, w + (indexed ? ": max_active must be >= 1" : ": nstreams and nhops must be >= 1"));
     if (flush && (r < 0 || r > 255)) return fail(GTCRN_ERR_ARG, w + ": the tail holds r = 0..255 samples");
     if (in_stride < (flush ? r : 256L * nhops) || out_stride < 256L * (flush ? 1 : nhops))
         return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate)) & 15)
-        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    if (int rc0 = check_state_alignment(w, {d_state, d_wstate})) return rc0;
     int rc = check_model(m);
     if (rc) return rc;
+    if (indexed && (rc = refuse_three_launch_form(w, m))) return rc;      // (before the analysis launch: nothing runs on a refusal)
     hipStream_t s = (hipStream_t)stream;
-    rc = ensure_workspace(m, nstreams, nhops, s);
+    rc = ensure_workspace(m, n, nhops, s);
     if (rc) return rc;
-    const long sb = (long)nhops * 514, sf = 2, st = 514;      // frame-major (N, nhops, 257, 2)
+    const long sb = (long)nhops * 514, sf = 2, st = 514;      // frame-major (n, nhops, 257, 2)
     float* ws = static_cast<float*>(d_wstate);
+    float* ms = static_cast<float*>(d_state);
     Timer tm(m, s);
     tm.begin(K_WAVE_ANALYSIS);
-    LAUNCH_TRY(gtk::launch_wave_analysis<S>(d_in, in_stride, nstreams, nhops, r, flush, ws, d_win, m->d_twid, m->d_spec_a, s));
+    LAUNCH_TRY(gtk::launch_wave_analysis<S>(d_in, in_stride, n, nhops, r, flush, ws, d_win, m->d_twid, m->d_spec_a, rows, s));
     tm.end();
-    rc = run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, nstreams, nhops, static_cast<float*>(d_state), s);
+    rc = indexed ? fused_stream_step(m, m->d_spec_a, sb, sf, m->d_spec_b, sb, sf, n, ms, rows, s)
+                 : run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, n, nhops, ms, s);
     if (rc) return rc;
     tm.begin(d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
-    LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, nstreams, nhops, r, flush, ws,
-                                             d_win, m->d_twid, s, d_gain));
+    LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, n, nhops, r, flush, ws, d_win,
+                                             m->d_twid, rows, d_gain, s));
     tm.end();
     return 0;
+}
+// a _slots entry point: one hop of the max_active rows the table names
+extern "C++" template <typename S>
+static int wave_step_slots(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots,
+                           const int* d_count, int max_active, const S* d_in, long in_stride, S* d_out, long out_stride,
+                           bool flush, int r, const float* d_gain, const float* d_win, void* stream) {
+    if (m && !d_slots) return fail(GTCRN_ERR_ARG, std::string(who) + ": null pointer");
+    return wave_step<S>(who, m, d_state, d_wstate, d_in, in_stride, d_out, out_stride, max_active, 1, flush, r, d_gain, d_win,
+                        gtk::Rows{d_slots, d_count}, stream);
 }
 
 int gtcrn_wave_stream_step(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_in, long in_stride, float* d_out,
                            long out_stride, int nstreams, int nhops, const float* d_win, void* stream) {
-    return wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
-                                   nstreams, nhops, false, 0, d_win, stream);
+    return wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                            nstreams, nhops, false, 0, nullptr, d_win, {}, stream);
 }
 int gtcrn_wave_stream_step_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_in, long in_stride,
                                  short* d_out, long out_stride, int nstreams, int nhops, const float* d_win, void* stream) {
-    return wave_stream_impl<short>("gtcrn_wave_stream_step_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
-                                   nstreams, nhops, false, 0, d_win, stream);
+    return wave_step<short>("gtcrn_wave_stream_step_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                            nstreams, nhops, false, 0, nullptr, d_win, {}, stream);
 }
 int gtcrn_wave_stream_flush(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_tail, long tail_stride, int r,
                             float* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
-    return wave_stream_impl<float>("gtcrn_wave_stream_flush", m, d_state, d_wstate, d_tail, tail_stride, d_out, out_stride,
-                                   nstreams, 1, true, r, d_win, stream);
+    return wave_step<float>("gtcrn_wave_stream_flush", m, d_state, d_wstate, d_tail, tail_stride, d_out, out_stride,
+                            nstreams, 1, true, r, nullptr, d_win, {}, stream);
 }
 int gtcrn_wave_stream_flush_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_tail, long tail_stride, int r,
                                   short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
-    return wave_stream_impl<short>("gtcrn_wave_stream_flush_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
-                                   out_stride, nstreams, 1, true, r, d_win, stream);
+    return wave_step<short>("gtcrn_wave_stream_flush_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                            out_stride, nstreams, 1, true, r, nullptr, d_win, {}, stream);
 }
 
 // the attenuation-limited forms: d_gain holds one dry gain per stream (NULL: the plain call)
 int gtcrn_wave_stream_step_limited(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_in, long in_stride,
                                    float* d_out, long out_stride, int nstreams, int nhops, const float* d_gain,
                                    const float* d_win, void* stream) {
-    return wave_stream_impl<float>("gtcrn_wave_stream_step_limited", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
-                                   nstreams, nhops, false, 0, d_win, stream, d_gain);
+    return wave_step<float>("gtcrn_wave_stream_step_limited", m, d_state, d_wstate, d_in, in_stride, d_out, out_stride,
+                            nstreams, nhops, false, 0, d_gain, d_win, {}, stream);
 }
 int gtcrn_wave_stream_step_limited_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_in, long in_stride,
                                          short* d_out, long out_stride, int nstreams, int nhops, const float* d_gain,
                                          const float* d_win, void* stream) {
-    return wave_stream_impl<short>("gtcrn_wave_stream_step_limited_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out,
-                                   out_stride, nstreams, nhops, false, 0, d_win, stream, d_gain);
+    return wave_step<short>("gtcrn_wave_stream_step_limited_pcm16", m, d_state, d_wstate, d_in, in_stride, d_out,
+                            out_stride, nstreams, nhops, false, 0, d_gain, d_win, {}, stream);
 }
 int gtcrn_wave_stream_flush_limited(gtcrn_model* m, void* d_state, void* d_wstate, const float* d_tail, long tail_stride,
                                     int r, float* d_out, long out_stride, int nstreams, const float* d_gain,
                                     const float* d_win, void* stream) {
-    return wave_stream_impl<float>("gtcrn_wave_stream_flush_limited", m, d_state, d_wstate, d_tail, tail_stride, d_out,
-                                   out_stride, nstreams, 1, true, r, d_win, stream, d_gain);
+    return wave_step<float>("gtcrn_wave_stream_flush_limited", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                            out_stride, nstreams, 1, true, r, d_gain, d_win, {}, stream);
 }
 int gtcrn_wave_stream_flush_limited_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const short* d_tail, long tail_stride,
                                           int r, short* d_out, long out_stride, int nstreams, const float* d_gain,
                                           const float* d_win, void* stream) {
-    return wave_stream_impl<short>("gtcrn_wave_stream_flush_limited_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
-                                   out_stride, nstreams, 1, true, r, d_win, stream, d_gain);
+    return wave_step<short>("gtcrn_wave_stream_flush_limited_pcm16", m, d_state, d_wstate, d_tail, tail_stride, d_out,
+                            out_stride, nstreams, 1, true, r, d_gain, d_win, {}, stream);
 }
 
-// ---- stream slots: the same steps for the rows a call names (contract: include/gtcrn_micro_hip.h) ---------------------------
-// Row i of a call is the stream whose states sit in slot d_slots[i]; *d_count rows (clamped to 0..max_active on the device)
-// step.  The host sizes the grid, the workspace and the form from max_active alone, so one captured graph serves any active set.
-namespace {
-int slots_args(const std::string& w, gtcrn_model* m, const void* d_state, const int* d_slots, int max_active) {
-    if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
-    if (!d_state || !d_slots) return fail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (max_active < 1) return fail(GTCRN_ERR_ARG, w + ": max_active must be >= 1");
-    if (reinterpret_cast<uintptr_t>(d_state) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
-    return 0;
-}
-// the single-launch model step of the named rows (spectra compact: row i of the call)
-int run_model_slots(const std::string& w, gtcrn_model* m, const float* spec_in, long isb, long isf, float* spec_out, long osb,
-                    long osf, int max_active, float* state, const int* slots, const int* cnt, hipStream_t s) {
-    if (m->stream_form == 1 || (m->debug && !m->debug_keep_fused))
-        return fail(GTCRN_ERR_STATE, w + ": the three-launch form (gtcrn_stream_form 1, gtcrn_debug_enable 1) has no indexed step");
-    if (!gtk::stream_ms_usable(isb, osb)) return fail(GTCRN_ERR_ARG, w + ": spectrogram row strides too large");
-    Timer tm(m, s);
-    const bool wide = m->stream_form == 3 || (m->stream_form == 0 && stream_wide_pays(max_active));
-    unsigned long long* stamps = (m->debug && m->d_stamps) ? m->d_stamps : nullptr;
-    m->last_quant = false;
-    tm.begin(wide ? K_STREAM_WIDE : K_STREAM_MS);
-    if (wide) LAUNCH_TRY(gtk::launch_stream_wide_slots(spec_in, isb, isf, spec_out, osb, osf, max_active, m->d_pf, m->d_pi, state,
-                                                       stamps, slots, cnt, s));
-    else LAUNCH_TRY(gtk::launch_stream_ms_slots(spec_in, isb, isf, spec_out, osb, osf, max_active, m->d_pf, m->d_pi, state, stamps,
-                                                slots, cnt, s));
-    tm.end();
-    m->last_fused_stream = true;
-    m->last_B = max_active;
-    m->last_T = 1;
-    return 0;
-}
-}  // namespace
-
+// ---- stream slots: the same steps for the rows a call names (slots_args, wave_step_slots above) ---------------------------
 int gtcrn_stream_step_slots(gtcrn_model* m, void* d_state, const int* d_slots, const int* d_count, int max_active,
                             const float* d_spec_t, long isb, long isf, long ist, float* d_spec_out_t, long osb, long osf,
                             long ost, void* stream) {
     const std::string w("gtcrn_stream_step_slots");
-    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
+    if (int rc0 = slots_args(w, m, d_state, nullptr, d_slots, max_active)) return rc0;
     if (!d_spec_t || !d_spec_out_t) return fail(GTCRN_ERR_ARG, w + ": null pointer");
     if (int rc0 = check_spec_layout(d_spec_t, isb, isf, ist)) return rc0;
     if (int rc0 = check_spec_layout(d_spec_out_t, osb, osf, ost)) return rc0;
@@ -745,15 +775,16 @@ int gtcrn_stream_step_slots(gtcrn_model* m, void* d_state, const int* d_slots, c
     hipStream_t s = (hipStream_t)stream;
     rc = ensure_workspace(m, max_active, 1, s);
     if (rc) return rc;
-    return run_model_slots(w, m, d_spec_t, isb, isf, d_spec_out_t, osb, osf, max_active, static_cast<float*>(d_state), d_slots,
-                           d_count, s);
+    if ((rc = refuse_three_launch_form(w, m))) return rc;
+    if (!gtk::stream_ms_usable(isb, osb)) return fail(GTCRN_ERR_ARG, w + ": spectrogram row strides too large");
+    return fused_stream_step(m, d_spec_t, isb, isf, d_spec_out_t, osb, osf, max_active, static_cast<float*>(d_state),
+                             gtk::Rows{d_slots, d_count}, s);
 }
 
 int gtcrn_stream_reset_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
                              int max_active, void* stream) {
     const std::string w("gtcrn_stream_reset_slots");
-    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
-    if (reinterpret_cast<uintptr_t>(d_wstate) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    if (int rc0 = slots_args(w, m, d_state, d_wstate, d_slots, max_active)) return rc0;
     int rc = check_model(m);
     if (rc) return rc;
     LAUNCH_TRY(gtk::launch_reset_slots(static_cast<float*>(d_state), static_cast<float*>(d_wstate), d_slots, d_count, max_active,
@@ -761,62 +792,29 @@ int gtcrn_stream_reset_slots(gtcrn_model* m, void* d_state, void* d_wstate, cons
     return 0;
 }
 
-extern "C++" template <typename S>
-static int wave_stream_slots_impl(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots,
-                                  const int* d_count, int max_active, const S* d_in, long in_stride, S* d_out, long out_stride,
-                                  bool flush, int r, const float* d_gain, const float* d_win, void* stream) {
-    const std::string w(who);
-    if (int rc0 = slots_args(w, m, d_state, d_slots, max_active)) return rc0;
-    if (!d_wstate || !d_out || !d_win || (!d_in && !(flush && r == 0))) return fail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (flush && (r < 0 || r > 255)) return fail(GTCRN_ERR_ARG, w + ": the tail holds r = 0..255 samples");
-    if (in_stride < (flush ? r : 256L) || out_stride < 256L) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if (reinterpret_cast<uintptr_t>(d_wstate) & 15) return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
-    int rc = check_model(m);
-    if (rc) return rc;
-    if (m->stream_form == 1 || (m->debug && !m->debug_keep_fused))      // (before the analysis launch: nothing runs on a refusal)
-        return fail(GTCRN_ERR_STATE, w + ": the three-launch form (gtcrn_stream_form 1, gtcrn_debug_enable 1) has no indexed step");
-    hipStream_t s = (hipStream_t)stream;
-    rc = ensure_workspace(m, max_active, 1, s);
-    if (rc) return rc;
-    const long sb = 514, sf = 2;                               // frame-major (max_active, 1, 257, 2), compact rows
-    float* ws = static_cast<float*>(d_wstate);
-    Timer tm(m, s);
-    tm.begin(K_WAVE_ANALYSIS);
-    LAUNCH_TRY(gtk::launch_wave_analysis_slots<S>(d_in, in_stride, max_active, r, flush, ws, d_win, m->d_twid, m->d_spec_a, d_slots,
-                                                  d_count, s));
-    tm.end();
-    rc = run_model_slots(w, m, m->d_spec_a, sb, sf, m->d_spec_b, sb, sf, max_active, static_cast<float*>(d_state), d_slots, d_count, s);
-    if (rc) return rc;
-    tm.begin(d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
-    LAUNCH_TRY(gtk::launch_wave_synthesis_slots<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, max_active, r, flush, ws, d_win,
-                                                   m->d_twid, d_slots, d_count, s, d_gain));
-    tm.end();
-    return 0;
-}
-
 int gtcrn_wave_stream_step_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
                                  int max_active, const float* d_in, long in_stride, float* d_out, long out_stride,
                                  const float* d_gain, const float* d_win, void* stream) {
-    return wave_stream_slots_impl<float>("gtcrn_wave_stream_step_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_in,
-                                         in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
+    return wave_step_slots<float>("gtcrn_wave_stream_step_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_in,
+                                  in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
 }
 int gtcrn_wave_stream_step_slots_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
                                        int max_active, const short* d_in, long in_stride, short* d_out, long out_stride,
                                        const float* d_gain, const float* d_win, void* stream) {
-    return wave_stream_slots_impl<short>("gtcrn_wave_stream_step_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
-                                         d_in, in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
+    return wave_step_slots<short>("gtcrn_wave_stream_step_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
+                                  d_in, in_stride, d_out, out_stride, false, 0, d_gain, d_win, stream);
 }
 int gtcrn_wave_stream_flush_slots(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
                                   int max_active, const float* d_tail, long tail_stride, int r, float* d_out, long out_stride,
                                   const float* d_gain, const float* d_win, void* stream) {
-    return wave_stream_slots_impl<float>("gtcrn_wave_stream_flush_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_tail,
-                                         tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
+    return wave_step_slots<float>("gtcrn_wave_stream_flush_slots", m, d_state, d_wstate, d_slots, d_count, max_active, d_tail,
+                                  tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
 }
 int gtcrn_wave_stream_flush_slots_pcm16(gtcrn_model* m, void* d_state, void* d_wstate, const int* d_slots, const int* d_count,
                                         int max_active, const short* d_tail, long tail_stride, int r, short* d_out,
                                         long out_stride, const float* d_gain, const float* d_win, void* stream) {
-    return wave_stream_slots_impl<short>("gtcrn_wave_stream_flush_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
-                                         d_tail, tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
+    return wave_step_slots<short>("gtcrn_wave_stream_flush_slots_pcm16", m, d_state, d_wstate, d_slots, d_count, max_active,
+                                  d_tail, tail_stride, d_out, out_stride, true, r, d_gain, d_win, stream);
 }
 
 // ---- sample-rate conversion ------------------------------------------------------------------------------------------
@@ -1012,10 +1010,8 @@ int rate_pair_check(const std::string& w, gtcrn_model* m, gtcrn_resampler* in, g
 int ensure_rate_workspace(gtcrn_model* m, int nstreams, int nhops, hipStream_t s) {
     const long need = (long)nstreams * nhops;
     if (need <= m->cap_rate) return 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(GTCRN_ERR_STATE, "rate hand-off buffers too small during stream capture: call gtcrn_rate_stream_reserve first");
-    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = before_growing(s, "rate hand-off buffers too small during stream capture: call gtcrn_rate_stream_reserve first"))
+        return rc;
     if (m->d_rate_a) (void)hipFree(m->d_rate_a);
     if (m->d_rate_b) (void)hipFree(m->d_rate_b);
     m->d_rate_a = m->d_rate_b = nullptr;
@@ -1065,8 +1061,7 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
     if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, w + ": nstreams and nhops must be >= 1");
     const int H = (int)(256L * in->fs_in / 16000);
     if (in_stride < (long)H * nhops || out_stride < (long)H * nhops) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate) | reinterpret_cast<uintptr_t>(d_rstate)) & 15)
-        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_rstate})) return rc0;
     int rc = check_model(m);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1077,8 +1072,8 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
     const long rs_stride = di.ntp + dout.ntp, row = 256L * nhops;
     LAUNCH_TRY(gtk::launch_rate_in<S>(d_in, in_stride, m->d_rate_a, row, rs, rs_stride, nstreams, nhops, H, di.up, di.down,
                                       di.ntp, in->d_taps, s));
-    rc = wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams,
-                                 nhops, false, 0, d_win, stream, d_gain);      // (the limit is mixed at 16 kHz)
+    rc = wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams,
+                          nhops, false, 0, d_gain, d_win, {}, stream);      // (the limit is mixed at 16 kHz)
     if (rc) return rc;
     LAUNCH_TRY(gtk::launch_rate_out<S>(m->d_rate_b, row, d_out, out_stride, rs + di.ntp, rs_stride, nstreams, nhops, H, dout.up,
                                        dout.down, dout.ntp, out->d_taps, s));
@@ -1267,8 +1262,7 @@ static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_
     if (nstreams < 1 || nstreams > ps->max_streams)
         return fail(GTCRN_ERR_ARG, w + ": nstreams must be >= 1 and at most the handle's max_streams");
     if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_wstate) | reinterpret_cast<uintptr_t>(d_pstate)) & 15)
-        return fail(GTCRN_ERR_ARG, w + ": the state buffers must be 16-byte aligned");
+    if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_pstate})) return rc0;
     gtcrn_model* m = ps->m;
     int rc = check_model(m);
     if (rc) return rc;
@@ -1284,8 +1278,8 @@ static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_
                                         p.in.down, p.in.ntp, ps->in ? ps->in->d_taps : nullptr, s));
     tm.end();
     if (h) {
-        rc = wave_stream_impl<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h,
-                                     false, 0, d_win, stream, ps->d_gain);
+        rc = wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h, false, 0,
+                              ps->d_gain, d_win, {}, stream);
         if (rc) return rc;
     }
     tm.begin(K_PACKET_OUT);

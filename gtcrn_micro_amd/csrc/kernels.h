@@ -62,6 +62,15 @@ int launch_pcm16_convert(const void* src, void* dst, long n, int dir, hipStream_
 int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, const int* lens, const float* win,
                  const float* twid, float* wave, hipStream_t s, const float* dry = nullptr, long dry_stride = 0,
                  const float* gain = nullptr);
+// Which streams a live launch steps.  slots == nullptr: rows 0 .. N-1 of the state range (the IDX = false kernels; cnt is
+// not read).  Otherwise (gtcrn_*_slots) row i is the stream whose state sits in slot slots[i] (device, int32[N], in range
+// and distinct); cnt (device int32, may be nullptr: N) is clamped to 0..N on the device and rows at or beyond it are neither
+// read nor written.  Spectrum / sample rows stay compact (row i of the call), gain is per SLOT, and a launch steps ONE hop /
+// frame: a launcher given a table and nhops != 1 returns hipErrorInvalidValue.
+struct Rows {
+    const int* slots = nullptr;
+    const int* cnt = nullptr;
+};
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
@@ -69,11 +78,11 @@ int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, con
 // mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
-                         const float* win, const float* twid, float* spec, hipStream_t s);
+                         const float* win, const float* twid, float* spec, Rows rows, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s,
-                          const float* gain = nullptr);
+                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
+                          hipStream_t s);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;
@@ -140,31 +149,11 @@ int launch_decoder(const float* xg, const float* en0, const float* en1, const fl
 // rounds of 256 workgroups, each taking an equal share of the frames that exist, instead of one workgroup per utterance.
 bool var_spans_usable(int B);
 int launch_len_prefix(const int* lens, int B, int T, int* pref, hipStream_t s);
-// single-frame streaming step of B streams as ONE launch (encoder -> both GTCN stacks -> decoder, nothing through HBM)
-int launch_stream_ms(const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
-                     const int* PI, float* state, unsigned long long* stamps, hipStream_t s);
-// the same step with stream_wide_streams() streams per workgroup (eight waves x two tiles, streamed parameters): the form
-// for stream counts that fill the chip more than once
-int launch_stream_wide(const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
-                       const int* PI, float* state, unsigned long long* stamps, hipStream_t s);
-// stream slots (gtcrn_*_slots): the same steps for the rows a call names -- row i is the stream whose state sits in slot
-// slots[i] (device, int32[max_active], in range and distinct); cnt (device int32, may be nullptr: max_active) is clamped to
-// 0..max_active on the device and rows at or beyond it are neither read nor written.  Spectrum / sample rows are compact
-// (row i of the call); gain is per SLOT.  One hop / frame per call.
-int launch_stream_ms_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active, const float* PF,
-                           const int* PI, float* state, unsigned long long* stamps, const int* slots, const int* cnt,
-                           hipStream_t s);
-int launch_stream_wide_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active,
-                             const float* PF, const int* PI, float* state, unsigned long long* stamps, const int* slots,
-                             const int* cnt, hipStream_t s);
-template <typename S>
-int launch_wave_analysis_slots(const S* in, long in_stride, int max_active, int r, bool flush, const float* wstate,
-                               const float* win, const float* twid, float* spec, const int* slots, const int* cnt,
-                               hipStream_t s);
-template <typename S>
-int launch_wave_synthesis_slots(const float* spec, const S* in, long in_stride, S* out, long out_stride, int max_active, int r,
-                                bool flush, float* wstate, const float* win, const float* twid, const int* slots,
-                                const int* cnt, hipStream_t s, const float* gain = nullptr);
+// single-frame streaming step of B streams as ONE launch (encoder -> both GTCN stacks -> decoder, nothing through HBM): four
+// streams per workgroup (k_stream_ms), or, wide, stream_wide_streams() of them (k_stream_wide: eight waves x two tiles,
+// streamed parameters), the form for stream counts that fill the chip more than once
+int launch_stream_step(bool wide, const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
+                       const int* PI, float* state, unsigned long long* stamps, Rows rows, hipStream_t s);
 // zeroes the model state and (wstate != nullptr) the wave state of the listed slots (k_reset_slots)
 int launch_reset_slots(float* state, float* wstate, const int* slots, const int* cnt, int max_active, hipStream_t s);
 int stream_wide_streams();

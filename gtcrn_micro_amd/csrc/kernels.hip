@@ -4382,70 +4382,51 @@ int launch_stft(const float* wave, int B, long L, int T, const int* lens, const 
     return 0;
 }
 
+// calls f(std::bool_constant<...>{}...) with the run-time flags as compile-time values: one spelling of a launch serves
+// every instantiation of its kernel template
+template <bool... Bs, class F>
+static void with_flags(F&& f) { f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, class F, class... R>
+static void with_flags(F&& f, bool b, R... rest) {
+    if (b) with_flags<Bs..., true>(f, rest...);
+    else with_flags<Bs..., false>(f, rest...);
+}
+
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
-                         const float* win, const float* twid, float* spec, hipStream_t s) {
+                         const float* win, const float* twid, float* spec, Rows rows, hipStream_t s) {
+    if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const long nframes = (long)N * nhops;
     const int per = FFT_WAVES * WAVE_FRAMES;
     const int grid = (int)((nframes + per - 1) / per);
     const float2* tw = reinterpret_cast<const float2*>(twid);
-    const int* nulli = nullptr;
-    if (flush) hipLaunchKernelGGL((k_wave_analysis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, N, 1, r, wstate, win, tw, spec, nulli, nulli);
-    else hipLaunchKernelGGL((k_wave_analysis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, N, nhops, 0, wstate, win, tw, spec, nulli, nulli);
+    with_flags([&](auto FLUSH, auto IDX) {
+        hipLaunchKernelGGL((k_wave_analysis<S, FLUSH.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, N,
+                           flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, spec, rows.slots, rows.cnt);
+    }, flush, rows.slots != nullptr);
     GT_LAUNCH_CHECK();
     return 0;
 }
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, hipStream_t s, const float* gain) {
+                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
+                          hipStream_t s) {
+    if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
-    const float* none = nullptr;
-    const int* nulli = nullptr;
-    if (gain) {
-        // a flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
-        if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw, gain, nulli, nulli);
-        else hipLaunchKernelGGL((k_wave_synthesis<S, false, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw, gain, nulli, nulli);
-    } else if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, 1, r, wstate, win, tw, none, nulli, nulli);
-    else hipLaunchKernelGGL((k_wave_synthesis<S, false>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, nhops, 0, wstate, win, tw, none, nulli, nulli);
+    // a mixed flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
+    with_flags([&](auto FLUSH, auto MIX, auto IDX) {
+        hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
+                           in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
+                           rows.cnt);
+    }, flush, gain != nullptr, rows.slots != nullptr);
     GT_LAUNCH_CHECK();
     return 0;
 }
-template <typename S>
-int launch_wave_analysis_slots(const S* in, long in_stride, int max_active, int r, bool flush, const float* wstate,
-                               const float* win, const float* twid, float* spec, const int* slots, const int* cnt,
-                               hipStream_t s) {
-    const int per = FFT_WAVES * WAVE_FRAMES;
-    const int grid = (max_active + per - 1) / per;
-    const float2* tw = reinterpret_cast<const float2*>(twid);
-    if (flush) hipLaunchKernelGGL((k_wave_analysis<S, true, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, max_active, 1, r, wstate, win, tw, spec, slots, cnt);
-    else hipLaunchKernelGGL((k_wave_analysis<S, false, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, in, in_stride, max_active, 1, 0, wstate, win, tw, spec, slots, cnt);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-template <typename S>
-int launch_wave_synthesis_slots(const float* spec, const S* in, long in_stride, S* out, long out_stride, int max_active, int r,
-                                bool flush, float* wstate, const float* win, const float* twid, const int* slots,
-                                const int* cnt, hipStream_t s, const float* gain) {
-    const int grid = (max_active + FFT_WAVES - 1) / FFT_WAVES;
-    const float2* tw = reinterpret_cast<const float2*>(twid);
-    const float* none = nullptr;
-    if (gain) {
-        if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true, true, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, max_active, 1, r, wstate, win, tw, gain, slots, cnt);
-        else hipLaunchKernelGGL((k_wave_synthesis<S, false, true, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, max_active, 1, 0, wstate, win, tw, gain, slots, cnt);
-    } else if (flush) hipLaunchKernelGGL((k_wave_synthesis<S, true, false, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, max_active, 1, r, wstate, win, tw, none, slots, cnt);
-    else hipLaunchKernelGGL((k_wave_synthesis<S, false, false, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, max_active, 1, 0, wstate, win, tw, none, slots, cnt);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-template int launch_wave_analysis_slots<float>(const float*, long, int, int, bool, const float*, const float*, const float*, float*, const int*, const int*, hipStream_t);
-template int launch_wave_analysis_slots<short>(const short*, long, int, int, bool, const float*, const float*, const float*, float*, const int*, const int*, hipStream_t);
-template int launch_wave_synthesis_slots<float>(const float*, const float*, long, float*, long, int, int, bool, float*, const float*, const float*, const int*, const int*, hipStream_t, const float*);
-template int launch_wave_synthesis_slots<short>(const float*, const short*, long, short*, long, int, int, bool, float*, const float*, const float*, const int*, const int*, hipStream_t, const float*);
-template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
-template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t, const float*);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, hipStream_t, const float*);
+template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
+template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {
@@ -4735,16 +4716,6 @@ int launch_decoder(const float* xg, const float* en0, const float* en1, const fl
     return 0;
 }
 
-// single-frame step for B streams, ONE launch (see k_stream_ms); strides in floats of (B,257,1,2)-shaped tensors
-int launch_stream_ms(const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
-                     const int* PI, float* state, unsigned long long* stamps, hipStream_t s) {
-    const int grid = (B + MS_STREAMS - 1) / MS_STREAMS;
-    // eight phase shifts over a ~33 us workgroup: ~10 k cycles each = 2 sleeps of 100 x 64 clocks; from four rounds on
-    hipLaunchKernelGGL(k_stream_ms, dim3(grid), dim3(NTHR), SM_LDS_FLOATS * 4, s, spec, sb, sf, out, osb, osf, B, PF, PI,
-                       state, stamps, 0);     // (measured: no gain for this form, and the first round's sleeps cost 20 % at four rounds)
-    GT_LAUNCH_CHECK();
-    return 0;
-}
 // (GTCRN_STAGGER = "phases,unit" overrides the default for measurements: tools/stream_form_ab.py)
 static int stagger_setting() {
     static const int v = [] {
@@ -4756,33 +4727,29 @@ static int stagger_setting() {
     }();
     return v;
 }
-// the wide form of the same step: SwCfg::NS streams per workgroup (see k_stream_wide)
-int launch_stream_wide(const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
-                       const int* PI, float* state, unsigned long long* stamps, hipStream_t s) {
-    const int grid = (B + SwCfg::NS - 1) / SwCfg::NS;
-    // from three rounds of workgroups on: 32 start shifts of 5 x 512 clocks (two thirds of a ~118 k-cycle workgroup in all;
-    // swept on the GPU, tools/stagger_sweep.sh -> profiles/r06_ab_stream_wide.txt)
-    hipLaunchKernelGGL(k_stream_wide<SwCfg>, dim3(grid), dim3(SwCfg::NT), SW_LDS_FLOATS * 4, s, spec, sb, sf, out, osb, osf, B,
-                       PF, PI, state, stamps, grid >= 3 * 256 ? stagger_setting() : 0, (const int*)nullptr, (const int*)nullptr);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-// the indexed forms of both steps: a grid for max_active rows, the device count and slot table decide what steps
-int launch_stream_ms_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active, const float* PF,
-                           const int* PI, float* state, unsigned long long* stamps, const int* slots, const int* cnt,
-                           hipStream_t s) {
-    const int grid = (max_active + MS_STREAMS - 1) / MS_STREAMS;
-    hipLaunchKernelGGL(k_stream_ms_slots, dim3(grid), dim3(NTHR), (SM_LDS_FLOATS + SLOT_WORDS) * 4, s, spec, sb, sf, out, osb, osf, max_active,
-                       PF, PI, state, stamps, 0, slots, cnt);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-int launch_stream_wide_slots(const float* spec, long sb, long sf, float* out, long osb, long osf, int max_active,
-                             const float* PF, const int* PI, float* state, unsigned long long* stamps, const int* slots,
-                             const int* cnt, hipStream_t s) {
-    const int grid = (max_active + SwCfg::NS - 1) / SwCfg::NS;
-    hipLaunchKernelGGL((k_stream_wide<SwCfg, true>), dim3(grid), dim3(SwCfg::NT), (SW_LDS_FLOATS + SLOT_WORDS) * 4, s, spec, sb, sf, out, osb,
-                       osf, max_active, PF, PI, state, stamps, grid >= 3 * 256 ? stagger_setting() : 0, slots, cnt);
+// single-frame step for B streams (rows.slots: max_active rows), ONE launch: the narrow form (k_stream_ms / k_stream_ms_slots,
+// MS_STREAMS streams per workgroup) or the wide one (k_stream_wide, SwCfg::NS); strides in floats of (B,257,1,2)-shaped tensors.
+// The indexed kernels keep their workgroup's slot ids in SLOT_WORDS more LDS words.
+int launch_stream_step(bool wide, const float* spec, long sb, long sf, float* out, long osb, long osf, int B, const float* PF,
+                       const int* PI, float* state, unsigned long long* stamps, Rows rows, hipStream_t s) {
+    const int per = wide ? SwCfg::NS : MS_STREAMS, grid = (B + per - 1) / per;
+    const size_t slot_lds = rows.slots ? SLOT_WORDS * 4 : 0;
+    if (wide) {
+        // from three rounds of workgroups on: 32 start shifts of 5 x 512 clocks (two thirds of a ~118 k-cycle workgroup in all;
+        // swept on the GPU, tools/stagger_sweep.sh -> profiles/r06_ab_stream_wide.txt)
+        const int stagger = grid >= 3 * 256 ? stagger_setting() : 0;
+        with_flags([&](auto IDX) {
+            hipLaunchKernelGGL((k_stream_wide<SwCfg, IDX.value>), dim3(grid), dim3(SwCfg::NT), SW_LDS_FLOATS * 4 + slot_lds, s, spec, sb,
+                               sf, out, osb, osf, B, PF, PI, state, stamps, stagger, rows.slots, rows.cnt);
+        }, rows.slots != nullptr);
+    } else if (rows.slots) {
+        hipLaunchKernelGGL(k_stream_ms_slots, dim3(grid), dim3(NTHR), SM_LDS_FLOATS * 4 + slot_lds, s, spec, sb, sf, out, osb, osf, B,
+                           PF, PI, state, stamps, 0, rows.slots, rows.cnt);
+    } else {
+        // no stagger: measured, no gain for this form, and the first round's sleeps cost 20 % at four rounds
+        hipLaunchKernelGGL(k_stream_ms, dim3(grid), dim3(NTHR), SM_LDS_FLOATS * 4, s, spec, sb, sf, out, osb, osf, B, PF, PI,
+                           state, stamps, 0);
+    }
     GT_LAUNCH_CHECK();
     return 0;
 }
