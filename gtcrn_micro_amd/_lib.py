@@ -134,6 +134,11 @@ def lib():
             getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, _vp, _vp, _vp]
         for fn in ("gtcrn_wave_stream_flush_slots", "gtcrn_wave_stream_flush_slots_pcm16"):
             getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, ci, _vp, cl, ci, _vp, cl, _vp, _vp, _vp]
+    # packet stream slots: (handle, state, wstate, pstate, phase, slots, count, max_active, ...)
+    if hasattr(L, "gtcrn_packet_stream_step_slots"):
+        L.gtcrn_packet_stream_reset_slots.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp]
+        for fn in ("gtcrn_packet_stream_step_slots", "gtcrn_packet_stream_step_slots_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, _vp, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -923,7 +928,7 @@ class Engine:
         front of their input, the group's latency."""
         hi = state.n if hi is None else int(hi)
         lo = int(lo)
-        if not isinstance(state, PacketStreamState):
+        if not isinstance(state, PacketStreamState) or isinstance(state, PacketSlotState):
             raise GtcrnError("state must come from new_packet_state")
         if not 0 <= lo < hi <= state.n:
             raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
@@ -936,7 +941,7 @@ class Engine:
         state.latency16 samples (counted at 16 kHz) late.  Steps state.next_hops hops of the model (possibly none) and
         advances the group's phase.  Asynchronous on the current stream; no allocation when `out` is given."""
         import torch
-        if not isinstance(state, PacketStreamState):
+        if not isinstance(state, PacketStreamState) or isinstance(state, PacketSlotState):
             raise GtcrnError("state must come from new_packet_state")
         x = self._wave_rows(state, x, "x")
         if x.shape[1] != state.packet:
@@ -961,6 +966,76 @@ class Engine:
                 _check(lib().gtcrn_packet_stream_debug_handoff(state._h, int(which), out.data_ptr(), out.numel(),
                                                                _stream_ptr()))
         return out
+
+    # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
+    def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None):
+        """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
+        plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
+        (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
+        one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db: as in
+        new_wave_state, per SLOT."""
+        import torch
+        fs, packet = int(fs), int(packet)
+        n16 = packet_stream_n16(fs, packet)
+        nbytes = packet_stream_state_bytes(fs, packet)
+        ws = self.new_wave_state(nslots, window)
+        m = ws.n if max_active is None else int(max_active)
+        if not 1 <= m <= ws.n:
+            raise GtcrnError(f"max_active must be 1..{ws.n} (the resident slots), got {m}")
+        rs_in = self.resampler(fs, 16000) if fs != 16000 else None
+        rs_out = self.resampler(16000, fs) if fs != 16000 else None
+        h = ctypes.c_void_p()
+        with self._dev():
+            _check(lib().gtcrn_packet_stream_create(ctypes.byref(h), self._h, rs_in._h if rs_in else None,
+                                                    rs_out._h if rs_out else None, fs, packet, m))
+        st = PacketSlotState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
+                             torch.zeros((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32),
+                             torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.int32), m)
+        if atten_lim_db is not None:
+            st.set_atten_lim_db(atten_lim_db)
+        return st
+
+    def _packet_slot_args(self, state, slots, count):
+        if not isinstance(state, PacketSlotState):
+            raise GtcrnError("state must come from new_packet_slot_state")
+        m, cnt = self._slot_args(slots, count, None)
+        if m > state.max_active:
+            raise GtcrnError(f"slots holds {m} rows, the state was made for max_active = {state.max_active}")
+        return m, cnt
+
+    def packet_stream_step_slots(self, state, slots, x, count=None, out=None):
+        """One packet for the rows a call names: x (M, state.packet) float32 or int16 at the state's rate, row i = the
+        stream in slot slots[i] (int32 device tensor, M <= state.max_active ids, in range and distinct); `count` (device
+        int32, None: all M) rows step.  Returns (M, state.packet), same dtype, state.latency16 samples (at 16 kHz) late per
+        stream; rows at or beyond count are not written and no other slot is touched.  The launch sequence is the same
+        for every call: asynchronous, capturable, no allocation when `out` is given."""
+        import torch
+        m, cnt = self._packet_slot_args(state, slots, count)
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
+            raise GtcrnError("x must be a float32 or int16 CUDA (ROCm) tensor")
+        if x.device.index != self.device or state.model.device != x.device:
+            raise GtcrnError(f"x and the state must be on cuda:{self.device}")
+        if x.dim() != 2 or tuple(x.shape) != (m, state.packet):
+            raise GtcrnError(f"x must be ({m}, {state.packet}): one packet per row of slots, got {tuple(x.shape)}")
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        out = self._wave_out(out, x, state.packet)
+        fn = lib().gtcrn_packet_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_slots
+        with self._dev():
+            # (a one-row tensor may report any stride)
+            _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
+                      slots.data_ptr(), cnt, m, x.data_ptr(), max(x.stride(0), state.packet), out.data_ptr(),
+                      max(out.stride(0), state.packet), state.window.data_ptr(), _stream_ptr()))
+        return out
+
+    def packet_stream_reset_slots(self, state, slots, count=None):
+        """Resets the named slots (all three states and the phase word) to the start of a new clip, with kernels:
+        asynchronous and capturable.  The streams join at phase 0 whatever the other slots' phases are."""
+        m, cnt = self._packet_slot_args(state, slots, count)
+        with self._dev():
+            _check(lib().gtcrn_packet_stream_reset_slots(state._h, state.model.data_ptr(), state.wave.data_ptr(),
+                                                         state.pkt.data_ptr(), state.phase.data_ptr(), slots.data_ptr(), cnt, m,
+                                                         _stream_ptr()))
 
     def _cache_ptrs(self, tcn_cache):
         flat = [tcn_cache[g][k] for g in range(2) for k in range(4)]
@@ -1157,6 +1232,20 @@ class PacketStreamState(WaveStreamState):
             self.close()
         except Exception:
             pass
+
+
+class PacketSlotState(PacketStreamState):
+    """PacketStreamState of RESIDENT packet streams with one phase each (Engine.new_packet_slot_state): ``phase`` is an
+    (nslots,) int32 device tensor, slot s holding (16 kHz samples stream s has taken) mod 256, and ``max_active`` the most
+    rows one call may name.  Stepped by Engine.packet_stream_step_slots only; the handle's host phase is not used."""
+
+    phase = None                    # (an instance attribute here: the group's host phase of the base class does not apply)
+    next_hops = None
+
+    def __init__(self, engine, handle, model, wave, window, fs, packet, n16, rs_in, rs_out, pkt, phase, max_active):
+        super().__init__(engine, handle, model, wave, window, fs, packet, n16, rs_in, rs_out, pkt)
+        self.phase = phase
+        self.max_active = max_active
 
 
 SUPPORTED_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)

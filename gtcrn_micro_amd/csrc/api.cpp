@@ -52,7 +52,8 @@ struct Timing {
     X(K_ISTFT, "k_istft") X(K_FRONT, "k_front") X(K_ENCODER_GT, "k_encoder_gt") X(K_GTCN_MS, "k_gtcn_ms")                 \
     X(K_STREAM_MS, "k_stream_ms") X(K_STREAM_WIDE, "k_stream_wide") X(K_WAVE_ANALYSIS, "k_wave_analysis")                 \
     X(K_WAVE_SYNTHESIS, "k_wave_synthesis") X(K_PACKET_IN, "k_packet_in") X(K_PACKET_OUT, "k_packet_out")                 \
-    X(K_WAVE_SYNTHESIS_MIX, "k_wave_synthesis_mix") X(K_ISTFT_MIX, "k_istft_mix")
+    X(K_WAVE_SYNTHESIS_MIX, "k_wave_synthesis_mix") X(K_ISTFT_MIX, "k_istft_mix") X(K_PACKET_PLAN, "k_packet_plan")       \
+    X(K_PACKET_IN_SLOTS, "k_packet_in_slots") X(K_PACKET_OUT_SLOTS, "k_packet_out_slots")
 #define GT_KERNEL_ID(id, name) id,
 #define GT_KERNEL_NAME(id, name) name,
 enum KernelId { GT_KERNELS(GT_KERNEL_ID) K_COUNT };
@@ -1157,6 +1158,13 @@ struct gtcrn_packet_stream {
     float* d_b = nullptr;       // wave step -> k_packet_out
     int last_h = 0, last_n = 0; // hops and streams of the most recent step (gtcrn_packet_stream_debug_handoff)
     const float* d_gain = nullptr;   // the caller's dry gains, max_streams floats (gtcrn_packet_stream_set_dry_gain); NULL: no limit
+    // the _slots calls: hmax tables and hmax position arrays of max_streams ints, the rows' old phases, the rounds' counts
+    // (k_packet_plan writes them, the later launches of the call read them); d_a / d_b then hold one block per round
+    int* d_plan = nullptr;
+    int* tab(int r) const { return d_plan + (size_t)r * max_streams; }
+    int* pos() const { return d_plan + (size_t)p.hmax * max_streams; }
+    int* phi_rec() const { return d_plan + 2 * (size_t)p.hmax * max_streams; }
+    int* cnts() const { return phi_rec() + max_streams; }
 };
 
 int gtcrn_packet_stream_n16(int fs, int n) {
@@ -1208,8 +1216,10 @@ int gtcrn_packet_stream_create(gtcrn_packet_stream** out, gtcrn_model* m, gtcrn_
     const size_t bytes = sizeof(float) * 256 * (size_t)p.hmax * (size_t)max_streams;
     hipError_t e = hipMalloc(&ps->d_a, bytes);
     if (e == hipSuccess) e = hipMalloc(&ps->d_b, bytes);
+    if (e == hipSuccess) e = hipMalloc(&ps->d_plan, sizeof(int) * ((2 * (size_t)p.hmax + 1) * (size_t)max_streams + (size_t)p.hmax));
     if (e != hipSuccess) {
         if (ps->d_a) (void)hipFree(ps->d_a);
+        if (ps->d_b) (void)hipFree(ps->d_b);
         delete ps;
         return hip_fail(e, "gtcrn_packet_stream_create");
     }
@@ -1223,6 +1233,7 @@ void gtcrn_packet_stream_destroy(gtcrn_packet_stream* ps) {
     (void)hipDeviceSynchronize();
     if (ps->d_a) (void)hipFree(ps->d_a);
     if (ps->d_b) (void)hipFree(ps->d_b);
+    if (ps->d_plan) (void)hipFree(ps->d_plan);
     delete ps;
 }
 
@@ -1301,6 +1312,89 @@ int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream* ps, void* d_state, void*
                                    long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
     return packet_stream_impl<short>("gtcrn_packet_stream_step_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
                                      out_stride, nstreams, d_win, stream);
+}
+
+// ---- packet stream slots (contract: include/gtcrn_micro_hip.h): the phase is one device word per slot, and a call is
+// plan -> k_packet_in_slots -> hmax rounds of the indexed wave step -> k_packet_out_slots whatever the phases are.
+namespace {
+int packet_slots_args(const std::string& w, gtcrn_packet_stream* ps, const void* d_state, const void* d_wstate,
+                      const void* d_pstate, const int* d_phase, const int* d_slots, int max_active) {
+    if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
+    if (!d_state || !d_wstate || !d_pstate || !d_phase || !d_slots) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (max_active < 1 || max_active > ps->max_streams)
+        return fail(GTCRN_ERR_ARG, w + ": max_active must be >= 1 and at most the handle's max_streams");
+    if (reinterpret_cast<uintptr_t>(d_phase) & 3) return fail(GTCRN_ERR_ARG, w + ": the phase words must be 4-byte aligned");
+    return check_state_alignment(w, {d_state, d_wstate, d_pstate});
+}
+}  // namespace
+
+int gtcrn_packet_stream_reset_slots(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                    const int* d_slots, const int* d_count, int max_active, void* stream) {
+    const std::string w("gtcrn_packet_stream_reset_slots");
+    if (int rc0 = packet_slots_args(w, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, max_active)) return rc0;
+    int rc = check_model(ps->m);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH_TRY(gtk::launch_reset_slots(static_cast<float*>(d_state), static_cast<float*>(d_wstate), d_slots, d_count, max_active, s));
+    LAUNCH_TRY(gtk::launch_packet_reset_slots(static_cast<float*>(d_pstate), (long)(gtcrn_packet_stream_state_bytes(ps->fs, ps->n) / sizeof(float)),
+                                              d_phase, d_slots, d_count, max_active, s));
+    return 0;
+}
+
+extern "C++" template <typename S>
+static int packet_slots_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
+                             int* d_phase, const int* d_slots, const int* d_count, int max_active, const S* d_in,
+                             long in_stride, S* d_out, long out_stride, const float* d_win, void* stream) {
+    const std::string w(who);
+    if (int rc0 = packet_slots_args(w, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, max_active)) return rc0;
+    if (!d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    gtcrn_model* m = ps->m;
+    int rc = check_model(m);
+    if (rc) return rc;
+    if ((rc = refuse_three_launch_form(w, m))) return rc;                 // (before the plan: nothing runs on a refusal)
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = ensure_workspace(m, max_active, 1, s))) return rc;          // (create reserved max_streams x hmax)
+    const PkGeom& p = ps->p;
+    const int M = ps->max_streams;
+    const long ps_stride = 2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp, block = 256L * M;
+    float* pst = static_cast<float*>(d_pstate);
+    Timer tm(m, s);
+    tm.begin(K_PACKET_PLAN);
+    LAUNCH_TRY(gtk::launch_packet_plan(d_slots, d_count, max_active, d_phase, p.n16, p.hmax, M, ps->tab(0), ps->pos(),
+                                       ps->phi_rec(), ps->cnts(), s));
+    tm.end();
+    tm.begin(K_PACKET_IN_SLOTS);
+    LAUNCH_TRY(gtk::launch_packet_in_slots<S>(d_in, in_stride, ps->n, ps->d_a, M, pst, ps_stride, d_slots, d_count, max_active,
+                                              ps->phi_rec(), ps->pos(), p.n16, p.in.up, p.in.down, p.in.ntp,
+                                              ps->in ? ps->in->d_taps : nullptr, s));
+    tm.end();
+    for (int r = 0; r < p.hmax; ++r) {
+        // round r: one hop of the rows that have more than r ready; an empty round's workgroups return at once
+        rc = wave_step<float>(who, m, d_state, d_wstate, ps->d_a + block * r, 256, ps->d_b + block * r, 256, max_active, 1, false,
+                              0, ps->d_gain, d_win, gtk::Rows{ps->tab(r), ps->cnts() + r}, stream);
+        if (rc) return rc;
+    }
+    tm.begin(K_PACKET_OUT_SLOTS);
+    LAUNCH_TRY(gtk::launch_packet_out_slots<S>(ps->d_b, M, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
+                                               d_slots, d_count, max_active, ps->phi_rec(), ps->pos(), p.g, p.n16, p.out.up,
+                                               p.out.down, p.out.ntp, ps->out ? ps->out->d_taps : nullptr, s));
+    tm.end();
+    ps->last_h = 0;     // (no contiguous hand-off to copy: gtcrn_packet_stream_debug_handoff is out of scope for slot calls)
+    ps->last_n = 0;
+    return 0;
+}
+int gtcrn_packet_stream_step_slots(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                   const int* d_slots, const int* d_count, int max_active, const float* d_in, long in_stride,
+                                   float* d_out, long out_stride, const float* d_win, void* stream) {
+    return packet_slots_impl<float>("gtcrn_packet_stream_step_slots", ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count,
+                                    max_active, d_in, in_stride, d_out, out_stride, d_win, stream);
+}
+int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                         const int* d_slots, const int* d_count, int max_active, const short* d_in,
+                                         long in_stride, short* d_out, long out_stride, const float* d_win, void* stream) {
+    return packet_slots_impl<short>("gtcrn_packet_stream_step_slots_pcm16", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
+                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream);
 }
 
 long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream* ps, int which, float* d_dst, long n, void* stream) {

@@ -123,6 +123,25 @@ int launch_packet_in(const S* in, long in_stride, int n, float* hand, long hand_
 template <typename S>
 int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stride, int n, float* pstate, long ps_stride,
                       int hist_off, int N, int lvl, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s);
+// packet stream slots (gtcrn_packet_stream_*_slots): the phase is one device word per slot.  plan: for the rows the call
+// names (slots / cnt / max_active as in Rows) reads phase[slot], writes per round r < hmax the table tab + r M (the slots
+// with more than r hops ready, in row order) and its count cnts[r], per row the record phi_rec[i] (the old phase) and
+// pos[r M + i] (the row's place in round r's table, or -1), and advances phase[slot].  M: the row capacity of every array
+// and of a round's block of the hand-off buffers (M rows of 256 floats).  in / out: launch_packet_in / _out per row, the state
+// at the slot, phi / h / lvl from the record, hop r of a row at row pos[r M + i] of round r's block.
+int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* phase, int n16, int hmax, int M, int* tab,
+                       int* pos, int* phi_rec, int* cnts, hipStream_t s);
+template <typename S>
+int launch_packet_in_slots(const S* in, long in_stride, int n, float* hand, int M, float* pstate, long ps_stride,
+                           const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos, int n16, int up,
+                           int down, int ntp, const float* taps, hipStream_t s);
+template <typename S>
+int launch_packet_out_slots(const float* hand, int M, S* out, long out_stride, int n, float* pstate, long ps_stride,
+                            int hist_off, const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos,
+                            int g, int n16, int up, int down, int ntp, const float* taps, hipStream_t s);
+// zeroes the packet state rows (ps_stride floats) and the phase words of the listed slots (k_packet_reset_slots)
+int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const int* slots, const int* cnt, int max_active,
+                              hipStream_t s);
 // gspec += adjoint(iSTFT)(gwave): gwave (B, 256 (T-1)) is the gradient w.r.t. the iSTFT output ALREADY divided by
 // the window envelope; gspec (B,257,T,2 by strides) receives the gradient w.r.t. the spectrogram (accumulated).
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,

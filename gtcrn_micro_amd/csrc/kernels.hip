@@ -4996,41 +4996,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_in(const S* __restrict__ 
                                                           long hand_stride, float* __restrict__ pstate, long ps_stride, int phi,
                                                           int n16, int h, int up, int down, int ntp,
                                                           const float* __restrict__ taps) {
-    __shared__ __attribute__((aligned(16))) float s_a[PK_SEQ];       // the FIFO's phi samples ++ this packet at 16 kHz
-    __shared__ __attribute__((aligned(16))) float s_x[PK_SPAN];
-    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
-    const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    const S* x = in + row * in_stride;
-    float* ps = pstate + row * ps_stride;
-    for (int i = tid; i < phi; i += RS_THREADS) s_a[i] = ps[i];
-    if (ntp == 0) {                                                  // 16 kHz: the packet as it is
-        for (int m = tid; m < n16; m += RS_THREADS) s_a[phi + m] = wave_ld<S>(x + m);
-        __syncthreads();
-    } else {
-        float* hist = ps + 2 * PK_FIFO;
-        const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);
-        for (int m0 = 0; m0 < n16; m0 += PK_TILE) {
-            const int m1 = m0 + PK_TILE < n16 ? m0 + PK_TILE : n16;
-            const int lo = (m0 * down) / up - (ntp - 1), cnt = ((m1 - 1) * down) / up - lo + 1;   // <= PK_SPAN (launch check)
-            for (int i = tid; i < cnt; i += RS_THREADS) {
-                const int g = lo + i;                                // >= 1 - ntp; < n
-                s_x[i] = g >= 0 ? wave_ld<S>(x + g) : hist[ntp + g];
-            }
-            __syncthreads();
-            for (int m = m0 + tid; m < m1; m += RS_THREADS) {
-                const int num = m * down, ih = num / up, k0 = num - ih * up;
-                const float* xs = s_x + (ih - lo);
-                s_a[phi + m] = tp ? rs_dot(tp + k0 * ntp, ntp, xs) : rs_dot(taps + (long)k0 * ntp, ntp, xs);
-            }
-            __syncthreads();
-        }
-        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = wave_ld<S>(x + n - ntp + i);        // (ntp <= n)
-    }
-    float* o = hand + row * hand_stride;
-    const int whole = 256 * h, rem = phi + n16 - whole;              // rem < 256: the next call's phi
-    for (int i = tid; i < whole; i += RS_THREADS) o[i] = s_a[i];
-    for (int i = tid; i < rem; i += RS_THREADS) ps[i] = s_a[whole + i];
+    const long srow = blockIdx.x;
+    [[maybe_unused]] const int* const pos = nullptr;                 // (the indexed kernel's; see packet_in_body.inc)
+    [[maybe_unused]] constexpr int M = 0;
+#define GT_PK_IDX false
+#include "packet_in_body.inc"
+#undef GT_PK_IDX
 }
 
 template <typename S>
@@ -5038,33 +5009,121 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_out(const float* __restri
                                                            long out_stride, int n, float* __restrict__ pstate, long ps_stride,
                                                            int hist_off, int lvl, int n16, int h, int up, int down, int ntp,
                                                            const float* __restrict__ taps) {
-    __shared__ __attribute__((aligned(16))) float s_q[PK_HIST + PK_SEQ];   // [stage history | the FIFO's lvl samples ++ 256 h new]
-    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
-    const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    float* ps = pstate + row * ps_stride;
-    float* fo = ps + PK_FIFO;
-    float* hist = ps + hist_off;
-    float* q = s_q + PK_HIST;
-    const float* hb = hand + row * hand_stride;
-    const int whole = 256 * h;
-    for (int i = tid; i < lvl; i += RS_THREADS) q[i] = fo[i];
-    for (int i = tid; i < whole; i += RS_THREADS) q[lvl + i] = hb[i];
-    for (int i = tid; i < ntp; i += RS_THREADS) q[i - ntp] = hist[i];
-    const float* tp = ntp ? rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS) : nullptr;
+    const long srow = blockIdx.x;
+    [[maybe_unused]] const int* const pos = nullptr;
+    [[maybe_unused]] constexpr int M = 0;
+#define GT_PK_IDX false
+#include "packet_out_body.inc"
+#undef GT_PK_IDX
+}
+
+// ---- packet stream slots (gtcrn_packet_stream_*_slots): the packet form for the resident streams a call names.  The phase
+// is one device word per slot, so every stream runs the schedule of a one-stream group created at phase 0 whatever the
+// others do.  A call is plan -> k_packet_in_slots -> hmax rounds of the indexed single-launch wave step -> k_packet_out_slots,
+// whatever the phases: round r steps the rows that have more than r hops ready, named by the table the plan wrote.
+//
+// k_packet_plan, ONE workgroup: for row i < count (clamped) it reads slot = slots[i] and phi = phase[slot], h_i = (phi + n16)
+// div 256, and writes the row's record (phi_rec[i] = phi, pos[r M + i] = the row's place in round r's table or -1), the
+// tables tab[r M + j] = slot IN ROW ORDER (an exclusive scan of "h_i > r" over the rows: wave ballots, the waves' counts
+// through LDS, a running base per round), the rounds' counts, and phase[slot] = (phi + n16) mod 256.  The later kernels
+// read the record, never `phase`.  A phase word the schedule cannot reach (a slot that was never reset) is masked into
+// 0..255 and, if it would still give more than hmax hops, read as 0: no later index depends on the caller's memory.  PLAN_THREADS rows per pass, three barriers a pass.
+constexpr int PK_HMAX = (255 + PK_MAX16) / 256;  // the most rounds any packet takes (16)
+constexpr int PLAN_THREADS = 1024, PLAN_WAVES = PLAN_THREADS / 64;
+__global__ __launch_bounds__(PLAN_THREADS) void k_packet_plan(const int* __restrict__ slots, const int* __restrict__ count,
+                                                              int max_active, int* __restrict__ phase, int n16, int hmax, int M,
+                                                              int* __restrict__ tab, int* __restrict__ pos,
+                                                              int* __restrict__ phi_rec, int* __restrict__ cnts) {
+    __shared__ int s_wc[PK_HMAX][PLAN_WAVES];
+    __shared__ int s_base[PK_HMAX];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int N = slot_count(count, max_active);
+    if (tid < PK_HMAX) s_base[tid] = 0;
     __syncthreads();
-    S* o = out + row * out_stride;
-    if (ntp == 0) {
-        for (int m = tid; m < n; m += RS_THREADS) wave_st<S>(o + m, q[m]);
-    } else {
-        for (int m = tid; m < n; m += RS_THREADS) {
-            const int num = m * down, ih = num / up, k0 = num - ih * up;       // ih < n16
-            wave_st<S>(o + m, tp ? rs_dot(tp + k0 * ntp, ntp, q + ih) : rs_dot(taps + (long)k0 * ntp, ntp, q + ih));
+    for (int i0 = 0; i0 < N; i0 += PLAN_THREADS) {                   // (workgroup uniform)
+        const int i = i0 + tid;
+        const bool live = i < N;
+        int slot = 0, h = 0;
+        if (live) {
+            slot = slots[i];
+            int phi = phase[slot] & 255;
+            if (((phi + n16) >> 8) > hmax) phi = 0;                  // (no phase the schedule reaches: see above)
+            h = (phi + n16) >> 8;
+            phase[slot] = (phi + n16) & 255;
+            phi_rec[i] = phi;
         }
-        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = q[n16 - ntp + i];
+        for (int r = 0; r < hmax; ++r) {
+            const unsigned long long b = __ballot(h > r);
+            if (lane == 0) s_wc[r][wv] = __popcll(b);
+        }
+        __syncthreads();
+        for (int r = 0; r < hmax; ++r) {
+            const unsigned long long b = __ballot(h > r);
+            int j = s_base[r] + __popcll(b & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wv; ++w) j += s_wc[r][w];
+            if (live) {
+                pos[(long)r * M + i] = h > r ? j : -1;
+                if (h > r) tab[(long)r * M + j] = slot;
+            }
+        }
+        __syncthreads();
+        if (tid < hmax) {
+            int t = s_base[tid];
+            for (int w = 0; w < PLAN_WAVES; ++w) t += s_wc[tid][w];
+            s_base[tid] = t;
+        }
+        __syncthreads();
     }
-    const int rem = lvl + whole - n16;                               // < 256: the next call's lvl
-    for (int i = tid; i < rem; i += RS_THREADS) fo[i] = q[n16 + i];
+    if (tid < hmax) cnts[tid] = s_base[tid];
+}
+
+// k_packet_in_slots / k_packet_out_slots: the contiguous kernels' bodies (packet_*_body.inc) with the state row taken at the
+// slot, phi / h / lvl per row from the plan record, and hop r of a row at row pos[r M + row] of round r's block of the
+// hand-off buffer (round-major: block r is M rows of 256 floats).  A workgroup at or beyond the count returns before its
+// first barrier and state access.
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_in_slots(const S* __restrict__ in, long in_stride, int n,
+                                                                float* __restrict__ hand, int M, float* __restrict__ pstate,
+                                                                long ps_stride, const int* __restrict__ slots,
+                                                                const int* __restrict__ count, int max_active,
+                                                                const int* __restrict__ phi_rec, const int* __restrict__ pos,
+                                                                int n16, int up, int down, int ntp,
+                                                                const float* __restrict__ taps) {
+    if ((int)blockIdx.x >= slot_count(count, max_active)) return;
+    const long srow = slots[blockIdx.x];
+    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8;
+    [[maybe_unused]] constexpr long hand_stride = 0;                 // (the contiguous kernel's)
+#define GT_PK_IDX true
+#include "packet_in_body.inc"
+#undef GT_PK_IDX
+}
+
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_out_slots(const float* __restrict__ hand, int M, S* __restrict__ out,
+                                                                 long out_stride, int n, float* __restrict__ pstate,
+                                                                 long ps_stride, int hist_off, const int* __restrict__ slots,
+                                                                 const int* __restrict__ count, int max_active,
+                                                                 const int* __restrict__ phi_rec, const int* __restrict__ pos,
+                                                                 int g, int n16, int up, int down, int ntp,
+                                                                 const float* __restrict__ taps) {
+    if ((int)blockIdx.x >= slot_count(count, max_active)) return;
+    const long srow = slots[blockIdx.x];
+    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8, lvl = 256 - g - phi;
+    [[maybe_unused]] constexpr long hand_stride = 0;
+#define GT_PK_IDX true
+#include "packet_out_body.inc"
+#undef GT_PK_IDX
+}
+
+// zeroes the packet state rows and the phase words of the listed slots (with k_reset_slots: gtcrn_packet_stream_reset_slots)
+__global__ __launch_bounds__(RS_THREADS) void k_packet_reset_slots(float* __restrict__ pstate, long ps_stride,
+                                                                   int* __restrict__ phase, const int* __restrict__ slots,
+                                                                   const int* __restrict__ count, int max_active) {
+    if ((int)blockIdx.x >= slot_count(count, max_active)) return;
+    const long slot = slots[blockIdx.x];
+    float* ps = pstate + slot * ps_stride;
+    for (int i = threadIdx.x; i < ps_stride; i += RS_THREADS) ps[i] = 0.f;
+    if (threadIdx.x == 0) phase[slot] = 0;
 }
 
 static bool packet_stage_ok(int n_in, int n_out, int up, int down, int ntp, const float* taps) {
@@ -5100,5 +5159,53 @@ template int launch_packet_in<float>(const float*, long, int, float*, long, floa
 template int launch_packet_in<short>(const short*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out<float>(const float*, long, float*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out<short>(const float*, long, short*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+
+// ---- packet stream slots: the launch sequence of a call depends on (fs, n, max_active) alone
+int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* phase, int n16, int hmax, int M, int* tab,
+                       int* pos, int* phi_rec, int* cnts, hipStream_t s) {
+    if (!slots || !phase || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || hmax < n16 / 256 || hmax < 1 ||
+        hmax > PK_HMAX)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_packet_plan, dim3(1), dim3(PLAN_THREADS), 0, s, slots, cnt, max_active, phase, n16, hmax, M, tab, pos,
+                       phi_rec, cnts);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_packet_in_slots(const S* in, long in_stride, int n, float* hand, int M, float* pstate, long ps_stride,
+                           const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos, int n16, int up,
+                           int down, int ntp, const float* taps, hipStream_t s) {
+    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || ps_stride < 2 * PK_FIFO + ntp ||
+        !packet_stage_ok(n, n16, up, down, ntp, taps) || (ntp && ((PK_TILE - 1) * down) / up + ntp + 1 > PK_SPAN))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_in_slots<S>), dim3(max_active), dim3(RS_THREADS), 0, s, in, in_stride, n, hand, M, pstate,
+                       ps_stride, slots, cnt, max_active, phi_rec, pos, n16, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_packet_out_slots(const float* hand, int M, S* out, long out_stride, int n, float* pstate, long ps_stride,
+                            int hist_off, const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos,
+                            int g, int n16, int up, int down, int ntp, const float* taps, hipStream_t s) {
+    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || g < 1 || g > 256 || 256 % g || n16 % g ||
+        hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST || !packet_stage_ok(n16, n, up, down, ntp, taps))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_out_slots<S>), dim3(max_active), dim3(RS_THREADS), 0, s, hand, M, out, out_stride, n, pstate,
+                       ps_stride, hist_off, slots, cnt, max_active, phi_rec, pos, g, n16, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const int* slots, const int* cnt, int max_active,
+                              hipStream_t s) {
+    if (!pstate || !phase || !slots || max_active < 1 || ps_stride < 2 * PK_FIFO) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_packet_reset_slots, dim3(max_active), dim3(RS_THREADS), 0, s, pstate, ps_stride, phase, slots, cnt,
+                       max_active);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_packet_in_slots<float>(const float*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in_slots<short>(const short*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots<float>(const float*, int, float*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots<short>(const float*, int, short*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
 
 }  // namespace gtk

@@ -229,7 +229,7 @@ class StreamGTCRNMicro(GTCRNMicro):
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
-                        count=None):
+                        count=None, resident=False, max_active=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -239,14 +239,25 @@ class StreamGTCRNMicro(GTCRNMicro):
         latency); state.set_atten_lim_db changes it while the streams run.
         state=, slots= (int32 device tensor), count= (device int32, optional): a stream JOINS -- the named slots of the
         existing 16 kHz `state` are reset to the start of a clip (Engine.wave_stream_reset_slots, a capturable kernel) and
-        `state` is returned; the other slots are not touched.  Rate and packet states cannot be addressed by slot (their
-        streams share a group phase)."""
+        `state` is returned; the other slots are not touched.  Rate states and plain packet states cannot be addressed by
+        slot (their streams share a group phase).
+        packet=, resident=True: `nstreams` RESIDENT packet streams with a phase each (Engine.new_packet_slot_state; at most
+        `max_active`, default all, step per call); state=<that state>, slots= resets its named slots
+        (Engine.packet_stream_reset_slots)."""
         eng = self.engine(torch.device(device))
         if slots is not None:
+            if isinstance(state, _lib.PacketSlotState):
+                eng.packet_stream_reset_slots(state, slots, count=count)
+                return state
             if state is None or packet is not None or int(fs) != 16000:
                 raise _lib.GtcrnError("slots= resets slots of an existing 16 kHz wave state: pass state=, no fs / packet")
             eng.wave_stream_reset_slots(state, slots, count=count)
             return state
+        if resident:
+            if packet is None:
+                raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
+            return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
+                                             atten_lim_db=atten_lim_db)
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db)
         if int(fs) != 16000:
@@ -259,8 +270,12 @@ class StreamGTCRNMicro(GTCRNMicro):
         state: exactly one packet of state.packet samples per stream, state.latency16 samples (at 16 kHz) late.
         slots= (int32 device tensor, M ids), count= (device int32, optional): the live tick of a server -- x (M, 256), row i
         is the stream in slot slots[i] of the 16 kHz `state`, `count` rows step, no other slot is touched
-        (Engine.wave_stream_step_slots).  Rate and packet states raise: their streams share a group phase."""
+        (Engine.wave_stream_step_slots).  With a packet slot state (init_wave_state(..., packet=, resident=True)): x
+        (M, state.packet), one packet per named slot (Engine.packet_stream_step_slots).  Rate states and plain packet
+        states raise: their streams share a group phase."""
         if slots is not None:
+            if isinstance(state, _lib.PacketSlotState):
+                return self.engine(x.device).packet_stream_step_slots(state, slots, x, count=count)
             return self.engine(x.device).wave_stream_step_slots(state, slots, x, count=count)
         if isinstance(state, _lib.PacketStreamState):
             return self.engine(x.device).packet_stream_step(state, x)

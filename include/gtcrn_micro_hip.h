@@ -436,7 +436,8 @@ int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream *ps, const float *d_gai
  * be captured.  One hop (frame) per call: this is the live tick.  Only the single-launch forms exist indexed: after
  * gtcrn_stream_form(m, 1), or with gtcrn_debug_enable(m, 1), the step calls return GTCRN_ERR_STATE.  Argument errors
  * (null pointers, max_active < 1, short strides, misaligned states, r outside 0..255) return GTCRN_ERR_ARG before any
- * launch.  Out of scope: the rate and packet forms (their streams share a group phase), several hops per call. */
+ * launch.  Out of scope: the rate form (its streams step whole hops at the caller's rate; for packets see "packet stream
+ * slots" below), several hops per call. */
 int gtcrn_stream_step_slots(gtcrn_model *m, void *d_state, const int *d_slots, const int *d_count, int max_active,
                             const float *d_spec_t, long isb, long isf, long ist, float *d_spec_out_t, long osb, long osf,
                             long ost, void *stream);   /* one frame per row: (max_active,257,1,2) by strides */
@@ -455,6 +456,45 @@ int gtcrn_wave_stream_flush_slots_pcm16(gtcrn_model *m, void *d_state, void *d_w
                                         const int *d_count, int max_active, const short *d_tail, long tail_stride, int r,
                                         short *d_out, long out_stride, const float *d_gain, const float *d_win,
                                         void *stream);
+
+/* ---- packet stream slots: per-stream phase, any subset of the resident packet streams per call -------------------------
+ * The packet form above keeps ONE phase per group in the host handle, so every stream of the group needs a packet at every
+ * call.  These calls keep the phase on the device, one word per resident slot, and take the slot table of "stream slots":
+ *   d_phase     int32[resident slots], owned by the caller like the three states: slot s holds phi_s in [0, 256), a
+ *               multiple of g = gcd(n16, 256).  d_state / d_wstate / d_pstate keep their layouts and sizes;
+ *   d_slots, d_count, max_active   as in the _slots calls above (count clamped on the device to 0 .. max_active, rows at
+ *               or beyond it neither read nor written, ids in range and distinct by the caller's precondition);
+ *               max_active <= the handle's max_streams.  How many slots are resident is the caller's own affair.
+ * Rows are COMPACT: row i of d_in / d_out is one packet of n samples for slot d_slots[i].  The dry gains are the pointer of
+ * gtcrn_packet_stream_set_dry_gain, read BY SLOT: gain[d_slots[i]].
+ * Contract:
+ *   - per slot, bit for bit: take the calls that name a slot after its reset; its outputs and its model, wave and packet
+ *     state are those of gtcrn_packet_stream_step(_pcm16) on a one-stream group created at phase 0 and fed the same
+ *     packets.  At 16 kHz: out = zeros(L16) ++ gtcrn_forward_wave(x), L16 = 512 - g; at other rates the stage-by-stage
+ *     contract of the packet form with z = 0.  The latency is the same constant for every stream, whenever it joined;
+ *   - a slot not named in a call is not touched, byte for byte, in all four arrays;
+ *   - gtcrn_packet_stream_reset_slots is a kernel (no memset): it zeroes the named slots' model, wave and packet state
+ *     and their phase word, so a captured graph can admit a stream at any slot;
+ *   - there is no flush: drain with packets of zeros, as in the packet form.
+ * A call makes a FIXED launch sequence that depends on (fs, n, max_active) alone, hmax = (256 - g + n16) div 256:
+ * plan (reads and advances the phases, writes per round the table of slots that still have a hop ready, in row order) ->
+ * inbound -> hmax rounds of the single-launch indexed wave step, one hop each -> outbound.  So ONE captured call serves
+ * every tick and every active set, and a 20 ms call runs single-launch one-frame steps.  It allocates nothing after
+ * gtcrn_packet_stream_create and neither reads nor advances the handle's host phase (gtcrn_packet_stream_phase).
+ * Mixing gtcrn_packet_stream_step and the _slots calls on the same states is not supported.  Only the single-launch stream
+ * forms exist indexed: after gtcrn_stream_form(m, 1), or with gtcrn_debug_enable(m, 1), the calls return GTCRN_ERR_STATE.
+ * Argument errors (null pointers, max_active < 1 or above the handle's max_streams, short strides, misaligned states)
+ * return GTCRN_ERR_ARG before any launch.  Out of scope: _slots for gtcrn_rate_stream_* (48 kHz / 768-sample packets ARE
+ * that form), the _quant paths, gtcrn_packet_stream_debug_handoff after a slot call. */
+int gtcrn_packet_stream_reset_slots(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, int *d_phase,
+                                    const int *d_slots, const int *d_count, int max_active, void *stream);
+int gtcrn_packet_stream_step_slots(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, int *d_phase,
+                                   const int *d_slots, const int *d_count, int max_active, const float *d_in,
+                                   long in_stride, float *d_out, long out_stride, const float *d_win, void *stream);
+int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                         int *d_phase, const int *d_slots, const int *d_count, int max_active,
+                                         const short *d_in, long in_stride, short *d_out, long out_stride,
+                                         const float *d_win, void *stream);
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward

@@ -12,6 +12,15 @@ alternating for `--reps` repetitions; medians:
 processes, new and parent library alternating, `--reps` each; both medians go into the JSON.
 --contiguous-only [--lib PATH]: what such a child runs (case (a) alone, one JSON line).
 Writes profiles/slot_stream_bench.json.
+
+--packet-slots: packet stream slots (gtcrn_packet_stream_step_slots) against the contiguous packet form, at 16 384 and 65 536
+resident streams (--sizes) and 16 kHz / 160, 16 kHz / 320 and 48 kHz / 480.  One process, the cases alternating, ms per CALL
+over one period of 256 / g calls, medians of `--reps` repetitions with their spread:
+  contiguous      gtcrn_packet_stream_step of all N streams;
+  slots_all       the slot form, all N slots named in identity order, phases equal;
+  slots_half      the slot form, a sorted random half, phases staggered over the period (slot s starts s mod period calls late);
+  plan_ms         k_packet_plan alone, from the library's launch records (a run of its own), for slots_all and slots_half.
+Writes profiles/packet_slots_bench.json.
 """
 import argparse
 import json
@@ -62,6 +71,71 @@ def contiguous_only(a):
     print(json.dumps({"lib": a.lib or "default", "N": N, "contiguous_ms": statistics.median(t), "reps_ms": t}), flush=True)
 
 
+def packet_slots(a):
+    from math import gcd
+    eng, win = engine()
+    res = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "reps": a.reps, "unit": "ms per call over one period",
+           "runs": []}
+    for N in a.sizes:
+        for fs, n in ((16000, 160), (16000, 320), (48000, 480)):
+            n16 = n * 16000 // fs
+            period = 256 // gcd(n16, 256)
+            H = N // 2
+            gen = torch.Generator(device="cuda").manual_seed(N + n)
+            x = torch.randn(N, n, device="cuda", generator=gen) * 0.1
+            y = torch.empty_like(x)
+            cs = eng.new_packet_state(N, win, n, fs)
+            sa = eng.new_packet_slot_state(N, win, n, fs)
+            sh = eng.new_packet_slot_state(N, win, n, fs)
+            ident = torch.arange(N, dtype=torch.int32, device="cuda")
+            cnt = torch.tensor([N], dtype=torch.int32, device="cuda")
+            for k in range(period - 1):                        # stagger: slot s has taken s mod period packets
+                late = ident[(ident % period) > k].contiguous()
+                if late.numel():
+                    eng.packet_stream_step_slots(sh, late, x[:late.numel()], out=y[:late.numel()])
+            staggered = sorted(set(sh.phase.tolist()))
+            pick = torch.sort(torch.randperm(N, device="cuda", generator=gen)[:H]).values.to(torch.int32)
+            cnt_h = torch.tensor([H], dtype=torch.int32, device="cuda")
+            xh, yh = x[:H], y[:H]
+
+            def per(fn):
+                def run():
+                    for _ in range(period):
+                        fn()
+                return run
+            cases = {
+                "contiguous": per(lambda: eng.packet_stream_step(cs, x, out=y)),
+                "slots_all": per(lambda: eng.packet_stream_step_slots(sa, ident, x, count=cnt, out=y)),
+                "slots_half": per(lambda: eng.packet_stream_step_slots(sh, pick, xh, count=cnt_h, out=yh)),
+            }
+            for f in cases.values():
+                timed(f, 1)                                    # warm-up: one period
+            t = {k: [] for k in cases}
+            for _ in range(a.reps):
+                for k, f in cases.items():
+                    t[k].append(timed(f, a.iters) / period)
+            plan = {}
+            for k in ("slots_all", "slots_half"):
+                eng.timing_enable(True, only="k_packet_plan")
+                cases[k]()
+                torch.cuda.synchronize()
+                plan[k] = eng.timing_read().get("k_packet_plan", (None, 0))[0]
+                eng.timing_enable(False)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            row = {"N": N, "fs": fs, "n": n, "n16": n16, "period": period, "half": H, "staggered_phases": staggered, "ms": med,
+                   "reps_ms": t, "spread": {k: spread(v) for k, v in t.items()}, "plan_ms": plan,
+                   "slots_all_over_contiguous": med["slots_all"] / med["contiguous"],
+                   "slots_half_per_stream_over_contiguous": (med["slots_half"] / H) / (med["contiguous"] / N)}
+            print(json.dumps({k: v for k, v in row.items() if k != "reps_ms"}), flush=True)
+            res["runs"].append(row)
+            del cs, sa, sh, cases
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=65536)
@@ -71,11 +145,17 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--contiguous-only", action="store_true")
     ap.add_argument("--lib", default=None)
+    ap.add_argument("--packet-slots", action="store_true")
+    ap.add_argument("--sizes", type=int, nargs="+", default=[16384, 65536])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("slot_stream_bench needs the GPU (nothing is measured on the CPU)")
     if a.contiguous_only:
         return contiguous_only(a)
+    if a.packet_slots:
+        if a.out.endswith("slot_stream_bench.json"):
+            a.out = os.path.join(ROOT, "profiles", "packet_slots_bench.json")
+        return packet_slots(a)
     eng, win = engine()
     N, H = a.streams, a.streams // 2
     eng.reserve(N, 1)
