@@ -14,6 +14,15 @@ written in include/gtcrn_micro_hip.h (gtcrn_forward_spec_quant) from the referen
 
 The HIP kernels accumulate in a different order than ATen, so values differ by fp32 rounding BEFORE each fp16
 rounding: a fraction of the elements lands on the neighbouring fp16 value (2^-11 relative).  Tests state the tolerance.
+
+Summation order.  QuantPort(blob, acc="f64") forms every conv / linear / energy sum in float64 from the same
+fp16-valued operands and rounds it once to float32 and then to fp16 at exactly the places where acc="f32" (ATen's
+float32 sums, the default) rounds to fp16.  split=True forms every conv / linear sum as two float32 sums over the two
+halves of its reduction, added: a third order.  The distance between two of them is the flip-noise floor of the contract
+(tests/quant_cases.py); the kernels' MFMA k-order is one more draw of the same noise.
+
+Mutants.  QuantPort(..., mutate=name) seeds ONE bug in ONE place (MUTANTS below): what a checker of this variant has to
+reject.  They exist for tests/test_quant_checker.py only.
 """
 import numpy as np
 import torch
@@ -25,18 +34,28 @@ CALIB_SCALE = 19.944473266601562          # streaming/tflite/calib_scale.txt:1
 
 
 def h16(x):
-    return x.half().float()
+    """Round to binary16 (through float32 when x is float64: once to float32, then to fp16); dtype is kept."""
+    return x.float().half().to(x.dtype)
 
 
-def int8_boundary(x, scale):
-    step = np.float32(scale / 255.0)
-    return torch.clamp(torch.round(x / step), -128, 127) * step
+def quant_step(scale):
+    """The quantiser step the library uses: the float32 quotient scale / 255 (include/gtcrn_micro_hip.h)."""
+    return np.float32(np.float32(scale) / np.float32(255.0))
 
 
-def quant_per_out_channel(w, out_dim=0):
-    """w -> fp16(int8 * scale), one scale per index of `out_dim`."""
+def int8_boundary(x, scale, lo=-128, ties_away=False):
+    """float32 in, float32 out: clip(rint(x / step), -128, 127) * step, ties to even."""
+    x = x.float()
+    step = quant_step(scale)
+    r = x / step
+    r = torch.sign(r) * torch.floor(r.abs() + 0.5) if ties_away else torch.round(r)
+    return torch.clamp(r, lo, 127) * step
+
+
+def quant_per_out_channel(w, out_dim=0, per_tensor=False):
+    """w -> fp16(int8 * scale), one scale per index of `out_dim` (per_tensor: one for all -- a seeded bug)."""
     w = w.double()
-    dims = [d for d in range(w.dim()) if d != out_dim]
+    dims = list(range(w.dim())) if per_tensor else [d for d in range(w.dim()) if d != out_dim]
     mx = w.abs().amax(dim=dims, keepdim=True)
     scale = (mx / 127.0).float().double()
     q = torch.where(scale > 0, torch.clamp(torch.round(w / torch.where(scale > 0, scale, torch.ones_like(scale))),
@@ -44,8 +63,25 @@ def quant_per_out_channel(w, out_dim=0):
     return h16((q * scale).float())
 
 
+# name -> the one place the bug is seeded in
+MUTANTS = {
+    "drop_tap": "encoder.en_convs.3.depth_conv: tap (current frame, centre bin) of channel 0 set to 0",
+    "drop_tcn_tap": "gtcn2.blocks.3.conv2 (d = 8): the oldest tap (16 frames back) set to 0",
+    "no_round": "decoder.de_convs.1.point_conv2: its fp16 rounding skipped",
+    "per_tensor_scale": "encoder.en_convs.2.point_conv2: one weight scale for the tensor, not one per output channel",
+    "clamp127": "input boundary clamped to -127 .. 127",
+    "ties_away": "input and output boundary round half away from zero",
+    "tra_hist": "encoder.en_convs.4.tra: one frame of energy history instead of two",
+    "skip_unrounded": "decoder.de_convs.1: its skip sum x + skips[3] left unrounded",
+    "stale_hist_16": "encoder.en_convs.2.depth_conv: the two history rows zero at every frame = 0 mod 16",
+}
+
+
 class QuantPort:
-    def __init__(self, blob):
+    def __init__(self, blob, acc="f32", mutate=None, split=False):
+        assert acc in ("f32", "f64") and (mutate is None or mutate in MUTANTS) and not (split and acc != "f32")
+        self.dt = torch.float64 if acc == "f64" else torch.float32
+        self.mutate, self.split = mutate, split
         p = {k: v.double() for k, v in blob_to_dict(blob).items()}
         self.p = p
         self.w, self.b = {}, {}
@@ -56,7 +92,8 @@ class QuantPort:
             w = w * (s.view(1, -1, 1, 1) if transposed else s.view(-1, 1, 1, 1))
             bias = p.get(conv + ".bias")
             bias = torch.zeros_like(s) if bias is None else bias
-            self.w[conv] = quant_per_out_channel(w.float(), 1 if transposed else 0)
+            per_tensor = mutate == "per_tensor_scale" and conv == "encoder.en_convs.2.point_conv2"
+            self.w[conv] = quant_per_out_channel(w.float(), 1 if transposed else 0, per_tensor)
             self.b[conv] = ((bias - p[bn + ".running_mean"]) * s + p[bn + ".bias"]).float()
         for i in range(2):
             fold(f"encoder.en_convs.{i}.conv", f"encoder.en_convs.{i}.bn", False)
@@ -77,52 +114,85 @@ class QuantPort:
         self.w["erb"] = quant_per_out_channel(p["erb.erb_fc.weight"].float())
         self.w["ierb"] = quant_per_out_channel(p["erb.ierb_fc.weight"].float())
         self.w["sfe"] = quant_per_out_channel(p["sfe.depth_conv.weight"].float())
-        self.f = {k: v.float() for k, v in p.items()}
+        if mutate == "drop_tap":
+            self.w["encoder.en_convs.3.depth_conv"][0, 0, 2, 1] = 0.0
+        if mutate == "drop_tcn_tap":
+            self.w["gtcn2.blocks.3.conv2"][:, :, 0, :] = 0.0
+        if mutate == "tra_hist":
+            self.w["encoder.en_convs.4.tra.depth_conv"][:, :, 0] = 0.0
+        self.w = {k: v.to(self.dt) for k, v in self.w.items()}
+        self.b = {k: v.to(self.dt) for k, v in self.b.items()}
+        self.f = {k: v.float().to(self.dt) for k, v in p.items()}
+
+    def _sum(self, fn, x, w, b=None, **kw):
+        """One conv / linear: its sums in self.dt; split: over the two halves of the weight tensor's elements (a
+        zeroed weight adds an exact 0, so each call IS the float32 sum of its half), added, then the bias."""
+        if not self.split:
+            return fn(x, w, b, **kw)
+        half = (torch.arange(w.numel()).view(w.shape) % 2 == 0) if w.numel() > 1 else torch.ones_like(w, dtype=torch.bool)
+        y = fn(x, torch.where(half, w, torch.zeros_like(w)), None, **kw) + \
+            fn(x, torch.where(half, torch.zeros_like(w), w), None, **kw)
+        if b is not None:
+            y = y + b.view([1, -1] + [1] * (y.dim() - 2)) if fn is not F.linear else y + b
+        return y
 
     def _tra(self, v, pre):
         f = self.f
         e = (v * v).mean(dim=3)
-        y = F.conv1d(F.pad(e, [2, 0]), self.w[pre + ".depth_conv"], f[pre + ".depth_conv.bias"], groups=8)
-        g = h16(torch.sigmoid(F.conv1d(y, self.w[pre + ".point_conv"], f[pre + ".point_conv.bias"])))
+        y = self._sum(F.conv1d, F.pad(e, [2, 0]), self.w[pre + ".depth_conv"], f[pre + ".depth_conv.bias"], groups=8)
+        g = h16(torch.sigmoid(self._sum(F.conv1d, y, self.w[pre + ".point_conv"], f[pre + ".point_conv.bias"])))
         return h16(v * g.unsqueeze(-1))
 
     def _gtconv(self, x, pre, deconv):
         f, w, b = self.f, self.w, self.b
         x1, x2 = x[:, :8], x[:, 8:]
         conv = F.conv_transpose2d if deconv else F.conv2d
-        h = h16(F.prelu(conv(x1, w[pre + ".point_conv1"], b[pre + ".point_conv1"]), f[pre + ".point_act.weight"]))
+        h = h16(F.prelu(self._sum(conv, x1, w[pre + ".point_conv1"], b[pre + ".point_conv1"]), f[pre + ".point_act.weight"]))
         if deconv:
-            h = F.conv_transpose2d(h, w[pre + ".depth_conv"], b[pre + ".depth_conv"], padding=(0, 1))[:, :, :x.shape[2]]
+            h = self._sum(F.conv_transpose2d, h, w[pre + ".depth_conv"], b[pre + ".depth_conv"], padding=(0, 1))[:, :, :x.shape[2]]
         else:
-            h = F.conv2d(F.pad(h, [0, 0, 2, 0]), w[pre + ".depth_conv"], b[pre + ".depth_conv"], padding=(0, 1), groups=16)
+            hp, wd = F.pad(h, [0, 0, 2, 0]), w[pre + ".depth_conv"]
+            h = self._sum(F.conv2d, hp, wd, b[pre + ".depth_conv"], padding=(0, 1), groups=16)
+            if self.mutate == "stale_hist_16" and pre == "encoder.en_convs.2":
+                wd = wd.clone()
+                wd[:, :, :2] = 0.0                              # no history rows: what a lost chunk hand-off leaves
+                h0 = self._sum(F.conv2d, hp, wd, b[pre + ".depth_conv"], padding=(0, 1), groups=16)
+                h[:, :, 16::16] = h0[:, :, 16::16]
         h = h16(F.prelu(h, f[pre + ".depth_act.weight"]))
-        v = h16(conv(h, w[pre + ".point_conv2"], b[pre + ".point_conv2"]))
+        v = self._sum(conv, h, w[pre + ".point_conv2"], b[pre + ".point_conv2"])
+        if not (self.mutate == "no_round" and pre == "decoder.de_convs.1"):
+            v = h16(v)
         v = self._tra(v, pre + ".tra")
         return torch.stack([v, x2], dim=2).flatten(1, 2)
 
     def _tcn(self, x, pre, d):
         f, w, b = self.f, self.w, self.b
-        y = h16(F.prelu(F.conv2d(x, w[pre + ".conv1"], b[pre + ".conv1"]), f[pre + ".act1.weight"]))
-        y = F.conv2d(F.pad(y, [0, 0, 2 * d, 0]), w[pre + ".conv2"], b[pre + ".conv2"], dilation=(d, 1), groups=16)
+        y = h16(F.prelu(self._sum(F.conv2d, x, w[pre + ".conv1"], b[pre + ".conv1"]), f[pre + ".act1.weight"]))
+        y = self._sum(F.conv2d, F.pad(y, [0, 0, 2 * d, 0]), w[pre + ".conv2"], b[pre + ".conv2"], dilation=(d, 1), groups=16)
         y = h16(F.prelu(y, f[pre + ".act2.weight"]))
-        y = F.conv2d(y, w[pre + ".conv3"], b[pre + ".conv3"])
+        y = self._sum(F.conv2d, y, w[pre + ".conv3"], b[pre + ".conv3"])
         return h16(F.prelu(y + x, f[pre + ".act3.weight"]))
+
+    def _skip(self, x, skips, i):
+        s = x + skips[i]
+        return s if self.mutate == "skip_unrounded" and i == 3 else h16(s)
 
     @torch.inference_mode()
     def forward(self, spec, in_scale=0.0, out_scale=0.0):
         f, w, b = self.f, self.w, self.b
+        away = self.mutate == "ties_away"
         spec = torch.as_tensor(spec, dtype=torch.float32)
         if in_scale > 0:
-            spec = int8_boundary(spec, in_scale)
-        spec = h16(spec)
+            spec = int8_boundary(spec, in_scale, -127 if self.mutate == "clamp127" else -128, away)
+        spec = h16(spec).to(self.dt)
         re, im = spec[..., 0].permute(0, 2, 1), spec[..., 1].permute(0, 2, 1)
         feat = torch.stack([h16(torch.sqrt(re * re + im * im + 1e-12)), re, im], dim=1)
-        feat = torch.cat([feat[..., :65], h16(F.linear(feat[..., 65:], w["erb"]))], dim=-1)
-        x = h16(F.conv2d(feat, w["sfe"], padding=(0, 1), groups=3))
+        feat = torch.cat([feat[..., :65], h16(self._sum(F.linear, feat[..., 65:], w["erb"]))], dim=-1)
+        x = h16(self._sum(F.conv2d, feat, w["sfe"], padding=(0, 1), groups=3))
         skips = []
         for i in range(2):
             pre = f"encoder.en_convs.{i}"
-            x = F.conv2d(x, w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
+            x = self._sum(F.conv2d, x, w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
             x = h16(F.prelu(x, f[pre + ".act.weight"]))
             skips.append(x)
         for i in range(2, 5):
@@ -132,15 +202,16 @@ class QuantPort:
             for k in range(4):
                 x = self._tcn(x, f"gtcn{g}.blocks.{k}", 1 << k)
         for i in range(3):
-            x = self._gtconv(h16(x + skips[4 - i]), f"decoder.de_convs.{i}", True)
+            x = self._gtconv(self._skip(x, skips, 4 - i), f"decoder.de_convs.{i}", True)
         pre = "decoder.de_convs.3"
-        x = F.conv_transpose2d(h16(x + skips[1]), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
+        x = self._sum(F.conv_transpose2d, self._skip(x, skips, 1), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
         x = h16(F.prelu(x, f[pre + ".act.weight"]))
         pre = "decoder.de_convs.4"
-        m = F.conv_transpose2d(h16(x + skips[0]), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
+        m = self._sum(F.conv_transpose2d, self._skip(x, skips, 0), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
         m = h16(torch.tanh(m))
-        m = torch.cat([m[..., :65], h16(F.linear(m[..., 65:], w["ierb"]))], dim=-1)
+        m = torch.cat([m[..., :65], h16(self._sum(F.linear, m[..., 65:], w["ierb"]))], dim=-1)
         out = torch.stack([h16(re * m[:, 0] - im * m[:, 1]), h16(im * m[:, 0] + re * m[:, 1])], dim=-1).permute(0, 2, 1, 3)
+        out = out.float()
         if out_scale > 0:
-            out = int8_boundary(out, out_scale)
-        return out.numpy()
+            out = int8_boundary(out, out_scale, ties_away=away)
+        return out.contiguous().numpy()
