@@ -139,6 +139,10 @@ def lib():
         L.gtcrn_packet_stream_reset_slots.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp]
         for fn in ("gtcrn_packet_stream_step_slots", "gtcrn_packet_stream_step_slots_pcm16"):
             getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, _vp, _vp]
+    # level meters (an earlier library has neither symbol: a state with meters then fails at its first step)
+    if hasattr(L, "gtcrn_wave_stream_set_meters"):
+        L.gtcrn_wave_stream_set_meters.argtypes = [_vp, _vp]
+        L.gtcrn_level_dbov.argtypes = [ctypes.c_double, ctypes.c_double]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -243,6 +247,17 @@ def atten_lim_to_gain(db):
     if db == float("inf"):
         return 0.0
     return float(10.0 ** (-db / 20.0))
+
+
+def level_dbov(energy, nsamples):
+    """RFC 6464 audio level of a window of `nsamples` samples whose squares sum to `energy` (full scale 1.0): -dBov rounded
+    to the nearest integer, 0 (loudest) .. 127 (silence, also for energy <= 0 or nsamples <= 0).  gtcrn_level_dbov, on the
+    host; scalars give an int, arrays (broadcast against each other) an int32 array."""
+    fn = lib().gtcrn_level_dbov
+    if np.ndim(energy) == 0 and np.ndim(nsamples) == 0:
+        return int(fn(float(energy), float(nsamples)))
+    e, n = np.broadcast_arrays(np.asarray(energy, np.float64), np.asarray(nsamples, np.float64))
+    return np.array([fn(float(a), float(b)) for a, b in zip(e.ravel(), n.ravel())], np.int32).reshape(e.shape)
 
 
 def _gains_of(db, n):
@@ -594,12 +609,15 @@ class Engine:
     def wave_state_bytes():
         return int(lib().gtcrn_wave_stream_state_bytes())
 
-    def new_wave_state(self, nstreams, window, atten_lim_db=None):
+    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False):
         """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
         counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
         one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it).  atten_lim_db (a
         number or one per stream; None: off): the attenuation limit, kept as the per-stream gains ``state.dry_gain``
-        that every step and flush of the state then applies (WaveStreamState.set_atten_lim_db rewrites them)."""
+        that every step and flush of the state then applies (WaveStreamState.set_atten_lim_db rewrites them).
+        meters=True: the state owns ``state.meters``, (n, 4) float32 records {E_dry, E_out, peak, blocks} per stream (the
+        header's "level meters"), zeroed here, which every step and flush through the state then updates on the device
+        (WaveStreamState.reset_meters starts a new window, .levels() reads the RFC 6464 levels)."""
         import torch
         n = int(nstreams)
         if n < 1:
@@ -616,7 +634,19 @@ class Engine:
         self.wave_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
+        if meters:
+            st.meters = torch.zeros((n, 4), device=win.device, dtype=torch.float32)
         return st
+
+    def _set_meters(self, state):
+        """Hands the state's records to the model ahead of a step or flush, or clears the model's pointer for a state
+        without meters: two states on one engine do not leak into each other."""
+        fn = getattr(lib(), "gtcrn_wave_stream_set_meters", None)
+        if fn is None and state.meters is None:
+            return                                       # (an earlier library, loaded for a comparison: nothing to clear)
+        if fn is None:
+            raise GtcrnError("this library has no level meters")
+        _check(fn(self._h, None if state.meters is None else state.meters.data_ptr()))
 
     def wave_stream_reset(self, state, lo=0, hi=None):
         """Resets streams lo..hi-1 (both states) to the start of a new clip."""
@@ -665,6 +695,7 @@ class Engine:
         pcm = x.dtype == torch.int16
         args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
                 out.stride(0), state.n, L // 256)
+        self._set_meters(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_step_pcm16 if pcm else lib().gtcrn_wave_stream_step
@@ -686,6 +717,7 @@ class Engine:
         pcm = tail.dtype == torch.int16
         args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
                 tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n)
+        self._set_meters(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_flush_pcm16 if pcm else lib().gtcrn_wave_stream_flush
@@ -783,6 +815,7 @@ class Engine:
         out = self._wave_out(out, x, 256)
         fn = lib().gtcrn_wave_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step_slots
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
+        self._set_meters(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m, x.data_ptr(), x.stride(0),
                       out.data_ptr(), out.stride(0), gain, state.window.data_ptr(), _stream_ptr()))
@@ -799,6 +832,7 @@ class Engine:
         out = self._wave_out(out, tail, 256)
         fn = lib().gtcrn_wave_stream_flush_slots_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush_slots
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
+        self._set_meters(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
                       tail.data_ptr() if r else None, tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), gain,
@@ -834,18 +868,20 @@ class Engine:
             return y
         return self.resampler(16000, int(out_fs))(y)
 
-    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None):
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
-        resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz)."""
+        resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz); meters: as in
+        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step)."""
         import torch
         fs = int(fs)
         hop = _check(lib().gtcrn_rate_stream_hop(fs))
-        ws = self.new_wave_state(nstreams, window)
+        ws = self.new_wave_state(nstreams, window, meters=meters)
         st = RateStreamState(ws.model, ws.wave, ws.window, fs, hop, self.resampler(fs, 16000), self.resampler(16000, fs),
                              torch.empty((ws.n, rate_stream_state_bytes(fs) // 4), device=ws.wave.device, dtype=torch.float32))
         self.rate_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
+        st.meters = ws.meters
         return st
 
     def rate_stream_reserve(self, state, nhops):
@@ -880,6 +916,7 @@ class Engine:
         pcm = x.dtype == torch.int16
         args = (self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
                 state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
+        self._set_meters(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_rate_stream_step_pcm16 if pcm else lib().gtcrn_rate_stream_step
@@ -899,17 +936,18 @@ class Engine:
         return out
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
-    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None):
+    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
         needs is reserved here.  atten_lim_db: as in new_wave_state; the handle keeps the gains' address
-        (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains."""
+        (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains.  meters: as in
+        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step; a call without a hop leaves them alone)."""
         import torch
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
-        ws = self.new_wave_state(nstreams, window)
+        ws = self.new_wave_state(nstreams, window, meters=meters)
         rs_in = self.resampler(fs, 16000) if fs != 16000 else None
         rs_out = self.resampler(16000, fs) if fs != 16000 else None
         h = ctypes.c_void_p()
@@ -921,6 +959,7 @@ class Engine:
         self.packet_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
+        st.meters = ws.meters
         return st
 
     def packet_stream_reset(self, state, lo=0, hi=None):
@@ -949,6 +988,7 @@ class Engine:
         out = self._wave_out(out, x, state.packet)
         fn = lib().gtcrn_packet_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step
         state.last_hops = state.next_hops
+        self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
@@ -968,17 +1008,17 @@ class Engine:
         return out
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
-    def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None):
+    def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
-        one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db: as in
+        one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db and meters: as in
         new_wave_state, per SLOT."""
         import torch
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
-        ws = self.new_wave_state(nslots, window)
+        ws = self.new_wave_state(nslots, window, meters=meters)
         m = ws.n if max_active is None else int(max_active)
         if not 1 <= m <= ws.n:
             raise GtcrnError(f"max_active must be 1..{ws.n} (the resident slots), got {m}")
@@ -993,6 +1033,7 @@ class Engine:
                              torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.int32), m)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
+        st.meters = ws.meters
         return st
 
     def _packet_slot_args(self, state, slots, count):
@@ -1021,6 +1062,7 @@ class Engine:
             x = x.contiguous()
         out = self._wave_out(out, x, state.packet)
         fn = lib().gtcrn_packet_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_slots
+        self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
@@ -1135,6 +1177,7 @@ class WaveStreamState:
         self.wave = wave
         self.window = window
         self.dry_gain = None        # (N,) float32 on the device: the attenuation limit's dry gains; None: limit off
+        self.meters = None          # (N, 4) float32 on the device: {E_dry, E_out, peak, blocks} per stream; None: no metering
 
     @property
     def n(self):
@@ -1167,6 +1210,29 @@ class WaveStreamState:
             self.dry_gain[lo:hi].fill_(g)
         else:
             self.dry_gain[lo:hi].copy_(torch.from_numpy(g), non_blocking=True)
+
+
+    def _metered(self):
+        if self.meters is None:
+            raise GtcrnError("the state has no level meters: create it with meters=True")
+        return self.meters
+
+    def reset_meters(self, lo=0, hi=None):
+        """Starts a new window for streams (slots) lo..hi-1: zeroes their records, asynchronously on the current stream and
+        without any allocation (a memset: capturable)."""
+        m = self._metered()
+        hi = self.n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        m[lo:hi].zero_()
+
+    def levels(self):
+        """The RFC 6464 audio level (0 loudest .. 127 silence, -dBov at full scale 1.0) of every stream's window since its
+        last reset_meters, from E_out and 256 * blocks of the records: an (N,) int32 numpy array.  SYNCHRONOUS: the
+        records (16 bytes per stream) are copied to the host."""
+        rec = self._metered().detach().cpu().numpy().astype(np.float64)
+        return level_dbov(rec[:, 1], 256.0 * rec[:, 3])
 
 
 class RateStreamState(WaveStreamState):

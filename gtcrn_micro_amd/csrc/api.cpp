@@ -53,7 +53,8 @@ struct Timing {
     X(K_STREAM_MS, "k_stream_ms") X(K_STREAM_WIDE, "k_stream_wide") X(K_WAVE_ANALYSIS, "k_wave_analysis")                 \
     X(K_WAVE_SYNTHESIS, "k_wave_synthesis") X(K_PACKET_IN, "k_packet_in") X(K_PACKET_OUT, "k_packet_out")                 \
     X(K_WAVE_SYNTHESIS_MIX, "k_wave_synthesis_mix") X(K_ISTFT_MIX, "k_istft_mix") X(K_PACKET_PLAN, "k_packet_plan")       \
-    X(K_PACKET_IN_SLOTS, "k_packet_in_slots") X(K_PACKET_OUT_SLOTS, "k_packet_out_slots")
+    X(K_PACKET_IN_SLOTS, "k_packet_in_slots") X(K_PACKET_OUT_SLOTS, "k_packet_out_slots")                                 \
+    X(K_WAVE_SYNTHESIS_METER, "k_wave_synthesis_meter")
 #define GT_KERNEL_ID(id, name) id,
 #define GT_KERNEL_NAME(id, name) name,
 enum KernelId { GT_KERNELS(GT_KERNEL_ID) K_COUNT };
@@ -89,6 +90,7 @@ struct gtcrn_model {
     float* d_spec_b = nullptr;
     float* d_rate_a = nullptr;  // 16 kHz hand-offs of gtcrn_rate_stream_step (nstreams x 256 nhops each): k_rate_in -> wave step,
     float* d_rate_b = nullptr;  // wave step -> k_rate_out; sized by gtcrn_rate_stream_reserve
+    float* d_meters = nullptr;  // the caller's level-meter records (gtcrn_wave_stream_set_meters); NULL: no metering
     long cap_rate = 0;          // capacity of each in (streams * hops)
     bool debug = false;
     bool debug_keep_fused = false;   // gtcrn_debug_enable(m, 2): phase stamps only -- single-frame steps stay ONE launch
@@ -648,6 +650,24 @@ int gtcrn_wave_stream_reset(gtcrn_model* m, void* d_state, void* d_wstate, int n
     return 0;
 }
 
+// Level meters (contract: include/gtcrn_micro_hip.h, "level meters"): the model keeps the address, wave_step hands it to the
+// synthesis launch.  Nothing is launched or read here.
+int gtcrn_wave_stream_set_meters(gtcrn_model* m, float* d_meters) {
+    if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_meters: null model");
+    if (reinterpret_cast<uintptr_t>(d_meters) & 15)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_meters: the records must be 16-byte aligned");
+    m->d_meters = d_meters;
+    return 0;
+}
+
+// RFC 6464 audio level of a window of `nsamples` samples with energy `energy` (full scale 1.0): -dBov rounded to the nearest
+// integer, 0 (loudest) .. 127 (silence).  Host arithmetic only.
+int gtcrn_level_dbov(double energy, double nsamples) {
+    if (!(energy > 0.0) || !(nsamples > 0.0)) return 127;
+    const double l = std::floor(-10.0 * std::log10(energy / nsamples) + 0.5);
+    return l < 0.0 ? 0 : l > 127.0 ? 127 : (int)l;
+}
+
 // Stream slots (contract: include/gtcrn_micro_hip.h): row i of a call is the stream whose states sit in slot d_slots[i];
 // *d_count rows (clamped to 0..max_active on the device) step.  The host sizes the grid, the workspace and the form from
 // max_active alone, so one captured graph serves any active set.  Only the single-launch step exists indexed.
@@ -665,7 +685,8 @@ int refuse_three_launch_form(const std::string& w, const gtcrn_model* m) {
 }
 }  // namespace
 
-// Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given) of n rows.
+// Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given, metered while
+// the model holds a meters address: the rate, packet and packet-slot forms come through here too) of n rows.
 // Without a table the rows are the n streams of a contiguous state range, nhops hops each; with one (the _slots calls)
 // they are the n = max_active rows it names, one hop.
 extern "C++" template <typename S>
@@ -699,9 +720,9 @@ static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wst
     rc = indexed ? fused_stream_step(m, m->d_spec_a, sb, sf, m->d_spec_b, sb, sf, n, ms, rows, s)
                  : run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, n, nhops, ms, s);
     if (rc) return rc;
-    tm.begin(d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
+    tm.begin(m->d_meters ? K_WAVE_SYNTHESIS_METER : d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
     LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, n, nhops, r, flush, ws, d_win,
-                                             m->d_twid, rows, d_gain, s));
+                                             m->d_twid, rows, d_gain, m->d_meters, s));
     tm.end();
     return 0;
 }

@@ -75,14 +75,16 @@ struct Rows {
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
 // wstate (not on flush).  flush = the end-reflected last frame.  gain (optional, device, float[N]): the attenuation limit,
-// mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.
+// mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.  meters (optional,
+// device, 4 floats per stream or slot, 16-byte aligned): the level-meter records, advanced by the METER instantiations, which
+// read `gain` at run time (nullptr or not); nullptr: the launches above.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
                          const float* win, const float* twid, float* spec, Rows rows, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          hipStream_t s);
+                          float* meters, hipStream_t s);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;

@@ -796,7 +796,23 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 // rounding of the int16 form; the zeros of a stream's first call and of an empty flush stay zeros.  The block of hop h is
 // block c0 + h - 1, so its dry samples are the ring's newest 256 (h == 0: the float2 pairs this lane loads for the ring
 // shift at nhops == 1 anyway) or hop h - 1 of this call's input rows.
-template <typename S, bool FLUSH, bool MIX = false, bool IDX = false>
+// METER: the level meters (include/gtcrn_micro_hip.h, "level meters") -- the stream's record meters[4 slot .. 4 slot + 3] =
+// {E_dry, E_out, peak, blocks} is read once, advanced hop by hop from the emitted floats y and the dry samples x that MIX
+// would use (both 0 for a structural zero block), and stored once by lane 0, in front of the flush's return.  The metered
+// instantiations take the limit as a wave-uniform run-time branch (MIX = false, gain may be null: the plain sample then).
+// wave_sum / wave_max: every lane ends with the same value, the xor butterfly over lane distances 1, 2, 4, 8, 16, 32 in
+// that order (an fp32 add is commutative, so both partners of a step round alike).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = __fadd_rn(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
                                                                   int N, int nhops, int r, float* __restrict__ wstate,
@@ -804,7 +820,9 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                                                                   const float2* __restrict__ twid,
                                                                   const float* __restrict__ gain,
                                                                   const int* __restrict__ slots,
-                                                                  const int* __restrict__ cnt) {
+                                                                  const int* __restrict__ cnt,
+                                                                  float* __restrict__ meters) {
+    static_assert(!(MIX && METER), "the metered instantiations branch on gain at run time");
     if constexpr (IDX) N = slot_count(cnt, N);
     __shared__ float2 s_tw[256];
     __shared__ float2 s_tw512[256];
@@ -842,6 +860,14 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
 #pragma unroll
         for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
     }
+    float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);      // METER: the stream's record, the same in every lane
+    float pk = 0.f;                                    // METER: this lane's max |y| over the call (a max is exact in any order)
+    if constexpr (METER) {
+        if (gain) g = gain[slot];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
+        rec = *reinterpret_cast<const float4*>(meters + 4 * slot);
+    }
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
         // merge: Z[k] = Xe + i Xo (k_istft); the imaginary parts of DC and Nyquist are ignored
@@ -870,11 +896,28 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
         }
         wave_lds_sync();     // A is rewritten by the next hop's merge
         const bool zero = none || c0 + h == 0;     // call 0 of a stream emits zeros (the one-hop delay)
+        float ed = 0.f, eo = 0.f;                  // METER: this lane's partial sums of the hop, ((s0^2 + s1^2) + s2^2) + s3^2
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int m = lane + 64 * q;
             const float a0 = prev[q].x + f[q].x, a1 = prev[q].y + f[q].y;
-            if constexpr (MIX) {
+            if constexpr (METER) {
+                float2 d = dry0[q];
+                if (h > 0) {
+                    const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
+                    d = make_float2(wave_ld(xd), wave_ld(xd + 1));
+                }
+                const float w0 = env[q][0] > 1e-11f ? a0 / env[q][0] : a0, w1 = env[q][1] > 1e-11f ? a1 / env[q][1] : a1;
+                // (without gains the plain sample itself: wave_mix(0, x, w) is not w for a non-finite x)
+                const float y0 = zero ? 0.f : (gain ? wave_mix(g, d.x, w0) : w0);
+                const float y1 = zero ? 0.f : (gain ? wave_mix(g, d.y, w1) : w1);
+                wave_st(o + 256L * h + 2 * m, y0);
+                wave_st(o + 256L * h + 2 * m + 1, y1);
+                const float x0 = zero ? 0.f : d.x, x1 = zero ? 0.f : d.y;
+                ed = __fadd_rn(q ? __fadd_rn(ed, __fmul_rn(x0, x0)) : __fmul_rn(x0, x0), __fmul_rn(x1, x1));
+                eo = __fadd_rn(q ? __fadd_rn(eo, __fmul_rn(y0, y0)) : __fmul_rn(y0, y0), __fmul_rn(y1, y1));
+                pk = fmaxf(pk, fmaxf(fabsf(y0), fabsf(y1)));
+            } else if constexpr (MIX) {
                 float2 d = dry0[q];
                 if (h > 0) {
                     const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
@@ -888,6 +931,15 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
             }
             prev[q] = f[q + 2];
         }
+        if constexpr (METER) {      // acc = fl(acc + e_h), hop after hop: the record does not depend on how the hops are cut into calls
+            rec.x = __fadd_rn(rec.x, wave_sum(ed));
+            rec.y = __fadd_rn(rec.y, wave_sum(eo));
+            rec.w = __fadd_rn(rec.w, 1.0f);
+        }
+    }
+    if constexpr (METER) {
+        rec.z = fmaxf(rec.z, wave_max(pk));
+        if (lane == 0) *reinterpret_cast<float4*>(meters + 4 * slot) = rec;
     }
     if constexpr (FLUSH) return;
     // the state: tail = the newest frame's windowed second half; ring = the last 512 input samples; counter (saturating)
@@ -898,8 +950,8 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int j = 2 * (lane + 64 * q);
-        if (q < 2 && nhops == 1) {      // (this lane's own q + 2; MIX holds the pair already)
-            if constexpr (MIX) ring[q] = dry0[q];
+        if (q < 2 && nhops == 1) {      // (this lane's own q + 2; MIX and METER hold the pair already)
+            if constexpr (MIX || METER) ring[q] = dry0[q];
             else ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);
         } else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
     }
@@ -4410,23 +4462,31 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          hipStream_t s) {
+                          float* meters, hipStream_t s) {
     if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
     // a mixed flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
-    with_flags([&](auto FLUSH, auto MIX, auto IDX) {
-        hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
-                           in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
-                           rows.cnt);
-    }, flush, gain != nullptr, rows.slots != nullptr);
+    if (meters) {       // the metered instantiations read `gain` at run time: one per (S, FLUSH, IDX)
+        with_flags([&](auto FLUSH, auto IDX) {
+            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s,
+                               spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain,
+                               rows.slots, rows.cnt, meters);
+        }, flush, rows.slots != nullptr);
+    } else {
+        with_flags([&](auto FLUSH, auto MIX, auto IDX) {
+            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
+                               in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
+                               rows.cnt, meters);
+        }, flush, gain != nullptr, rows.slots != nullptr);
+    }
     GT_LAUNCH_CHECK();
     return 0;
 }
 template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
 template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, hipStream_t);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {

@@ -496,6 +496,59 @@ int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream *ps, void *d_state,
                                          const short *d_in, long in_stride, short *d_out, long out_stride,
                                          const float *d_win, void *stream);
 
+/* ---- level meters: per-stream energies, peak and block count on every live waveform path ------------------------------
+ * A conferencing or telephony front end needs, per stream and per tick, how loud the stream is: the RTP audio-level header
+ * extension (RFC 6464), a silence / DTX decision, a clip indicator, and "how much is the enhancer taking out" as dry against
+ * wet energy.  The emitted block and the dry hop aligned with it meet in registers where the block is written, so the
+ * figures cost no launch and no copy of the audio: one 16-byte record per stream.
+ *
+ * gtcrn_wave_stream_set_meters stores d_meters in the model (as gtcrn_packet_stream_set_dry_gain stores the gains in its
+ * handle).  NULL, the default, means no metering: the plain launches, nothing else changes.  While an address is set, every
+ * call that runs the wave step -- gtcrn_wave_stream_step*, _flush*, _limited*, _slots*, gtcrn_rate_stream_step*,
+ * gtcrn_packet_stream_step* and gtcrn_packet_stream_step_slots* -- updates one RECORD of four floats per stepped stream.
+ * The record index follows the dry gains: the contiguous calls use d_meters + 4 n for row n of the call, the slot calls
+ * d_meters + 4 d_slots[i].  The array is caller-owned device memory, 16-byte aligned, and must cover every row or slot a
+ * call can name; a captured graph holds the address, as it does for the gains.  A null model or a misaligned pointer is
+ * GTCRN_ERR_ARG.
+ *
+ * The record.  All values are taken at 16 kHz, where the wave step works (also in the rate and packet forms):
+ *   [0] E_dry  += sum of x^2 over the dry samples aligned with each emitted block: exactly the x of the attenuation limit
+ *              (the ring's newest 256 samples for the first hop of a call and for the flush, hop h - 1 of the call's input
+ *              rows after that);
+ *   [1] E_out  += sum of y^2 over the emitted samples, y the float handed to the store: after the attenuation mix if there
+ *              is one, BEFORE the rounding to int16 of the _pcm16 forms;
+ *   [2] peak    = max(peak, max |y|): above 1.0 the PCM16 form clipped;
+ *   [3] blocks += 1 per emitted 256-sample block (a float: exact to 2^24).
+ * Every block the kernel writes counts.  The structural zero blocks -- the first hop of a stream, the flush of a stream that
+ * holds fewer than 257 samples -- add 1 to blocks and 0 to both energies.  Rows a call does not step are neither written
+ * nor read: slots not named, rows at or beyond the device count, rows of a packet-slot call that have no hop in a round.
+ *
+ * Accumulation order.  The wave that owns the stream reads the record once, adds hop after hop in order,
+ * acc = fl(acc + e_h), and stores it once (lane 0, one 16-byte store; in the flush too).  e_h, the hop's sum, is reduced in
+ * ONE fixed order: lane l (0..63) holds samples 2l, 2l + 1, 128 + 2l, 129 + 2l of the block and forms
+ * p_l = fl(fl(fl(s0^2 + s1^2) + s2^2) + s3^2), every square and every add one fp32 rounding and no fused multiply-add; then
+ * six butterfly steps v_l = fl(v_l + v_(l xor d)), d = 1, 2, 4, 8, 16, 32 in that order, leave e_h in every lane.  The
+ * DEPTH D of this order -- the most roundings on a path from a sample to e_h -- is 1 + 3 + 6:
+ *     D = 10
+ * (and D <= 16 is required of any later change).  So each energy is within m u / (1 - m u), u = 2^-24, m = D + K + 1, of the
+ * exact sum after K hops, and a numpy float32 emulation of the order reproduces it bit for bit.  The peak is exact.  Hence
+ * metered values do not depend on how a hop sequence is cut into calls or launches: a 2-hop contiguous packet call and two
+ * 1-hop rounds of the slot form give the same bits.
+ *
+ * The caller starts a window by zeroing records (hipMemsetAsync, also as a graph node).  There is no meter state anywhere
+ * else: every *_state_bytes and gtcrn_abi_version() are what they were, and the outputs and the model, wave, rate and packet
+ * states after a metered call equal the plain call's bit for bit.  A metered call makes the launches of its plain form, one
+ * for one (the synthesis is timed as k_wave_synthesis_meter, with or without gains).
+ *
+ * gtcrn_level_dbov is a pure host function (no device is touched): RFC 6464's level of a window,
+ * floor(-10 log10(energy / nsamples) + 0.5) clamped to 0..127, and 127 for energy <= 0 or nsamples <= 0.  Full scale is 1.0,
+ * so a full-scale sine gives 3.  Feed it E_out and 256 * blocks.
+ * Out of scope: the offline calls (gtcrn_forward_wave* leaves both arrays on the device for the caller to reduce); the
+ * spectral gtcrn_stream_step*; the _quant paths; per-packet windows at the caller's rate (the meter is per 16 kHz hop, the
+ * caller chooses the window by when it zeroes); a voice-activity decision. */
+int gtcrn_wave_stream_set_meters(gtcrn_model *m, float *d_meters);
+int gtcrn_level_dbov(double energy, double nsamples);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),

@@ -23,6 +23,11 @@ offline, the library's event times of k_istft and k_istft_mix at B = 256 x 4 s. 
 plain one of the SAME run and that run's own repetition spread.  Writes profiles/dry_gain_bench.json.  With
 --trace-only N: plain and limited wave steps alternating, then plain and limited offline calls (for one rocprofv3
 --kernel-trace --stats run that holds k_wave_synthesis and k_istft in both forms).
+
+--meters: the level meters.  At 16 384 and 65 536 streams (or --sizes) the plain and the metered 16 kHz wave step alternate
+in one run, then one period of the plain and the metered packet form at 16 kHz / 160, as --dry-gain does; the library's
+event times of k_wave_synthesis against k_wave_synthesis_meter come from that run's launch records.  Each metered figure
+stands next to the plain one of the SAME run and that run's own repetition spread.  Writes profiles/meters_bench.json.
 """
 import argparse
 import json
@@ -201,13 +206,27 @@ def spread(v):
 
 
 def compare_dry_gain(eng, win, N, iters, reps, db=12.0, packet=160):
-    """Plain against limited at N streams, alternating in one run: the one-hop 16 kHz wave step, then one whole period of
-    the packet form at 16 kHz / `packet`."""
+    """Plain against limited at N streams (compare_pair)."""
+    return compare_pair(eng, win, N, iters, reps, "limited", {"atten_lim_db": db}, packet)
+
+
+def compare_meters(eng, win, N, iters, reps, packet=160):
+    """Plain against metered at N streams (compare_pair), plus the synthesis kernels' own event times side by side."""
+    r = compare_pair(eng, win, N, iters, reps, "metered", {"meters": True}, packet)
+    k = r["kernels_event_timed"]
+    r["k_wave_synthesis_ms"], r["k_wave_synthesis_meter_ms"] = k["k_wave_synthesis"]["avg_ms"], k["k_wave_synthesis_meter"]["avg_ms"]
+    r["k_wave_synthesis_ratio"] = r["k_wave_synthesis_meter_ms"] / r["k_wave_synthesis_ms"]
+    return r
+
+
+def compare_pair(eng, win, N, iters, reps, tag, kw, packet):
+    """Plain against the states made with `kw` (keys named `tag`) at N streams, alternating in one run: the one-hop 16 kHz
+    wave step, then one whole period of the packet form at 16 kHz / `packet`."""
     gen = torch.Generator(device="cuda").manual_seed(N)
     eng.reserve(N, 1)
     x = torch.randn(N, 256, device="cuda", generator=gen) * 0.1
     y = torch.empty_like(x)
-    sp, sl = eng.new_wave_state(N, win), eng.new_wave_state(N, win, atten_lim_db=db)
+    sp, sl = eng.new_wave_state(N, win), eng.new_wave_state(N, win, **kw)
     plain = lambda: eng.wave_stream_step(sp, x, out=y)             # noqa: E731
     lim = lambda: eng.wave_stream_step(sl, x, out=y)               # noqa: E731
     for f in (plain, lim):
@@ -223,13 +242,13 @@ def compare_dry_gain(eng, win, N, iters, reps, db=12.0, packet=160):
     torch.cuda.synchronize()
     kern = {k: {"avg_ms": v[0], "launches": v[1]} for k, v in eng.timing_read().items()}
     eng.timing_enable(False)
-    r = {"N": N, "iters": iters, "atten_lim_db": db, "wave_step_plain_ms": statistics.median(tp),
-         "wave_step_limited_ms": statistics.median(tl), "wave_step_plain_reps_ms": tp, "wave_step_limited_reps_ms": tl,
-         "wave_step_plain_spread": spread(tp), "wave_step_limited_spread": spread(tl), "kernels_event_timed": kern}
-    r["wave_step_ratio"] = r["wave_step_limited_ms"] / r["wave_step_plain_ms"]
+    r = {"N": N, "iters": iters, **kw, "wave_step_plain_ms": statistics.median(tp),
+         f"wave_step_{tag}_ms": statistics.median(tl), "wave_step_plain_reps_ms": tp, f"wave_step_{tag}_reps_ms": tl,
+         "wave_step_plain_spread": spread(tp), f"wave_step_{tag}_spread": spread(tl), "kernels_event_timed": kern}
+    r["wave_step_ratio"] = r[f"wave_step_{tag}_ms"] / r["wave_step_plain_ms"]
     del sp, sl
     torch.cuda.empty_cache()
-    pp, pl = eng.new_packet_state(N, win, packet), eng.new_packet_state(N, win, packet, atten_lim_db=db)
+    pp, pl = eng.new_packet_state(N, win, packet), eng.new_packet_state(N, win, packet, **kw)
     P = pp.period
     xp = torch.randn(N, packet, device="cuda", generator=gen) * 0.1
     yp = torch.empty_like(xp)
@@ -246,10 +265,10 @@ def compare_dry_gain(eng, win, N, iters, reps, db=12.0, packet=160):
         qp.append(timed(lambda: period(pp), nper))
         ql.append(timed(lambda: period(pl), nper))
     r.update({"packet": packet, "period_calls": P, "packet_period_plain_ms": statistics.median(qp),
-              "packet_period_limited_ms": statistics.median(ql), "packet_period_plain_reps_ms": qp,
-              "packet_period_limited_reps_ms": ql, "packet_period_plain_spread": spread(qp),
-              "packet_period_limited_spread": spread(ql)})
-    r["packet_period_ratio"] = r["packet_period_limited_ms"] / r["packet_period_plain_ms"]
+              f"packet_period_{tag}_ms": statistics.median(ql), "packet_period_plain_reps_ms": qp,
+              f"packet_period_{tag}_reps_ms": ql, "packet_period_plain_spread": spread(qp),
+              f"packet_period_{tag}_spread": spread(ql)})
+    r["packet_period_ratio"] = r[f"packet_period_{tag}_ms"] / r["packet_period_plain_ms"]
     del pp, pl
     torch.cuda.empty_cache()
     return r
@@ -322,6 +341,8 @@ def main():
     ap.add_argument("--trace-packet", type=int, default=480, help="--packet --trace-only: the packet, in samples at --trace-fs")
     ap.add_argument("--dry-gain", action="store_true",
                     help="the attenuation limit: plain against limited wave step, packet period (16 kHz / 160) and k_istft")
+    ap.add_argument("--meters", action="store_true",
+                    help="the level meters: plain against metered wave step and packet period (16 kHz / 160)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wave_stream_bench needs the GPU (nothing is measured on the CPU)")
@@ -329,6 +350,19 @@ def main():
     params = np.fromfile(os.path.join(ROOT, "tests", "golden", "params_dns3.f32"), dtype=np.float32)
     eng = Engine(params, 0)
     win = torch.hann_window(512).pow(0.5).cuda()
+    if a.meters:
+        sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "meters_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in sizes:
+            r = compare_meters(eng, win, N, a.iters, a.reps)
+            print(json.dumps({k: v for k, v in r.items() if "reps" not in k and k != "kernels_event_timed"}), flush=True)
+            res["compare"].append(r)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
     if a.dry_gain:
         sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
         if a.trace_only:
