@@ -143,6 +143,14 @@ def lib():
     if hasattr(L, "gtcrn_wave_stream_set_meters"):
         L.gtcrn_wave_stream_set_meters.argtypes = [_vp, _vp]
         L.gtcrn_level_dbov.argtypes = [ctypes.c_double, ctypes.c_double]
+    # G.711 payloads (an earlier library has none of these: a G.711 state or converter then fails at its first call)
+    if hasattr(L, "gtcrn_packet_stream_step_g711"):
+        L.gtcrn_packet_stream_step_g711.argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
+        L.gtcrn_packet_stream_step_slots_g711.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, ci, _vp, _vp]
+        L.gtcrn_g711_to_f32.argtypes = [ci, ci, _vp, _vp, cl, _vp]
+        L.gtcrn_f32_to_g711.argtypes = [ci, ci, _vp, _vp, cl, _vp]
+        L.gtcrn_g711_decode_table.argtypes = [ci, ctypes.POINTER(ctypes.c_short)]
+        L.gtcrn_g711_encode_pcm16.argtypes = [ci, ci]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -658,9 +666,10 @@ class Engine:
             _check(lib().gtcrn_wave_stream_reset(self._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
                                                  hi - lo, _stream_ptr()))
 
-    def _wave_rows(self, state, x, what):
+    def _wave_rows(self, state, x, what, g711=False):
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
+        kinds = (torch.float32, torch.int16, torch.uint8) if g711 else (torch.float32, torch.int16)   # (uint8: the packet forms)
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in kinds:
             raise GtcrnError(f"{what} must be a float32 or int16 CUDA (ROCm) tensor")
         if x.device.index != self.device:
             raise GtcrnError(f"{what} is on cuda:{x.device.index}, the model on cuda:{self.device}")
@@ -936,14 +945,17 @@ class Engine:
         return out
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
-    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False):
+    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
         needs is reserved here.  atten_lim_db: as in new_wave_state; the handle keeps the gains' address
         (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains.  meters: as in
-        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step; a call without a hop leaves them alone)."""
+        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step; a call without a hop leaves them alone).
+        g711: "ulaw", "alaw" or None -- the law of the torch.uint8 rows packet_stream_step then takes and returns (RTP payload
+        types 0 / 8; float32 and int16 rows stay legal); without a law uint8 rows are refused."""
         import torch
+        law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
@@ -956,6 +968,7 @@ class Engine:
                                                     rs_out._h if rs_out else None, fs, packet, ws.n))
         st = PacketStreamState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
                                torch.empty((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32))
+        st.g711 = law
         self.packet_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
@@ -978,21 +991,26 @@ class Engine:
     def packet_stream_step(self, state, x, out=None):
         """x (N, state.packet) float32 or int16 at the state's rate -> the enhanced (N, state.packet), same dtype,
         state.latency16 samples (counted at 16 kHz) late.  Steps state.next_hops hops of the model (possibly none) and
-        advances the group's phase.  Asynchronous on the current stream; no allocation when `out` is given."""
+        advances the group's phase.  Asynchronous on the current stream; no allocation when `out` is given.  On a state
+        made with g711=, x may be torch.uint8: G.711 codes of that law in, codes out (gtcrn_packet_stream_step_g711)."""
         import torch
         if not isinstance(state, PacketStreamState) or isinstance(state, PacketSlotState):
             raise GtcrnError("state must come from new_packet_state")
-        x = self._wave_rows(state, x, "x")
+        _g711_rows(state, x, "x")
+        x = self._wave_rows(state, x, "x", g711=True)
         if x.shape[1] != state.packet:
             raise GtcrnError(f"x must hold one packet of {state.packet} samples per stream, got {x.shape[1]}")
         out = self._wave_out(out, x, state.packet)
         fn = lib().gtcrn_packet_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step
+        law = (state.g711,) if x.dtype == torch.uint8 else ()
+        if law:
+            fn = lib().gtcrn_packet_stream_step_g711
         state.last_hops = state.next_hops
         self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
-                      max(x.stride(0), state.packet), out.data_ptr(), max(out.stride(0), state.packet), state.n,
+                      max(x.stride(0), state.packet), out.data_ptr(), max(out.stride(0), state.packet), state.n, *law,
                       state.window.data_ptr(), _stream_ptr()))
         return out
 
@@ -1008,13 +1026,15 @@ class Engine:
         return out
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
-    def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False):
+    def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False,
+                              g711=None):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
         one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db and meters: as in
-        new_wave_state, per SLOT."""
+        new_wave_state, per SLOT.  g711: as in new_packet_state."""
         import torch
+        law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
@@ -1031,6 +1051,7 @@ class Engine:
         st = PacketSlotState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
                              torch.zeros((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32),
                              torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.int32), m)
+        st.g711 = law
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
         st.meters = ws.meters
@@ -1045,15 +1066,18 @@ class Engine:
         return m, cnt
 
     def packet_stream_step_slots(self, state, slots, x, count=None, out=None):
-        """One packet for the rows a call names: x (M, state.packet) float32 or int16 at the state's rate, row i = the
+        """One packet for the rows a call names: x (M, state.packet) float32 or int16 (or, on a state made with g711=,
+        torch.uint8 G.711 codes: gtcrn_packet_stream_step_slots_g711) at the state's rate, row i = the
         stream in slot slots[i] (int32 device tensor, M <= state.max_active ids, in range and distinct); `count` (device
         int32, None: all M) rows step.  Returns (M, state.packet), same dtype, state.latency16 samples (at 16 kHz) late per
         stream; rows at or beyond count are not written and no other slot is touched.  The launch sequence is the same
         for every call: asynchronous, capturable, no allocation when `out` is given."""
         import torch
+        if isinstance(state, PacketSlotState):
+            _g711_rows(state, x, "x")
         m, cnt = self._packet_slot_args(state, slots, count)
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16):
-            raise GtcrnError("x must be a float32 or int16 CUDA (ROCm) tensor")
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16, torch.uint8):
+            raise GtcrnError("x must be a float32 or int16 CUDA (ROCm) tensor (uint8 G.711 codes on a state made with g711=)")
         if x.device.index != self.device or state.model.device != x.device:
             raise GtcrnError(f"x and the state must be on cuda:{self.device}")
         if x.dim() != 2 or tuple(x.shape) != (m, state.packet):
@@ -1062,12 +1086,15 @@ class Engine:
             x = x.contiguous()
         out = self._wave_out(out, x, state.packet)
         fn = lib().gtcrn_packet_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_slots
+        law = (state.g711,) if x.dtype == torch.uint8 else ()
+        if law:
+            fn = lib().gtcrn_packet_stream_step_slots_g711
         self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
                       slots.data_ptr(), cnt, m, x.data_ptr(), max(x.stride(0), state.packet), out.data_ptr(),
-                      max(out.stride(0), state.packet), state.window.data_ptr(), _stream_ptr()))
+                      max(out.stride(0), state.packet), *law, state.window.data_ptr(), _stream_ptr()))
         return out
 
     def packet_stream_reset_slots(self, state, slots, count=None):
@@ -1253,7 +1280,8 @@ class PacketStreamState(WaveStreamState):
     """WaveStreamState of a group of live streams fed in packets (Engine.new_packet_state): plus ``pkt``
     (N, packet_stream_state_bytes / 4: two FIFOs and the two filter histories per stream), the rate ``fs``, the packet
     ``packet`` in samples at fs and ``n16`` at 16 kHz, ``latency16`` (the end-to-end delay in 16 kHz samples; at fs it is
-    latency16 * fs / 16000, not a whole number in the 44.1 kHz family), and the host handle with the group's ``phase``."""
+    latency16 * fs / 16000, not a whole number in the 44.1 kHz family), the host handle with the group's ``phase``, and
+    ``g711`` (None, or the law 0 / 1 of the torch.uint8 rows the state takes)."""
 
     def __init__(self, engine, handle, model, wave, window, fs, packet, n16, rs_in, rs_out, pkt):
         super().__init__(model, wave, window)
@@ -1267,6 +1295,7 @@ class PacketStreamState(WaveStreamState):
         self.rs_out = rs_out
         self.pkt = pkt
         self.last_hops = 0
+        self.g711 = None            # the law of uint8 rows (0 mu-law, 1 A-law), or None: no uint8 rows
 
     def set_dry_gain(self, gain):
         super().set_dry_gain(gain)
@@ -1444,6 +1473,87 @@ class Resampler:
         if out is not None:
             return out
         return out2[0] if one else out2
+
+
+G711_LAWS = {"ulaw": 0, "alaw": 1}
+
+
+def g711_law(law):
+    """"ulaw" / "alaw" (or 0 / 1) -> the C ABI's law number; None stays None (no G.711)."""
+    if law is None:
+        return None
+    if isinstance(law, str) and law in G711_LAWS:
+        return G711_LAWS[law]
+    if not isinstance(law, (str, bool)) and law in (0, 1):
+        return int(law)
+    raise GtcrnError(f'g711 must be "ulaw", "alaw" or None, got {law!r}')
+
+
+def _need_law(law, who):
+    law = g711_law(law)
+    if law is None:
+        raise GtcrnError(f'{who}: law must be "ulaw" or "alaw"')
+    return law
+
+
+def _g711_rows(state, x, what):
+    """uint8 rows are G.711 codes and need the law the state was made with: refused here, before any library call."""
+    import torch
+    if isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and getattr(state, "g711", None) is None:
+        raise GtcrnError(f'{what} is uint8 (G.711 codes) but the state was made without a law: pass g711="ulaw" or "alaw" '
+                         "to new_packet_state / new_packet_slot_state")
+
+
+def g711_decode_table(law):
+    """D_law as a numpy int16 array of 256 entries: code c is the sample D_law[c] / 32768 (host only)."""
+    import numpy as np
+    tab = np.empty(256, dtype=np.int16)
+    _check(lib().gtcrn_g711_decode_table(_need_law(law, "g711_decode_table"), tab.ctypes.data_as(ctypes.POINTER(ctypes.c_short))))
+    return tab
+
+
+def g711_encode_pcm16(law, p):
+    """E_law(p): the code of the int16 value p (host only; raises for p outside -32768 .. 32767)."""
+    return _check(lib().gtcrn_g711_encode_pcm16(_need_law(law, "g711_encode_pcm16"), int(p)))
+
+
+def _g711_pair(codes, wave, who):
+    import torch
+    for t, dt, what in ((codes, torch.uint8, "uint8"), (wave, torch.float32, "float32")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise GtcrnError(f"{who}: a contiguous {what} CUDA tensor is required")
+    if codes.numel() != wave.numel() or codes.device != wave.device:
+        raise GtcrnError(f"{who}: the two tensors must hold the same number of samples on one device")
+    if codes.numel() % 16 or codes.data_ptr() % 16 or wave.data_ptr() % 16:
+        raise GtcrnError(f"{who}: 16-byte aligned tensors, a sample count that is a multiple of 16")
+
+
+def g711_to_f32(codes, law, out=None):
+    """G.711 codes (uint8) -> float32 waveform on the device, x = D_law[c] / 32768 (exact); asynchronous on the current
+    stream of the tensor's device (gtcrn_g711_to_f32).  For the offline and hop-form caller."""
+    import torch
+    law = _need_law(law, "g711_to_f32")
+    if out is None:
+        out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+    _g711_pair(codes, out, "g711_to_f32")
+    with torch.cuda.device(codes.device):
+        _check(lib().gtcrn_g711_to_f32(codes.device.index, law, ctypes.c_void_p(codes.data_ptr()),
+                                       ctypes.c_void_p(out.data_ptr()), int(codes.numel()), _stream_ptr()))
+    return out
+
+
+def f32_to_g711(wave, law, out=None):
+    """float32 waveform -> G.711 codes (uint8) on the device: E_law(clip(rint(y * 32768), -32768, 32767)), i.e. f32_to_pcm16
+    and then the integer map; asynchronous on the current stream of the tensor's device (gtcrn_f32_to_g711)."""
+    import torch
+    law = _need_law(law, "f32_to_g711")
+    if out is None:
+        out = torch.empty(wave.shape, dtype=torch.uint8, device=wave.device)
+    _g711_pair(out, wave, "f32_to_g711")
+    with torch.cuda.device(wave.device):
+        _check(lib().gtcrn_f32_to_g711(wave.device.index, law, ctypes.c_void_p(wave.data_ptr()),
+                                       ctypes.c_void_p(out.data_ptr()), int(wave.numel()), _stream_ptr()))
+    return out
 
 
 def _pcm_pair(pcm, wave, who):

@@ -1334,6 +1334,18 @@ int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream* ps, void* d_state, void*
     return packet_stream_impl<short>("gtcrn_packet_stream_step_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
                                      out_stride, nstreams, d_win, stream);
 }
+// G.711 rows: the same call with the law as the sample type (gtk::g711u / g711a); the strides are in bytes = samples
+int gtcrn_packet_stream_step_g711(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
+                                  const unsigned char* d_in, long in_stride, unsigned char* d_out, long out_stride, int nstreams,
+                                  int law, const float* d_win, void* stream) {
+    const char* who = "gtcrn_packet_stream_step_g711";
+    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
+    if (law == 0)
+        return packet_stream_impl<gtk::g711u>(who, ps, d_state, d_wstate, d_pstate, reinterpret_cast<const gtk::g711u*>(d_in),
+                                              in_stride, reinterpret_cast<gtk::g711u*>(d_out), out_stride, nstreams, d_win, stream);
+    return packet_stream_impl<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, reinterpret_cast<const gtk::g711a*>(d_in),
+                                          in_stride, reinterpret_cast<gtk::g711a*>(d_out), out_stride, nstreams, d_win, stream);
+}
 
 // ---- packet stream slots (contract: include/gtcrn_micro_hip.h): the phase is one device word per slot, and a call is
 // plan -> k_packet_in_slots -> hmax rounds of the indexed wave step -> k_packet_out_slots whatever the phases are.
@@ -1416,6 +1428,20 @@ int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream* ps, void* d_state,
                                          long in_stride, short* d_out, long out_stride, const float* d_win, void* stream) {
     return packet_slots_impl<short>("gtcrn_packet_stream_step_slots_pcm16", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
                                     d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream);
+}
+int gtcrn_packet_stream_step_slots_g711(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                        const int* d_slots, const int* d_count, int max_active, const unsigned char* d_in,
+                                        long in_stride, unsigned char* d_out, long out_stride, int law, const float* d_win,
+                                        void* stream) {
+    const char* who = "gtcrn_packet_stream_step_slots_g711";
+    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
+    if (law == 0)
+        return packet_slots_impl<gtk::g711u>(who, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count, max_active,
+                                             reinterpret_cast<const gtk::g711u*>(d_in), in_stride,
+                                             reinterpret_cast<gtk::g711u*>(d_out), out_stride, d_win, stream);
+    return packet_slots_impl<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count, max_active,
+                                         reinterpret_cast<const gtk::g711a*>(d_in), in_stride,
+                                         reinterpret_cast<gtk::g711a*>(d_out), out_stride, d_win, stream);
 }
 
 long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream* ps, int which, float* d_dst, long n, void* stream) {
@@ -1597,6 +1623,34 @@ int gtcrn_pcm16_to_f32(int device, const short* d_pcm, float* d_wave, long n, vo
 }
 int gtcrn_f32_to_pcm16(int device, const float* d_wave, short* d_pcm, long n, void* stream) {
     return pcm16_convert(device, d_wave, d_pcm, n, 1, stream, "gtcrn_f32_to_pcm16");
+}
+
+static int g711_convert(int device, int law, const void* src, void* dst, long n, int dir, void* stream, const char* who) {
+    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
+    if (!dst || !src) return fail(GTCRN_ERR_ARG, std::string(who) + ": null pointer");
+    if (n <= 0 || (n & 15) || ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15))
+        return fail(GTCRN_ERR_ARG, std::string(who) + ": 16-byte aligned device pointers and a sample count that is a multiple of 16");
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    LAUNCH_TRY(gtk::launch_g711_convert(src, dst, n, law, dir, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int gtcrn_g711_to_f32(int device, int law, const unsigned char* d_codes, float* d_wave, long n, void* stream) {
+    return g711_convert(device, law, d_codes, d_wave, n, 0, stream, "gtcrn_g711_to_f32");
+}
+int gtcrn_f32_to_g711(int device, int law, const float* d_wave, unsigned char* d_codes, long n, void* stream) {
+    return g711_convert(device, law, d_wave, d_codes, n, 1, stream, "gtcrn_f32_to_g711");
+}
+// host only: the kernels' own decode / encode functions (kernels.h), so the table and the map ARE what the device computes
+int gtcrn_g711_decode_table(int law, short* h_table) {
+    if ((law != 0 && law != 1) || !h_table) return fail(GTCRN_ERR_ARG, "gtcrn_g711_decode_table: law must be 0 or 1 and the table not NULL");
+    for (unsigned c = 0; c < 256; ++c) h_table[c] = (short)gtk::g711_decode(law, c);
+    return 0;
+}
+int gtcrn_g711_encode_pcm16(int law, int p) {
+    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, "gtcrn_g711_encode_pcm16: law must be 0 (mu-law) or 1 (A-law)");
+    if (p < -32768 || p > 32767) return fail(GTCRN_ERR_ARG, "gtcrn_g711_encode_pcm16: p outside the int16 range");
+    return (int)gtk::g711_encode(law, p);
 }
 
 int gtcrn_selftest_mfma(int device) {

@@ -57,6 +57,38 @@ int launch_stft(const float* wave, int B, long L, int T, const int* lens, const 
                 float* spec, long sb, long sf, long st, float* frames, hipStream_t s);
 // 16-bit PCM <-> float32 at the host boundary (n samples, a multiple of 8; dir 0: int16 / 32768, 1: clip(rint(y * 32768)))
 int launch_pcm16_convert(const void* src, void* dst, long n, int dir, hipStream_t s);
+// G.711 (contract: include/gtcrn_micro_hip.h, "G.711 payloads").  One statement of both laws in integer arithmetic, for
+// the host calls (gtcrn_g711_decode_table / gtcrn_g711_encode_pcm16) and the kernels alike: law 0 mu-law, 1 A-law; the
+// decoded value and the encoder's input are on the 16-bit linear scale of the PCM16 forms.
+constexpr int g711_decode(int law, unsigned c) {
+    if (law == 0) {
+        const unsigned u = ~c & 0xFFu;
+        const int mag = (int)((((u & 15u) << 3) + 132u) << ((u >> 4) & 7u)) - 132;
+        return (u & 0x80u) ? -mag : mag;
+    }
+    const unsigned a = (c ^ 0x55u) & 0xFFu, m = a & 15u, s = (a >> 4) & 7u;
+    const int t = s == 0 ? (int)((m << 4) + 8u) : (int)(((m << 4) + 264u) << (s - 1u));
+    return (a & 0x80u) ? t : -t;
+}
+// p in -32768 .. 32767 (the caller clips).  The segment is the position of the leading bit: __builtin_clz.
+constexpr unsigned g711_encode(int law, int p) {
+    if (law == 0) {
+        const int mag = p < 0 ? -p : p;
+        const unsigned a = (unsigned)(mag < 32635 ? mag : 32635) + 132u;          // 132 .. 32767
+        const unsigned e = 24u - (unsigned)__builtin_clz(a);                      // floor(log2 a) - 7: 0 .. 7
+        return ~((p < 0 ? 0x80u : 0u) | (e << 4) | ((a >> (e + 3u)) & 15u)) & 0xFFu;
+    }
+    const unsigned q = (unsigned)(p >= 0 ? p : ~p) >> 3;                          // 0 .. 4095
+    const unsigned s = q < 32u ? 0u : 27u - (unsigned)__builtin_clz(q);           // floor(log2 q) - 4: 1 .. 7
+    const unsigned m = (s < 2u ? q >> 1 : q >> s) & 15u;
+    return ((p >= 0 ? 0x80u : 0u) | (s << 4) | m) ^ 0x55u;
+}
+// The one-byte sample types of the packet kernels: the law is a compile-time property of S, as int16 is of `short`.
+struct g711u { unsigned char code; static constexpr int law = 0; };
+struct g711a { unsigned char code; static constexpr int law = 1; };
+static_assert(sizeof(g711u) == 1 && sizeof(g711a) == 1, "a G.711 sample is one byte");
+// G.711 codes <-> float32 in bulk (n codes, a multiple of 16; dir 0: D_law[c] / 32768, 1: E_law(clip(rint(y * 32768))))
+int launch_g711_convert(const void* src, void* dst, long n, int law, int dir, hipStream_t s);
 // gain (optional, device, float[B]): the attenuation limit -- sample n of row b becomes the mix of dry[b * dry_stride + n]
 // and the iSTFT's sample with dry gain gain[b] (k_istft_mix); nullptr: the plain kernel
 int launch_istft(const float* spec, long sb, long sf, long st, int B, int T, const int* lens, const float* win,

@@ -694,14 +694,21 @@ constexpr int SLOT_WORDS = 8;
 // expression for expression, so the stream equals gtcrn_forward_wave one hop late, bit for bit.
 // Samples are float or int16 (widened as / 32768, stored as clip(rint(y * 32768)): the PCM16 kernels' expressions).
 // FLUSH: the stream's last frame from the ring and r < 256 extra samples, end-reflected as reflect_idx does.
+// The packet kernels also take G.711 codes (g711u / g711a, kernels.h): read as D_law[c] / 32768, stored as E_law of the
+// int16 the PCM16 store would have written -- integer arithmetic in registers, no table.
+template <typename S>
+inline constexpr bool is_g711 = std::is_same<S, g711u>::value || std::is_same<S, g711a>::value;
 template <typename S>
 __device__ __forceinline__ float wave_ld(const S* p) {
     if constexpr (std::is_same<S, short>::value) return (float)*p * (1.0f / 32768.0f);
+    else if constexpr (is_g711<S>) return (float)g711_decode(S::law, p->code) * (1.0f / 32768.0f);
     else return *p;
 }
 template <typename S>
 __device__ __forceinline__ void wave_st(S* p, float y) {
     if constexpr (std::is_same<S, short>::value) *p = (short)(int)fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f);
+    else if constexpr (is_g711<S>)
+        p->code = (unsigned char)g711_encode(S::law, (int)fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f));
     else *p = y;
 }
 
@@ -4423,6 +4430,63 @@ int launch_pcm16_convert(const void* src, void* dst, long n, int dir, hipStream_
     return 0;
 }
 
+// G.711 at the host boundary, for the offline and hop-form caller (the packet forms take the codes themselves): one byte
+// a sample over the host link.  In: x = D_law[c] / 32768 (exact).  Out: E_law(clip(rint(y * 32768))), the PCM16 rounding and
+// then the integer map (kernels.h).  16 codes per lane and step: one 16-byte access on the byte side, four on the float side.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int LAW>
+__global__ __launch_bounds__(256) void k_g711_to_f32(const u32x4* __restrict__ src, f32x4* __restrict__ dst, long n16) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) {
+        const u32x4 v = __builtin_nontemporal_load(src + i);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            f32x4 a;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = (float)g711_decode(LAW, (v[w] >> (8 * k)) & 0xFFu) * (1.0f / 32768.0f);
+            dst[4 * i + w] = a;
+        }
+    }
+}
+template <int LAW>
+__global__ __launch_bounds__(256) void k_f32_to_g711(const f32x4* __restrict__ src, u32x4* __restrict__ dst, long n16) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) {
+        u32x4 v;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const f32x4 a = __builtin_nontemporal_load(src + 4 * i + w);
+            unsigned word = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                word |= g711_encode(LAW, (int)fminf(fmaxf(__builtin_rintf(a[k] * 32768.0f), -32768.0f), 32767.0f)) << (8 * k);
+            v[w] = word;
+        }
+        dst[i] = v;
+    }
+}
+// n codes (a multiple of 16), both pointers 16-byte aligned; law 0 / 1; dir 0: codes -> float32, 1: float32 -> codes
+int launch_g711_convert(const void* src, void* dst, long n, int law, int dir, hipStream_t s) {
+    if (n <= 0 || (n & 15) || (law != 0 && law != 1) || (dir != 0 && dir != 1) ||
+        ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15))
+        return (int)hipErrorInvalidValue;
+    const long n16 = n / 16;
+    const int grid = (int)std::min<long>((n16 + 255) / 256, 256 * 16);
+    if (dir == 0) {
+        const u32x4* a = reinterpret_cast<const u32x4*>(src);
+        f32x4* b = reinterpret_cast<f32x4*>(dst);
+        if (law == 0) hipLaunchKernelGGL((k_g711_to_f32<0>), dim3(grid), dim3(256), 0, s, a, b, n16);
+        else hipLaunchKernelGGL((k_g711_to_f32<1>), dim3(grid), dim3(256), 0, s, a, b, n16);
+    } else {
+        const f32x4* a = reinterpret_cast<const f32x4*>(src);
+        u32x4* b = reinterpret_cast<u32x4*>(dst);
+        if (law == 0) hipLaunchKernelGGL((k_f32_to_g711<0>), dim3(grid), dim3(256), 0, s, a, b, n16);
+        else hipLaunchKernelGGL((k_f32_to_g711<1>), dim3(grid), dim3(256), 0, s, a, b, n16);
+    }
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_stft(const float* wave, int B, long L, int T, const int* lens, const float* win, const float* twid,
                 float* spec, long sb, long sf, long st, float* frames, hipStream_t s) {
     const long nframes = (long)B * T;
@@ -5217,8 +5281,12 @@ int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stri
 }
 template int launch_packet_in<float>(const float*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_in<short>(const short*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in<g711u>(const g711u*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in<g711a>(const g711a*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out<float>(const float*, long, float*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out<short>(const float*, long, short*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out<g711u>(const float*, long, g711u*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out<g711a>(const float*, long, g711a*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
 
 // ---- packet stream slots: the launch sequence of a call depends on (fs, n, max_active) alone
 int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* phase, int n16, int hmax, int M, int* tab,
@@ -5265,7 +5333,11 @@ int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const i
 }
 template int launch_packet_in_slots<float>(const float*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_in_slots<short>(const short*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in_slots<g711u>(const g711u*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in_slots<g711a>(const g711a*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out_slots<float>(const float*, int, float*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_out_slots<short>(const float*, int, short*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots<g711u>(const float*, int, g711u*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots<g711a>(const float*, int, g711a*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
 
 }  // namespace gtk

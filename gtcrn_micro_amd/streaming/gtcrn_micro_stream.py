@@ -229,7 +229,7 @@ class StreamGTCRNMicro(GTCRNMicro):
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
-                        count=None, resident=False, max_active=None, meters=False):
+                        count=None, resident=False, max_active=None, meters=False, g711=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -245,7 +245,11 @@ class StreamGTCRNMicro(GTCRNMicro):
         slot (their streams share a group phase).
         packet=, resident=True: `nstreams` RESIDENT packet streams with a phase each (Engine.new_packet_slot_state; at most
         `max_active`, default all, step per call); state=<that state>, slots= resets its named slots
-        (Engine.packet_stream_reset_slots)."""
+        (Engine.packet_stream_reset_slots).
+        g711="ulaw" | "alaw" (with packet=): step_wave then also takes and returns torch.uint8 rows of G.711 codes of that
+        law (fs=8000, packet=160, g711="ulaw": 20 ms PCMU packets); float32 and int16 rows stay legal."""
+        if g711 is not None and (packet is None or slots is not None):
+            raise _lib.GtcrnError("g711= goes with packet=: G.711 codes are taken by the packet forms only")
         eng = self.engine(torch.device(device))
         if slots is not None:
             if isinstance(state, _lib.PacketSlotState):
@@ -259,9 +263,10 @@ class StreamGTCRNMicro(GTCRNMicro):
             if packet is None:
                 raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
             return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
-                                             atten_lim_db=atten_lim_db, meters=meters)
+                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711)
         if packet is not None:
-            return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters)
+            return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
+                                        g711=g711)
         if int(fs) != 16000:
             return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters)
         return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters)
@@ -269,7 +274,8 @@ class StreamGTCRNMicro(GTCRNMicro):
     def step_wave(self, x, state, slots=None, count=None):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a
         state made for another rate: hops of state.hop samples at that rate, state.latency samples late.  With a packet
-        state: exactly one packet of state.packet samples per stream, state.latency16 samples (at 16 kHz) late.
+        state: exactly one packet of state.packet samples per stream, state.latency16 samples (at 16 kHz) late; made with
+        g711=, it also takes torch.uint8 rows of G.711 codes and returns codes.
         slots= (int32 device tensor, M ids), count= (device int32, optional): the live tick of a server -- x (M, 256), row i
         is the stream in slot slots[i] of the 16 kHz `state`, `count` rows step, no other slot is touched
         (Engine.wave_stream_step_slots).  With a packet slot state (init_wave_state(..., packet=, resident=True)): x

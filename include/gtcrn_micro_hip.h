@@ -496,6 +496,62 @@ int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream *ps, void *d_state,
                                          const short *d_in, long in_stride, short *d_out, long out_stride,
                                          const float *d_win, void *stream);
 
+/* ---- G.711 payloads (mu-law / A-law) on the packet form, the packet slots and a pair of bulk converters ----------------
+ * Most 8 kHz RTP carries G.711: payload type 0 (PCMU) and 8 (PCMA), one byte a sample, 160 bytes per 20 ms packet.  The
+ * packet kernels read and write their samples through one load / store function per sample type, so the companding sits
+ * exactly where the packet is read and written: no launch, no extra pass, a quarter of the float bytes over the host link,
+ * and no rounding beyond the ONE the PCM16 form already makes.
+ *
+ * Two laws: law = 0 mu-law, law = 1 A-law.  Everything is defined on the 16-bit linear scale of the _pcm16 forms.
+ *
+ * Decode.  A byte c is the integer D_law[c], the sample D_law[c] / 32768 exactly (ITU-T G.711's tables):
+ *   mu-law:  u = ~c & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 132) << e) - 132; -mag if u & 0x80, else +mag.
+ *            Range +-32124; 255 distinct values: 0xFF and 0x7F both decode to 0.
+ *   A-law:   a = c ^ 0x55, m = a & 15, s = (a >> 4) & 7, t = (m << 4) + 8 if s == 0, else ((m << 4) + 264) << (s - 1);
+ *            +t if a & 0x80, else -t.  Range +-32256; 256 distinct values, no zero.
+ * Encode.  A float y becomes p = clip(rint(y * 32768), -32768, 32767) -- exactly the _pcm16 rounding, half to even -- and
+ * then the byte E_law(p), an integer map:
+ *   mu-law (sign-magnitude):  s = 0x80 if p < 0, else 0; a = min(|p|, 32635) + 132; e = floor(log2 a) - 7 (0..7);
+ *            m = (a >> (e + 3)) & 15; byte = ~(s | e << 4 | m) & 0xFF.  There is no "zero trap".
+ *   A-law (ones-complement magnitude):  g = p if p >= 0, else ~p; q = g >> 3 (0..4095); s = 0 if q < 32, else
+ *            floor(log2 q) - 4 (1..7); m = (q >> 1) & 15 if s < 2, else (q >> s) & 15;
+ *            byte = ((p >= 0 ? 0x80 : 0) | s << 4 | m) ^ 0x55.
+ * Both encoders are monotone in p, and E(D[c]) == c for every code except mu-law 0x7F (negative zero re-encodes as 0xFF).
+ * The A-law encoder equals Python's audioop.lin2alaw on all 65 536 inputs.  The mu-law encoder differs from
+ * audioop.lin2ulaw on 381 negative inputs: audioop floors p >> 2 BEFORE it takes the magnitude, this one is symmetric
+ * (E(-p) == E(p) ^ 0x80 for p != 0).  That is by design.
+ *
+ * Contract, by construction and bit for bit: a _g711 call equals the _pcm16 call followed by E_law on its output, and
+ * input bytes c equal the float call's input D_law[c] / 32768; the model, wave and packet states after it are the float
+ * call's.  Samples a form emits as structural zeros leave as 0xFF (mu) / 0xD5 (A): the first block, the FIFO pre-fill and a limited
+ * stream's zeros.  The handle's dry gains (gtcrn_packet_stream_set_dry_gain) and the model's level meters apply unchanged:
+ * the mix and the meter values are taken in float at 16 kHz, before the encode.
+ *
+ * gtcrn_packet_stream_step_g711 / _step_slots_g711: the _pcm16 signatures with byte rows and `law`, the same law in and
+ * out, strides in samples (= bytes).  They make the launches of their plain forms one for one under the same timing rows,
+ * capture as they do (the contiguous form one period, the slot form one call), and make the same argument checks before any
+ * launch, plus law outside {0, 1} -> GTCRN_ERR_ARG.  No state layout, no *_state_bytes and no ABI version changes.
+ *
+ * gtcrn_g711_to_f32 / gtcrn_f32_to_g711, for the offline and hop-form caller: device pointers, both 16-byte aligned, n a
+ * multiple of 16, asynchronous on `stream`.  gtcrn_g711_decode_table (h_table[c] = D_law[c]) and gtcrn_g711_encode_pcm16
+ * (returns E_law(p); p outside -32768 .. 32767 -> GTCRN_ERR_ARG) are host only and touch no device: they run the very
+ * functions the kernels compile.
+ *
+ * Out of scope: different laws in and out; G.711 on the hop and rate forms and on the offline calls (the bulk converters
+ * serve those); G.711 WAV files in the folder driver; Appendix I / II (packet-loss concealment, comfort noise); the _quant
+ * paths. */
+int gtcrn_packet_stream_step_g711(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                  const unsigned char *d_in, long in_stride, unsigned char *d_out, long out_stride,
+                                  int nstreams, int law, const float *d_win, void *stream);
+int gtcrn_packet_stream_step_slots_g711(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                        int *d_phase, const int *d_slots, const int *d_count, int max_active,
+                                        const unsigned char *d_in, long in_stride, unsigned char *d_out, long out_stride,
+                                        int law, const float *d_win, void *stream);
+int gtcrn_g711_to_f32(int device, int law, const unsigned char *d_codes, float *d_wave, long n, void *stream);
+int gtcrn_f32_to_g711(int device, int law, const float *d_wave, unsigned char *d_codes, long n, void *stream);
+int gtcrn_g711_decode_table(int law, short *h_table /* [256] */);
+int gtcrn_g711_encode_pcm16(int law, int p);
+
 /* ---- level meters: per-stream energies, peak and block count on every live waveform path ------------------------------
  * A conferencing or telephony front end needs, per stream and per tick, how loud the stream is: the RTP audio-level header
  * extension (RFC 6464), a silence / DTX decision, a clip indicator, and "how much is the enhancer taking out" as dry against
