@@ -187,6 +187,7 @@ def lib():
     L.gtcrn_train_loss.argtypes = [_vp, _vp, cl, cl, cl, _vp, cl, cl, cl, ci, ci, _vp, _vp, _vp]
     L.gtcrn_train_loss_strided.argtypes = [_vp, _vp, cl, cl, cl, _vp, cl, cl, cl, ci, ci, _vp, _vp, cl, cl, cl, _vp]
     cd = ctypes.c_double
+    L.gtcrn_train_loss_terms.argtypes = [_vp, _vp, ci, _vp]
     L.gtcrn_clip_adam_step.argtypes = [ci, _vp, _vp, _vp, _vp, _vp, cl, cf, cd, cd, cd, cd, cd, cl, _vp, _vp, _vp]
     L.gtcrn_clip_adam_workspace_bytes.restype = cl
     L.gtcrn_clip_adam_workspace_bytes.argtypes = [cl]
@@ -1737,7 +1738,20 @@ class Trainer:
             _check(lib().gtcrn_train_loss_strided(self._h, pred.data_ptr(), psb, psf, pst, true.data_ptr(), tsb, tsf, tst,
                                                   B, T, loss.data_ptr(), grad.data_ptr() if want_grad else None,
                                                   gsb, gsf, gst, _stream_ptr()))
+        self._loss_B = B
         return loss, grad
+
+    def hybrid_loss_terms(self):
+        """Test hook: the per-utterance SI-SNR terms (float64 numpy, (B,)) of the most recent hybrid_loss call on this
+        trainer, read before any other call on it (gtcrn_train_loss_terms)."""
+        import torch
+        B = getattr(self, "_loss_B", 0)
+        if B < 1:
+            raise GtcrnError("hybrid_loss_terms: no hybrid_loss call on this trainer yet")
+        out = np.empty(B, np.float64)
+        with torch.cuda.device(self.device):
+            _check(lib().gtcrn_train_loss_terms(self._h, out.ctypes.data_as(_vp), B, _stream_ptr()))
+        return out
 
     def tap(self, name):
         """A tensor the most recent forward stored, as (B,C,T,F) float32: a stage boundary (en0..en4, tcn0..tcn7,

@@ -162,6 +162,7 @@ struct gtcrn_trainer {
     float* loss_ws = nullptr;
     size_t loss_ws_floats = 0;
     float* d_win = nullptr;
+    int loss_B = 0;               // utterances of the most recent loss call (gtcrn_train_loss_terms)
 };
 
 namespace {
@@ -1203,6 +1204,18 @@ int gtcrn_train_loss_strided(gtcrn_trainer* t, const float* d_pred, long pb, lon
     T_RUN(gtt::sisnr_terms(yp, yt, B, Lw, spec_partial, parts, (long)B * 257 * T, t->d_win, dwork, coef, d_loss,
                            d_grad != nullptr, s));
     if (d_grad) T_RUN(gtk::launch_istft_adjoint(yp, B, T, t->d_win, tw, d_grad, gb, gf, gt, s));
+    t->loss_B = B;
+    return 0;
+}
+
+int gtcrn_train_loss_terms(gtcrn_trainer* t, double* h_terms, int B, void* stream) {
+    if (!t || !h_terms || B < 1 || B != t->loss_B)
+        return tfail(GTCRN_ERR_ARG, "gtcrn_train_loss_terms: bad argument (B must be the batch of the most recent loss call)");
+    T_HIP(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    const double* vals = t->dscratch + 2 * gtt::MAX_PARTIALS + (size_t)B * gtt::SISNR_CHUNKS * 3;
+    T_HIP(hipMemcpyAsync(h_terms, vals, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+    T_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -238,7 +238,9 @@ int tra_gate_shuffle_bwd(const float* dout, const float* v, const float* g, cons
 // compressed real+imag differences, sum of squared compressed-magnitude differences) into `partial`, and their
 // gradient w.r.t. pred into grad (contiguous (B,257,T,2); nullptr: value only).  sisnr_terms: from the two
 // waveforms, the SI-SNR term, the closed loss value (loss[0]) and, if want_grad, yp := d loss / d yp already
-// divided by the iSTFT envelope (input of the iSTFT adjoint).  dwork: B * 25 doubles, coef: 2 * B floats.
+// divided by the iSTFT envelope (input of the iSTFT adjoint).  dwork: B * 25 doubles, coef: 2 * B floats; the
+// per-utterance SI-SNR terms are left in dwork[B * SISNR_CHUNKS * 3 ..] (B doubles).
+constexpr int SISNR_CHUNKS = 8;      // workgroups per utterance of the three sums
 int hybrid_loss_spec(const float* pred, long pb, long pf, long pt, const float* tru, long tb, long tf, long tt, int B,
                      int T, float* grad, long gb, long gf, long gt, double* partial, int* parts, hipStream_t s);
 int sisnr_terms(float* yp, const float* yt, int B, long Lw, const double* spec_partial, int spec_parts, long N,

@@ -4267,7 +4267,10 @@ __global__ __launch_bounds__(NT) void k_hloss_spec(const float* __restrict__ pre
         }
     }
 }
-// per utterance: dot = <yt, yp>, ett = <yt, yt>, epp = <yp, yp>; grid (chunks, B)
+// per utterance: dot = <yt, yp>, ett = <yt, yt>, epp = <yp, yp>; grid (chunks, B).  The products are formed in double,
+// where the product of two floats is exact: k_sisnr_coef expands |yp - s|^2 from these three sums, and for a
+// prediction close to its target that expansion cancels down to the rounding of the sums (products rounded to float
+// first lost the residual from 60 dB SI-SNR on: tests/reports/README.md)
 __global__ __launch_bounds__(NT) void k_sisnr_sums(const float* __restrict__ yp, const float* __restrict__ yt, long Lw,
                                                   double* __restrict__ partial) {
     __shared__ double sh[NT];
@@ -4275,8 +4278,8 @@ __global__ __launch_bounds__(NT) void k_sisnr_sums(const float* __restrict__ yp,
     const float* b = yt + (long)blockIdx.y * Lw;
     double v[3] = {0.0, 0.0, 0.0};
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < Lw; i += (long)gridDim.x * NT) {
-        const float x = a[i], y = b[i];
-        v[0] += (double)(x * y); v[1] += (double)(y * y); v[2] += (double)(x * x);
+        const double x = (double)a[i], y = (double)b[i];
+        v[0] += x * y; v[1] += y * y; v[2] += x * x;
     }
     for (int k = 0; k < 3; ++k) {
         __syncthreads();
@@ -5356,7 +5359,7 @@ int hybrid_loss_spec(const float* pred, long pb, long pf, long pt, const float* 
 int sisnr_terms(float* yp, const float* yt, int B, long Lw, const double* spec_partial, int spec_parts, long N,
                 const float* win, double* dwork, float* coef, float* loss, int want_grad, hipStream_t s) {
     if (B > 1024) return (int)hipErrorInvalidValue;
-    const int chunks = 8;
+    const int chunks = SISNR_CHUNKS;
     double* part = dwork;                      // B * chunks * 3
     double* vals = dwork + (long)B * chunks * 3;
     hipLaunchKernelGGL(k_sisnr_sums, dim3(chunks, B), dim3(NT), 0, s, yp, yt, Lw, part);

@@ -781,6 +781,10 @@ int gtcrn_train_loss(gtcrn_trainer *t, const float *d_pred, long pb, long pf, lo
 int gtcrn_train_loss_strided(gtcrn_trainer *t, const float *d_pred, long pb, long pf, long pt, const float *d_true,
                              long tb, long tf, long tt, int B, int T, float *d_loss, float *d_grad, long gb, long gf,
                              long gt, void *stream);
+/* Test hook: the per-utterance SI-SNR terms -log10(|s|^2 / (|yp - s|^2 + 1e-8) + 1e-8) of the most recent loss call
+ * on this trainer (B doubles, host memory; B must be that call's), whose batch mean went into the loss.  Valid until the
+ * trainer's next call of any kind; `stream` must be the loss call's.  Synchronises the stream. */
+int gtcrn_train_loss_terms(gtcrn_trainer *t, double *h_terms, int B, void *stream);
 /* clip_grad_norm_ + Adam over flat blobs in two launches.  Replaces `torch.nn.utils.clip_grad_norm_(self.model.parameters(),
  * clip_grad_norm_value)` + `self.optimizer.step()` (train.py:282-285; Adam(lr) from train.py:90, conf/cfg_train_DNS3.yaml
  * clip 3.0) for a model whose parameters, gradients and Adam moments are views of four blobs in the canonical layout
