@@ -151,6 +151,14 @@ def lib():
         L.gtcrn_f32_to_g711.argtypes = [ci, ci, _vp, _vp, cl, _vp]
         L.gtcrn_g711_decode_table.argtypes = [ci, ctypes.POINTER(ctypes.c_short)]
         L.gtcrn_g711_encode_pcm16.argtypes = [ci, ci]
+    # high band (an earlier library has none of these: a state with highband= then fails at its creation)
+    if hasattr(L, "gtcrn_rate_stream_step_hb"):
+        L.gtcrn_rate_stream_hb_state_bytes.restype = ctypes.c_size_t
+        L.gtcrn_rate_stream_hb_state_bytes.argtypes = [ci]
+        L.gtcrn_rate_stream_hb_reset.argtypes = [ci, _vp, ci, _vp]
+        for fn in ("gtcrn_rate_stream_step_hb", "gtcrn_rate_stream_step_hb_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp, _vp, _vp]
+        L.gtcrn_resample_hb.argtypes = [_vp, _vp, cl, _vp, cl, _vp, cl, _vp, cl, _vp, cl, _vp, _vp, cl, ci, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -867,27 +875,81 @@ class Engine:
             cache[key] = Resampler(key[0], key[1], self.device)
         return cache[key]
 
-    def forward_wave_rate(self, wave, fs, window, out_fs=None, dry_gain=None):
+    def forward_wave_rate(self, wave, fs, window, out_fs=None, dry_gain=None, highband=None, lengths=None):
         """wave (B,L) or (L,) at `fs` Hz -> the enhanced waveform at 16 kHz (out_fs None or 16000) or at `out_fs`: exactly
         resampler(fs, 16000)(wave) -> forward_wave -> resampler(16000, out_fs), the three public calls composed.
-        dry_gain goes to forward_wave: the attenuation limit is mixed at 16 kHz."""
+        dry_gain goes to forward_wave: the attenuation limit is mixed at 16 kHz.
+        highband (None, a float or a (B,) CUDA float tensor, each in [0, 1]; fs = out_fs in 24000, 32000, 48000): the
+        header's "high band", offline form -- the last call becomes gtcrn_resample_hb, which resamples
+        fl(y - fl(gamma x16)) and adds fl(gamma wave[j]) for j < L: the band above 8 kHz comes out with gain gamma.
+        lengths (B ints, with highband only): row b holds lengths[b] samples; forward_wave_var runs in the middle and the
+        output row carries the samples of that clip alone, zeros behind them."""
         fs = int(fs)
+        if highband is not None:
+            return self._forward_wave_rate_hb(wave, fs, window, out_fs, dry_gain, highband, lengths)
+        if lengths is not None:
+            raise GtcrnError("lengths= is taken with highband= only")
         x = wave if fs == 16000 else self.resampler(fs, 16000)(wave)
         y = self.forward_wave(x, window, dry_gain=dry_gain)
         if out_fs is None or int(out_fs) == 16000:
             return y
         return self.resampler(16000, int(out_fs))(y)
 
-    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False):
+    def _forward_wave_rate_hb(self, wave, fs, window, out_fs, dry_gain, highband, lengths):
+        import torch
+        if fs not in HIGHBAND_RATES or out_fs is None or int(out_fs) != fs:
+            raise GtcrnError(f"highband= needs fs == out_fs in {HIGHBAND_RATES}, got fs {fs} out_fs {out_fs}")
+        self._check_on_device(wave, "wave")
+        w2 = (wave.reshape(1, -1) if wave.dim() == 1 else wave).contiguous()
+        if w2.dim() != 2:
+            raise GtcrnError(f"wave must be (B,L) or (L,), got {tuple(wave.shape)}")
+        B, L = w2.shape
+        gamma = self._dry_gain(highband, B, w2.device)               # (the same checks: [0, 1], (B,) float32 on the device)
+        down, up = self.resampler(fs, 16000), self.resampler(16000, fs)
+        if lengths is None:
+            xlens = lens16 = None
+            x16 = down(w2)
+            y = self.forward_wave(x16, window, dry_gain=dry_gain)
+        else:
+            xl = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).cpu()
+            if xl.numel() != B or int(xl.min()) < 0 or int(xl.max()) > L:
+                raise GtcrnError(f"lengths must hold {B} entries in [0, L={L}]")
+            l16 = torch.tensor([down.out_len(int(v)) for v in xl], dtype=torch.int32)
+            x16 = torch.zeros((B, down.out_len(L)), device=w2.device, dtype=torch.float32)
+            down(w2, lengths=xl, out=x16)
+            y = self.forward_wave_var(x16, l16, window, dry_gain=dry_gain)
+            xlens = xl.to(device=w2.device, dtype=torch.int32)
+            lens16 = (256 * (l16 // 256)).to(device=w2.device, dtype=torch.int32)
+        L16 = y.shape[1]
+        if L16 < 1:
+            raise GtcrnError("the clip holds less than one hop at 16 kHz")
+        n = up.out_len(L16)
+        out = torch.zeros((B, n), device=w2.device, dtype=torch.float32)
+        with self._dev():
+            _check(lib().gtcrn_resample_hb(up._h, y.data_ptr(), y.stride(0), x16.data_ptr(), x16.stride(0),
+                                           lens16.data_ptr() if lens16 is not None else None, L16, w2.data_ptr(), w2.stride(0),
+                                           xlens.data_ptr() if xlens is not None else None, L, gamma.data_ptr(),
+                                           out.data_ptr(), out.stride(0), B, _stream_ptr()))
+        return out[0] if wave.dim() == 1 else out
+
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
         resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz); meters: as in
-        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step)."""
+        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step).  highband (a float or one per stream, each
+        in [0, 1]; fs = 24000, 32000 or 48000; None: off, the plain calls): the header's "high band" -- the state gets
+        ``hb`` (N, rate_stream_hb_state_bytes/4) and the per-stream gains ``hb_gain`` that every step then applies
+        (RateStreamState.set_highband_gain rewrites them in place)."""
         import torch
         fs = int(fs)
         hop = _check(lib().gtcrn_rate_stream_hop(fs))
+        nhb = rate_stream_hb_state_bytes(fs) // 4 if highband is not None else 0        # (raises without a high band at fs)
         ws = self.new_wave_state(nstreams, window, meters=meters)
         st = RateStreamState(ws.model, ws.wave, ws.window, fs, hop, self.resampler(fs, 16000), self.resampler(16000, fs),
                              torch.empty((ws.n, rate_stream_state_bytes(fs) // 4), device=ws.wave.device, dtype=torch.float32))
+        if highband is not None:
+            st.hb = torch.empty((ws.n, nhb), device=ws.wave.device, dtype=torch.float32)
+            st.hb_gain = torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.float32)
+            st.set_highband_gain(highband)
         self.rate_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
@@ -910,11 +972,14 @@ class Engine:
             _check(lib().gtcrn_rate_stream_reset(self._h, state.rs_in._h, state.rs_out._h, state.model[lo:hi].data_ptr(),
                                                  state.wave[lo:hi].data_ptr(), state.rate[lo:hi].data_ptr(), hi - lo,
                                                  _stream_ptr()))
+            if state.hb is not None:
+                _check(lib().gtcrn_rate_stream_hb_reset(state.fs, state.hb[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
 
     def rate_stream_step(self, state, x, out=None):
         """x (N, H*nhops) float32 or int16 at the state's rate (H = state.hop) -> the enhanced (N, H*nhops) at that rate,
         same dtype, state.latency samples late.  Asynchronous on the current stream; no allocation when `out` is given
-        and rate_stream_reserve(state, nhops) was called."""
+        and rate_stream_reserve(state, nhops) was called.  A state with highband= runs gtcrn_rate_stream_step_hb: `out`
+        must not overlap x (the call is not legal in place)."""
         import torch
         if not isinstance(state, RateStreamState):
             raise GtcrnError("state must come from new_rate_state")
@@ -928,7 +993,11 @@ class Engine:
                 state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
         self._set_meters(state)
         with self._dev():
-            if state.dry_gain is None:
+            if state.hb is not None:
+                fn = lib().gtcrn_rate_stream_step_hb_pcm16 if pcm else lib().gtcrn_rate_stream_step_hb
+                _check(fn(*args, state.dry_gain.data_ptr() if state.dry_gain is not None else None, state.window.data_ptr(),
+                          state.hb.data_ptr(), state.hb_gain.data_ptr(), _stream_ptr()))
+            elif state.dry_gain is None:
                 fn = lib().gtcrn_rate_stream_step_pcm16 if pcm else lib().gtcrn_rate_stream_step
                 _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
             else:
@@ -1275,6 +1344,27 @@ class RateStreamState(WaveStreamState):
         self.rs_in = rs_in
         self.rs_out = rs_out
         self.rate = rate
+        self.hb = None              # (N, rate_stream_hb_state_bytes/4): the high band's state; None: the plain calls
+        self.hb_gain = None         # (N,) float32 on the device: the high-band gains
+
+    def set_highband_gain(self, g):
+        """Rewrites the high-band gains in place (a float for every stream, or N of them: a sequence or a tensor; each in
+        [0, 1]), asynchronously on the current stream: the next step, also the next replay of a captured one, follows."""
+        import torch
+        if self.hb_gain is None:
+            raise GtcrnError("the state has no high band: create it with highband=")
+        if isinstance(g, torch.Tensor):
+            if tuple(g.shape) != (self.n,):
+                raise GtcrnError(f"the high-band gains must hold {self.n} values, got {tuple(g.shape)}")
+            self.hb_gain.copy_(g.to(torch.float32), non_blocking=True)        # (a device tensor is not read back)
+            return
+        v = np.asarray(g, np.float32)
+        if v.ndim > 1 or (v.ndim == 1 and v.size != self.n) or not np.all((v >= 0) & (v <= 1)):
+            raise GtcrnError(f"the high-band gains must be one value or {self.n} of them, each in [0, 1]")
+        if v.ndim == 0:
+            self.hb_gain.fill_(float(v))
+        else:
+            self.hb_gain.copy_(torch.from_numpy(v), non_blocking=True)
 
 
 class PacketStreamState(WaveStreamState):
@@ -1399,6 +1489,20 @@ def rate_stream_latency(fs):
 
 def rate_stream_state_bytes(fs):
     n = int(lib().gtcrn_rate_stream_state_bytes(int(fs)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+HIGHBAND_RATES = (24000, 32000, 48000)
+
+
+def rate_stream_hb_state_bytes(fs):
+    """Bytes per stream of the high band's state, 4 * (256 + latency) (host only; raises at a rate without a high band)."""
+    fn = getattr(lib(), "gtcrn_rate_stream_hb_state_bytes", None)
+    if fn is None:
+        raise GtcrnError("this library has no high band")
+    n = int(fn(int(fs)))
     if n == 0:
         raise GtcrnError(lib().gtcrn_last_error().decode())
     return n

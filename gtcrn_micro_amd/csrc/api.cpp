@@ -1021,6 +1021,19 @@ size_t gtcrn_rate_stream_state_bytes(int fs) {
 }
 
 namespace {
+// high band: the rates above 16 kHz that have a hop form
+bool hb_rate_ok(int fs) { return fs == 24000 || fs == 32000 || fs == 48000; }
+// do any of the N input rows (len samples each, in_stride apart) share a byte with any of the N output rows?
+extern "C++" template <typename S>
+bool rows_overlap(const S* in, long in_stride, const S* out, long out_stride, long len, int N) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t ea = a + sizeof(S) * (uintptr_t)((long)(N - 1) * in_stride + len);
+    const uintptr_t eb = b + sizeof(S) * (uintptr_t)((long)(N - 1) * out_stride + len);
+    if (ea <= b || eb <= a) return false;                 // the two extents are disjoint
+    if (in_stride != out_stride || (a > b ? a - b : b - a) % sizeof(S)) return true;      // (interleavings not analysed)
+    const long d = (long)((a > b ? a - b : b - a) / sizeof(S)) % in_stride;              // rows interleaved at one pitch
+    return d < len || in_stride - d < len;
+}
 int rate_pair_check(const std::string& w, gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out) {
     if (!m) return fail(GTCRN_ERR_ARG, w + ": null model");
     if (!in || !out || !in->d_taps || !out->d_taps) return fail(GTCRN_ERR_ARG, w + ": null resampler");
@@ -1076,14 +1089,20 @@ int gtcrn_rate_stream_reset(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler
 extern "C++" template <typename S>
 static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state,
                             void* d_wstate, void* d_rstate, const S* d_in, long in_stride, S* d_out, long out_stride,
-                            int nstreams, int nhops, const float* d_win, void* stream, const float* d_gain = nullptr) {
+                            int nstreams, int nhops, const float* d_win, void* stream, const float* d_gain = nullptr,
+                            bool hb = false, void* d_hbstate = nullptr, const float* d_hb_gain = nullptr) {
     const std::string w(who);
     if (int rc = rate_pair_check(w, m, in, out)) return rc;
+    if (hb && !hb_rate_ok(in->fs_in)) return fail(GTCRN_ERR_ARG, w + ": the high band exists at 24000, 32000 and 48000 Hz");
     if (!d_state || !d_wstate || !d_rstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (hb && (!d_hbstate || !d_hb_gain)) return fail(GTCRN_ERR_ARG, w + ": null high-band state or gain pointer");
     if (nstreams < 1 || nhops < 1) return fail(GTCRN_ERR_ARG, w + ": nstreams and nhops must be >= 1");
     const int H = (int)(256L * in->fs_in / 16000);
     if (in_stride < (long)H * nhops || out_stride < (long)H * nhops) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_rstate})) return rc0;
+    if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_rstate, d_hbstate})) return rc0;
+    // the high-band kernel reads x[n - latency] while other threads write out: no in-place call
+    if (hb && rows_overlap(d_in, in_stride, d_out, out_stride, (long)H * nhops, nstreams))
+        return fail(GTCRN_ERR_ARG, w + ": the input and output rows overlap (the high-band step is not legal in place)");
     int rc = check_model(m);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -1097,6 +1116,12 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
     rc = wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, m->d_rate_a, row, m->d_rate_b, row, nstreams,
                           nhops, false, 0, d_gain, d_win, {}, stream);      // (the limit is mixed at 16 kHz)
     if (rc) return rc;
+    if (hb) {
+        LAUNCH_TRY(gtk::launch_rate_out_hb<S>(m->d_rate_b, m->d_rate_a, row, d_in, in_stride, d_out, out_stride, rs + di.ntp,
+                                              rs_stride, static_cast<float*>(d_hbstate), d_hb_gain, nstreams, nhops, H,
+                                              H + 2 * (di.half / di.up), dout.up, dout.down, dout.ntp, out->d_taps, s));
+        return 0;
+    }
     LAUNCH_TRY(gtk::launch_rate_out<S>(m->d_rate_b, row, d_out, out_stride, rs + di.ntp, rs_stride, nstreams, nhops, H, dout.up,
                                        dout.down, dout.ntp, out->d_taps, s));
     return 0;
@@ -1126,6 +1151,53 @@ int gtcrn_rate_stream_step_limited_pcm16(gtcrn_model* m, gtcrn_resampler* in, gt
                                          void* stream) {
     return rate_stream_impl<short>("gtcrn_rate_stream_step_limited_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in,
                                    in_stride, d_out, out_stride, nstreams, nhops, d_win, stream, d_gain);
+}
+
+// ---- high band: the rate step with k_rate_out_hb as its fifth launch; the batch kernel for the offline composition
+size_t gtcrn_rate_stream_hb_state_bytes(int fs) {
+    if (!hb_rate_ok(fs)) { (void)fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_hb_state_bytes: the high band exists at 24000, 32000 and 48000 Hz"); return 0; }
+    return sizeof(float) * (size_t)(256 + gtcrn_rate_stream_latency(fs));
+}
+int gtcrn_rate_stream_hb_reset(int fs, void* d_hbstate, int nstreams, void* stream) {
+    if (!hb_rate_ok(fs)) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_hb_reset: the high band exists at 24000, 32000 and 48000 Hz");
+    if (!d_hbstate || nstreams < 1) return fail(GTCRN_ERR_ARG, "gtcrn_rate_stream_hb_reset: null state or nstreams < 1");
+    if (int rc = check_state_alignment("gtcrn_rate_stream_hb_reset", {d_hbstate})) return rc;
+    HIP_TRY(hipMemsetAsync(d_hbstate, 0, gtcrn_rate_stream_hb_state_bytes(fs) * nstreams, (hipStream_t)stream));
+    return 0;
+}
+int gtcrn_rate_stream_step_hb(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                              void* d_rstate, const float* d_in, long in_stride, float* d_out, long out_stride, int nstreams,
+                              int nhops, const float* d_gain, const float* d_win, void* d_hbstate, const float* d_hb_gain,
+                              void* stream) {
+    return rate_stream_impl<float>("gtcrn_rate_stream_step_hb", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride, d_out,
+                                   out_stride, nstreams, nhops, d_win, stream, d_gain, true, d_hbstate, d_hb_gain);
+}
+int gtcrn_rate_stream_step_hb_pcm16(gtcrn_model* m, gtcrn_resampler* in, gtcrn_resampler* out, void* d_state, void* d_wstate,
+                                    void* d_rstate, const short* d_in, long in_stride, short* d_out, long out_stride,
+                                    int nstreams, int nhops, const float* d_gain, const float* d_win, void* d_hbstate,
+                                    const float* d_hb_gain, void* stream) {
+    return rate_stream_impl<short>("gtcrn_rate_stream_step_hb_pcm16", m, in, out, d_state, d_wstate, d_rstate, d_in, in_stride,
+                                   d_out, out_stride, nstreams, nhops, d_win, stream, d_gain, true, d_hbstate, d_hb_gain);
+}
+int gtcrn_resample_hb(gtcrn_resampler* r, const float* d_wet, long wet_stride, const float* d_dry, long dry_stride,
+                      const int* d_lengths, long L, const float* d_x, long x_stride, const int* d_xlengths, long Lx,
+                      const float* d_hb_gain, float* d_out, long out_stride, int B, void* stream) {
+    const std::string w("gtcrn_resample_hb");
+    if (!r || !r->d_taps) return fail(GTCRN_ERR_ARG, w + ": null resampler");
+    if (r->fs_in != 16000 || !hb_rate_ok(r->fs_out)) return fail(GTCRN_ERR_ARG, w + ": the resampler must be 16000 -> 24000, 32000 or 48000");
+    if (!d_wet || !d_dry || !d_x || !d_hb_gain || !d_out) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (B < 1 || L < 1 || Lx < 1) return fail(GTCRN_ERR_ARG, w + ": B, L and Lx must be >= 1");
+    const RsDesign& d = r->d;
+    const long nout = (L * d.up + d.down - 1) / d.down;
+    if (wet_stride < L || dry_stride < L || x_stride < Lx || out_stride < nout)
+        return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if (rows_overlap(d_x, x_stride, static_cast<const float*>(d_out), out_stride, Lx < nout ? Lx : nout, B))
+        return fail(GTCRN_ERR_ARG, w + ": the x and output rows overlap");
+    HIP_TRY(hipSetDevice(r->device));
+    LAUNCH_TRY(gtk::launch_resample_hb(d_wet, wet_stride, d_dry, dry_stride, d_lengths, L, d_x, x_stride, d_xlengths, Lx,
+                                       d_hb_gain, d_out, out_stride, B, d.up, d.down, d.half, d.ntp, r->d_taps,
+                                       static_cast<hipStream_t>(stream)));
+    return 0;
 }
 
 // ---- packet-sized live streaming: k_packet_in -> the wave step for h hops (nothing when h == 0) -> k_packet_out.

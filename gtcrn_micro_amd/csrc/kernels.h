@@ -137,6 +137,20 @@ int launch_rate_in(const S* in, long in_stride, float* out, long out_stride, flo
 template <typename S>
 int launch_rate_out(const float* in, long in_stride, S* out, long out_stride, float* rstate, long rs_stride, int N, int nhops,
                     int hout, int up, int down, int ntp, const float* taps, hipStream_t s);
+// high band (gtcrn_rate_stream_step_hb / gtcrn_resample_hb; fs = 24000, 32000, 48000): launch_rate_out with
+// fl(wet - fl(g dry[k - 256])) staged instead of the wave step's row (wet, dry: the two 16 kHz hand-offs, one row stride) and
+// fl(g in[n - lat]) added at the store, g = hb_gain[stream], lat = H + 2 D; hbstate + n * (256 + lat) = the stream's last 256
+// dry samples and last lat input samples as floats, read and advanced.  in and out rows must not overlap.
+constexpr int HB_DELAY = 960;                    // the longest delay line: lat at 48 kHz
+template <typename S>
+int launch_rate_out_hb(const float* wet, const float* dry, long hand_stride, const S* in, long in_stride, S* out, long out_stride,
+                       float* rstate, long rs_stride, float* hbstate, const float* hb_gain, int N, int nhops, int hout, int lat,
+                       int up, int down, int ntp, const float* taps, hipStream_t s);
+// batch form, 16 kHz -> fs: launch_resample of fl(wet - fl(g dry)) (row b: lens[b] <= L samples of each) plus fl(g x[j]) for
+// j < xlens[b] <= Lx, g = hb_gain[b]
+int launch_resample_hb(const float* wet, long wet_stride, const float* dry, long dry_stride, const int* lens, long L,
+                       const float* x, long x_stride, const int* xlens, long Lx, const float* hb_gain, float* out,
+                       long out_stride, int B, int up, int down, int half, int ntp, const float* taps, hipStream_t s);
 // packet-sized live streaming (gtcrn_packet_stream_*): packets of n samples at the caller's rate = n16 samples at 16 kHz,
 // re-blocked on the device to the 256-sample hops of the wave step and back.  Per-stream state row (floats):
 // [inbound FIFO PK_FIFO | outbound FIFO PK_FIFO | inbound stage history ntp_in | outbound stage history ntp_out]; both FIFO

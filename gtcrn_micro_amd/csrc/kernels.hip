@@ -5097,6 +5097,152 @@ template int launch_rate_in<short>(const short*, long, float*, long, float*, lon
 template int launch_rate_out<float>(const float*, long, float*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
 template int launch_rate_out<short>(const float*, long, short*, long, float*, long, int, int, int, int, int, int, const float*, hipStream_t);
 
+// ===================================================================== high band (gtcrn_rate_stream_step_hb, gtcrn_resample_hb)
+// The band above 8 kHz of a 24 / 32 / 48 kHz stream goes AROUND the model (include/gtcrn_micro_hip.h, "high band"): with
+// g the stream's high-band gain, a the 16 kHz hand-off of k_rate_in and w what the wave step emitted for it one hop late,
+//     s[k] = w[k] - g a[k - 256]       out[n] = outbound stage(s)[n] + g x[n - lat]       lat = H + 2 D
+// every product and sum ONE fp32 rounding (__fmul_rn / __fsub_rn / __fadd_rn: no contraction into an fma).  Both stages are
+// linear phase with whole delays that sum to lat, so the stage applied to -g a removes from g x[n - lat] exactly the band
+// the model path carries.  k_rate_out_hb is k_rate_out with s staged instead of w -- the same rs_dot on the same layout --
+// and the dry term added at the store.  Per-stream state row (floats): [the last 256 samples of a | the last lat input
+// samples], zeros after a reset; the outbound history of d_rstate holds s.
+// One workgroup per stream.  Every word of the three state rows is read before a barrier and written after it: the delay
+// line sits in LDS for the whole call (with one hop per call H < lat: part of it survives and moves), the a block and the
+// history are read while hop 0 is staged and written after the last hop's outputs.  x is read while other threads write
+// out: the rows must not overlap (gtcrn_rate_stream_step_hb checks).
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_rate_out_hb(const float* __restrict__ wet, const float* __restrict__ dry,
+                                                            long hand_stride, const S* __restrict__ in, long in_stride,
+                                                            S* __restrict__ out, long out_stride, float* __restrict__ rstate,
+                                                            long rs_stride, float* __restrict__ hbstate,
+                                                            const float* __restrict__ hb_gain, int nhops, int hout, int lat,
+                                                            int up, int down, int ntp, const float* __restrict__ taps) {
+    __shared__ __attribute__((aligned(16))) float s_x[RATE_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    __shared__ float s_dl[HB_DELAY];
+    const int tid = threadIdx.x;
+    const long n = blockIdx.x;
+    const float g = hb_gain[n];
+    const float* w = wet + n * hand_stride;
+    const float* a = dry + n * hand_stride;
+    const S* x = in + n * in_stride;
+    S* o = out + n * out_stride;
+    float* hist = rstate + n * rs_stride;
+    float* sa = hbstate + n * (256 + lat);
+    float* dl = sa + 256;
+    const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);      // (never nullptr: launch_rate_out_hb checks)
+    for (int i = tid; i < lat; i += RS_THREADS) s_dl[i] = dl[i];
+    for (int h = 0; h < nhops; ++h) {
+        for (int i = tid; i < ntp + 256; i += RS_THREADS) {
+            const long k = (long)h * 256 + i - ntp;
+            float v;
+            if (k >= 0) v = __fsub_rn(w[k], __fmul_rn(g, k >= 256 ? a[k - 256] : sa[k]));
+            else v = hist[ntp + k];
+            s_x[i] = v;
+        }
+        __syncthreads();
+        for (int m = tid; m < hout; m += RS_THREADS) {
+            const int num = m * down, ih = num / up, k0 = num - ih * up;
+            const long j = (long)h * hout + m;
+            const float xd = j >= lat ? wave_ld<S>(x + (j - lat)) : s_dl[j];
+            wave_st<S>(o + j, __fadd_rn(rs_dot(tp + k0 * ntp, ntp, s_x + ntp + ih), __fmul_rn(g, xd)));
+        }
+        if (h == nhops - 1)
+            for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = s_x[256 + i];
+        __syncthreads();
+    }
+    for (int i = tid; i < 256; i += RS_THREADS) sa[i] = a[(long)(nhops - 1) * 256 + i];
+    for (int i = tid; i < lat; i += RS_THREADS) {
+        const long p = (long)nhops * hout - lat + i;
+        dl[i] = p >= 0 ? wave_ld<S>(x + p) : s_dl[(long)nhops * hout + i];
+    }
+}
+
+// Batch form, 16 kHz -> fs: k_resample with fl(wet - fl(g dry)) staged instead of the input row and fl(g x[j]) added at the
+// store for j < the row's length at fs (outputs of a length-rounding tail past it get no dry term).  Rows have their own
+// lengths: lens (device; nullptr: all L) at 16 kHz, xlens (device; nullptr: all Lx) at fs.
+__global__ __launch_bounds__(RS_THREADS) void k_resample_hb(const float* __restrict__ wet, long wet_stride,
+                                                            const float* __restrict__ dry, long dry_stride,
+                                                            const int* __restrict__ lens, long L, const float* __restrict__ xin,
+                                                            long x_stride, const int* __restrict__ xlens, long Lx,
+                                                            const float* __restrict__ hb_gain, float* __restrict__ out,
+                                                            long out_stride, int tiles, int up, int down, int half, int ntp,
+                                                            const float* __restrict__ taps, int vec) {
+    __shared__ __attribute__((aligned(16))) float s_x[RS_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const int row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
+    long len = lens ? (long)lens[row] : L;
+    len = len < 0 ? 0 : (len > L ? L : len);
+    long xlen = xlens ? (long)xlens[row] : Lx;
+    xlen = xlen < 0 ? 0 : (xlen > Lx ? Lx : xlen);
+    const long nout = (len * up + down - 1) / down;
+    const long j0 = (long)tile * RS_TILE;
+    if (j0 >= nout) return;                                         // (workgroup uniform)
+    const long j1 = j0 + RS_TILE < nout ? j0 + RS_TILE : nout;
+    const float g = hb_gain[row];
+    const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);      // (never nullptr: launch_resample_hb checks)
+    const long lo = (j0 * down + half) / up - (ntp - 1), hi = ((j1 - 1) * down + half) / up;
+    const long a0 = lo - (((lo % 4) + 4) % 4);                     // the span starts on a 16-byte boundary of the rows
+    const int nv = (int)((hi - a0) / 4) + 1;                       // nv * 4 <= RS_SPAN: launch_resample_hb checks the worst tile
+    const float* w = wet + (long)row * wet_stride;
+    const float* d = dry + (long)row * dry_stride;
+    for (int v = tid; v < nv; v += RS_THREADS) {
+        const long i = a0 + (long)v * 4;
+        f32x4 f;
+        if (vec && i >= 0 && i + 4 <= len) {
+            const f32x4 qw = *reinterpret_cast<const f32x4*>(w + i), qd = *reinterpret_cast<const f32x4*>(d + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[e] = __fsub_rn(qw[e], __fmul_rn(g, qd[e]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[e] = (i + e >= 0 && i + e < len) ? __fsub_rn(w[i + e], __fmul_rn(g, d[i + e])) : 0.f;
+        }
+        st4(s_x + v * 4, f);
+    }
+    __syncthreads();
+    const float* x = xin + (long)row * x_stride;
+    float* o = out + (long)row * out_stride;
+    for (long j = j0 + tid; j < j1; j += RS_THREADS) {
+        const long num = j * down + half, ih = num / up;
+        const int k0 = (int)(num - ih * up);
+        const float y = rs_dot(tp + k0 * ntp, ntp, s_x + (ih - a0));
+        o[j] = j < xlen ? __fadd_rn(y, __fmul_rn(g, x[j])) : y;
+    }
+}
+
+template <typename S>
+int launch_rate_out_hb(const float* wet, const float* dry, long hand_stride, const S* in, long in_stride, S* out, long out_stride,
+                       float* rstate, long rs_stride, float* hbstate, const float* hb_gain, int N, int nhops, int hout, int lat,
+                       int up, int down, int ntp, const float* taps, hipStream_t s) {
+    if (!rate_geometry_ok(256, hout, up, down, ntp) || lat < 1 || lat > HB_DELAY || (lat & 3)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_rate_out_hb<S>), dim3(N), dim3(RS_THREADS), 0, s, wet, dry, hand_stride, in, in_stride, out, out_stride,
+                       rstate, rs_stride, hbstate, hb_gain, nhops, hout, lat, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_rate_out_hb<float>(const float*, const float*, long, const float*, long, float*, long, float*, long, float*,
+                                       const float*, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_rate_out_hb<short>(const float*, const float*, long, const short*, long, short*, long, float*, long, float*,
+                                       const float*, int, int, int, int, int, int, int, const float*, hipStream_t);
+
+int launch_resample_hb(const float* wet, long wet_stride, const float* dry, long dry_stride, const int* lens, long L,
+                       const float* x, long x_stride, const int* xlens, long Lx, const float* hb_gain, float* out,
+                       long out_stride, int B, int up, int down, int half, int ntp, const float* taps, hipStream_t s) {
+    if (resample_tile_span(up, down, ntp) > RS_SPAN || (ntp & 3) || up * ntp > RS_LDS_TAPS ||
+        (reinterpret_cast<uintptr_t>(taps) & 15))
+        return (int)hipErrorInvalidValue;
+    const long nout = (L * up + down - 1) / down;
+    const long tiles = (nout + RS_TILE - 1) / RS_TILE;
+    if (tiles < 1 || tiles * B > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    const int vec = !((reinterpret_cast<uintptr_t>(wet) | reinterpret_cast<uintptr_t>(dry)) & 15) && wet_stride % 4 == 0 &&
+                    dry_stride % 4 == 0;
+    hipLaunchKernelGGL(k_resample_hb, dim3((unsigned)(tiles * B)), dim3(RS_THREADS), 0, s, wet, wet_stride, dry, dry_stride, lens,
+                       L, x, x_stride, xlens, Lx, hb_gain, out, out_stride, (int)tiles, up, down, half, ntp, taps, vec);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+
 // ===================================================================== packet-sized live streaming (gtcrn_packet_stream_*)
 // A caller's packet of n samples at fs (n16 = n 16000 / fs samples at 16 kHz, a whole number) in, n enhanced samples out,
 // around the UNCHANGED wave step: k_packet_in cuts the group's 16 kHz sample sequence into 256-sample hops, k_packet_out

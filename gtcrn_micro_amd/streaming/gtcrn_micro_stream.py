@@ -229,7 +229,7 @@ class StreamGTCRNMicro(GTCRNMicro):
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
-                        count=None, resident=False, max_active=None, meters=False, g711=None):
+                        count=None, resident=False, max_active=None, meters=False, g711=None, highband=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -247,7 +247,12 @@ class StreamGTCRNMicro(GTCRNMicro):
         `max_active`, default all, step per call); state=<that state>, slots= resets its named slots
         (Engine.packet_stream_reset_slots).
         g711="ulaw" | "alaw" (with packet=): step_wave then also takes and returns torch.uint8 rows of G.711 codes of that
-        law (fs=8000, packet=160, g711="ulaw": 20 ms PCMU packets); float32 and int16 rows stay legal."""
+        law (fs=8000, packet=160, g711="ulaw": 20 ms PCMU packets); float32 and int16 rows stay legal.
+        highband= (with fs = 24000, 32000 or 48000 and no packet=): the gain, one value or one per stream in [0, 1], with which
+        the band above 8 kHz is carried around the model (Engine.new_rate_state; state.set_highband_gain changes it while
+        the streams run).  None: that band is not in the output."""
+        if highband is not None and (packet is not None or slots is not None or resident):
+            raise _lib.GtcrnError("highband= goes with the hop-level rate form: fs = 24000, 32000 or 48000, no packet= / slots=")
         if g711 is not None and (packet is None or slots is not None):
             raise _lib.GtcrnError("g711= goes with packet=: G.711 codes are taken by the packet forms only")
         eng = self.engine(torch.device(device))
@@ -268,7 +273,9 @@ class StreamGTCRNMicro(GTCRNMicro):
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
                                         g711=g711)
         if int(fs) != 16000:
-            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters)
+            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband)
+        if highband is not None:
+            raise _lib.GtcrnError("highband= needs fs = 24000, 32000 or 48000: a 16 kHz stream has no band above 8 kHz")
         return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters)
 
     def step_wave(self, x, state, slots=None, count=None):

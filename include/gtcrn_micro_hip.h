@@ -214,7 +214,8 @@ int gtcrn_wave_stream_flush_pcm16(gtcrn_model *m, void *d_state, void *d_wstate,
  *          j = 0 .. ceil(L * up / down) - 1; samples outside x are zero (zero padding, centred: no delay)
  * Within +0.0003 / -0.112 dB up to 0.875 of the lower Nyquist frequency, >= 96 dB down from 1.125 x it (whatever
  * aliases lands in 7 - 8 kHz-equivalent only).  Audio above 8 kHz of a wide-band input never reaches the model, and the
- * output at fs is band-limited to 8 kHz.  fs_in == fs_out == 16000 is a one-tap copy.  Any other pair of rates is
+ * output at fs is band-limited to 8 kHz unless the caller asks for the band above it to be carried around the model: see
+ * "high band" below (the hop-level rate form and the offline composition at 24 / 32 / 48 kHz).  fs_in == fs_out == 16000 is a one-tap copy.  Any other pair of rates is
  * GTCRN_ERR_ARG.  Arithmetic: fp32 fmaf, each output's products in a fixed order into four accumulators, so one signal
  * gives the same bits in a batch of any shape and in the streaming form below.
  *
@@ -405,6 +406,67 @@ int gtcrn_rate_stream_step_limited_pcm16(gtcrn_model *m, gtcrn_resampler *in, gt
                                          long out_stride, int nstreams, int nhops, const float *d_gain, const float *d_win,
                                          void *stream);
 int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream *ps, const float *d_gain);
+
+/* ---- high band: the band above 8 kHz of a 24 / 32 / 48 kHz stream, carried around the model ---------------------------
+ * The model runs at 16 kHz, so the plain rate form returns a stream at fs with nothing above 8 kHz (>= 96 dB down), and
+ * its attenuation limit at 0 dB is a low-pass filter, not a bypass.  Deployed enhancers that run a 16 kHz model inside a
+ * wide-band call split the band: the model cleans the low band, the high band goes around it, delayed to match, with a
+ * gain the application controls.  The library holds the 16 kHz dry signal and the outbound stage where the output is
+ * written, so the control costs no launch and no pass over the audio by the caller.
+ *
+ * Contract.  A HIGH-BAND GAIN gamma in [0, 1] per stream: d_hb_gain, a device array of floats, read by the kernel at
+ * every call like d_gain (it may be rewritten between calls and between the replays of a captured graph; 0 <= gamma <= 1 is
+ * the caller's precondition).  fs in {24000, 32000, 48000}.  The wave step is called as it is: `w` below is whatever it
+ * emits, limited (d_gain) or not (d_gain == NULL), and the meters see what they saw.
+ *   Live form.  For one stream after a reset, with x[n] the input at fs (PCM16: s / 32768), x[n < 0] = 0; a[k] the 16 kHz
+ *   hand-off of the inbound stage, a[k < 0] = 0; w[k] what the wave step emits for it (one hop late); H and D as in the
+ *   rate form and LAT = H + 2 D = gtcrn_rate_stream_latency(fs):
+ *       s[k]   = fl( w[k] - fl(gamma * a[k - 256]) )        fp32, every fl() ONE rounding, no fused multiply-add
+ *       v      = the causal outbound stage applied to s      (what gtcrn_rate_stream_step would emit if handed s for w)
+ *       out[n] = fl( v[n] + fl(gamma * x[n - LAT]) )         then the form's one rounding to int16 (_pcm16)
+ *   Both stages are linear phase with whole delays that sum to LAT, so the stage applied to -gamma a removes from
+ *   gamma x[n - LAT] exactly the band the model path carries: in exact arithmetic out = R(w) + gamma highpass(x delayed by
+ *   LAT), R the outbound stage.  Hence
+ *     - gamma = 0 equals the plain / limited step in value (the products are +-0: a zero may change its sign), outputs and
+ *       the model, wave and rate states;
+ *     - with the attenuation limit at 0 dB (beta = 1: w[k] == a[k - 256] exactly) and gamma = 1: s == 0, v == 0 and
+ *       out[n] == x[n - LAT] bit for bit, float and PCM16: the true bypass at the caller's rate;
+ *     - the output and all four states do not depend on how the hops are cut into calls.
+ *   Offline form.  With x16 = gtcrn_resample(fs -> 16000)(x), y = gtcrn_forward_wave[_limited](x16) and no delay anywhere,
+ *       out[j] = fl( gtcrn_resample(16000 -> fs)( fl(y - fl(gamma * x16)) )[j] + fl(gamma * x[j]) )     j < min(Lx, outputs)
+ *   and outputs at j >= Lx (a length-rounding tail, if any) get no dry term.  gtcrn_resample_hb is that last step: row b
+ *   holds d_lengths[b] <= L samples of d_wet (y) and d_dry (x16), d_xlengths[b] <= Lx samples of d_x (either array NULL: all
+ *   rows full) and receives ceil(d_lengths[b] * up / down) samples; `r` is a resampler 16000 -> fs.  One launch, asynchronous;
+ *   null pointers, B, L or Lx < 1, short strides, another resampler and d_x rows that overlap the output rows return
+ *   GTCRN_ERR_ARG before it.
+ *
+ * State.  d_hbstate holds gtcrn_rate_stream_hb_state_bytes(fs) = 4 * (256 + LAT) bytes per stream: the last 256 samples of
+ * a and the last LAT input samples as floats (the outbound history in d_rstate then holds s).  16-byte aligned; zeroed by
+ * gtcrn_rate_stream_hb_reset, a sub-range by offsetting the pointer.  It is a buffer of its own: d_rstate and
+ * gtcrn_rate_stream_state_bytes, every other state and GTCRN_ABI_VERSION are what they were.
+ *
+ * Calls.  gtcrn_rate_stream_step_hb[_pcm16] take the arguments of the _limited calls (d_gain may be NULL: no limit) plus
+ * d_hbstate and d_hb_gain.  A step is still five launches (k_rate_out_hb in the place of k_rate_out), asynchronous,
+ * allocates nothing after gtcrn_rate_stream_reserve and is capturable.  The kernel reads x[n - LAT] from the call's input
+ * rows while other threads write the output rows, so a call is NOT legal in place: input and output rows that overlap
+ * return GTCRN_ERR_ARG, as do fs = 8000 or 16000 (no high band), the 44.1 kHz family, a NULL d_hbstate or d_hb_gain and
+ * everything the plain step refuses, all before any launch.
+ * Out of scope: the packet forms (contiguous, slots, G.711; their latency is whole at these rates, so they can follow); the
+ * folder driver; a gain the library derives from the mask or the meters (a caller computes one on the device from the
+ * meter records without a synchronisation); ramping gamma inside a block. */
+size_t gtcrn_rate_stream_hb_state_bytes(int fs);   /* per stream; 0 (and GTCRN_ERR_ARG recorded) without a high band */
+int gtcrn_rate_stream_hb_reset(int fs, void *d_hbstate, int nstreams, void *stream);
+int gtcrn_rate_stream_step_hb(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                              void *d_rstate, const float *d_in, long in_stride, float *d_out, long out_stride, int nstreams,
+                              int nhops, const float *d_gain, const float *d_win, void *d_hbstate, const float *d_hb_gain,
+                              void *stream);
+int gtcrn_rate_stream_step_hb_pcm16(gtcrn_model *m, gtcrn_resampler *in, gtcrn_resampler *out, void *d_state, void *d_wstate,
+                                    void *d_rstate, const short *d_in, long in_stride, short *d_out, long out_stride,
+                                    int nstreams, int nhops, const float *d_gain, const float *d_win, void *d_hbstate,
+                                    const float *d_hb_gain, void *stream);
+int gtcrn_resample_hb(gtcrn_resampler *r, const float *d_wet, long wet_stride, const float *d_dry, long dry_stride,
+                      const int *d_lengths, long L, const float *d_x, long x_stride, const int *d_xlengths, long Lx,
+                      const float *d_hb_gain, float *d_out, long out_stride, int B, void *stream);
 
 /* ---- stream slots: step any subset of the resident live streams per call -----------------------------------------------
  * The contiguous live calls step every stream of a state range.  In a server some streams have no packet this tick and

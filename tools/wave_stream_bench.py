@@ -11,6 +11,10 @@ bytes the two wave kernels add per stream-step (from shapes).  Writes profiles/w
 against the 16 kHz wave step of the SAME run, same warm-up, repetitions and medians; writes
 profiles/rate_stream_bench.json.  With --trace-only N: rate steps at --trace-fs (default 48000).
 
+--rate --highband: the high band.  At 16 384 and 65 536 streams (or --sizes), 48 kHz, the plain rate step and the rate step
+of a state with highband=0.5 (gtcrn_rate_stream_step_hb: k_rate_out_hb as the fifth launch) alternate in one run; each
+figure stands next to that run's own repetition spread.  Writes profiles/highband_rate_bench.json.
+
 --packet: the packet form (gtcrn_packet_stream_step) at 16 384 and 65 536 streams (or --sizes): 16 kHz / 160 and 320,
 48 kHz / 480, 44.1 kHz / 441.  The timed unit is one whole period of calls, divided by the hops it steps, next to the
 per-hop time of the 16 kHz wave step and the 48 kHz rate step of the SAME run; plus every call of a period on its own
@@ -119,6 +123,31 @@ def compare_rate(eng, win, N, iters, reps, rates=(48000, 8000)):
         r[f"rate_step_{fs}_ms"] = med[fs]
         r[f"ratio_{fs}"] = med[fs] / med[16000]
         r[f"rate_reps_{fs}_ms"] = t[fs]
+    return r
+
+
+def compare_highband(eng, win, N, iters, reps, fs=48000, gain=0.5):
+    """One hop per stream and step at `fs`: the plain rate step and the step with the high band, alternating."""
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    sp, sh = eng.new_rate_state(N, win, fs), eng.new_rate_state(N, win, fs, highband=gain)
+    eng.rate_stream_reserve(sp, 1)
+    x = torch.randn(N, sp.hop, device="cuda", generator=gen) * 0.1
+    y = torch.empty_like(x)
+    plain = lambda: eng.rate_stream_step(sp, x, out=y)             # noqa: E731
+    hb = lambda: eng.rate_stream_step(sh, x, out=y)                # noqa: E731
+    for f in (plain, hb):
+        timed(f, max(3, iters // 4))                              # warm-up
+    tp, th = [], []
+    for _ in range(reps):
+        tp.append(timed(plain, iters))
+        th.append(timed(hb, iters))
+    r = {"N": N, "fs": fs, "highband": gain, "iters": iters, "rate_step_plain_ms": statistics.median(tp),
+         "rate_step_highband_ms": statistics.median(th), "rate_step_plain_reps_ms": tp, "rate_step_highband_reps_ms": th,
+         "rate_step_plain_spread": spread(tp), "rate_step_highband_spread": spread(th),
+         "highband_state_bytes_per_stream": sh.hb.shape[1] * 4}
+    r["ratio"] = r["rate_step_highband_ms"] / r["rate_step_plain_ms"]
+    del sp, sh
+    torch.cuda.empty_cache()
     return r
 
 
@@ -335,6 +364,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wave_stream_bench.json"))
     ap.add_argument("--trace-only", type=int, default=0)
     ap.add_argument("--rate", action="store_true", help="the rate step at 48 / 8 kHz against the 16 kHz wave step")
+    ap.add_argument("--highband", action="store_true",
+                    help="with --rate: the plain 48 kHz rate step against the step with the high band, alternating")
     ap.add_argument("--trace-fs", type=int, default=48000)
     ap.add_argument("--packet", action="store_true",
                     help="the packet form at 16 kHz / 160, 320, 48 kHz / 480 and 44.1 kHz / 441 against the wave and rate steps")
@@ -409,6 +440,21 @@ def main():
             for c in r["cases"]:
                 print(json.dumps({"N": N, **{k: v for k, v in c.items() if "reps" not in k and k != "kernels_one_period"}}),
                       flush=True)
+            res["compare"].append(r)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
+    if a.highband:
+        if not a.rate or a.trace_only:
+            raise SystemExit("--highband goes with --rate (and without --trace-only)")
+        sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "highband_rate_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in sizes:
+            r = compare_highband(eng, win, N, a.iters, a.reps)
+            print(json.dumps({k: v for k, v in r.items() if "reps" not in k}), flush=True)
             res["compare"].append(r)
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
