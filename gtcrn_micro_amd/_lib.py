@@ -159,6 +159,17 @@ def lib():
         for fn in ("gtcrn_rate_stream_step_hb", "gtcrn_rate_stream_step_hb_pcm16"):
             getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp, _vp, _vp]
         L.gtcrn_resample_hb.argtypes = [_vp, _vp, cl, _vp, cl, _vp, cl, _vp, cl, _vp, cl, _vp, _vp, cl, ci, _vp]
+    # high band on the packet forms (an earlier library has none of these: a packet state with highband= fails at its creation)
+    if hasattr(L, "gtcrn_packet_stream_step_hb"):
+        L.gtcrn_packet_stream_hb_latency.argtypes = [ci, ci]
+        L.gtcrn_packet_stream_hb_state_bytes.restype = ctypes.c_size_t
+        L.gtcrn_packet_stream_hb_state_bytes.argtypes = [ci, ci]
+        L.gtcrn_packet_stream_hb_reset.argtypes = [_vp, _vp, ci, _vp]
+        L.gtcrn_packet_stream_hb_reset_slots.argtypes = [_vp, _vp, _vp, _vp, ci, _vp]
+        for fn in ("gtcrn_packet_stream_step_hb", "gtcrn_packet_stream_step_hb_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, _vp, _vp, _vp, _vp]
+        for fn in ("gtcrn_packet_stream_step_slots_hb", "gtcrn_packet_stream_step_slots_hb_pcm16"):
+            getattr(L, fn).argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ci, _vp, cl, _vp, cl, _vp, _vp, _vp, _vp]
     L.gtcrn_stream_conv2d.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp] + [ci] * 12 + [_vp]
     L.gtcrn_pack_sizes.argtypes = [ctypes.POINTER(cl), ctypes.POINTER(cl)]
     L.gtcrn_pack_sizes.restype = None
@@ -1015,7 +1026,8 @@ class Engine:
         return out
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
-    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None):
+    def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None,
+                         highband=None):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
@@ -1023,12 +1035,17 @@ class Engine:
         (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains.  meters: as in
         new_wave_state (taken at 16 kHz, per 256-sample block of the wave step; a call without a hop leaves them alone).
         g711: "ulaw", "alaw" or None -- the law of the torch.uint8 rows packet_stream_step then takes and returns (RTP payload
-        types 0 / 8; float32 and int16 rows stay legal); without a law uint8 rows are refused."""
+        types 0 / 8; float32 and int16 rows stay legal); without a law uint8 rows are refused.
+        highband (a float or one per stream, each in [0, 1]; fs = 24000, 32000 or 48000 and a latency that is whole at fs;
+        None: off, the plain calls): the header's "high band on the packet forms" -- the state gets ``hb``
+        (N, packet_stream_hb_state_bytes / 4), the per-stream gains ``hb_gain`` every step then applies
+        (set_highband_gain rewrites them in place) and ``hb_latency`` in samples at fs; not together with g711=."""
         import torch
         law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
+        nhb = _packet_hb_floats(fs, packet, highband, law)
         ws = self.new_wave_state(nstreams, window, meters=meters)
         rs_in = self.resampler(fs, 16000) if fs != 16000 else None
         rs_out = self.resampler(16000, fs) if fs != 16000 else None
@@ -1039,6 +1056,7 @@ class Engine:
         st = PacketStreamState(self, h, ws.model, ws.wave, ws.window, fs, packet, n16, rs_in, rs_out,
                                torch.empty((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32))
         st.g711 = law
+        st._new_highband(nhb, highband)
         self.packet_stream_reset(st)
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
@@ -1057,12 +1075,15 @@ class Engine:
         with self._dev():
             _check(lib().gtcrn_packet_stream_reset(state._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
                                                    state.pkt[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
+            if state.hb is not None:
+                _check(lib().gtcrn_packet_stream_hb_reset(state._h, state.hb[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
 
     def packet_stream_step(self, state, x, out=None):
         """x (N, state.packet) float32 or int16 at the state's rate -> the enhanced (N, state.packet), same dtype,
         state.latency16 samples (counted at 16 kHz) late.  Steps state.next_hops hops of the model (possibly none) and
         advances the group's phase.  Asynchronous on the current stream; no allocation when `out` is given.  On a state
-        made with g711=, x may be torch.uint8: G.711 codes of that law in, codes out (gtcrn_packet_stream_step_g711)."""
+        made with g711=, x may be torch.uint8: G.711 codes of that law in, codes out (gtcrn_packet_stream_step_g711).  A
+        state with highband= runs gtcrn_packet_stream_step_hb: `out` must not overlap x (the call is not legal in place)."""
         import torch
         if not isinstance(state, PacketStreamState) or isinstance(state, PacketSlotState):
             raise GtcrnError("state must come from new_packet_state")
@@ -1075,13 +1096,17 @@ class Engine:
         law = (state.g711,) if x.dtype == torch.uint8 else ()
         if law:
             fn = lib().gtcrn_packet_stream_step_g711
+        hb = ()
+        if state.hb is not None:
+            fn = lib().gtcrn_packet_stream_step_hb_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_hb
+            hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         state.last_hops = state.next_hops
         self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
                       max(x.stride(0), state.packet), out.data_ptr(), max(out.stride(0), state.packet), state.n, *law,
-                      state.window.data_ptr(), _stream_ptr()))
+                      state.window.data_ptr(), *hb, _stream_ptr()))
         return out
 
     def packet_stream_handoff(self, state, which=0):
@@ -1097,17 +1122,19 @@ class Engine:
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
     def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False,
-                              g711=None):
+                              g711=None, highband=None):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
         one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db and meters: as in
-        new_wave_state, per SLOT.  g711: as in new_packet_state."""
+        new_wave_state, per SLOT.  g711: as in new_packet_state.  highband: as in new_packet_state, one gain per SLOT;
+        packet_stream_reset_slots then zeroes the named slots' rows of ``hb`` too."""
         import torch
         law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
         nbytes = packet_stream_state_bytes(fs, packet)
+        nhb = _packet_hb_floats(fs, packet, highband, law)
         ws = self.new_wave_state(nslots, window, meters=meters)
         m = ws.n if max_active is None else int(max_active)
         if not 1 <= m <= ws.n:
@@ -1122,6 +1149,9 @@ class Engine:
                              torch.zeros((ws.n, nbytes // 4), device=ws.wave.device, dtype=torch.float32),
                              torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.int32), m)
         st.g711 = law
+        st._new_highband(nhb, highband)
+        if st.hb is not None:
+            st.hb.zero_()
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
         st.meters = ws.meters
@@ -1141,7 +1171,8 @@ class Engine:
         stream in slot slots[i] (int32 device tensor, M <= state.max_active ids, in range and distinct); `count` (device
         int32, None: all M) rows step.  Returns (M, state.packet), same dtype, state.latency16 samples (at 16 kHz) late per
         stream; rows at or beyond count are not written and no other slot is touched.  The launch sequence is the same
-        for every call: asynchronous, capturable, no allocation when `out` is given."""
+        for every call: asynchronous, capturable, no allocation when `out` is given.  A state with highband= runs
+        gtcrn_packet_stream_step_slots_hb: `out` must not overlap x."""
         import torch
         if isinstance(state, PacketSlotState):
             _g711_rows(state, x, "x")
@@ -1159,12 +1190,17 @@ class Engine:
         law = (state.g711,) if x.dtype == torch.uint8 else ()
         if law:
             fn = lib().gtcrn_packet_stream_step_slots_g711
+        hb = ()
+        if state.hb is not None:
+            fn = (lib().gtcrn_packet_stream_step_slots_hb_pcm16 if x.dtype == torch.int16
+                  else lib().gtcrn_packet_stream_step_slots_hb)
+            hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         self._set_meters(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
                       slots.data_ptr(), cnt, m, x.data_ptr(), max(x.stride(0), state.packet), out.data_ptr(),
-                      max(out.stride(0), state.packet), *law, state.window.data_ptr(), _stream_ptr()))
+                      max(out.stride(0), state.packet), *law, state.window.data_ptr(), *hb, _stream_ptr()))
         return out
 
     def packet_stream_reset_slots(self, state, slots, count=None):
@@ -1175,6 +1211,9 @@ class Engine:
             _check(lib().gtcrn_packet_stream_reset_slots(state._h, state.model.data_ptr(), state.wave.data_ptr(),
                                                          state.pkt.data_ptr(), state.phase.data_ptr(), slots.data_ptr(), cnt, m,
                                                          _stream_ptr()))
+            if state.hb is not None:
+                _check(lib().gtcrn_packet_stream_hb_reset_slots(state._h, state.hb.data_ptr(), slots.data_ptr(), cnt, m,
+                                                                _stream_ptr()))
 
     def _cache_ptrs(self, tcn_cache):
         flat = [tcn_cache[g][k] for g in range(2) for k in range(4)]
@@ -1387,6 +1426,20 @@ class PacketStreamState(WaveStreamState):
         self.pkt = pkt
         self.last_hops = 0
         self.g711 = None            # the law of uint8 rows (0 mu-law, 1 A-law), or None: no uint8 rows
+        self.hb = None              # (N, packet_stream_hb_state_bytes/4): the high band's state; None: the plain calls
+        self.hb_gain = None         # (N,) float32 on the device: the high-band gains, per stream / slot
+        self.hb_latency = None      # the end-to-end delay in samples at fs (whole wherever the high band exists)
+
+    def _new_highband(self, nfloats, highband):
+        import torch
+        if highband is None:
+            return
+        self.hb = torch.empty((self.n, nfloats), device=self.wave.device, dtype=torch.float32)
+        self.hb_gain = torch.zeros((self.n,), device=self.wave.device, dtype=torch.float32)
+        self.hb_latency = packet_stream_hb_latency(self.fs, self.packet)
+        self.set_highband_gain(highband)
+
+    set_highband_gain = RateStreamState.set_highband_gain
 
     def set_dry_gain(self, gain):
         super().set_dry_gain(gain)
@@ -1455,6 +1508,36 @@ def packet_stream_state_bytes(fs, packet):
     if n == 0:
         raise GtcrnError(lib().gtcrn_last_error().decode())
     return n
+
+
+def packet_stream_hb_latency(fs, packet):
+    """End-to-end delay in samples at `fs` of a packet form that carries the high band: packet_stream_latency16 * fs / 16000
+    (host only; raises where there is no high band: 8 / 16 kHz, the 44.1 kHz family, 24 kHz with an odd n16)."""
+    fn = getattr(lib(), "gtcrn_packet_stream_hb_latency", None)
+    if fn is None:
+        raise GtcrnError("this library has no high band on the packet forms")
+    return _check(fn(int(fs), int(packet)))
+
+
+def packet_stream_hb_state_bytes(fs, packet):
+    """Bytes per stream of the packet forms' high-band state: 4 * (512 - gcd(n16, 256) + packet_stream_hb_latency), rounded
+    up to a multiple of 16 (host only; raises where there is no high band)."""
+    fn = getattr(lib(), "gtcrn_packet_stream_hb_state_bytes", None)
+    if fn is None:
+        raise GtcrnError("this library has no high band on the packet forms")
+    n = int(fn(int(fs), int(packet)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+def _packet_hb_floats(fs, packet, highband, law):
+    """Floats per stream of ``hb`` for a packet state made with highband= (0 without), after the checks that need no device."""
+    if highband is None:
+        return 0
+    if law is not None:
+        raise GtcrnError("highband= and g711= exclude each other: G.711 is an 8 kHz payload and has no high band")
+    return packet_stream_hb_state_bytes(fs, packet) // 4
 
 
 def packet_stream_schedule(fs, packet, phase=0):

@@ -1239,6 +1239,27 @@ bool pk_geometry(int fs, int n, PkGeom* p) {
 const char* const kPkBad = ": packets are n samples at fs in {8000, 16000, 22050, 24000, 32000, 44100, 48000} with n * 16000 / fs a "
                            "whole number in 1..4096 and, at fs != 16000, no shorter than either filter's history";
 
+// high band on the packet forms: fs in {24000, 32000, 48000} and the latency a whole number of samples at fs
+// (always at 32 / 48 kHz; at 24 kHz it needs an even n16).  *lat = latency16 * fs / 16000, *l16 = 512 - g.
+bool pk_hb_geometry(int fs, int n, PkGeom* p, int* l16, int* lat) {
+    if (!hb_rate_ok(fs) || !pk_geometry(fs, n, p)) return false;
+    const long lat16 = 512 - p->g + p->d_in + p->d_out;
+    if ((lat16 * fs) % 16000) return false;
+    *l16 = 512 - p->g;
+    *lat = (int)(lat16 * fs / 16000);
+    return *lat <= gtk::PKHB_DELAY && *l16 <= gtk::PKHB_A;
+}
+// floats per stream of d_hbstate: [l16 | lat], the row rounded up to a multiple of 4 floats
+long pk_hb_stride(int l16, int lat) { return ((long)l16 + lat + 3) & ~3L; }
+const char* const kPkHbBad = ": the packet high band exists at fs in {24000, 32000, 48000} for packets the packet form takes "
+                             "whose latency is a whole number of samples at fs (at 24000: n * 16000 / fs even)";
+
+// the high-band arguments of a packet step (null: the plain call)
+struct PkHb {
+    void* d_hbstate = nullptr;
+    const float* d_gain = nullptr;
+};
+
 }  // namespace
 
 struct gtcrn_packet_stream {
@@ -1259,6 +1280,22 @@ struct gtcrn_packet_stream {
     int* phi_rec() const { return d_plan + 2 * (size_t)p.hmax * max_streams; }
     int* cnts() const { return phi_rec() + max_streams; }
 };
+
+namespace {
+// the checks a high-band packet step adds to its plain form's: (fs, n), the two pointers, the state's alignment and rows
+// that overlap (the kernel reads x[m - latency] from the input rows while other threads write the output rows)
+extern "C++" template <typename S>
+int packet_hb_args(const std::string& w, const gtcrn_packet_stream* ps, const PkHb* hb, const S* d_in, long in_stride,
+                   const S* d_out, long out_stride, int rows, int* l16, int* lat) {
+    PkGeom p;
+    if (!pk_hb_geometry(ps->fs, ps->n, &p, l16, lat)) return fail(GTCRN_ERR_ARG, w + kPkHbBad);
+    if (!hb->d_hbstate || !hb->d_gain) return fail(GTCRN_ERR_ARG, w + ": null high-band state or gain pointer");
+    if (int rc = check_state_alignment(w, {hb->d_hbstate})) return rc;
+    if (rows_overlap(d_in, in_stride, d_out, out_stride, (long)ps->n, rows))
+        return fail(GTCRN_ERR_ARG, w + ": the input and output rows overlap (the high-band step is not legal in place)");
+    return 0;
+}
+}  // namespace
 
 int gtcrn_packet_stream_n16(int fs, int n) {
     PkGeom p;
@@ -1359,7 +1396,7 @@ int gtcrn_packet_stream_reset(gtcrn_packet_stream* ps, void* d_state, void* d_ws
 extern "C++" template <typename S>
 static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
                               const S* d_in, long in_stride, S* d_out, long out_stride, int nstreams, const float* d_win,
-                              void* stream) {
+                              void* stream, const PkHb* hb = nullptr) {
     const std::string w(who);
     if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
     if (!d_state || !d_wstate || !d_pstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
@@ -1367,6 +1404,9 @@ static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_
         return fail(GTCRN_ERR_ARG, w + ": nstreams must be >= 1 and at most the handle's max_streams");
     if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
     if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_pstate})) return rc0;
+    int l16 = 0, lat = 0;
+    if (hb)
+        if (int rc0 = packet_hb_args(w, ps, hb, d_in, in_stride, d_out, out_stride, nstreams, &l16, &lat)) return rc0;
     gtcrn_model* m = ps->m;
     int rc = check_model(m);
     if (rc) return rc;
@@ -1386,10 +1426,18 @@ static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_
                               ps->d_gain, d_win, {}, stream);
         if (rc) return rc;
     }
-    tm.begin(K_PACKET_OUT);
-    LAUNCH_TRY(gtk::launch_packet_out<S>(ps->d_b, row, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
-                                         nstreams, lvl, p.n16, h, p.out.up, p.out.down, p.out.ntp,
-                                         ps->out ? ps->out->d_taps : nullptr, s));
+    tm.begin(K_PACKET_OUT);                 // (the high-band kernel is timed in the row of the kernel it stands in for)
+    if constexpr (std::is_same<S, float>::value || std::is_same<S, short>::value) {
+        if (hb)
+            LAUNCH_TRY(gtk::launch_packet_out_hb<S>(ps->d_b, ps->d_a, row, d_in, in_stride, d_out, out_stride, ps->n, pst, ps_stride,
+                                                    2 * gtk::PK_FIFO + p.in.ntp, static_cast<float*>(hb->d_hbstate),
+                                                    pk_hb_stride(l16, lat), hb->d_gain, l16, lat, nstreams, phi, p.n16, h,
+                                                    p.out.up, p.out.down, p.out.ntp, ps->out->d_taps, s));
+    }
+    if (!hb)
+        LAUNCH_TRY(gtk::launch_packet_out<S>(ps->d_b, row, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
+                                             nstreams, lvl, p.n16, h, p.out.up, p.out.down, p.out.ntp,
+                                             ps->out ? ps->out->d_taps : nullptr, s));
     tm.end();
     ps->phase = (phi + p.n16) % 256;
     ps->last_h = h;
@@ -1449,11 +1497,15 @@ int gtcrn_packet_stream_reset_slots(gtcrn_packet_stream* ps, void* d_state, void
 extern "C++" template <typename S>
 static int packet_slots_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
                              int* d_phase, const int* d_slots, const int* d_count, int max_active, const S* d_in,
-                             long in_stride, S* d_out, long out_stride, const float* d_win, void* stream) {
+                             long in_stride, S* d_out, long out_stride, const float* d_win, void* stream,
+                             const PkHb* hb = nullptr) {
     const std::string w(who);
     if (int rc0 = packet_slots_args(w, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, max_active)) return rc0;
     if (!d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
     if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    int l16 = 0, lat = 0;
+    if (hb)
+        if (int rc0 = packet_hb_args(w, ps, hb, d_in, in_stride, d_out, out_stride, max_active, &l16, &lat)) return rc0;
     gtcrn_model* m = ps->m;
     int rc = check_model(m);
     if (rc) return rc;
@@ -1481,9 +1533,19 @@ static int packet_slots_impl(const char* who, gtcrn_packet_stream* ps, void* d_s
         if (rc) return rc;
     }
     tm.begin(K_PACKET_OUT_SLOTS);
-    LAUNCH_TRY(gtk::launch_packet_out_slots<S>(ps->d_b, M, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
-                                               d_slots, d_count, max_active, ps->phi_rec(), ps->pos(), p.g, p.n16, p.out.up,
-                                               p.out.down, p.out.ntp, ps->out ? ps->out->d_taps : nullptr, s));
+    if constexpr (std::is_same<S, float>::value || std::is_same<S, short>::value) {
+        if (hb)
+            LAUNCH_TRY(gtk::launch_packet_out_slots_hb<S>(ps->d_b, ps->d_a, M, d_in, in_stride, d_out, out_stride, ps->n, pst,
+                                                          ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
+                                                          static_cast<float*>(hb->d_hbstate), pk_hb_stride(l16, lat), hb->d_gain,
+                                                          l16, lat, d_slots, d_count, max_active, ps->phi_rec(), ps->pos(), p.g,
+                                                          p.n16, p.out.up, p.out.down, p.out.ntp, ps->out->d_taps, s));
+    }
+    if (!hb)
+        LAUNCH_TRY(gtk::launch_packet_out_slots<S>(ps->d_b, M, d_out, out_stride, ps->n, pst, ps_stride,
+                                                   2 * gtk::PK_FIFO + p.in.ntp, d_slots, d_count, max_active, ps->phi_rec(),
+                                                   ps->pos(), p.g, p.n16, p.out.up, p.out.down, p.out.ntp,
+                                                   ps->out ? ps->out->d_taps : nullptr, s));
     tm.end();
     ps->last_h = 0;     // (no contiguous hand-off to copy: gtcrn_packet_stream_debug_handoff is out of scope for slot calls)
     ps->last_n = 0;
@@ -1514,6 +1576,77 @@ int gtcrn_packet_stream_step_slots_g711(gtcrn_packet_stream* ps, void* d_state, 
     return packet_slots_impl<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count, max_active,
                                          reinterpret_cast<const gtk::g711a*>(d_in), in_stride,
                                          reinterpret_cast<gtk::g711a*>(d_out), out_stride, d_win, stream);
+}
+
+// ---- high band on the packet forms: the plain launch sequences with k_packet_out_hb / k_packet_out_slots_hb as the last launch
+int gtcrn_packet_stream_hb_latency(int fs, int n) {
+    PkGeom p;
+    int l16 = 0, lat = 0;
+    if (!pk_hb_geometry(fs, n, &p, &l16, &lat)) return fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_hb_latency") + kPkHbBad);
+    return lat;
+}
+size_t gtcrn_packet_stream_hb_state_bytes(int fs, int n) {
+    PkGeom p;
+    int l16 = 0, lat = 0;
+    if (!pk_hb_geometry(fs, n, &p, &l16, &lat)) { (void)fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_hb_state_bytes") + kPkHbBad); return 0; }
+    return sizeof(float) * (size_t)pk_hb_stride(l16, lat);
+}
+int gtcrn_packet_stream_hb_reset(gtcrn_packet_stream* ps, void* d_hbstate, int nstreams, void* stream) {
+    const std::string w("gtcrn_packet_stream_hb_reset");
+    if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
+    const size_t bytes = gtcrn_packet_stream_hb_state_bytes(ps->fs, ps->n);
+    if (!bytes) return GTCRN_ERR_ARG;
+    if (!d_hbstate || nstreams < 1) return fail(GTCRN_ERR_ARG, w + ": null state or nstreams < 1");
+    if (nstreams > ps->max_streams) return fail(GTCRN_ERR_ARG, w + ": more streams than the handle was created for");
+    if (int rc = check_state_alignment(w, {d_hbstate})) return rc;
+    HIP_TRY(hipSetDevice(ps->device));
+    HIP_TRY(hipMemsetAsync(d_hbstate, 0, bytes * nstreams, (hipStream_t)stream));
+    return 0;
+}
+int gtcrn_packet_stream_hb_reset_slots(gtcrn_packet_stream* ps, void* d_hbstate, const int* d_slots, const int* d_count,
+                                       int max_active, void* stream) {
+    const std::string w("gtcrn_packet_stream_hb_reset_slots");
+    if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
+    const size_t bytes = gtcrn_packet_stream_hb_state_bytes(ps->fs, ps->n);
+    if (!bytes) return GTCRN_ERR_ARG;
+    if (!d_hbstate || !d_slots) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (max_active < 1 || max_active > ps->max_streams)
+        return fail(GTCRN_ERR_ARG, w + ": max_active must be >= 1 and at most the handle's max_streams");
+    if (int rc = check_state_alignment(w, {d_hbstate})) return rc;
+    HIP_TRY(hipSetDevice(ps->device));
+    LAUNCH_TRY(gtk::launch_packet_hb_reset_slots(static_cast<float*>(d_hbstate), (long)(bytes / sizeof(float)), d_slots, d_count,
+                                                 max_active, (hipStream_t)stream));
+    return 0;
+}
+int gtcrn_packet_stream_step_hb(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const float* d_in,
+                                long in_stride, float* d_out, long out_stride, int nstreams, const float* d_win, void* d_hbstate,
+                                const float* d_hb_gain, void* stream) {
+    const PkHb hb{d_hbstate, d_hb_gain};
+    return packet_stream_impl<float>("gtcrn_packet_stream_step_hb", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
+                                     out_stride, nstreams, d_win, stream, &hb);
+}
+int gtcrn_packet_stream_step_hb_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const short* d_in,
+                                      long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win,
+                                      void* d_hbstate, const float* d_hb_gain, void* stream) {
+    const PkHb hb{d_hbstate, d_hb_gain};
+    return packet_stream_impl<short>("gtcrn_packet_stream_step_hb_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
+                                     out_stride, nstreams, d_win, stream, &hb);
+}
+int gtcrn_packet_stream_step_slots_hb(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                      const int* d_slots, const int* d_count, int max_active, const float* d_in, long in_stride,
+                                      float* d_out, long out_stride, const float* d_win, void* d_hbstate, const float* d_hb_gain,
+                                      void* stream) {
+    const PkHb hb{d_hbstate, d_hb_gain};
+    return packet_slots_impl<float>("gtcrn_packet_stream_step_slots_hb", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
+                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream, &hb);
+}
+int gtcrn_packet_stream_step_slots_hb_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
+                                            const int* d_slots, const int* d_count, int max_active, const short* d_in,
+                                            long in_stride, short* d_out, long out_stride, const float* d_win, void* d_hbstate,
+                                            const float* d_hb_gain, void* stream) {
+    const PkHb hb{d_hbstate, d_hb_gain};
+    return packet_slots_impl<short>("gtcrn_packet_stream_step_slots_hb_pcm16", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
+                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream, &hb);
 }
 
 long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream* ps, int which, float* d_dst, long n, void* stream) {

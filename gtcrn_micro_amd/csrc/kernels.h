@@ -190,6 +190,27 @@ int launch_packet_out_slots(const float* hand, int M, S* out, long out_stride, i
 // zeroes the packet state rows (ps_stride floats) and the phase words of the listed slots (k_packet_reset_slots)
 int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const int* slots, const int* cnt, int max_active,
                               hipStream_t s);
+// high band on the packet forms (gtcrn_packet_stream_step_hb / _step_slots_hb; fs = 24000, 32000, 48000): launch_packet_out /
+// _out_slots with fl(P - fl(gam A[t - l16])) staged in the place of the n16 popped samples and fl(gam in[m - lat]) added at the
+// store, gam = hb_gain[stream or slot].  hand_a: the inbound hand-off of the same call (rows as `hand`), phi: the phase before
+// the call (lvl = l16 - 256 - phi).  hbstate + stream * hb_stride = [the last l16 = 512 - g samples of A | the last lat input
+// samples] as floats, read and advanced.  in and out rows must not overlap.
+constexpr int PKHB_A = 512;                      // floats of LDS for A's line: l16 <= 511
+constexpr int PKHB_DELAY = 1728;                 // the longest input delay line: (511 + 64) * 3 = 1725 samples at 48 kHz
+template <typename S>
+int launch_packet_out_hb(const float* hand, const float* hand_a, long hand_stride, const S* in, long in_stride, S* out,
+                         long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate, long hb_stride,
+                         const float* hb_gain, int l16, int lat, int N, int phi, int n16, int h, int up, int down, int ntp,
+                         const float* taps, hipStream_t s);
+template <typename S>
+int launch_packet_out_slots_hb(const float* hand, const float* hand_a, int M, const S* in, long in_stride, S* out,
+                               long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate,
+                               long hb_stride, const float* hb_gain, int l16, int lat, const int* slots, const int* cnt,
+                               int max_active, const int* phi_rec, const int* pos, int g, int n16, int up, int down, int ntp,
+                               const float* taps, hipStream_t s);
+// zeroes the high-band rows (hb_stride floats) of the listed slots (k_packet_hb_reset_slots)
+int launch_packet_hb_reset_slots(float* hbstate, long hb_stride, const int* slots, const int* cnt, int max_active,
+                                 hipStream_t s);
 // gspec += adjoint(iSTFT)(gwave): gwave (B, 256 (T-1)) is the gradient w.r.t. the iSTFT output ALREADY divided by
 // the window envelope; gspec (B,257,T,2 by strides) receives the gradient w.r.t. the spectrogram (accumulated).
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,

@@ -5396,6 +5396,56 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_reset_slots(float* __rest
     if (threadIdx.x == 0) phase[slot] = 0;
 }
 
+// ---- high band on the packet forms (gtcrn_packet_stream_step_hb, _step_slots_hb): k_packet_out / k_packet_out_slots with
+// the band above 8 kHz carried around the model (packet_out_hb_body.inc states the arithmetic and the state row).  They take
+// BOTH hand-offs (hand_a: what the inbound kernel produced, read only), the call's input rows, the old inbound phase and
+// the high-band state and gains; the gain and the state row are the stream's (by row, or by slot).
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_out_hb(const float* __restrict__ hand, const float* __restrict__ hand_a,
+                                                              long hand_stride, const S* __restrict__ in, long in_stride,
+                                                              S* __restrict__ out, long out_stride, int n,
+                                                              float* __restrict__ pstate, long ps_stride, int hist_off,
+                                                              float* __restrict__ hbstate, long hb_stride,
+                                                              const float* __restrict__ hb_gain, int l16, int lat, int phi,
+                                                              int lvl, int n16, int h, int up, int down, int ntp,
+                                                              const float* __restrict__ taps) {
+    const long srow = blockIdx.x;
+    [[maybe_unused]] const int* const pos = nullptr;
+    [[maybe_unused]] constexpr int M = 0;
+#define GT_PK_IDX false
+#include "packet_out_hb_body.inc"
+#undef GT_PK_IDX
+}
+
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void k_packet_out_slots_hb(const float* __restrict__ hand, const float* __restrict__ hand_a,
+                                                                    int M, const S* __restrict__ in, long in_stride,
+                                                                    S* __restrict__ out, long out_stride, int n,
+                                                                    float* __restrict__ pstate, long ps_stride, int hist_off,
+                                                                    float* __restrict__ hbstate, long hb_stride,
+                                                                    const float* __restrict__ hb_gain, int l16, int lat,
+                                                                    const int* __restrict__ slots, const int* __restrict__ count,
+                                                                    int max_active, const int* __restrict__ phi_rec,
+                                                                    const int* __restrict__ pos, int g, int n16, int up,
+                                                                    int down, int ntp, const float* __restrict__ taps) {
+    if ((int)blockIdx.x >= slot_count(count, max_active)) return;
+    const long srow = slots[blockIdx.x];
+    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8, lvl = 256 - g - phi;
+    [[maybe_unused]] constexpr long hand_stride = 0;
+#define GT_PK_IDX true
+#include "packet_out_hb_body.inc"
+#undef GT_PK_IDX
+}
+
+// zeroes the high-band rows of the listed slots (gtcrn_packet_stream_hb_reset_slots)
+__global__ __launch_bounds__(RS_THREADS) void k_packet_hb_reset_slots(float* __restrict__ hbstate, long hb_stride,
+                                                                      const int* __restrict__ slots,
+                                                                      const int* __restrict__ count, int max_active) {
+    if ((int)blockIdx.x >= slot_count(count, max_active)) return;
+    float* hb = hbstate + (long)slots[blockIdx.x] * hb_stride;
+    for (int i = threadIdx.x; i < hb_stride; i += RS_THREADS) hb[i] = 0.f;
+}
+
 static bool packet_stage_ok(int n_in, int n_out, int up, int down, int ntp, const float* taps) {
     if (ntp == 0) return n_in == n_out;
     return taps && !(reinterpret_cast<uintptr_t>(taps) & 15) && up >= 1 && down >= 1 && (long)n_in * up == (long)n_out * down &&
@@ -5477,6 +5527,56 @@ int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const i
     GT_LAUNCH_CHECK();
     return 0;
 }
+// high band: the two outbound launchers with the extra rows; the stage exists (ntp > 0) and its table sits in LDS
+static bool packet_hb_ok(const float* hand_a, const void* in, float* hbstate, long hb_stride, const float* hb_gain, int l16,
+                         int lat, int up, int ntp) {
+    return hand_a && in && hbstate && hb_gain && l16 >= 256 && l16 <= PKHB_A && lat >= 1 && lat <= PKHB_DELAY &&
+           hb_stride >= l16 + lat && ntp > 0 && up * ntp <= RS_LDS_TAPS;
+}
+template <typename S>
+int launch_packet_out_hb(const float* hand, const float* hand_a, long hand_stride, const S* in, long in_stride, S* out,
+                         long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate, long hb_stride,
+                         const float* hb_gain, int l16, int lat, int N, int phi, int n16, int h, int up, int down, int ntp,
+                         const float* taps, hipStream_t s) {
+    const int lvl = l16 - 256 - phi, rem = lvl + 256 * h - n16;
+    if (phi < 0 || phi >= 256 || lvl < 0 || lvl >= 256 || n16 < 1 || n16 > PK_MAX16 || h != (phi + n16) / 256 || rem < 0 ||
+        rem >= 256 || hand_stride < 256L * h || hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST ||
+        !packet_stage_ok(n16, n, up, down, ntp, taps) || !packet_hb_ok(hand_a, in, hbstate, hb_stride, hb_gain, l16, lat, up, ntp))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_out_hb<S>), dim3(N), dim3(RS_THREADS), 0, s, hand, hand_a, hand_stride, in, in_stride, out,
+                       out_stride, n, pstate, ps_stride, hist_off, hbstate, hb_stride, hb_gain, l16, lat, phi, lvl, n16, h, up,
+                       down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template <typename S>
+int launch_packet_out_slots_hb(const float* hand, const float* hand_a, int M, const S* in, long in_stride, S* out,
+                               long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate,
+                               long hb_stride, const float* hb_gain, int l16, int lat, const int* slots, const int* cnt,
+                               int max_active, const int* phi_rec, const int* pos, int g, int n16, int up, int down, int ntp,
+                               const float* taps, hipStream_t s) {
+    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || g < 1 || g > 256 || 256 % g || n16 % g ||
+        l16 != 512 - g || hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST ||
+        !packet_stage_ok(n16, n, up, down, ntp, taps) || !packet_hb_ok(hand_a, in, hbstate, hb_stride, hb_gain, l16, lat, up, ntp))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_packet_out_slots_hb<S>), dim3(max_active), dim3(RS_THREADS), 0, s, hand, hand_a, M, in, in_stride, out,
+                       out_stride, n, pstate, ps_stride, hist_off, hbstate, hb_stride, hb_gain, l16, lat, slots, cnt, max_active,
+                       phi_rec, pos, g, n16, up, down, ntp, taps);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_packet_hb_reset_slots(float* hbstate, long hb_stride, const int* slots, const int* cnt, int max_active,
+                                 hipStream_t s) {
+    if (!hbstate || !slots || max_active < 1 || hb_stride < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_packet_hb_reset_slots, dim3(max_active), dim3(RS_THREADS), 0, s, hbstate, hb_stride, slots, cnt,
+                       max_active);
+    GT_LAUNCH_CHECK();
+    return 0;
+}
+template int launch_packet_out_hb<float>(const float*, const float*, long, const float*, long, float*, long, int, float*, long, int, float*, long, const float*, int, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_hb<short>(const float*, const float*, long, const short*, long, short*, long, int, float*, long, int, float*, long, const float*, int, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots_hb<float>(const float*, const float*, int, const float*, long, float*, long, int, float*, long, int, float*, long, const float*, int, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_out_slots_hb<short>(const float*, const float*, int, const short*, long, short*, long, int, float*, long, int, float*, long, const float*, int, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_in_slots<float>(const float*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_in_slots<short>(const short*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
 template int launch_packet_in_slots<g711u>(const g711u*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);

@@ -248,11 +248,12 @@ class StreamGTCRNMicro(GTCRNMicro):
         (Engine.packet_stream_reset_slots).
         g711="ulaw" | "alaw" (with packet=): step_wave then also takes and returns torch.uint8 rows of G.711 codes of that
         law (fs=8000, packet=160, g711="ulaw": 20 ms PCMU packets); float32 and int16 rows stay legal.
-        highband= (with fs = 24000, 32000 or 48000 and no packet=): the gain, one value or one per stream in [0, 1], with which
-        the band above 8 kHz is carried around the model (Engine.new_rate_state; state.set_highband_gain changes it while
-        the streams run).  None: that band is not in the output."""
-        if highband is not None and (packet is not None or slots is not None or resident):
-            raise _lib.GtcrnError("highband= goes with the hop-level rate form: fs = 24000, 32000 or 48000, no packet= / slots=")
+        highband= (with fs = 24000, 32000 or 48000): the gain, one value or one per stream (slot) in [0, 1], with which the
+        band above 8 kHz is carried around the model (state.set_highband_gain changes it while the streams run): the rate
+        form without packet= (Engine.new_rate_state), the packet form and the resident packet slots with it
+        (Engine.new_packet_state / new_packet_slot_state; not with g711=).  None: that band is not in the output."""
+        if highband is not None and slots is not None:
+            raise _lib.GtcrnError("highband= is given when a state is made, not when slots= resets some of its streams")
         if g711 is not None and (packet is None or slots is not None):
             raise _lib.GtcrnError("g711= goes with packet=: G.711 codes are taken by the packet forms only")
         eng = self.engine(torch.device(device))
@@ -268,10 +269,10 @@ class StreamGTCRNMicro(GTCRNMicro):
             if packet is None:
                 raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
             return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
-                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711)
+                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband)
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
-                                        g711=g711)
+                                        g711=g711, highband=highband)
         if int(fs) != 16000:
             return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband)
         if highband is not None:

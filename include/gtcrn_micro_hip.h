@@ -451,8 +451,7 @@ int gtcrn_packet_stream_set_dry_gain(gtcrn_packet_stream *ps, const float *d_gai
  * rows while other threads write the output rows, so a call is NOT legal in place: input and output rows that overlap
  * return GTCRN_ERR_ARG, as do fs = 8000 or 16000 (no high band), the 44.1 kHz family, a NULL d_hbstate or d_hb_gain and
  * everything the plain step refuses, all before any launch.
- * Out of scope: the packet forms (contiguous, slots, G.711; their latency is whole at these rates, so they can follow); the
- * folder driver; a gain the library derives from the mask or the meters (a caller computes one on the device from the
+ * Out of scope: the folder driver (the packet forms carry the high band through "high band on the packet forms" below); a gain the library derives from the mask or the meters (a caller computes one on the device from the
  * meter records without a synchronisation); ramping gamma inside a block. */
 size_t gtcrn_rate_stream_hb_state_bytes(int fs);   /* per stream; 0 (and GTCRN_ERR_ARG recorded) without a high band */
 int gtcrn_rate_stream_hb_reset(int fs, void *d_hbstate, int nstreams, void *stream);
@@ -557,6 +556,79 @@ int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream *ps, void *d_state,
                                          int *d_phase, const int *d_slots, const int *d_count, int max_active,
                                          const short *d_in, long in_stride, short *d_out, long out_stride,
                                          const float *d_win, void *stream);
+
+/* ---- high band on the packet forms: 24 / 32 / 48 kHz packets, group and slots ----------------------------------------------
+ * "high band" above, for the caller whose audio arrives in 10 or 20 ms packets (gtcrn_packet_stream_step, the packet slots):
+ * the 16 kHz samples the inbound kernel produced, the outbound FIFO, the outbound stage and the call's input rows are all on
+ * the device where the output is written, so the band above 8 kHz costs no launch and no extra pass over the audio, only one
+ * more per-stream state buffer.
+ *
+ * Contract (every fl() ONE fp32 rounding, no fused multiply-add).  Per stream, counted from the stream's own reset: x[n] the
+ * input at fs (PCM16: s / 32768); A[t] the 16 kHz output of the packet form's causal inbound stage (what the inbound kernel
+ * appends to the inbound FIFO); P[t] the 16 kHz sequence the outbound FIFO pops (its pre-fill, then what the wave step
+ * emitted); negative indices are zero.  g = gcd(n16, 256), L16 = 512 - g, LAT16 = L16 + d_in + d_out =
+ * gtcrn_packet_stream_latency16(fs, n), LAT = LAT16 * fs / 16000 = gtcrn_packet_stream_hb_latency(fs, n), and gamma the
+ * stream's HIGH-BAND GAIN in [0, 1] (the caller's precondition, read from device memory at every call):
+ *     s[t]   = fl( P[t] - fl(gamma * A[t - L16]) )
+ *     v      = the packet form's causal outbound stage applied to s (in the place of P)
+ *     out[n] = fl( v[n] + fl(gamma * x[n - LAT]) )          then the form's one rounding to int16 (_pcm16)
+ * L16 holds whatever the join phase: a stream that joins a group at phase z has z zeros in front of A in the inbound FIFO and
+ * 256 - g - z zeros of outbound pre-fill, and the wave step is one hop late, so P[t] pairs with
+ * A[t - (256 - g - z) - 256 - z + z] = A[t - L16]; the slot form has z = 0.  Both stages are linear phase with whole delays
+ * (d_in = d_out = 32 16 kHz samples at the three rates), so the low band of x arrives at the output delayed by exactly LAT and
+ * the stage applied to -gamma A removes it from gamma x[n - LAT]: LAT = 1632 / 1536 / 960 samples for 480 / 960 / 768-sample
+ * packets at 48 kHz, 1088 for 320 at 32 kHz, 816 / 768 for 240 / 480 at 24 kHz.  Hence, bit for bit:
+ *   - with the attenuation limit at 0 dB (beta = 1: the wave step emits the dry block) and gamma = 1: s == 0, v == 0 and
+ *     out[n] == x[n - LAT], float and PCM16: the true bypass at the caller's rate and packet size;
+ *   - gamma = 0 equals the plain / limited packet call in value (the products are +-0), outputs and the model, wave and packet
+ *     states;
+ *   - at 48 kHz with n = 768 a group created at phase 0 equals gtcrn_rate_stream_step_hb call by call (L16 = 256, LAT = 960);
+ *   - the limit (gtcrn_packet_stream_set_dry_gain) and the level meters compose with nothing added: the wave step is called
+ *     exactly as it is and P is whatever it emitted;
+ *   - per slot, the slot form equals a one-stream group created at phase 0 and fed the same packets.
+ *
+ * Rates and packets.  fs in {24000, 32000, 48000} and LAT16 * fs / 16000 whole: always at 32 and 48 kHz, at 24 kHz for an even
+ * n16 (10 and 20 ms packets are).  8 / 16 kHz (no high band), 22.05 / 44.1 kHz (1499.4 samples) and an odd n16 at 24 kHz:
+ * gtcrn_packet_stream_hb_latency returns GTCRN_ERR_ARG, gtcrn_packet_stream_hb_state_bytes 0 with the error recorded, and
+ * the steps GTCRN_ERR_ARG before any launch.
+ *
+ * State.  d_hbstate, a buffer of its own: gtcrn_packet_stream_hb_state_bytes(fs, n) per stream = L16 floats (the last L16
+ * samples of A) ++ LAT floats (the last LAT input samples), the row rounded up to a multiple of 4 floats (8 448 bytes at
+ * 48 kHz / 480).  16-byte aligned, zeros after a reset; the outbound history in d_pstate then holds s.  d_pstate,
+ * gtcrn_packet_stream_state_bytes, every other state and GTCRN_ABI_VERSION are what they were.  gtcrn_packet_stream_hb_reset
+ * zeroes nstreams rows (a sub-range by offsetting the pointer) next to gtcrn_packet_stream_reset;
+ * gtcrn_packet_stream_hb_reset_slots is a kernel, next to gtcrn_packet_stream_reset_slots, so a captured graph can admit a
+ * stream.
+ *
+ * Calls.  The plain signatures plus d_hbstate and d_hb_gain; d_hb_gain is read by ROW in the group form and BY SLOT in the
+ * slot form (like the dry gains), at every call, so it may change between calls and between graph replays.  A call makes the
+ * launch sequence of its plain form one for one, k_packet_out_hb / k_packet_out_slots_hb in the place of the outbound kernel
+ * (timed in that kernel's row of the launch records), the two launches of an h = 0 call included; it allocates nothing after
+ * gtcrn_packet_stream_create and captures as the plain form does (one period for the group form, one call for the slot
+ * form).  The kernel reads x[n - LAT] from the call's input rows while other threads write the output rows: rows that overlap
+ * return GTCRN_ERR_ARG, as do a NULL or misaligned d_hbstate, a NULL d_hb_gain, an unsupported (fs, n) and everything the
+ * plain call refuses, all before any launch.
+ * Out of scope: G.711 (an 8 kHz payload: no high band); 44.1 / 22.05 kHz; the folder driver; a gain the library derives;
+ * ramping gamma inside a packet. */
+int gtcrn_packet_stream_hb_latency(int fs, int n);          /* LAT in samples at fs, or GTCRN_ERR_ARG */
+size_t gtcrn_packet_stream_hb_state_bytes(int fs, int n);   /* per stream; 0 (and GTCRN_ERR_ARG recorded) without a high band */
+int gtcrn_packet_stream_hb_reset(gtcrn_packet_stream *ps, void *d_hbstate, int nstreams, void *stream);
+int gtcrn_packet_stream_hb_reset_slots(gtcrn_packet_stream *ps, void *d_hbstate, const int *d_slots, const int *d_count,
+                                       int max_active, void *stream);
+int gtcrn_packet_stream_step_hb(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, const float *d_in,
+                                long in_stride, float *d_out, long out_stride, int nstreams, const float *d_win,
+                                void *d_hbstate, const float *d_hb_gain, void *stream);
+int gtcrn_packet_stream_step_hb_pcm16(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                      const short *d_in, long in_stride, short *d_out, long out_stride, int nstreams,
+                                      const float *d_win, void *d_hbstate, const float *d_hb_gain, void *stream);
+int gtcrn_packet_stream_step_slots_hb(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate, int *d_phase,
+                                      const int *d_slots, const int *d_count, int max_active, const float *d_in,
+                                      long in_stride, float *d_out, long out_stride, const float *d_win, void *d_hbstate,
+                                      const float *d_hb_gain, void *stream);
+int gtcrn_packet_stream_step_slots_hb_pcm16(gtcrn_packet_stream *ps, void *d_state, void *d_wstate, void *d_pstate,
+                                            int *d_phase, const int *d_slots, const int *d_count, int max_active,
+                                            const short *d_in, long in_stride, short *d_out, long out_stride,
+                                            const float *d_win, void *d_hbstate, const float *d_hb_gain, void *stream);
 
 /* ---- G.711 payloads (mu-law / A-law) on the packet form, the packet slots and a pair of bulk converters ----------------
  * Most 8 kHz RTP carries G.711: payload type 0 (PCMU) and 8 (PCMA), one byte a sample, 160 bytes per 20 ms packet.  The

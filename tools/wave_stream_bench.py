@@ -21,6 +21,12 @@ per-hop time of the 16 kHz wave step and the 48 kHz rate step of the SAME run; p
 (the cost follows the hops of the call) and the library's per-kernel event times over one period.  Writes
 profiles/packet_stream_bench.json.  With --trace-only N: packet steps at --trace-fs / --trace-packet.
 
+--packet --highband: the high band on the packet form.  At 16 384 and 65 536 streams (or --sizes), 48 kHz / 480 and 48 kHz /
+960, one whole period of the plain packet call and of the call of a state with highband=0.5 (gtcrn_packet_stream_step_hb:
+k_packet_out_hb in the place of k_packet_out) alternate in one run; each ratio stands next to that run's own repetition
+spread, the plain figure next to the one profiles/packet_stream_bench.json holds for the same case, and the outbound
+kernel's own event times of both forms come from the library's launch records.  Writes profiles/highband_packet_bench.json.
+
 --dry-gain: the attenuation limit.  At 16 384 and 65 536 streams (or --sizes) the plain and the limited 16 kHz wave step
 (12 dB on every stream) alternate in one run, then one period of the plain and the limited packet form at 16 kHz / 160;
 offline, the library's event times of k_istft and k_istft_mix at B = 256 x 4 s.  Each limited figure stands next to the
@@ -229,6 +235,67 @@ def compare_packet(eng, win, N, iters, reps, cases=PACKET_CASES):
     return res
 
 
+HIGHBAND_PACKET_CASES = ((48000, 480), (48000, 960))
+
+
+def compare_packet_highband(eng, win, N, iters, reps, cases=HIGHBAND_PACKET_CASES, gain=0.5):
+    """One whole period of the plain packet call and of the call with the high band at N streams, alternating."""
+    gen = torch.Generator(device="cuda").manual_seed(N)
+    earlier = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "packet_stream_bench.json")) as f:
+            for r in json.load(f)["compare"]:
+                if r["N"] == N:
+                    earlier = {(c["fs"], c["packet"]): c["period_ms"] for c in r["cases"]}
+    except (OSError, KeyError, ValueError):
+        pass
+    res = {"N": N, "iters": iters, "highband": gain, "cases": []}
+    for fs, n in cases:
+        sp, sh = eng.new_packet_state(N, win, n, fs), eng.new_packet_state(N, win, n, fs, highband=gain)
+        P = sp.period
+        x = torch.randn(N, n, device="cuda", generator=gen) * 0.1
+        y = torch.empty_like(x)
+
+        def period(st):
+            for _ in range(P):
+                eng.packet_stream_step(st, x, out=y)
+
+        hops = []
+        for _ in range(P):
+            hops.append(sp.next_hops)
+            eng.packet_stream_step(sp, x, out=y)
+        period(sh)                                                 # (every h of the period ran on both states)
+        nper = max(2, iters // P)
+        for st in (sp, sh):
+            timed(lambda: period(st), 2)
+        tp, th = [], []
+        for _ in range(reps):
+            tp.append(timed(lambda: period(sp), nper))
+            th.append(timed(lambda: period(sh), nper))
+        kern = {}
+        for tag, st in (("plain", sp), ("highband", sh)):
+            eng.timing_enable(True)
+            period(st)
+            torch.cuda.synchronize()
+            kern[tag] = {k: {"avg_ms": v[0], "launches": v[1]} for k, v in eng.timing_read().items()}
+            eng.timing_enable(False)
+        c = {"fs": fs, "packet": n, "n16": sp.n16, "period_calls": P, "hops_per_period": sum(hops), "hops_by_call": hops,
+             "latency_samples": sh.hb_latency, "highband_state_bytes_per_stream": sh.hb.shape[1] * 4,
+             "period_plain_ms": statistics.median(tp), "period_highband_ms": statistics.median(th),
+             "period_plain_reps_ms": tp, "period_highband_reps_ms": th, "period_plain_spread": spread(tp),
+             "period_highband_spread": spread(th), "period_plain_ms_in_packet_stream_bench": earlier.get((fs, n)),
+             "k_packet_out_ms": kern["plain"]["k_packet_out"]["avg_ms"],
+             "k_packet_out_hb_ms": kern["highband"]["k_packet_out"]["avg_ms"], "kernels_one_period": kern}
+        c["ratio"] = c["period_highband_ms"] / c["period_plain_ms"]
+        c["k_packet_out_ratio"] = c["k_packet_out_hb_ms"] / c["k_packet_out_ms"]
+        # what the two delay lines move per stream and call: read and written once each
+        c["delay_line_bytes_per_stream_call"] = 2 * c["highband_state_bytes_per_stream"]
+        res["cases"].append(c)
+        del sp, sh
+        torch.cuda.empty_cache()
+    return res
+
+
 def spread(v):
     """(max - min) / median of the repetitions of one side: the run's own noise."""
     return (max(v) - min(v)) / statistics.median(v)
@@ -365,7 +432,8 @@ def main():
     ap.add_argument("--trace-only", type=int, default=0)
     ap.add_argument("--rate", action="store_true", help="the rate step at 48 / 8 kHz against the 16 kHz wave step")
     ap.add_argument("--highband", action="store_true",
-                    help="with --rate: the plain 48 kHz rate step against the step with the high band, alternating")
+                    help="with --rate: the plain 48 kHz rate step against the step with the high band, alternating; with "
+                         "--packet: one period of the plain packet call against the call with the high band, 48 kHz / 480, 960")
     ap.add_argument("--trace-fs", type=int, default=48000)
     ap.add_argument("--packet", action="store_true",
                     help="the packet form at 16 kHz / 160, 320, 48 kHz / 480 and 44.1 kHz / 441 against the wave and rate steps")
@@ -418,6 +486,23 @@ def main():
             res["compare"].append(r)
         res["offline"] = offline_dry_gain(eng, win, reps=a.reps)
         print(json.dumps({k: v for k, v in res["offline"].items() if k != "kernels_event_timed"}), flush=True)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", out)
+        return
+    if a.packet and a.highband:
+        if a.trace_only:
+            raise SystemExit("--packet --highband goes without --trace-only")
+        sizes = [int(s) for s in a.sizes.split(",")] if a.sizes != ap.get_default("sizes") else [16384, 65536]
+        out = a.out if "wave_stream_bench" not in a.out else os.path.join(ROOT, "profiles", "highband_packet_bench.json")
+        res = {"device": torch.cuda.get_device_name(0), "compare": []}
+        for N in sizes:
+            r = compare_packet_highband(eng, win, N, a.iters, a.reps)
+            for c in r["cases"]:
+                print(json.dumps({"N": N, **{k: v for k, v in c.items() if "reps" not in k and k != "kernels_one_period"}}),
+                      flush=True)
+            res["compare"].append(r)
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
             json.dump(res, f, indent=1)
