@@ -606,9 +606,20 @@ class Engine:
     def new_state(self, nstreams):
         import torch
         st = torch.empty((nstreams, self.state_bytes() // 4), device=f"cuda:{self.device}", dtype=torch.float32)
-        with self._dev():
-            _check(lib().gtcrn_stream_reset(self._h, st.data_ptr(), nstreams, _stream_ptr()))
+        self.stream_reset(st)
         return st
+
+    def stream_reset(self, state, lo=0, hi=None):
+        """Resets streams lo..hi-1 of a state of new_state to the start of a new clip (gtcrn_stream_reset on those rows)."""
+        self._check_on_device(state, "state")
+        if state.dim() != 2 or state.shape[1] != self.state_bytes() // 4 or not state.is_contiguous():
+            raise GtcrnError(f"state must be a contiguous (N, {self.state_bytes() // 4}) tensor of new_state")
+        hi = state.shape[0] if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= state.shape[0]:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.shape[0]})")
+        with self._dev():
+            _check(lib().gtcrn_stream_reset(self._h, state[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
 
     def stream_step(self, state, spec_t, out=None):
         import torch

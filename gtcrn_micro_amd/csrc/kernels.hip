@@ -4930,15 +4930,29 @@ int launch_selftest(const float* A, const float* Bm, const float* C, float* D, h
 // accumulators (tap t into accumulator t mod 4) by fmaf, joined (a0 + a1) + (a2 + a3).  Samples outside the signal are
 // staged as +0.0f and multiplied like any other.  The batch kernel and the two per-stream causal kernels stage the same
 // sample values around the same expression, so a stream equals the batch call on the same signal bit for bit.
+//
+// A padding tap reads NO sample.  Every phase holds the longest phase's taps or one fewer, so a row ends in at most four
+// +0.0f, all of them in its last group of four; a designed tap is never zero (gtcrn_resample_taps; the tests assert it for
+// every supported pair).  0 * x is 0 only for a finite x: multiplied like the rest, a NaN or Inf sample would meet up to
+// four padding taps in each of the `up` phases and so reach up to 4 * up outputs the filter's definition does not connect
+// it with (3 + 4 + 4 = 11 at 16 -> 48 kHz).  So the last group selects the sample away (+0.0f, which the product would
+// have been) where the tap's word is zero -- an integer compare, nothing -fno-honor-nans can reason about.
+__device__ __forceinline__ float rs_pad(float h, float x) { return __float_as_uint(h) ? x : 0.f; }
 __device__ __forceinline__ float rs_dot(const float* __restrict__ tp, int ntp, const float* __restrict__ xs) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    for (int t = 0; t < ntp; t += 4) {
+    const int last = ntp - 4;
+    for (int t = 0; t < last; t += 4) {
         const f32x4 h = ld4(tp + t);
         a0 = fmaf(h[0], xs[-t], a0);
         a1 = fmaf(h[1], xs[-t - 1], a1);
         a2 = fmaf(h[2], xs[-t - 2], a2);
         a3 = fmaf(h[3], xs[-t - 3], a3);
     }
+    const f32x4 h = ld4(tp + last);
+    a0 = fmaf(h[0], rs_pad(h[0], xs[-last]), a0);
+    a1 = fmaf(h[1], rs_pad(h[1], xs[-last - 1]), a1);
+    a2 = fmaf(h[2], rs_pad(h[2], xs[-last - 2]), a2);
+    a3 = fmaf(h[3], rs_pad(h[3], xs[-last - 3]), a3);
     return (a0 + a1) + (a2 + a3);
 }
 

@@ -217,7 +217,9 @@ int gtcrn_wave_stream_flush_pcm16(gtcrn_model *m, void *d_state, void *d_wstate,
  * output at fs is band-limited to 8 kHz unless the caller asks for the band above it to be carried around the model: see
  * "high band" below (the hop-level rate form and the offline composition at 24 / 32 / 48 kHz).  fs_in == fs_out == 16000 is a one-tap copy.  Any other pair of rates is
  * GTCRN_ERR_ARG.  Arithmetic: fp32 fmaf, each output's products in a fixed order into four accumulators, so one signal
- * gives the same bits in a batch of any shape and in the streaming form below.
+ * gives the same bits in a batch of any shape and in the streaming form below.  No designed tap is zero, and the zeros that
+ * pad the kernels' phase tables read no sample: a NaN or Inf at x[i0] makes exactly the outputs j with
+ * |j * down - i0 * up| <= half non-finite, and every other output keeps its bits.
  *
  * gtcrn_resample_taps (host only, no device): up, down and the 2 half + 1 coefficients exactly as the kernels use
  * them; returns the tap count (h_taps may be NULL to query it; cap = capacity of h_taps in floats).
@@ -359,7 +361,9 @@ int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream *ps, void *d_state, void 
  * the sample the plain call emits and x the input sample aligned with it,
  *     y = fl( fl(beta * x) + fl( fl(1 - beta) * w ) )        every fl() ONE fp32 rounding, no fused multiply-add
  * so a numpy float32 expression reproduces y bit for bit.  Hence beta = 0 gives w and beta = 1 gives x, exactly, for finite
- * inputs (as values: a zero may change its sign).  The mix is made in float BEFORE the one rounding to int16 of the _pcm16
+ * inputs (as values: a zero may change its sign).  Bypass is bit for bit the input for finite wet samples only: at beta = 1
+ * y = x + 0 * w, so a bypassed stream repeats a non-finite model output ("non-finite input" below) instead of the input.
+ * The mix is made in float BEFORE the one rounding to int16 of the _pcm16
  * forms.  Samples a form emits as structural zeros stay zeros: the first block of a hop stream, the FIFO pre-fill of the
  * packet form, the flush of a stream that holds fewer than 257 samples.  The limit changes no state: model state and wave
  * state after a limited call equal those after the plain call, and no state layout or *_state_bytes differs.
@@ -738,6 +742,33 @@ int gtcrn_g711_encode_pcm16(int law, int p);
  * caller chooses the window by when it zeroes); a voice-activity decision. */
 int gtcrn_wave_stream_set_meters(gtcrn_model *m, float *d_meters);
 int gtcrn_level_dbov(double energy, double nsamples);
+
+/* ---- non-finite input: what a NaN or Inf in one stream may touch ---------------------------------------------------------
+ * The library seats unrelated callers side by side -- four or seven streams in a workgroup, MFMA tiles that straddle two
+ * streams, time spans that run across utterance boundaries -- and a float sample is whatever the caller sent.  The contract
+ * for an input that holds a NaN, an Inf, or a finite value whose square overflows, in ONE stream, utterance or row (the
+ * victim), on every inference call of this header, offline and live, and on gtcrn_resample:
+ *   P1 isolation   every other stream / utterance / row / slot keeps every bit: its outputs at every call and its rows of
+ *                  every state (model, wave, rate, packet, high-band state, phase word, meter record).
+ *   P2 causality   the victim's outputs before the call that took the value keep every bit.
+ *   P3 cone        the model is a FIR in time: spectrum frame t0 reaches output frames t0 .. t0 + 84 and no other -- 85 =
+ *                  1 + 2 * 12 + 2 * 30 frames, the encoder / decoder blocks' and the two GTCN stacks' histories.  A NaN in
+ *                  one element of frame t0 makes every bin of exactly those frames non-finite, as the float64 reference
+ *                  does: no kernel turns it into a finite value.  A sample inside hop h (not the hop's first sample) lies in
+ *                  frames h and h + 1 and makes offline output blocks h - 1 .. h + 85 non-finite, 87 blocks of 256 samples,
+ *                  every sample of them; the hop form emits them one hop later, the rate and packet forms at their latency
+ *                  with the edges widened by the two filters' spans (one contiguous run of samples).  An Inf or an
+ *                  overflowing value stays inside the same frames; which of their values are finite is unspecified.
+ *   P4 recovery    from the first frame behind the cone on the victim's outputs keep every bit, and 16 frames later (the
+ *                  deepest ring of the state) so does its whole state: no field accumulates.  A meter record holds what it
+ *                  summed until the caller zeroes it.
+ *   P5 reset       resetting the victim through its form's reset (and zeroing its meter record) at any call makes it, from
+ *                  that call on, a fresh stream, bit for bit, whatever it held.
+ * One legitimate difference between forms: a non-finite x[256] -- the hop form frames hop 0 without its future sample
+ * x[256], which meets win[0] == 0, while the offline frame 0 (the reflected one) reads it -- so there the live stream's
+ * first frames are finite where the offline call's are not.  Stores of a non-finite value to PCM16 or G.711 outputs are
+ * unspecified (the integer forms cannot carry one in).  Training is outside all this: train-mode BatchNorm and the
+ * batch-mean loss couple the clips of a batch by definition. */
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
