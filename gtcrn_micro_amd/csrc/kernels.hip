@@ -2181,19 +2181,15 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
     __syncthreads();          // the only workgroup barrier: from here on every wave works on its own frames
     const long nframes = (long)B * T, stride = (long)gridDim.x * FR_WAVES;
     long fr = (long)blockIdx.x * FR_WAVES + wv;
-    // frame `fr` of the flattened (utterance, frame) axis; with per-utterance lengths the frames past an utterance's
-    // end do not exist (skipped)
-    auto frame_of = [&](long f, int& b, int& t, long& Lb) -> bool {
-        if (f >= nframes) return false;
-        b = (int)(f / T);
-        t = (int)(f - (long)b * T);
-        Lb = lens ? (long)lens[b] : L;
-        return !lens || t <= (int)(Lb >> 8);
-    };
-    auto fetch = [&](long f, float2 (&v)[4]) {
-        int b, t;
-        long Lb;
-        if (!frame_of(f, b, t, Lb)) { b = 0; t = 0; Lb = lens ? (long)lens[0] : L; }     // a valid frame, not used
+    // frame `fr` of the flattened (utterance, frame) axis is frame t of utterance b.  fr advances by the constant
+    // `stride`, so (b, t) are divided out ONCE and then stepped by (stride / T, stride % T) with one carry; with
+    // per-utterance lengths the frames past an utterance's end do not exist (skipped), and an utterance's length is
+    // read when b changes, not per frame.
+    int b = (int)(fr / T), t = (int)(fr - (long)b * T);
+    const int step_b = (int)(stride / T), step_t = (int)(stride - (long)step_b * T);
+    int b_len = -1;                            // the utterance Lb belongs to
+    long Lb = L;
+    auto fetch = [&](int b, int t, long Lb, float2 (&v)[4]) {
         const float* x = in + (long)b * L;
         const long lo = 256L * t - 256;
         if (lo >= 0 && lo + 512 <= Lb && ((reinterpret_cast<uintptr_t>(x + lo) & 7) == 0)) {
@@ -2232,12 +2228,20 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
         }
     };
     float2 cur[4];
-    for (; fr < nframes; fr += stride) {
-        int b, t;
-        long Lb;
-        const bool live = frame_of(fr, b, t, Lb);
+    // the frame's records in the three outputs, as byte offsets from the frame's first byte: the frame bases are wave
+    // uniform (scalar registers, stepped by the loop), so a store is base + 32-bit lane offset with no 64-bit vector
+    // pointer formed per store
+    using ht = typename HandOff<Q>::t;
+    constexpr unsigned EB = (unsigned)sizeof(ht);
+    const unsigned rec_off = (unsigned)(n * 16 + 4 * g) * EB;      // record n, slot group g, of a tile's first record
+    // ERB.bm: the band's first bin and width (lane = band) do not change from frame to frame
+    const int erb_lo = sI[lane], erb_cnt = sI[64 + lane];
+    for (; fr < nframes; fr += stride, b += step_b, t += step_t) {
+        if (t >= T) { t -= T; ++b; }
+        if (lens && b != b_len) { Lb = (long)lens[b]; b_len = b; }
+        const bool live = !lens || t <= (int)(Lb >> 8);
         // (no prefetch of the next frame: four waves per SIMD hide the load, and its eight registers would spill)
-        if (WAVE_IN && live) fetch(fr, cur);
+        if (WAVE_IN && live) fetch(b, t, Lb, cur);
         if (live) {
             // ---- the frame -> [mag, re, im] in LDS (+ the spectrogram written out) --------------------------------
             if constexpr (WAVE_IN) {
@@ -2283,7 +2287,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
             // ---- A: ERB.bm: lane = band; the three channels share the band's (re, im) reads ----------------------
             {
                 const int band = lane;
-                const int lo = sI[band], cnt = sI[64 + band];
+                const int lo = erb_lo, cnt = erb_cnt;
                 float w[ERB_MAXBW];
 #pragma unroll
                 for (int i = 0; i < ERB_MAXBW; i += 4) {
@@ -2334,8 +2338,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
                     const int e = 4 * g + s, c = e < 15 ? e / 5 : 0, k = e < 15 ? e % 5 : 0;
                     off[s] = c * F0_ROW + k;
                 }
-                using ht = typename HandOff<Q>::t;
-                ht* en0c = reinterpret_cast<ht*>(en0) + fr * (F1 * 16);
+                char* en0c = reinterpret_cast<char*>(reinterpret_cast<ht*>(en0) + fr * (F1 * 16));
 #pragma unroll
                 for (int tile = 0; tile < 5; ++tile) {
                     const int q = tile * 16 + n;
@@ -2347,7 +2350,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
                     acc = rq<Q>(prelu4(acc, a));
                     if (q < F1) {
                         st4(sE0 + pl(2 + fo, g), acc);
-                        stx<Q>(en0c + (unsigned)(q * 16 + 4 * g), acc);
+                        stx<Q>(reinterpret_cast<ht*>(en0c + (rec_off + (unsigned)(tile * 256) * EB)), acc);
                     }
                 }
             }
@@ -2357,8 +2360,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
                 const f32x4 Bv = ld4(sP + E_EN1_B + 4 * g);
                 const float a = sP[E_EN1_S] - 1.0f;
                 const int* ix = sI + 128 + 4 * g;
-                using ht = typename HandOff<Q>::t;
-                ht* en1pc = reinterpret_cast<ht*>(en1p) + fr * 528;
+                char* en1pc = reinterpret_cast<char*>(reinterpret_cast<ht*>(en1p) + fr * 528);
                 f32x4 x[3];
                 int ffv[3];
 #pragma unroll
@@ -2388,7 +2390,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
                     permute_tiles_via_lds<3>(sE0, po, ix, g, x, y);     // E0's taps are consumed: X region
 #pragma unroll
                     for (int i = 0; i < 3; ++i)
-                        if (i * 16 + n < 33) stx<Q>(en1pc + (unsigned)((i * 16 + n) * 16 + 4 * g), y[i]);
+                        if (i * 16 + n < 33) stx<Q>(reinterpret_cast<ht*>(en1pc + (rec_off + (unsigned)(i * 256) * EB)), y[i]);
                 }
             }
             wave_lds_sync();     // every region is rewritten by the next frame
@@ -2649,12 +2651,13 @@ static_assert(GB_LDS_FLOATS * 4 <= 160 * 1024, "band GTCN LDS budget");
 // cw: this wave's 3 tiles of the current-chunk image; hw: this wave's 3 bins of block D's history ring
 // (row = frame mod 2d); n = lane's frame inside the chunk; t0 is a multiple of 16 >= 2d, so
 // (t0 + n) mod 2d == n mod 2d.
+// am1: the block's three PReLU slopes minus one, wave uniform and the same for every chunk (formed once, in k_gtcn_band).
 template <int D, bool Q>
-__device__ __forceinline__ void tcn_block_band(f32x4 (&x)[TPW], const float* pk, float* cw, float* hw, bool live,
-                                               const Lane& L) {
+__device__ __forceinline__ void tcn_block_band(f32x4 (&x)[TPW], const float* pk, const float (&am1)[3], float* cw,
+                                               float* hw, bool live, const Lane& L) {
     const int n = L.n, g = L.g;
     constexpr int M2D = 2 * D - 1, HR = 2 * D * GB_RS, RS = GB_RS;   // ring mask, floats per bin of the ring
-    const float a1 = pk[TCN_SLOPE] - 1.0f, a2 = pk[TCN_SLOPE + 1] - 1.0f, a3 = pk[TCN_SLOPE + 2] - 1.0f;
+    const float a1 = am1[0], a2 = am1[1], a3 = am1[2];
     f32x4 y1[TPW], acc[TPW];
     const long h_minus_c = hw - cw;
     // ring rows of the taps that lie before the chunk
@@ -2733,6 +2736,21 @@ __global__ __launch_bounds__(NTHR) void k_gtcn_band(const float* __restrict__ xi
     using ht = typename HandOff<Q>::t;
     const int f0 = L.wave * TPW;                         // first bin of this wave
     float* cw = sC + f0 * 16 * GB_RS;
+    // the PReLU slopes of the four blocks, minus one: twelve wave-uniform numbers that no chunk changes, kept in
+    // scalar registers instead of being read from LDS and decremented in every block of every chunk.  (Not in the
+    // SPANS form, whose span iterator leaves no room for them: it would spill, so it reads them per chunk.)
+    auto slopes = [&](const float* pk, float (&a)[3]) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float v = pk[TCN_SLOPE + j] - 1.0f;
+            a[j] = SPANS ? v : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+        }
+    };
+    float am1[4][3];
+    if constexpr (!SPANS) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) slopes(sP + k * TCN_SIZE, am1[k]);
+    }
     for (int sg = 0;; ++sg) {
         if constexpr (SPANS) {
             if (!span_next(sit, B, T, lens, HALO_GTCN, s_b, s_fb, s_wlo, s_nT)) break;
@@ -2757,37 +2775,69 @@ __global__ __launch_bounds__(NTHR) void k_gtcn_band(const float* __restrict__ xi
         }
         // the chunk's input is fetched one chunk ahead into registers (the waves run decoupled here, so an exposed
         // HBM latency at the top of every chunk is not hidden by a barrier wait elsewhere); the addend is only
-        // needed at the store, so it is requested at the top of its own chunk
-        f32x4 xn[TPW];
-        auto fetch = [&](int t0f) {
-            const int tcf = t0f + n < Ts ? t0f + n : Ts - 1;   // clamped frame: no select behind the loads
-#pragma unroll
-            for (int i = 0; i < TPW; ++i) xn[i] = ldx<Q>(xinh + (unsigned)((tcf * 33 + f0 + i) * 16 + 4 * g));
+        // needed at the store, so it is requested at the top of its own chunk.
+        // Addresses: the three tensors are walked with one wave-uniform row counter (the chunk's first row, added to
+        // the bases as a scalar) and ONE per-lane byte offset inside the chunk, (min(n, last live row) * 33 + f0) *
+        // 16 + 4g records: a constant except in the final, partial chunk, where the rows past the end are clamped to
+        // the last one (no select behind the loads).  The offset of chunk t0 + TC is formed when that chunk is
+        // fetched and carried into the next trip, so a trip costs two vector instructions of address arithmetic.
+        constexpr int EB = (int)sizeof(ht);
+        const unsigned lane_off = (unsigned)(((f0 * 16 + 4 * g) * EB));
+        auto chunk_off = [&](int t0f) -> unsigned {       // byte offset of the lane's record from row t0f of the segment
+            return (unsigned)min(n, max(Ts - 1 - t0f, 0)) * (unsigned)(528 * EB) + lane_off;
         };
-        fetch(0);
+        auto row_ptr = [&](const ht* base, int t0f, unsigned off) {
+            return reinterpret_cast<const ht*>(reinterpret_cast<const char*>(base + (long)t0f * 528) + off);
+        };
+        f32x4 xn[TPW];
+        unsigned off_n = chunk_off(0);
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) xn[i] = ldx<Q>(row_ptr(xinh, 0, off_n) + i * 16);
         for (int t0 = 0; t0 < Ts; t0 += TC) {
-            const bool live = t0 + n < Ts;
-            const int tc = live ? t0 + n : Ts - 1;
-            const bool wr = live && t0 + n >= wlo;             // warm-up frames of a segment are not stored
+            const bool live = n < Ts - t0;
+            const bool wr = live && n >= wlo - t0;             // warm-up frames of a segment are not stored
+            const unsigned off = off_n;
             f32x4 x[TPW], ad[TPW];
 #pragma unroll
-            for (int i = 0; i < TPW; ++i) {
-                x[i] = xn[i];
-                if (addend) ad[i] = ldx<Q>(addh + (unsigned)((tc * 33 + f0 + i) * 16 + 4 * g));
+            for (int i = 0; i < TPW; ++i) x[i] = xn[i];
+            if (addend) {
+#pragma unroll
+                for (int i = 0; i < TPW; ++i) ad[i] = ldx<Q>(row_ptr(addh, t0, off) + i * 16);
             }
-            if (t0 + TC < Ts) fetch(t0 + TC);
             // opaque offset: the block parameters are re-read from LDS every chunk; hoisting the four
             // blocks' fragments out of the chunk loop would need 128 registers and spill
             int po = 0;
             asm volatile("" : "+v"(po));
-            // block k's ring: [33 bins][2d rows][16], blocks back to back (2, 4, 8, 16 rows per bin)
-            tcn_block_band<1, Q>(x, sP + po + 0 * TCN_SIZE, cw, sHh + (33 * 0 + f0 * 2) * GB_RS, live, L);
-            tcn_block_band<2, Q>(x, sP + po + 1 * TCN_SIZE, cw, sHh + (33 * 2 + f0 * 4) * GB_RS, live, L);
-            tcn_block_band<4, Q>(x, sP + po + 2 * TCN_SIZE, cw, sHh + (33 * 6 + f0 * 8) * GB_RS, live, L);
-            tcn_block_band<8, Q>(x, sP + po + 3 * TCN_SIZE, cw, sHh + (33 * 14 + f0 * 16) * GB_RS, live, L);
+            if constexpr (SPANS) {
 #pragma unroll
-            for (int i = 0; i < TPW; ++i)
-                if (wr) stx<Q>(xouth + (unsigned)((tc * 33 + f0 + i) * 16 + 4 * g), addend ? rq<Q>(x[i] + ad[i]) : x[i]);
+                for (int k = 0; k < 4; ++k) slopes(sP + po + k * TCN_SIZE, am1[k]);
+            }
+            // block k's ring: [33 bins][2d rows][16], blocks back to back (2, 4, 8, 16 rows per bin)
+            tcn_block_band<1, Q>(x, sP + po + 0 * TCN_SIZE, am1[0], cw, sHh + (33 * 0 + f0 * 2) * GB_RS, live, L);
+            // The next chunk is requested HERE, not at the top: the first block's residual is the last reader of this
+            // chunk's input, so the loads land in the registers that held it and the loop carries xn without a copy
+            // (requested at the top, xn -> x cost twelve moves a trip).  Three blocks remain to cover the latency.
+            // Behind the last chunk it re-reads the segment's last row: the clamp keeps the address inside the
+            // segment, and a load that is not conditional needs no second copy of xn either.
+            const int t1 = t0 + TC < Ts ? t0 + TC : t0;
+            off_n = chunk_off(t1);
+#pragma unroll
+            for (int i = 0; i < TPW; ++i) xn[i] = ldx<Q>(row_ptr(xinh, t1, off_n) + i * 16);
+            tcn_block_band<2, Q>(x, sP + po + 1 * TCN_SIZE, am1[1], cw, sHh + (33 * 2 + f0 * 4) * GB_RS, live, L);
+            tcn_block_band<4, Q>(x, sP + po + 2 * TCN_SIZE, am1[2], cw, sHh + (33 * 6 + f0 * 8) * GB_RS, live, L);
+            tcn_block_band<8, Q>(x, sP + po + 3 * TCN_SIZE, am1[3], cw, sHh + (33 * 14 + f0 * 16) * GB_RS, live, L);
+            ht* const o = const_cast<ht*>(row_ptr(xouth, t0, off));
+            // one uniform branch around each form of the store: with a select per tile the compiler gave `ad` a value on
+            // the path that has none (twelve moves a trip)
+            if (addend) {
+#pragma unroll
+                for (int i = 0; i < TPW; ++i)
+                    if (wr) stx<Q>(o + i * 16, rq<Q>(x[i] + ad[i]));
+            } else {
+#pragma unroll
+                for (int i = 0; i < TPW; ++i)
+                    if (wr) stx<Q>(o + i * 16, x[i]);
+            }
         }
     }
 }
