@@ -15,7 +15,14 @@ Storage "bf16_grads" rounds the gradients handed between units as well; the chec
 (grad_round=True), but those roundings cannot be pinned, so its bounds are the level of that noise (the CPU stand-in
 measures the same, tests/test_pinned_checker.py).  Fusion masks: all (65535), the layer-at-a-time passes (0; 16 -- skip
 gradients accumulated in place -- for "bf16_grads", which needs that bit), and all but normalise-on-load and the
-recomputed activations (bits 1 and 8)."""
+recomputed activations (bits 1 and 8).
+
+The fp32 storage mode (the default, what GTCRNMicro.train() runs and "bf16_saves" is held to) is checked the same way:
+every "<bn prefix>.y" is then the plain fp32 conv output, and the pinned float64 checker sees the inputs each HIP unit
+saw, so a PReLU element on the other side of its kink no longer parts the two gradients (unpinned: up to 1e-2 in blob
+rel-L2 at some inputs, tests/test_pinned_checker.py).  Its cases sit round the tilings -- the 8- and 12-frame tiles with
+two-frame halos, the 32-frame tile of train_kernels.hip, the TCN's dilations -- under four fusion masks, with finer
+seeded bugs, one of them the upstream gradient of a single frame lost (a dropped halo frame)."""
 import os
 
 import numpy as np
@@ -60,6 +67,43 @@ def test_bf16_train_step_per_unit_against_the_pinned_checker(storage, mask, shap
     assert bool(torch.isfinite(grads).all())
     PC.assert_pinned_step(storage, blob_np, spec_np, gout_np, taps, grads.cpu().numpy(),
                           blob.cpu().numpy().astype(np.float64), out.cpu().numpy(), f"{storage} fusions {fusions} {shape}")
+    tr.close()
+
+
+# 65535: the default; 0: layer-at-a-time; no normalise-on-load, no recomputed activations; 1023: the LDS-tiled backward
+# passes without the in-launch finishes, sums in the producer, k_pw_fwd, the column depthwise and the batched finishes
+F32_MASKS = {"all": 65535, "none": 0, "no_load_norm": 65535 & ~(1 | 8), "round4": 1023}
+
+
+def _f32_shapes():
+    from oracle import pinned_check as PC
+    return PC.F32_SHAPES
+
+
+@pytest.mark.parametrize("B,T", _f32_shapes())
+@pytest.mark.parametrize("mask", list(F32_MASKS))
+@pytest.mark.parametrize("tag", ["dns3", "rand"])
+def test_f32_train_step_per_unit_against_the_pinned_checker(tag, mask, B, T):
+    import torch
+    from gtcrn_micro_amd import Trainer
+    from oracle import pinned_check as PC
+    torch.set_num_threads(min(8, torch.get_num_threads()))
+    blob_np, spec_np, gout_np = PC.f32_inputs(tag, B, T)
+    fusions = F32_MASKS[mask]
+    tr = Trainer(0)
+    tr.set_storage("f32")
+    tr.set_fusions(fusions)
+    blob = torch.from_numpy(blob_np.copy()).cuda()
+    spec = torch.from_numpy(spec_np).cuda()
+    out = tr.forward(blob, spec)
+    taps = PC.read_taps(tr, fusions)
+    grads = tr.backward(blob, spec, torch.from_numpy(gout_np).cuda())
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(grads).all())
+    assert len(taps) == (65 if fusions & 2048 else 71)      # (bit 11: the six sum-minus-skip taps give way to the sums)
+    PC.assert_pinned_step("f32", blob_np, spec_np, gout_np, taps, grads.cpu().numpy(),
+                          blob.cpu().numpy().astype(np.float64), out.cpu().numpy(), f"f32 fusions {fusions} {tag} {B}x{T}",
+                          lost_frame=PC.F32_LOST_FRAME.get((B, T)))
     tr.close()
 
 
