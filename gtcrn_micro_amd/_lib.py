@@ -210,6 +210,21 @@ def lib():
     L.gtcrn_clip_adam_step.argtypes = [ci, _vp, _vp, _vp, _vp, _vp, cl, cf, cd, cd, cd, cd, cd, cl, _vp, _vp, _vp]
     L.gtcrn_clip_adam_workspace_bytes.restype = cl
     L.gtcrn_clip_adam_workspace_bytes.argtypes = [cl]
+    L.gtcrn_scorer_create.argtypes = [ctypes.POINTER(_vp), ci]
+    L.gtcrn_scorer_destroy.argtypes = [_vp]
+    L.gtcrn_scorer_destroy.restype = None
+    L.gtcrn_score_workspace_bytes.restype = ctypes.c_size_t
+    L.gtcrn_score_workspace_bytes.argtypes = [ci, cl]
+    L.gtcrn_score.argtypes = [_vp, _vp, cl, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp]
+    L.gtcrn_score_taps.restype = cl
+    L.gtcrn_score_taps.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci), _c_f32p, cl]
+    L.gtcrn_score_bands.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.gtcrn_score_frames.restype = cl
+    L.gtcrn_score_frames.argtypes = [cl]
+    L.gtcrn_score_debug.restype = cl
+    L.gtcrn_score_debug.argtypes = [_vp, ci, ci, _vp, cl, _vp]
+    L.gtcrn_score_timing.argtypes = [_vp, ci]
+    L.gtcrn_score_timing_read.argtypes = [_vp, ci, ctypes.c_char_p, ci, _c_f32p]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L
@@ -1672,6 +1687,151 @@ class Resampler:
         if out is not None:
             return out
         return out2[0] if one else out2
+
+
+SCORE_BITS = {"sdr": 1, "sisnr": 2, "stoi": 4}
+SCORE_STAGES = 6
+
+
+def score_taps():
+    """(up, down, h) of the scorer's 16 kHz -> 10 kHz stage: 5, 8 and the 513 float32 taps the kernel uses (host only)."""
+    up, down = ctypes.c_int(), ctypes.c_int()
+    n = _check(lib().gtcrn_score_taps(ctypes.byref(up), ctypes.byref(down), None, 0))
+    h = np.empty(n, np.float32)
+    _check(lib().gtcrn_score_taps(ctypes.byref(up), ctypes.byref(down), h.ctypes.data_as(_c_f32p), n))
+    return up.value, down.value, h
+
+
+def score_bands():
+    """(lo, hi): the 15 third-octave bin ranges lo[j] .. hi[j] - 1 of STOI's envelopes (host only)."""
+    lo, hi = (ctypes.c_int * 15)(), (ctypes.c_int * 15)()
+    _check(lib().gtcrn_score_bands(lo, hi))
+    return list(lo), list(hi)
+
+
+def score_frames(L):
+    """Analysis frames of an L-sample 16 kHz clip at STOI's 10 kHz (host only)."""
+    return _check(lib().gtcrn_score_frames(int(L)))
+
+
+class Scorer:
+    """SDR, SI-SNR and STOI of (clean, enhanced) 16 kHz pairs on one device (gtcrn_scorer; "scores" in
+    include/gtcrn_micro_hip.h): eval/eval_intrusive_metrics.py's three arithmetic metrics without a copy to the host.
+    Not PESQ, not DNSMOS."""
+
+    def __init__(self, device=0):
+        self.device = int(device)
+        h = ctypes.c_void_p()
+        _check(lib().gtcrn_scorer_create(ctypes.byref(h), self.device))
+        self._h = h
+        self._ws = {}          # (B, L) -> workspace
+        self._captured = set()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gtcrn_scorer_destroy(self._h)
+            self._h = None
+            self._ws = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, B, L):
+        n = int(lib().gtcrn_score_workspace_bytes(int(B), int(L)))
+        if n == 0:
+            raise GtcrnError(lib().gtcrn_last_error().decode())
+        return n
+
+    def _rows(self, x, name):
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+            raise GtcrnError(f"{name} must be a float32 CUDA (ROCm) tensor")
+        if x.device.index != self.device:
+            raise GtcrnError(f"{name} is on cuda:{x.device.index}, the scorer on cuda:{self.device}")
+        x2 = x.reshape(1, -1) if x.dim() == 1 else x
+        if x2.dim() != 2 or x2.shape[0] < 1 or x2.shape[1] < 1:
+            raise GtcrnError(f"{name} must be (B,L) or (L,) with L >= 1, got {tuple(x.shape)}")
+        if (x2.stride(1) != 1 and x2.shape[1] > 1) or (x2.shape[0] > 1 and x2.stride(0) < x2.shape[1]):
+            x2 = x2.contiguous()      # (also a broadcast row, clean.expand(B, L): stride 0 between the rows)
+        return x2
+
+    def score(self, ref, inf, lengths=None, what=("sdr", "sisnr", "stoi"), out=None):
+        """ref, inf: (B,L) or (L,) float32 CUDA tensors of equal shape, 16 kHz.  lengths (optional, B ints, host or
+        device): row b holds lengths[b] <= L samples.  what: names out of "sdr", "sisnr", "stoi".  out (optional): a
+        contiguous (B,4) float64 tensor that receives the 32-byte records (for a captured call).  Returns a dict of (B,)
+        device tensors: float64 "sdr", "sisnr", "stoi" (0 where not asked for), int32 "kept_frames" and "segments", all
+        views of "records".  Asynchronous on the current stream; nothing is copied to the host."""
+        import torch
+        r2, y2 = self._rows(ref, "ref"), self._rows(inf, "inf")
+        if r2.shape != y2.shape:
+            raise GtcrnError(f"ref {tuple(ref.shape)} and inf {tuple(inf.shape)} must have one shape")
+        B, L = r2.shape
+        bits = 0
+        for name in ((what,) if isinstance(what, str) else what):
+            if name not in SCORE_BITS:
+                raise GtcrnError(f"unknown score {name!r}: choose from {sorted(SCORE_BITS)}")
+            bits |= SCORE_BITS[name]
+        lens = None
+        if lengths is not None:
+            lens = torch.as_tensor(lengths).reshape(-1)
+            if lens.numel() != B:
+                raise GtcrnError(f"lengths must hold {B} entries, got {lens.numel()}")
+            if not lens.is_cuda and (int(lens.min()) < 0 or int(lens.max()) > L):
+                raise GtcrnError(f"every length must lie in [0, L={L}]")
+            lens = lens.to(device=r2.device, dtype=torch.int32).contiguous()
+        if out is None:
+            rec = torch.empty((B, 4), device=r2.device, dtype=torch.float64)
+        else:
+            rec = out
+            if (not isinstance(rec, torch.Tensor) or rec.device != r2.device or rec.dtype != torch.float64
+                    or tuple(rec.shape) != (B, 4) or not rec.is_contiguous()):
+                raise GtcrnError(f"out must be a contiguous float64 tensor of shape ({B}, 4) on the inputs' device")
+        ws = None
+        if bits & 4:
+            ws = self._ws.get((B, L))
+            if ws is None:
+                free = [k for k in self._ws if k not in self._captured]
+                if len(free) >= 8:          # a folder of many lengths: keep the eight most recent shapes
+                    self._ws.pop(free[0])
+                ws = self._ws[(B, L)] = torch.empty(self.workspace_bytes(B, L), device=r2.device, dtype=torch.uint8)
+        if ws is not None and torch.cuda.is_current_stream_capturing():
+            self._captured.add((B, L))      # a graph holds this workspace's address: never dropped
+        with torch.cuda.device(r2.device):
+            # (a one-row tensor may report any stride)
+            _check(lib().gtcrn_score(self._h, r2.data_ptr(), max(r2.stride(0), L), y2.data_ptr(), max(y2.stride(0), L),
+                                     lens.data_ptr() if lens is not None else None, L, B, bits, rec.data_ptr(),
+                                     ws.data_ptr() if ws is not None else None, _stream_ptr()))
+        self._last_L = L
+        counts = rec.view(torch.int32)[:, 6:8]
+        return {"sdr": rec[:, 0], "sisnr": rec[:, 1], "stoi": rec[:, 2], "kept_frames": counts[:, 0],
+                "segments": counts[:, 1], "records": rec}
+
+    def debug(self, which, b=0):
+        """Test hook (gtcrn_score_debug; synchronises): one intermediate of row b of the most recent call with STOI as a
+        float32 tensor: 0 the 10 kHz ref, 1 frame energies in dB, 2 the keep mask, 3 / 4 the ref / inf envelopes (15, M)."""
+        import torch
+        L = getattr(self, "_last_L", 1)
+        cap = max(L, 15 * (score_frames(L) + 1))
+        dst = torch.empty(cap, device=f"cuda:{self.device}", dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            n = _check(lib().gtcrn_score_debug(self._h, int(which), int(b), dst.data_ptr(), cap, _stream_ptr()))
+        got = dst[:n].clone()
+        return got.reshape(15, n // 15) if which in (3, 4) else got
+
+    def timing(self, on=True):
+        _check(lib().gtcrn_score_timing(self._h, 1 if on else 0))
+
+    def timing_read(self):
+        """{launch name: milliseconds} of the most recent call made with timing on (synchronises on its last event)."""
+        res = {}
+        for i in range(SCORE_STAGES):
+            name, ms = ctypes.create_string_buffer(64), ctypes.c_float()
+            _check(lib().gtcrn_score_timing_read(self._h, i, name, 64, ctypes.byref(ms)))
+            res[name.value.decode()] = float(ms.value)
+        return res
 
 
 G711_LAWS = {"ulaw": 0, "alaw": 1}

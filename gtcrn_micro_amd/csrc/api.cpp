@@ -926,6 +926,22 @@ long gtcrn_resample_taps(int fs_in, int fs_out, int* up, int* down, float* h_tap
     return n;
 }
 
+// Library-internal, like gtcrn_set_error_ (not in the header, no contract): the same design for any ratio.  metrics_host.cpp
+// takes the scorer's 16 kHz -> 10 kHz stage from it, which is no rate of gtcrn_resample.
+extern "C" long gtcrn_resample_design_(int fs_in, int fs_out, int* up, int* down, float* h_taps, long cap) {
+    if (fs_in < 1 || fs_out < 1) return fail(GTCRN_ERR_ARG, "gtcrn_resample_design_: rates must be positive");
+    RsDesign d;
+    rs_design(fs_in, fs_out, &d, h_taps != nullptr);
+    if (up) *up = d.up;
+    if (down) *down = d.down;
+    const long n = 2L * d.half + 1;
+    if (h_taps) {
+        if (cap < n) return fail(GTCRN_ERR_ARG, "gtcrn_resample_design_: the buffer holds fewer than 2 half + 1 taps");
+        std::memcpy(h_taps, d.h.data(), sizeof(float) * n);
+    }
+    return n;
+}
+
 long gtcrn_resample_out_len(int fs_in, int fs_out, long L) {
     if (!rs_pair_ok(fs_in, fs_out) || L < 0) return fail(GTCRN_ERR_ARG, "gtcrn_resample_out_len: unsupported rate pair or L < 0");
     int up, down;

@@ -17,7 +17,14 @@ checkpoint, length-matched to its clean reference (zero-pad / crop, ``:98-102``)
   which is not reproducible to the sample), batched per rate with the clips' lengths, and then enhanced like any
   other; the file is written at 16 kHz as the reference writes it, and a reference file at another rate counts
   with its 16 kHz length (``:90-93``).  Any other rate raises;
-* configuration comes from command-line flags (the reference reads two OmegaConf YAML files, ``:27-28``).
+* configuration comes from command-line flags (the reference reads two OmegaConf YAML files, ``:27-28``);
+* ``--score`` (off by default; without it the output is what it always was) scores every (clean, enhanced) pair on the
+  GPU right behind its batch -- SDR, SI-SNR and STOI, ``eval/eval_intrusive_metrics.py``'s three arithmetic metrics
+  (``gtcrn_score``; STOI behind the library's own 10 kHz filter, see ``include/gtcrn_micro_hip.h``) -- and writes
+  ``SDR.scp`` / ``SISNR.scp`` / ``STOI.scp`` (``uid value``) and ``RESULTS.txt`` (``METRIC: %.4f``, nan-mean) into the
+  enhanced folder in that script's format and in the order of ``inf.scp``.  There is no PESQ line.  The clean
+  files are read by the launching thread, which blocks once per batch: the pipeline overlaps less with the flag on.
+  Only 16 kHz clips are scored; the others are listed in ``RESULTS.txt`` as skipped.
 
     python -m gtcrn_micro_amd.infer --noisy-dir N --clean-dir C --enh-dir E --checkpoint best_model_dns3.tar
 """
@@ -107,7 +114,7 @@ def _check_rate(path, fs):
                              "are resampled on the GPU); resample the file first")
 
 
-def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta=None):
+def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta=None, scores=None):
     """The clips that are not at 16 kHz (other: item index -> (rate, samples at that rate)): per rate one Resampler and
     batches of similar lengths; a batch is resampled on the device with its lengths (gtcrn_resample), enhanced with
     its 16 kHz lengths and finished like any other clip.  beta: the attenuation limit's dry gain (mixed at 16 kHz).
@@ -137,6 +144,8 @@ def _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, 
             down += 4 * y.size
             for j, i in enumerate(sel):
                 rows[i] = _finish_clip(y[j], items[i], enh_dir)
+                if scores is not None:
+                    scores.skip(rows[i][0], f"clip at {fs} Hz")
     return up, down
 
 
@@ -147,6 +156,103 @@ def merge_scp(enh_dir, world):
             for r in range(world):
                 with open(os.path.join(enh_dir, f"{fname}.rank{r}")) as f:
                     out.write(f.read())
+
+
+SCORE_METRICS = (("SDR", "sdr"), ("SISNR", "sisnr"), ("STOI", "stoi"))
+
+
+class _FolderScores:
+    """--score: the (clean, enhanced) pairs of each batch, scored on the device in the batch's own stream
+    (_lib.Scorer).  The enhanced signal is the one the file holds: the 16-bit samples, cut at the enhanced length and
+    zero-padded / cropped to the clean length (infer.py:98-102), so both have the clean file's length -- the equal shapes
+    eval_intrusive_metrics.py:147 asserts.  One 32-byte record per clip comes back, at the end.  The clean files are read
+    and uploaded (pageable) by the thread that launches the batches, so with --score that thread blocks once per batch
+    and the pipeline's overlap is reduced; reading them in the reader pool into pinned slots is the follow-up."""
+
+    def __init__(self, device):
+        from . import _lib
+        self.scorer = _lib.Scorer(device)
+        self.pending = []        # (item indices, uids, records on the device)
+        self.skipped = []        # (uid, why)
+
+    def skip(self, uid, why):
+        self.skipped.append((uid, why))
+
+    def batch(self, pcm, sel, items, dev):
+        """pcm: (len(sel), Lout) int16 device tensor, row j the enhanced samples of items[sel[j]] as they are written."""
+        import torch
+        keep, cleans = [], []
+        for j, i in enumerate(sel):
+            uid = items[i][0].split(".wav")[0]
+            fs, c = read_wav_f32(items[i][2])
+            if fs != 16000:
+                self.skip(uid, f"reference at {fs} Hz")
+                continue
+            keep.append(j)
+            cleans.append(c)
+        if not keep:
+            return
+        n_clean = [len(c) for c in cleans]
+        Lc = max(n_clean)
+        host = np.zeros((len(keep), Lc), np.float32)
+        for r, c in enumerate(cleans):
+            host[r, :len(c)] = c
+        ref = torch.from_numpy(host).to(dev, non_blocking=False)
+        rows = pcm[torch.as_tensor(keep, device=dev)]
+        m = min(rows.shape[1], Lc)
+        valid = torch.as_tensor([min(256 * (items[sel[j]][4] // 256), items[sel[j]][3]) for j in keep], device=dev)
+        inf = torch.zeros((len(keep), Lc), device=dev)
+        inside = torch.arange(m, device=dev)[None, :] < valid[:, None]
+        inf[:, :m] = torch.where(inside, rows[:, :m].to(torch.float32) / 32768.0, torch.zeros((), device=dev))
+        res = self.scorer.score(ref, inf, lengths=n_clean)
+        self.pending.append(([sel[j] for j in keep], [items[sel[j]][0].split(".wav")[0] for j in keep], res["records"]))
+
+    def rows(self):
+        """[(uid, {"SDR": .., "SISNR": .., "STOI": ..})] in sorted file order, the order of inf.scp / ref.scp (the
+        reference's eval writes its score files in scp order, eval_intrusive_metrics.py:104-130)."""
+        out = []
+        for idx, uids, rec in self.pending:
+            r = rec.cpu().numpy()
+            for k, uid in enumerate(uids):
+                out.append((idx[k], uid, {"SDR": float(r[k, 0]), "SISNR": float(r[k, 1]), "STOI": float(r[k, 2])}))
+        return [(uid, sc) for _, uid, sc in sorted(out, key=lambda t: t[0])]
+
+
+def write_scores(enh_dir, rows, skipped, suffix=""):
+    """SDR.scp / SISNR.scp / STOI.scp (`uid value` per line) and RESULTS.txt (`METRIC: %.4f`, nan-mean), the format of
+    eval_intrusive_metrics.py:124-138 without its PESQ line; clips that were not scored are listed behind the means."""
+    for metric, _ in SCORE_METRICS:
+        with open(os.path.join(enh_dir, f"{metric}.scp{suffix}"), "w") as f:
+            for uid, sc in rows:
+                f.write(f"{uid} {sc[metric]!r}\n")
+    with open(os.path.join(enh_dir, "RESULTS.txt" + suffix), "w") as f:
+        for metric, _ in SCORE_METRICS:
+            vals = np.array([sc[metric] for _, sc in rows], np.float64)
+            mean = float(np.nanmean(vals)) if np.any(~np.isnan(vals)) else float("nan")
+            f.write(f"{metric}: {mean:.4f}\n")
+        for uid, why in skipped:
+            f.write(f"SKIPPED: {uid} ({why}; only 16 kHz clips are scored)\n")
+
+
+def merge_scores(enh_dir, world):
+    """The per-rank score files -> SDR.scp / SISNR.scp / STOI.scp / RESULTS.txt in rank order, as merge_scp does."""
+    per_metric = {}
+    for metric, _ in SCORE_METRICS:
+        lines = []
+        for r in range(world):
+            with open(os.path.join(enh_dir, f"{metric}.scp.rank{r}")) as f:
+                lines += [ln.split() for ln in f if ln.strip()]
+        per_metric[metric] = lines
+    uids = [uid for uid, _ in per_metric[SCORE_METRICS[0][0]]]
+    rows = [(uid, {m: float(per_metric[m][k][1]) for m, _ in SCORE_METRICS}) for k, uid in enumerate(uids)]
+    skipped = []
+    for r in range(world):
+        with open(os.path.join(enh_dir, f"RESULTS.txt.rank{r}")) as f:
+            for ln in f:
+                if ln.startswith("SKIPPED: "):
+                    uid, why = ln[len("SKIPPED: "):].rstrip("\n").split(" (", 1)
+                    skipped.append((uid, why.rsplit(";", 1)[0]))
+    write_scores(enh_dir, rows, skipped)
 
 
 def _finish_clip(y_row, item, enh_dir):
@@ -164,7 +270,7 @@ def _finish_clip(y_row, item, enh_dir):
 
 
 def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1,
-                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4, atten_lim_db=None):
+                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4, atten_lim_db=None, score=False):
     """barrier: a callable all ranks call once their lists are written (multi-GPU runs; main() passes
     torch.distributed.barrier); rank 0 then merges the per-rank scp files.
 
@@ -180,6 +286,8 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     batch after the other, what round 4 shipped), so every output file is bit-identical between the two.
     atten_lim_db: the attenuation limit in dB for every clip (None: off), applied by the iSTFT launch of the same calls
     (Engine.forward_wave's dry_gain) on the 16 kHz path and the other-rate path alike.
+    score=True: every batch's (clean, enhanced) pairs are scored on the device behind it (_FolderScores) and the score
+    files are written next to the scp lists (write_scores).
     stats (optional dict) receives: clips, frames, wall_s, frames_per_s, gpu_busy_frac (device time of the kernel
     sequences / wall time, from events), h2d_bytes, d2h_bytes."""
     import queue
@@ -196,6 +304,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     dev = f"cuda:{device}"
     beta = None if atten_lim_db is None else _lib.atten_lim_to_gain(atten_lim_db)
     win = torch.hann_window(512).pow(0.5).to(dev)                   # infer.py:65
+    scores = _FolderScores(device) if score else None
     names = sorted(f for f in os.listdir(noisy_dir) if f.endswith("wav"))
     lo, hi = shard_range(len(names), world, rank)
     # pass 1 (headers only): pair every clip with its reference, learn the lengths
@@ -229,7 +338,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     setup_s = 0.0
     nbytes = [0, 0]
     if other:
-        nbytes[0], nbytes[1] = _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta)
+        nbytes[0], nbytes[1] = _enhance_other_rates(eng, win, dev, items, other, max_batch, enh_dir, rows, beta, scores)
 
     if not pipeline or not batches:
         for sel in batches:
@@ -237,12 +346,15 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
             lens = [len(w) for w in waves]
             Lmax = max(lens)
             if min(lens) == Lmax:
-                y = eng.forward_wave(torch.from_numpy(np.stack(waves)).to(dev), win, dry_gain=beta).cpu().numpy()
+                yd = eng.forward_wave(torch.from_numpy(np.stack(waves)).to(dev), win, dry_gain=beta)
             else:
                 host = np.zeros((len(sel), Lmax), np.float32)
                 for j, w in enumerate(waves):
                     host[j, :len(w)] = w
-                y = eng.forward_wave_var(torch.from_numpy(host).to(dev), lens, win, dry_gain=beta).cpu().numpy()
+                yd = eng.forward_wave_var(torch.from_numpy(host).to(dev), lens, win, dry_gain=beta)
+            y = yd.cpu().numpy()
+            if scores is not None:      # the samples write_wav_pcm16 puts into the files, formed on the device
+                scores.batch(_lib.f32_to_pcm16(yd.contiguous().view(-1)).view(len(sel), -1), sel, items, dev)
             nbytes[0] += 4 * len(sel) * Lmax
             nbytes[1] += 4 * y.size
             for j, i in enumerate(sel):
@@ -390,6 +502,8 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
                         # (gtcrn_f32_to_pcm16; n * Lout is a multiple of 256)
                         _lib.f32_to_pcm16(yf[:n * Lout], out=sl["dout"][:n * Lout])
                         ev_b.record()
+                        if scores is not None:
+                            scores.batch(sl["dout"][:n * Lout].view(n, Lout), sel, items, dev)
                     with torch.cuda.stream(s_out):
                         s_out.wait_event(ev_b)
                         sl["hout"][:n * Lout].copy_(sl["dout"][:n * Lout], non_blocking=True)
@@ -427,11 +541,13 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
         with open(os.path.join(enh_dir, fname + suffix), "w") as f:
             for uid, p in lst:
                 f.write(f"{uid} {p}\n")
+    if scores is not None:
+        write_scores(enh_dir, scores.rows(), sorted(scores.skipped), suffix)
     return inf_scp, ref_scp
 
 
 def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1, barrier=None,
-                   agree=None, pipeline=True, stats=None, io_threads=4, atten_lim_db=None):
+                   agree=None, pipeline=True, stats=None, io_threads=4, atten_lim_db=None, score=False):
     """Counterpart of infer.py:26-119 for a folder (see ``_enhance_shard``): every rank enhances its contiguous shard of
     the sorted file list, then rank 0 merges the per-rank scp lists.
 
@@ -444,7 +560,8 @@ def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     result = None
     try:
         result = _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device, max_batch, rank, world, barrier,
-                                pipeline=pipeline, stats=stats, io_threads=io_threads, atten_lim_db=atten_lim_db)
+                                pipeline=pipeline, stats=stats, io_threads=io_threads, atten_lim_db=atten_lim_db,
+                                score=score)
     except Exception as e:           # re-raised below, after the exchange.  NOT BaseException: a KeyboardInterrupt or
         err = e                      # SystemExit must leave at once instead of waiting in a collective first
     all_ok = err is None
@@ -459,6 +576,8 @@ def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
         raise RuntimeError("enhance_folder: another rank failed; its shard is incomplete, the scp lists were not merged")
     if world > 1 and rank == 0 and (agree is not None or barrier is not None):
         merge_scp(enh_dir, world)
+        if score:
+            merge_scores(enh_dir, world)
     return result
 
 
@@ -474,6 +593,9 @@ def main(argv=None):
                     help="one batch after the other with pageable copies (the A/B of the pipelined default)")
     ap.add_argument("--atten-lim-db", type=float, default=None,
                     help="attenuation limit: remove at most this many dB of noise (0 = bypass; default: no limit)")
+    ap.add_argument("--score", action="store_true",
+                    help="score every (clean, enhanced) pair on the GPU: SDR.scp, SISNR.scp, STOI.scp and RESULTS.txt "
+                         "in the enhanced folder (SDR, SI-SNR, STOI; no PESQ)")
     ap.add_argument("--stats", action="store_true", help="print this rank's throughput / GPU-busy figures as JSON")
     a = ap.parse_args(argv)
     from .sharding import rank_world
@@ -499,7 +621,7 @@ def main(argv=None):
     try:
         st = {} if a.stats else None
         enhance_folder(a.noisy_dir, a.clean_dir, a.enh_dir, a.checkpoint, dev, a.max_batch, rank, world, barrier, agree,
-                       pipeline=not a.serial, stats=st, atten_lim_db=a.atten_lim_db)
+                       pipeline=not a.serial, stats=st, atten_lim_db=a.atten_lim_db, score=a.score)
         if st is not None:
             import json
             print(json.dumps({"rank": rank, **st}), flush=True)

@@ -248,6 +248,17 @@ def validate_batch(model, loss_func, noisy, clean, world_size=1, window=None):
     return loss, wave
 
 
+def score_batch(clean, enhanced, scorer, lengths=None, what=("sdr", "sisnr", "stoi")):
+    """The device-side stand-in for the scoring lines of Trainer._validation_epoch (train.py:343-362), which copy every
+    enhanced clip to the host and run PESQ on it: here the (clean, enhanced) pairs of a validate_batch output are scored
+    where they lie, with SDR, SI-SNR and STOI (``_lib.Scorer``, "scores" in include/gtcrn_micro_hip.h).  This is NOT
+    PESQ -- PESQ is ITU C code and stays the caller's -- so a checkpoint picked by these numbers is picked by another
+    criterion than the reference's.  clean, enhanced: (B,L) float32 device tensors at 16 kHz (validate_batch pads / crops
+    the enhanced one to the clean length); scorer: a ``_lib.Scorer`` on their device.  Returns Scorer.score's dict of (B,)
+    device tensors; nothing is copied to the host and the call is asynchronous."""
+    return scorer.score(clean, enhanced, lengths=lengths, what=what)
+
+
 def train_step(model, optimizer, scheduler, loss_func, noisy, clean, clip_grad_norm_value=3.0, world_size=1,
                window=None, stats=None):
     """One iteration of Trainer._train_epoch (train.py:244-288); returns (loss, grad_norm) as 0-d device tensors (no host

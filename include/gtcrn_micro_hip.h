@@ -770,6 +770,81 @@ int gtcrn_level_dbov(double energy, double nsamples);
  * unspecified (the integer forms cannot carry one in).  Training is outside all this: train-mode BatchNorm and the
  * batch-mean loss couple the clips of a batch by definition. */
 
+/* ---- scores: SDR, SI-SNR and STOI of (clean, enhanced) pairs, on the device ------------------------------------------------
+ * Replaces sdr_metric / sisnr_metric / stoi_metric of eval/eval_intrusive_metrics.py:22-32,74-91 and stands in for the
+ * scoring lines of train.py:_validation_epoch (train.py:343-362) without a copy to the host: B clips at 16 kHz in, one
+ * 32-byte record per clip out.  PESQ (ITU C code) and DNSMOS (an ONNX model) stay the caller's.
+ *
+ * gtcrn_score: row b of d_ref / d_inf holds d_lengths[b] <= L samples (int32 on the device, clamped to 0 .. L; NULL = all L)
+ * at d_ref + b * ref_stride / d_inf + b * inf_stride; `what` is a sum of 1 (SDR), 2 (SI-SNR), 4 (STOI); d_out receives B
+ * records, fields not asked for written as 0 (kept_frames and segments belong to STOI).  d_workspace: 16-byte aligned,
+ * gtcrn_score_workspace_bytes(B, L) bytes (B times a function of L alone); needed only with STOI.  Asynchronous on `stream`;
+ * allocates nothing, never synchronises the host, can be captured in a graph.  A null pointer, B outside 1 .. 65535, L
+ * outside 1 .. 2^28, a stride shorter than L, `what` outside 1 .. 7 and a missing or misaligned workspace return
+ * GTCRN_ERR_ARG before any launch.
+ *
+ * SDR and SI-SNR, to the letter of the reference, its quirk included (the projection divides by sum(ref^2 + 1e-8), which is
+ * sum(ref^2) + n * 1e-8).  With n the clip's length, r = ref - mean(ref), y = inf - mean(inf):
+ *     sdr   = 10 log10((sum r^2 + 1e-8) / (sum (y - r)^2 + 1e-8))
+ *     a     = sum(y r) / (sum r^2 + n * 1e-8)
+ *     sisnr = 10 log10((sum (a r)^2 + 1e-8) / (sum (y - a r)^2 + 1e-8))
+ * Samples are read as fp32; every sum is a double one in a fixed order; three passes (the means; the centred sums and a;
+ * the two sums of SI-SNR formed from the residual y - a r itself, never expanded from moments).  The reference computes in
+ * float32; the tests hold the difference to the reference's own noise floor.  n = 0 gives NaN.
+ *
+ * STOI: the structure and constants of Taal et al. 2011 as the reference calls it (stoi(ref, inf, 16000, extended=False)).
+ * Only the 10 kHz resampling filter is this library's own: pystoi resamples with an Octave-style resampler whose taps differ,
+ * so decimal parity with pystoi is neither claimed nor tested; the tests compare with an independent float64 statement of the
+ * definition below.  EPS = 2^-52.
+ *   1. Both signals 16 kHz -> 10 kHz by the formula of "sample-rate conversion" above with up / down = 5 / 8: q = 8,
+ *      half = 256, 513 taps, fc = 0.9375 * 0.5 / 8, the same Kaiser beta, sum(h) = 5, taps rounded once to float, zero
+ *      padding, centred; ceil(len * 5 / 8) outputs, each the double sum of its exact products, rounded once to float.
+ *      (gtcrn_resampler_create(16000, 10000) stays GTCRN_ERR_ARG: the taps are designed inside the scorer.)
+ *   2. Analysis frames start at s = 0, 128, ... < len10 - 256 (strict): n of them.  w[i] = 0.5 (1 - cos(2 pi (i + 1) / 257)),
+ *      i = 0 .. 255.  e_j = 20 log10(||w ref_frame_j||_2 + EPS).  Frame j is kept iff e_j > max_j e - 40; the mask comes from
+ *      ref alone and applies to both signals; K = the number of kept frames.
+ *   3. The kept, windowed frames of each signal are overlap-added at hop 128, in order: (K - 1) * 128 + 256 samples.
+ *   4. The result is framed again by the rule of 2, which gives M = K - 1 frames (0 for K = 0); each is windowed by w,
+ *      zero-padded to 512, and transformed (rFFT).
+ *   5. env[j, m] = sqrt(sum over k = lo_j .. hi_j - 1 of |X[k, m]|^2), 15 bands whose edges are the bins nearest to
+ *      150 * 2^((2 j -/+ 1) / 6) Hz on the grid k * 10000 / 512:
+ *        lo = 7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174
+ *        hi = 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219
+ *   6. S = M - 29 segments of 30 consecutive frames if M >= 30.  Per band and segment, x of ref and y of inf:
+ *      alpha = ||x|| / (||y|| + EPS); y' = min(alpha y, x (1 + 10^(15/20))); the mean over the 30 frames is removed from x
+ *      and from y'; each is divided by (its norm + EPS); d = sum x y'.  stoi = the mean of d over the 15 S pairs.  Steps 3
+ *      to 5 run in fp32 (the envelopes are stored as float), this step in double.
+ *   7. M < 30: stoi = 1e-5 (pystoi's value for this case), segments = 0, kept_frames = K.
+ * Properties that belong to the contract:
+ *   batch invariance  a clip's record has the same bits whatever B, L and the row it sits in, and whatever lengths the other
+ *                     rows have: every reduction is a fixed-order one over the clip's own samples, frames and segments.
+ *   non-finite input  ("non-finite input" above) a NaN or Inf in one clip changes no bit of another clip's record, and moves
+ *                     no index: K <= n by construction, and every store lands in the clip's own slice of the workspace.
+ *                     That clip's own scores are unspecified (NaN or 1e-5).
+ *   silence           an all-zero ref, inf or both keeps every score defined by the formulas above (EPS and the 1e-8 terms):
+ *                     no division by zero.
+ *
+ * Host only, no device: gtcrn_score_taps (up = 5, down = 8 and the 513 taps as the kernel uses them; returns the count,
+ * h_taps may be NULL), gtcrn_score_bands (the two tables of step 5), gtcrn_score_frames (n of step 2 for an L-sample clip).
+ * gtcrn_score_debug (test hook, synchronises `stream`): copies one intermediate of row b of the most recent call with STOI
+ * to d_dst as floats and returns the element count: which = 0 the 10 kHz ref (len10), 1 the frame energies in dB (n),
+ * 2 the keep mask as 0 / 1 (n), 3 / 4 the ref / inf band envelopes (15 x M, band-major).  The workspace of that call must
+ * still be alive.  gtcrn_score_timing(s, 1) records events around the launches of each following call (not under capture);
+ * gtcrn_score_timing_read returns launch `stage`'s name and milliseconds of the most recent one, stage = 0 .. 5. */
+typedef struct gtcrn_scorer gtcrn_scorer;
+typedef struct { double sdr, sisnr, stoi; int kept_frames, segments; } gtcrn_score_record;   /* 32 bytes */
+int gtcrn_scorer_create(gtcrn_scorer **out, int device);   /* designs taps / window / tables in double, uploads them */
+void gtcrn_scorer_destroy(gtcrn_scorer *s);
+size_t gtcrn_score_workspace_bytes(int B, long L);
+int gtcrn_score(gtcrn_scorer *s, const float *d_ref, long ref_stride, const float *d_inf, long inf_stride,
+                const int *d_lengths, long L, int B, int what, gtcrn_score_record *d_out, void *d_workspace, void *stream);
+long gtcrn_score_taps(int *up, int *down, float *h_taps, long cap);
+int gtcrn_score_bands(int *lo15, int *hi15);
+long gtcrn_score_frames(long L);
+long gtcrn_score_debug(gtcrn_scorer *s, int which, int b, float *d_dst, long cap, void *stream);
+int gtcrn_score_timing(gtcrn_scorer *s, int on);
+int gtcrn_score_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap, float *ms);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
