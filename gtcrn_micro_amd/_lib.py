@@ -225,6 +225,14 @@ def lib():
     L.gtcrn_score_debug.argtypes = [_vp, ci, ci, _vp, cl, _vp]
     L.gtcrn_score_timing.argtypes = [_vp, ci]
     L.gtcrn_score_timing_read.argtypes = [_vp, ci, ctypes.c_char_p, ci, _c_f32p]
+    # training batches from a resident corpus (an earlier library has none of these: data.BatchSource then fails at its creation)
+    if hasattr(L, "gtcrn_batch_plan"):
+        L.gtcrn_batch_plan.argtypes = [_vp, ci, _vp, ci, ci, cl, cl, ci, cf, cf, cf, cf, _vp, _vp, ci, _vp, _vp]
+        L.gtcrn_batch_plan_host.argtypes = [_vp, ci, _vp, ci, ci, cl, cl, ci, cf, cf, cf, cf, _vp, _vp, _vp]
+        L.gtcrn_batch_workspace_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_workspace_bytes.argtypes = [ci, cl]
+        L.gtcrn_batch_pairs.argtypes = [_vp, _vp, _vp, ci, _vp, ci, cl, _vp, cl, _vp, cl, _vp]
+        L.gtcrn_batch_mix.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, ci, cl, _vp, cl, _vp, cl, _vp, _vp, ci, _vp]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

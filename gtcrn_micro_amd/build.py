@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgtcrn_micro_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["kernels.hip", "api.cpp", "pack.cpp", "train_kernels.hip", "train.cpp", "metrics.hip", "metrics_host.cpp"]
-HEADERS = ["kernels.h", "stream_ms_body.inc", "packet_in_body.inc", "packet_out_body.inc", "packet_out_hb_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
+SOURCES = ["kernels.hip", "api.cpp", "pack.cpp", "train_kernels.hip", "train.cpp", "metrics.hip", "metrics_host.cpp", "batch.hip", "batch_host.cpp"]
+HEADERS = ["kernels.h", "stream_ms_body.inc", "packet_in_body.inc", "packet_out_body.inc", "packet_out_hb_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", "batch.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
 
 
 def _stale(target, deps):
@@ -37,7 +37,10 @@ def build_native(force=False, verbose=False, stamps=False, exp=False):
     #     multi-stream) then rounds identically, which is what makes streamed == chunked == offline hold BIT FOR BIT.
     # Training kernels keep the defaults: NaN/Inf of a diverged run must propagate, and their fp32 statistics are
     # measurably more accurate with the back end's contraction (tests/test_gpu_train.py, fp64 comparison).
-    per_file = {"kernels.hip": ["-fno-honor-nans", "-ffp-contract=on"]}
+    # Batch kernels (batch.hip, and the plan's host twin in batch_host.cpp): -ffp-contract=off, because their contract is
+    #     stated operation by operation (a rounded multiply, then a rounded add) and numpy restates it bit for bit.
+    per_file = {"kernels.hip": ["-fno-honor-nans", "-ffp-contract=on"], "batch.hip": ["-ffp-contract=off"],
+                "batch_host.cpp": ["-ffp-contract=off"]}
     suffix = ""
     lib = LIB
     if stamps:

@@ -1,0 +1,250 @@
+"""Training batches from a corpus that lives in device memory (include/gtcrn_micro_hip.h, "training batches from a
+resident corpus").
+
+Counterpart of the reference's ``DNS3Dataset`` + ``DataLoader`` + ``.to(device)`` (dataloader.py:113-170): the training
+set is held as int16 on the GPU (the reference's 180 000 pairs of 10 s are 115 GB, inside one MI355X's 288 GB) and
+``BatchSource.draw()`` cuts -- and, with a noise corpus, mixes -- a batch where it lies, on the current stream, inside a
+captured graph if the caller wants.  Nothing here falls back to the CPU; the arithmetic is csrc/batch.hip.
+
+Out of scope: room impulse responses, active-speech levels (a VAD), sample rates other than 16 kHz, float corpora, and
+streaming a corpus larger than device memory from disk.
+"""
+import numpy as np
+
+from ._lib import GtcrnError, _check, _stream_ptr, lib
+
+PLAN_DTYPE = np.dtype([("sclip", "<i4"), ("sstart", "<i4"), ("nclip", "<i4"), ("nstart", "<i4"),
+                       ("snr_db", "<f4"), ("snr_amp", "<f4"), ("lvl_db", "<f4"), ("lvl_amp", "<f4")])
+RECORD_DTYPE = np.dtype([("Ss", "<i8"), ("Sn", "<i8"), ("Ssn", "<i8"), ("gn", "<f4"), ("Gf", "<f4"), ("peak", "<f4"),
+                         ("flags", "<i4")])
+FLAG_NOISE_ZERO, FLAG_SPEECH_ZERO, FLAG_MIX_ZERO, FLAG_LIMITED = 1, 2, 4, 8
+_U64 = (1 << 64) - 1
+
+
+def _batch_lib():
+    L = lib()
+    if not hasattr(L, "gtcrn_batch_plan"):
+        raise GtcrnError("this library has no resident-corpus batches (gtcrn_batch_*)")
+    return L
+
+
+def _i64(v):
+    """A Python int as the int64 that carries the same 64 bits."""
+    v = int(v) & _U64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def workspace_bytes(B, L):
+    n = int(_batch_lib().gtcrn_batch_workspace_bytes(int(B), int(L)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+def plan_host(speech_offsets, noise_offsets, B, L, seed, step, item0=0, granule=1, snr_db=(-5.0, 20.0),
+              level_db=(-35.0, -15.0), clips=None):
+    """gtcrn_batch_plan_host: the plan the device would draw for (seed, step), computed on the host from host offset
+    tables (int64 arrays of n + 1 entries; noise_offsets None: no noise).  Returns a PLAN_DTYPE array of B items."""
+    so = np.ascontiguousarray(speech_offsets, np.int64)
+    no = None if noise_offsets is None else np.ascontiguousarray(noise_offsets, np.int64)
+    cl = None if clips is None else np.ascontiguousarray(clips, np.int32)
+    if cl is not None and cl.size != B:
+        raise GtcrnError(f"clips must hold {B} entries, got {cl.size}")
+    ss = np.array([int(seed) & _U64, int(step) & _U64], np.uint64)
+    plan = np.zeros(max(int(B), 0), PLAN_DTYPE)
+    _check(_batch_lib().gtcrn_batch_plan_host(
+        so.ctypes.data, so.size - 1, None if no is None else no.ctypes.data, 0 if no is None else no.size - 1, int(B), int(L),
+        int(item0), int(granule), float(snr_db[0]), float(snr_db[1]), float(level_db[0]), float(level_db[1]),
+        None if cl is None else cl.ctypes.data, ss.ctypes.data, plan.ctypes.data if plan.size else None))
+    return plan
+
+
+def plan_to_device(plan, device):
+    """A PLAN_DTYPE array -> the (B, 8) int32 device tensor ``BatchSource.draw(plan=...)`` takes."""
+    import torch
+    p = np.ascontiguousarray(plan, PLAN_DTYPE)
+    return torch.from_numpy(p.view(np.int32).reshape(p.size, 8).copy()).to(device)
+
+
+class Corpus:
+    """int16 clips back to back in one device buffer: ``pcm`` (int16, 1-D) and ``offsets`` (int64, n + 1; clip c is
+    pcm[offsets[c]:offsets[c + 1]]), both caller-visible device tensors."""
+
+    def __init__(self, pcm, offsets):
+        import torch
+        if not isinstance(pcm, torch.Tensor) or not pcm.is_cuda or pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+            raise GtcrnError("pcm must be a contiguous 1-D int16 CUDA (ROCm) tensor")
+        if (not isinstance(offsets, torch.Tensor) or offsets.device != pcm.device or offsets.dtype != torch.int64
+                or offsets.dim() != 1 or not offsets.is_contiguous()):
+            raise GtcrnError("offsets must be a contiguous 1-D int64 tensor on pcm's device")
+        n = offsets.numel() - 1
+        if n < 1:
+            raise GtcrnError("the corpus is empty")
+        if n >= 1 << 31:
+            raise GtcrnError("a corpus holds fewer than 2^31 clips")
+        lens = offsets[1:] - offsets[:-1]                     # checked once, here (one synchronisation)
+        lo, hi = int(lens.min()), int(lens.max())
+        if int(offsets[0]) < 0 or int(offsets[-1]) > pcm.numel() or lo < 1 or hi >= 1 << 31:
+            raise GtcrnError("offsets must rise by 1 .. 2^31 - 1 samples per clip and stay inside pcm")
+        self.pcm, self.offsets, self.n = pcm, offsets, n
+
+    @property
+    def device(self):
+        return self.pcm.device
+
+    @classmethod
+    def from_tensors(cls, pcm, offsets):
+        return cls(pcm, offsets)
+
+    @classmethod
+    def from_arrays(cls, arrays, device="cuda"):
+        import torch
+        arrays = [np.asarray(a) for a in arrays]
+        for a in arrays:
+            if a.dtype != np.int16 or a.ndim != 1 or a.size < 1:
+                raise GtcrnError("every clip must be a 1-D int16 array of at least one sample")
+        if not arrays:
+            raise GtcrnError("the corpus is empty")
+        off = np.zeros(len(arrays) + 1, np.int64)
+        np.cumsum([a.size for a in arrays], out=off[1:])
+        return cls(torch.from_numpy(np.concatenate(arrays)).to(device), torch.from_numpy(off).to(device))
+
+    @classmethod
+    def from_wavs(cls, paths, device="cuda"):
+        """16 kHz mono 16-bit PCM files (the reference's data), read with the reader infer.py uses."""
+        from scipy.io import wavfile
+        clips = []
+        for p in paths:
+            fs, x = wavfile.read(p, mmap=True)
+            if fs != 16000 or x.ndim != 1 or x.dtype != np.int16:
+                raise GtcrnError(f"{p}: a corpus takes 16 kHz mono 16-bit PCM, got {fs} Hz, shape {tuple(x.shape)}, {x.dtype}")
+            clips.append(np.asarray(x))
+        return cls.from_arrays(clips, device)
+
+    def save(self, prefix):
+        """Writes ``prefix + '.pcm.npy'`` and ``prefix + '.offsets.npy'``."""
+        np.save(prefix + ".pcm.npy", self.pcm.cpu().numpy())
+        np.save(prefix + ".offsets.npy", self.offsets.cpu().numpy())
+
+    @classmethod
+    def load(cls, prefix, device="cuda"):
+        import torch
+        pcm, off = np.load(prefix + ".pcm.npy"), np.load(prefix + ".offsets.npy")
+        if pcm.dtype != np.int16 or off.dtype != np.int64 or pcm.ndim != 1 or off.ndim != 1:
+            raise GtcrnError(f"{prefix}: not a saved corpus (int16 pcm, int64 offsets)")
+        return cls(torch.from_numpy(pcm).to(device), torch.from_numpy(off).to(device))
+
+
+class BatchSource:
+    """Draws (noisy, clean) batches of B rows of L samples from resident corpora.
+
+    ``noise=`` a second Corpus: dynamic mixing of ``speech`` with wrapped noise at an SNR from U(snr_db) and a mixture
+    level from U(level_db) dB RMS re full scale (gtcrn_batch_mix).  ``paired_clean=`` a Corpus under the same offsets
+    table as ``speech`` (which is then the noisy side): the reference's loader, exactly (gtcrn_batch_pairs).
+    A batch is a pure function of (seed, step, item0 + row); ``item0`` = rank * B makes ranks cut one global batch.
+    granule = 1: sample-exact starts; 16000: the reference's whole-second random_start."""
+
+    def __init__(self, speech, noise=None, paired_clean=None, B=1, L=64000, seed=0, snr_db=(-5.0, 20.0), level_db=(-35.0, -15.0),
+                 granule=1, item0=0):
+        import torch
+        _batch_lib()
+        if (noise is None) == (paired_clean is None):
+            raise GtcrnError("give exactly one of noise= (mix) and paired_clean= (pairs)")
+        other = noise if noise is not None else paired_clean
+        if not isinstance(speech, Corpus) or not isinstance(other, Corpus) or other.device != speech.device:
+            raise GtcrnError("the corpora must be data.Corpus objects on one device")
+        if paired_clean is not None and (paired_clean.n != speech.n or not torch.equal(paired_clean.offsets, speech.offsets)):
+            raise GtcrnError("paired corpora must share one offsets table")
+        B, L, granule, item0 = int(B), int(L), int(granule), int(item0)
+        self.snr_db = (float(snr_db[0]), float(snr_db[1]))
+        self.level_db = (float(level_db[0]), float(level_db[1]))
+        if B < 1 or L < 1 or L >= 1 << 31:
+            raise GtcrnError("B and L must be positive (L below 2^31)")
+        if granule < 1:
+            raise GtcrnError("granule must be at least 1")
+        if self.snr_db[1] < self.snr_db[0] or self.level_db[1] < self.level_db[0]:
+            raise GtcrnError("a range has hi < lo")
+        if item0 < 0 or item0 + B > 1 << 32:
+            raise GtcrnError("item0 .. item0 + B must lie in 0 .. 2^32")
+        self.speech, self.noise, self.paired_clean = speech, noise, paired_clean
+        self.B, self.L, self.granule, self.item0 = B, L, granule, item0
+        dev = self.device = speech.device
+        self.plan = torch.zeros((B, 8), device=dev, dtype=torch.int32)          # gtcrn_batch_item rows
+        self.records = torch.zeros((B, 10), device=dev, dtype=torch.int32)      # gtcrn_batch_record rows (mix only)
+        self.seed_step = torch.tensor([_i64(seed), 0], device=dev, dtype=torch.int64)
+        self.noisy = torch.empty((B, L), device=dev, dtype=torch.float32)
+        self.clean = torch.empty((B, L), device=dev, dtype=torch.float32)
+        self._ws = torch.empty(workspace_bytes(B, L), device=dev, dtype=torch.uint8) if noise is not None else None
+
+    # ---- the step word ----------------------------------------------------------------------------------------------
+    def set_step(self, k):
+        """The next drawn plan is step k's (stream-ordered, for a resume)."""
+        self.seed_step[1:2].fill_(_i64(k))
+
+    def step(self):
+        """The step the next drawn plan will use (reads the device word: synchronises)."""
+        return int(self.seed_step[1].item()) & _U64
+
+    def plan_numpy(self):
+        return self.plan.cpu().numpy().view(PLAN_DTYPE).reshape(self.B)
+
+    def records_numpy(self):
+        return self.records.cpu().numpy().view(RECORD_DTYPE).reshape(self.B)
+
+    # ---- drawing ----------------------------------------------------------------------------------------------------
+    def _rows(self, t, what):
+        import torch
+        if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float32 or t.dim() != 2
+                or tuple(t.shape) != (self.B, self.L) or (self.L > 1 and t.stride(1) != 1)):
+            raise GtcrnError(f"{what} must be a ({self.B}, {self.L}) float32 tensor on {self.device} with contiguous rows")
+        stride = t.stride(0) if self.B > 1 else max(t.stride(0), self.L)      # (a one-row tensor may report any stride)
+        if stride < self.L:
+            raise GtcrnError(f"{what}: rows overlap (stride {stride} < {self.L})")
+        return t, stride
+
+    def draw_plan(self, clips=None, advance=True):
+        """Fills ``self.plan`` for the current (seed, step) and, with advance, moves the step word on by one.  clips: an
+        int32 device tensor of B clip ids (e.g. a slice of ``torch.randperm(n, device=...)``: an epoch without
+        replacement) instead of drawn ones."""
+        import torch
+        if clips is not None and (not isinstance(clips, torch.Tensor) or clips.device != self.device or clips.dtype != torch.int32
+                                  or clips.dim() != 1 or clips.numel() != self.B or not clips.is_contiguous()):
+            raise GtcrnError(f"clips must be a contiguous int32 tensor of {self.B} ids on {self.device}")
+        nz = self.noise
+        with torch.cuda.device(self.device):
+            _check(lib().gtcrn_batch_plan(
+                self.speech.offsets.data_ptr(), self.speech.n, nz.offsets.data_ptr() if nz is not None else None,
+                nz.n if nz is not None else 0, self.B, self.L, self.item0, self.granule, self.snr_db[0], self.snr_db[1],
+                self.level_db[0], self.level_db[1], clips.data_ptr() if clips is not None else None,
+                self.seed_step.data_ptr(), int(bool(advance)), self.plan.data_ptr(), _stream_ptr()))
+        return self.plan
+
+    def draw(self, clips=None, plan=None, out=None, passes=7):
+        """-> (noisy, clean), (B, L) float32: ``self.noisy`` / ``self.clean`` or the pair given as ``out`` (row strides
+        >= L).  plan: a (B, 8) int32 device tensor of gtcrn_batch_item rows to use instead of drawing one (the step word
+        then stays).  Asynchronous on the current stream, allocates nothing, capturable.  passes: measurement hook of
+        the mix form (gtcrn_batch_mix)."""
+        import torch
+        if plan is None:
+            p = self.draw_plan(clips)
+        else:
+            if clips is not None:
+                raise GtcrnError("give clips= or plan=, not both")
+            p = plan
+            if (not isinstance(p, torch.Tensor) or p.device != self.device or p.dtype != torch.int32
+                    or tuple(p.shape) != (self.B, 8) or not p.is_contiguous()):
+                raise GtcrnError(f"plan must be a contiguous ({self.B}, 8) int32 tensor on {self.device}")
+        noisy, clean = (self.noisy, self.clean) if out is None else out
+        (noisy, ns), (clean, cs) = self._rows(noisy, "noisy"), self._rows(clean, "clean")
+        sp = self.speech
+        with torch.cuda.device(self.device):
+            if self.noise is not None:
+                nz = self.noise
+                _check(lib().gtcrn_batch_mix(sp.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n, nz.pcm.data_ptr(), nz.offsets.data_ptr(),
+                                             nz.n, p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
+                                             self.records.data_ptr(), self._ws.data_ptr(), int(passes), _stream_ptr()))
+            else:
+                _check(lib().gtcrn_batch_pairs(sp.pcm.data_ptr(), self.paired_clean.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n,
+                                               p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
+                                               _stream_ptr()))
+        return noisy, clean

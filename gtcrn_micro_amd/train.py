@@ -306,6 +306,24 @@ def train_step(model, optimizer, scheduler, loss_func, noisy, clean, clip_grad_n
     return loss.detach(), gn
 
 
+def resident_epoch(source, steps, model, optimizer, scheduler, loss_func, clip_grad_norm_value=3.0, world_size=1, window=None,
+                   clips=None, stats=None):
+    """``steps`` iterations of Trainer._train_epoch (train.py:244-288) fed from a resident corpus instead of a DataLoader:
+    ``source.draw()`` (``data.BatchSource``: a batch cut, and with a noise corpus mixed, on the device) and ``train_step``,
+    nothing else.  clips (optional): an int32 device tensor of at least steps * B clip ids, sliced per step into
+    ``draw(clips=...)`` -- the reference's per-epoch subset (dataloader.py:108-111) is ``torch.randperm(n, device=...)[:num]``;
+    without it clips are drawn with replacement.  Returns (losses, grad_norms), (steps,) device tensors; no host
+    synchronisation inside the loop."""
+    losses, norms = [], []
+    B = source.B
+    for k in range(int(steps)):
+        noisy, clean = source.draw(clips=None if clips is None else clips[k * B:(k + 1) * B])
+        loss, gn = train_step(model, optimizer, scheduler, loss_func, noisy, clean, clip_grad_norm_value, world_size, window, stats)
+        losses.append(loss)
+        norms.append(gn.detach() if isinstance(gn, torch.Tensor) else torch.as_tensor(gn, device=loss.device))
+    return torch.stack(losses), torch.stack(norms)
+
+
 def save_checkpoint(path, model, optimizer, scheduler, epoch):
     """The reference's checkpoint dict (train.py:200-216): {"epoch", "optimizer", "scheduler", "model"}, with the
     model's 388-key state_dict on the CPU (DDP's wrapper is peeled like ``self.model.module`` there), so a

@@ -845,6 +845,67 @@ long gtcrn_score_debug(gtcrn_scorer *s, int which, int b, float *d_dst, long cap
 int gtcrn_score_timing(gtcrn_scorer *s, int on);
 int gtcrn_score_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap, float *ms);
 
+/* ---- training batches from a resident corpus ---------------------------------------------------------------------------
+ * Replaces DNS3Dataset.__getitem__ + DataLoader + .to(device) (dataloader.py:113-170, train.py:244-250): the training set
+ * lives in device memory as int16 and a batch is cut (and, optionally, mixed) where it lies.  No handle, no host state.
+ *
+ * Corpus: two caller-owned device buffers.  pcm: int16, all clips back to back, no alignment or padding between them.
+ * offsets: int64 [n + 1], clip c = pcm[offsets[c] .. offsets[c + 1]).  Every clip holds 1 .. 2^31 - 1 samples, n < 2^31; the
+ * total is unbounded (pcm is indexed with 64 bits).  16 kHz mono is assumed, nothing here looks at a rate.
+ *
+ * Plan: one 32-byte gtcrn_batch_item per row of the batch, drawn by gtcrn_batch_plan or written by the caller.
+ *   Philox4x32-10, key = (seed_lo, seed_hi), counter = (uint32(item0 + b), step_lo, step_hi, k): k = 0 gives r0..r3, k = 1
+ *   gives q0..q3.  mulhi(r, K) = (uint64(r) * K) >> 32.
+ *     sclip  = d_clips[b] if d_clips, else mulhi(r0, n_speech)          (a d_clips entry outside 0 .. n - 1 is clamped)
+ *     Ks     = max(1, (len_s - L) / granule + 1) by integer division, 1 when len_s < L;  sstart = granule * mulhi(r1, Ks)
+ *     nclip  = mulhi(r2, n_noise);  nstart = mulhi(r3, len_n)           (both 0 without a noise table)
+ *     u(q)   = float(q >> 8) * 2^-24 (exact);  snr_db = lo + (hi - lo) * u(q0), lvl_db likewise from q1: float, every
+ *              operation rounded once
+ *     snr_amp = float(pow(10.0, -double(snr_db) / 20));  lvl_amp = float(pow(10.0, double(lvl_db) / 20))
+ *   d_seed_step: two uint64 on the device, {seed, step}; a batch is a pure function of (seed, step, item0 + b).  item0 is
+ *   the first global row of this rank (rank * B): ranks then cut one global batch, whatever the world size.  granule = 1:
+ *   sample-exact starts; 16000: the reference's whole-second random_start (dataloader.py:137) on the clip's true length.
+ *   advance != 0: a one-thread launch after the plan's adds 1 to step, in stream order.  gtcrn_batch_plan_host is the same
+ *   function body on host pointers (it never advances).
+ *
+ * gtcrn_batch_pairs (the reference's loader; two corpora under ONE offsets table): noisy[b][i] =
+ *   float(pcm_noisy[offsets[sclip] + sstart + i]) / 32768 where sstart + i < len, else 0; clean alike.  One launch.
+ *
+ * gtcrn_batch_mix (dynamic mixing), per row, s_i the speech window (0 past the clip's end), n_i = noise[(nstart + i) mod len_n]:
+ *   Ss = sum s_i^2, Sn = sum n_i^2, Ssn = sum s_i n_i as 64-bit integers over the int16 values (exact, order-free).
+ *   gn = 0 and flag 1 if Sn == 0; else 1 and flag 2 if Ss == 0; else float(sqrt(double(Ss) / double(Sn)) * double(snr_amp)).
+ *   sf_i = float(s_i) / 32768, nf_i = float(n_i) / 32768;  m_i = sf_i + (gn * nf_i): a rounded multiply, a rounded add, NO fma.
+ *   g = double(gn);  Sm = double(Ss) + g * (2.0 * double(Ssn) + g * double(Sn)), clamped at 0;  peak = max |m_i| (float).
+ *   G = 1 and flag 4 if Sm == 0; else rms = sqrt(Sm / L) / 32768, G = double(lvl_amp) / rms, and if double(peak) * G > 0.99
+ *   then G = 0.99 / double(peak), flag 8.  Gf = float(G);  noisy[b][i] = Gf * m_i, clean[b][i] = Gf * sf_i.
+ *   d_records[b] = {Ss, Sn, Ssn, gn, Gf, peak, flags}.  Given a plan the output is defined bit for bit.
+ *   Three launches over (row, chunk) grids: integer partial sums, peak, write; d_workspace (16-byte aligned,
+ *   gtcrn_batch_workspace_bytes(B, L)) holds the partials.  passes = 7 is a draw; a subset (1 sums, 2 peak, 4 write) repeats
+ *   single launches on a workspace a full draw has filled (tools/batch_bench.py times them).
+ *   A plan entry outside its table is clamped into it (sclip, nclip, nstart; sstart < 0 counts as 0): a wrong plan gives
+ *   wrong audio, never an access outside pcm.
+ *
+ * Output rows are float32 with noisy_stride / clean_stride >= L floats between them.  Everything is asynchronous on `stream`,
+ * allocates nothing and is capturable.  B <= 0, L <= 0 or L >= 2^31, an empty corpus, a null table or buffer, granule < 1,
+ * hi < lo and a stride below L return GTCRN_ERR_ARG before anything is enqueued.  Out of scope: room impulse responses,
+ * active-speech levels (a VAD), other sample rates, float corpora, streaming a corpus larger than device memory from disk. */
+typedef struct { int sclip, sstart, nclip, nstart; float snr_db, snr_amp, lvl_db, lvl_amp; } gtcrn_batch_item;   /* 32 bytes */
+typedef struct { long long Ss, Sn, Ssn; float gn, Gf, peak; int flags; } gtcrn_batch_record;                   /* 40 bytes */
+int gtcrn_batch_plan(const long long *d_speech_offsets, int n_speech, const long long *d_noise_offsets, int n_noise, int B,
+                     long L, long item0, int granule, float snr_lo, float snr_hi, float lvl_lo, float lvl_hi,
+                     const int *d_clips, unsigned long long *d_seed_step, int advance, gtcrn_batch_item *d_plan, void *stream);
+int gtcrn_batch_plan_host(const long long *h_speech_offsets, int n_speech, const long long *h_noise_offsets, int n_noise, int B,
+                          long L, long item0, int granule, float snr_lo, float snr_hi, float lvl_lo, float lvl_hi,
+                          const int *h_clips, const unsigned long long *h_seed_step, gtcrn_batch_item *h_plan);
+size_t gtcrn_batch_workspace_bytes(int B, long L);   /* 0 (and GTCRN_ERR_ARG recorded) for a bad shape */
+int gtcrn_batch_pairs(const short *d_noisy_pcm, const short *d_clean_pcm, const long long *d_offsets, int n,
+                      const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy, long noisy_stride, float *d_clean,
+                      long clean_stride, void *stream);
+int gtcrn_batch_mix(const short *d_speech_pcm, const long long *d_speech_offsets, int n_speech, const short *d_noise_pcm,
+                    const long long *d_noise_offsets, int n_noise, const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy,
+                    long noisy_stride, float *d_clean, long clean_stride, gtcrn_batch_record *d_records, void *d_workspace,
+                    int passes, void *stream);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
