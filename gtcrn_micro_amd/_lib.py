@@ -233,6 +233,18 @@ def lib():
         L.gtcrn_batch_workspace_bytes.argtypes = [ci, cl]
         L.gtcrn_batch_pairs.argtypes = [_vp, _vp, _vp, ci, _vp, ci, cl, _vp, cl, _vp, cl, _vp]
         L.gtcrn_batch_mix.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, ci, cl, _vp, cl, _vp, cl, _vp, _vp, ci, _vp]
+    # reverberant speech for those batches (an earlier library has none of these: data.RirBank then fails at its creation)
+    if hasattr(L, "gtcrn_batch_reverb"):
+        L.gtcrn_batch_reverb_plan.argtypes = [ci, cf, ci, cl, _vp, _vp, _vp]
+        L.gtcrn_batch_reverb_plan_host.argtypes = [ci, cf, ci, cl, _vp, _vp]
+        L.gtcrn_batch_reverb_table_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_reverb_table_bytes.argtypes = [_vp, ci]
+        L.gtcrn_batch_reverb_prepare.argtypes = [_vp, _vp, ci, _vp, ctypes.c_size_t, _vp]
+        L.gtcrn_batch_reverb_workspace_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_reverb_workspace_bytes.argtypes = [ci, cl]
+        L.gtcrn_batch_reverb.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, ctypes.c_size_t, _vp, _vp, ci, cl, _vp, cl, _vp, _vp,
+                                         _vp, _vp, ci, _vp]
+        L.gtcrn_selftest_mfma_i8.argtypes = [ci]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L
@@ -1969,6 +1981,11 @@ def stream_streams_per_workgroup(nstreams):
 
 def selftest_mfma(device=0):
     _check(lib().gtcrn_selftest_mfma(int(device)))
+
+
+def selftest_mfma_i8(device=0):
+    """The lane maps of v_mfma_i32_16x16x64_i8 that the reverb convolution's matrix form relies on (exact integer data)."""
+    _check(lib().gtcrn_selftest_mfma_i8(int(device)))
 
 
 def selftest_split3(x, A=None, B=None, device=0):

@@ -6,8 +6,13 @@ set is held as int16 on the GPU (the reference's 180 000 pairs of 10 s are 115 G
 ``BatchSource.draw()`` cuts -- and, with a noise corpus, mixes -- a batch where it lies, on the current stream, inside a
 captured graph if the caller wants.  Nothing here falls back to the CPU; the arithmetic is csrc/batch.hip.
 
-Out of scope: room impulse responses, active-speech levels (a VAD), sample rates other than 16 kHz, float corpora, and
-streaming a corpus larger than device memory from disk.
+With a ``RirBank`` (``rirs=``, ``p_reverb=``) a drawn share of the rows is convolved with a room impulse response before
+the mix -- the DNS noisy files were synthesised from reverberant speech -- in exact integer arithmetic (csrc/reverb.hip;
+"reverberant speech: exact RIR convolution" in the header).
+
+Out of scope: active-speech levels (a VAD), sample rates other than 16 kHz, float corpora, streaming a corpus larger than
+device memory from disk; for the reverberation: early-reflection or dry targets, responses longer than 16384 taps, and
+multichannel responses.
 """
 import numpy as np
 
@@ -18,6 +23,10 @@ PLAN_DTYPE = np.dtype([("sclip", "<i4"), ("sstart", "<i4"), ("nclip", "<i4"), ("
 RECORD_DTYPE = np.dtype([("Ss", "<i8"), ("Sn", "<i8"), ("Ssn", "<i8"), ("gn", "<f4"), ("Gf", "<f4"), ("peak", "<f4"),
                          ("flags", "<i4")])
 FLAG_NOISE_ZERO, FLAG_SPEECH_ZERO, FLAG_MIX_ZERO, FLAG_LIMITED = 1, 2, 4, 8
+REVERB_PLAN_DTYPE = np.dtype([("rir", "<i4"), ("reserved", "<i4")])
+REVERB_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("reserved", "<i4")])
+REVERB_MAX_TAPS = 16384        # GTCRN_REVERB_MAX_TAPS
+REVERB_TAP_MAX = 32639         # GTCRN_REVERB_TAP_MAX
 _U64 = (1 << 64) - 1
 
 
@@ -57,6 +66,37 @@ def plan_host(speech_offsets, noise_offsets, B, L, seed, step, item0=0, granule=
         int(item0), int(granule), float(snr_db[0]), float(snr_db[1]), float(level_db[0]), float(level_db[1]),
         None if cl is None else cl.ctypes.data, ss.ctypes.data, plan.ctypes.data if plan.size else None))
     return plan
+
+
+def _reverb_lib():
+    L = _batch_lib()
+    if not hasattr(L, "gtcrn_batch_reverb"):
+        raise GtcrnError("this library has no reverberation (gtcrn_batch_reverb*)")
+    return L
+
+
+def reverb_plan_host(n_rir, p_reverb, B, seed, step, item0=0):
+    """gtcrn_batch_reverb_plan_host: the reverb plan the device would draw for (seed, step), computed on the host.
+    Returns a REVERB_PLAN_DTYPE array of B items (rir = -1: the row stays dry)."""
+    ss = np.array([int(seed) & _U64, int(step) & _U64], np.uint64)
+    plan = np.zeros(max(int(B), 0), REVERB_PLAN_DTYPE)
+    _check(_reverb_lib().gtcrn_batch_reverb_plan_host(int(n_rir), float(p_reverb), int(B), int(item0), ss.ctypes.data,
+                                                      plan.ctypes.data if plan.size else None))
+    return plan
+
+
+def reverb_plan_to_device(plan, device):
+    """A REVERB_PLAN_DTYPE array -> the (B, 2) int32 device tensor ``BatchSource.draw(reverb_plan=...)`` takes."""
+    import torch
+    p = np.ascontiguousarray(plan, REVERB_PLAN_DTYPE)
+    return torch.from_numpy(p.view(np.int32).reshape(p.size, 2).copy()).to(device)
+
+
+def reverb_workspace_bytes(B, L):
+    n = int(_reverb_lib().gtcrn_batch_reverb_workspace_bytes(int(B), int(L)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
 
 
 def plan_to_device(plan, device):
@@ -135,6 +175,124 @@ class Corpus:
         return cls(torch.from_numpy(pcm).to(device), torch.from_numpy(off).to(device))
 
 
+def quantize_rirs(arrays, normalize="peak", trim_direct=True):
+    """The host side of ``RirBank.from_arrays``: a list of 1-D responses -> a list of int16 Q15 arrays inside
+    +-REVERB_TAP_MAX.  An int16 array is Q15 already and is only trimmed and checked.  A float array is scaled first:
+    normalize="peak": its largest |tap| becomes REVERB_TAP_MAX / 32768 (0.996: a direct path of all but unit gain);
+    normalize="energy": its taps' sum of squares becomes 1, or as near to it as the peak bound allows; then
+    tap = rint(32768 * h), round half to even.  trim_direct: the taps before the direct path -- the first tap of the
+    largest magnitude -- are dropped, so that a wet row is not delayed against its noise by the measurement's lead-in."""
+    if normalize not in ("peak", "energy"):
+        raise GtcrnError('normalize is "peak" or "energy"')
+    out = []
+    for k, a in enumerate(arrays):
+        a = np.asarray(a)
+        if a.ndim != 1 or a.size < 1:
+            raise GtcrnError(f"response {k}: a 1-D array of at least one tap")
+        if a.dtype == np.int16:
+            q = a.astype(np.int64)
+        elif a.dtype.kind == "f":
+            h = a.astype(np.float64)
+            if not np.isfinite(h).all():
+                raise GtcrnError(f"response {k}: not finite")
+            peak = np.abs(h).max()
+            if peak == 0.0:
+                raise GtcrnError(f"response {k}: all taps are zero")
+            top = REVERB_TAP_MAX / 32768.0
+            g = top / peak
+            if normalize == "energy":
+                g = min(g, 1.0 / np.sqrt((h * h).sum()))
+            q = np.clip(np.rint(h * g * 32768.0), -REVERB_TAP_MAX, REVERB_TAP_MAX).astype(np.int64)
+        else:
+            raise GtcrnError(f"response {k}: float or int16 taps, got {a.dtype}")
+        if trim_direct:
+            q = q[int(np.argmax(np.abs(q))):]
+        if q.size > REVERB_MAX_TAPS:
+            raise GtcrnError(f"response {k}: {q.size} taps; at most {REVERB_MAX_TAPS} (1.024 s)")
+        if np.abs(q).max() > REVERB_TAP_MAX:
+            raise GtcrnError(f"response {k}: an int16 tap outside +-{REVERB_TAP_MAX}")
+        out.append(q.astype(np.int16))
+    if not out:
+        raise GtcrnError("the bank is empty")
+    return out
+
+
+class RirBank:
+    """Room impulse responses in device memory, shaped like a corpus: ``taps`` (int16 Q15, 1-D, the responses back to
+    back) and ``offsets`` (int64, n + 1), plus ``table``, the derived tap table of the convolution's matrix form
+    (gtcrn_batch_reverb_prepare, filled here, once).  Every response holds 1 .. 16384 taps inside +-32639; checked here,
+    once (one synchronisation)."""
+
+    def __init__(self, taps, offsets):
+        import torch
+        L = _reverb_lib()
+        if not isinstance(taps, torch.Tensor) or not taps.is_cuda or taps.dtype != torch.int16 or taps.dim() != 1 or not taps.is_contiguous():
+            raise GtcrnError("taps must be a contiguous 1-D int16 CUDA (ROCm) tensor")
+        if (not isinstance(offsets, torch.Tensor) or offsets.device != taps.device or offsets.dtype != torch.int64
+                or offsets.dim() != 1 or not offsets.is_contiguous()):
+            raise GtcrnError("offsets must be a contiguous 1-D int64 tensor on taps' device")
+        n = offsets.numel() - 1
+        if n < 1:
+            raise GtcrnError("the bank is empty")
+        if n >= 1 << 31:
+            raise GtcrnError("a bank holds fewer than 2^31 responses")
+        off = offsets.cpu().numpy()
+        lens = off[1:] - off[:-1]
+        if int(off[0]) < 0 or int(off[-1]) > taps.numel() or int(lens.min()) < 1 or int(lens.max()) > REVERB_MAX_TAPS:
+            raise GtcrnError(f"offsets must rise by 1 .. {REVERB_MAX_TAPS} taps per response and stay inside taps")
+        used = taps[int(off[0]):int(off[-1])]
+        if int(used.min()) < -REVERB_TAP_MAX or int(used.max()) > REVERB_TAP_MAX:
+            raise GtcrnError(f"every tap must lie in +-{REVERB_TAP_MAX}")
+        self.taps, self.offsets, self.n = taps, offsets, n
+        nbytes = int(L.gtcrn_batch_reverb_table_bytes(off.ctypes.data, n))
+        if nbytes == 0:
+            raise GtcrnError(lib().gtcrn_last_error().decode())
+        self.table = torch.empty(nbytes, device=taps.device, dtype=torch.uint8)
+        with torch.cuda.device(taps.device):
+            _check(L.gtcrn_batch_reverb_prepare(taps.data_ptr(), offsets.data_ptr(), n, self.table.data_ptr(), nbytes, _stream_ptr()))
+
+    @property
+    def device(self):
+        return self.taps.device
+
+    @classmethod
+    def from_tensors(cls, taps, offsets):
+        return cls(taps, offsets)
+
+    @classmethod
+    def from_arrays(cls, arrays, normalize="peak", trim_direct=True, device="cuda"):
+        import torch
+        q = quantize_rirs(arrays, normalize, trim_direct)
+        off = np.zeros(len(q) + 1, np.int64)
+        np.cumsum([a.size for a in q], out=off[1:])
+        return cls(torch.from_numpy(np.concatenate(q)).to(device), torch.from_numpy(off).to(device))
+
+    @classmethod
+    def from_wavs(cls, paths, normalize="peak", trim_direct=True, device="cuda"):
+        """16 kHz mono files, 16-bit PCM or float, each one response."""
+        from scipy.io import wavfile
+        hs = []
+        for p in paths:
+            fs, x = wavfile.read(p, mmap=True)
+            if fs != 16000 or x.ndim != 1:
+                raise GtcrnError(f"{p}: a bank takes 16 kHz mono files, got {fs} Hz, shape {tuple(x.shape)}")
+            hs.append(np.asarray(x, np.float64) / 32768.0 if x.dtype == np.int16 else np.asarray(x))
+        return cls.from_arrays(hs, normalize, trim_direct, device)
+
+    def save(self, prefix):
+        """Writes ``prefix + '.taps.npy'`` and ``prefix + '.offsets.npy'`` (the table is derived again on load)."""
+        np.save(prefix + ".taps.npy", self.taps.cpu().numpy())
+        np.save(prefix + ".offsets.npy", self.offsets.cpu().numpy())
+
+    @classmethod
+    def load(cls, prefix, device="cuda"):
+        import torch
+        taps, off = np.load(prefix + ".taps.npy"), np.load(prefix + ".offsets.npy")
+        if taps.dtype != np.int16 or off.dtype != np.int64 or taps.ndim != 1 or off.ndim != 1:
+            raise GtcrnError(f"{prefix}: not a saved bank (int16 taps, int64 offsets)")
+        return cls(torch.from_numpy(taps).to(device), torch.from_numpy(off).to(device))
+
+
 class BatchSource:
     """Draws (noisy, clean) batches of B rows of L samples from resident corpora.
 
@@ -142,10 +300,14 @@ class BatchSource:
     level from U(level_db) dB RMS re full scale (gtcrn_batch_mix).  ``paired_clean=`` a Corpus under the same offsets
     table as ``speech`` (which is then the noisy side): the reference's loader, exactly (gtcrn_batch_pairs).
     A batch is a pure function of (seed, step, item0 + row); ``item0`` = rank * B makes ranks cut one global batch.
-    granule = 1: sample-exact starts; 16000: the reference's whole-second random_start."""
+    granule = 1: sample-exact starts; 16000: the reference's whole-second random_start.
+    ``rirs=`` a RirBank (mix form only): each row is reverberant with probability ``p_reverb`` -- its speech window, with
+    its true history, convolved with a drawn response (gtcrn_batch_reverb) -- and ``clean`` is then the reverberant
+    speech.  With p_reverb = 0 every draw is bit-identical to the source without ``rirs=``.  ``reverb_form``: gtcrn_batch_reverb's
+    `form` (0: the library chooses; 1 plain, 2 matrix, 3 / 4 matrix with the block pinned: bit-identical, for measurements)."""
 
     def __init__(self, speech, noise=None, paired_clean=None, B=1, L=64000, seed=0, snr_db=(-5.0, 20.0), level_db=(-35.0, -15.0),
-                 granule=1, item0=0):
+                 granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0):
         import torch
         _batch_lib()
         if (noise is None) == (paired_clean is None):
@@ -175,6 +337,26 @@ class BatchSource:
         self.noisy = torch.empty((B, L), device=dev, dtype=torch.float32)
         self.clean = torch.empty((B, L), device=dev, dtype=torch.float32)
         self._ws = torch.empty(workspace_bytes(B, L), device=dev, dtype=torch.uint8) if noise is not None else None
+        self.rirs, self.p_reverb, self.reverb_form = rirs, float(p_reverb), int(reverb_form)
+        if rirs is not None:
+            _reverb_lib()
+            if paired_clean is not None:
+                raise GtcrnError("rirs= goes with noise= (the mix); a paired corpus is what it is")
+            if not isinstance(rirs, RirBank) or rirs.device != dev:
+                raise GtcrnError("rirs must be a data.RirBank on the corpora's device")
+            if not 0.0 <= self.p_reverb <= 1.0:
+                raise GtcrnError("p_reverb must lie in 0 .. 1")
+            if self.reverb_form not in (0, 1, 2, 3, 4):
+                raise GtcrnError("reverb_form is 0 (the library chooses), 1 (plain), 2 (matrix) or 3 / 4 (matrix, block pinned)")
+            self.staged_stride = (L + 7) // 8 * 8                                # rows of whole 16 bytes
+            self.staged = torch.zeros(B * self.staged_stride, device=dev, dtype=torch.int16)
+            self.staged_offsets = torch.zeros(B + 1, device=dev, dtype=torch.int64)
+            self.staged_plan = torch.zeros((B, 8), device=dev, dtype=torch.int32)
+            self.reverb_plan = torch.full((B, 2), -1, device=dev, dtype=torch.int32)   # gtcrn_reverb_item rows
+            self.reverb_records = torch.zeros((B, 4), device=dev, dtype=torch.int32)   # gtcrn_reverb_record rows
+            self._rws = torch.empty(reverb_workspace_bytes(B, L), device=dev, dtype=torch.uint8)
+        elif self.p_reverb != 0.0:
+            raise GtcrnError("p_reverb needs rirs=")
 
     # ---- the step word ----------------------------------------------------------------------------------------------
     def set_step(self, k):
@@ -190,6 +372,13 @@ class BatchSource:
 
     def records_numpy(self):
         return self.records.cpu().numpy().view(RECORD_DTYPE).reshape(self.B)
+
+    def reverb_plan_numpy(self):
+        """The reverb plan of the most recent draw (a source with ``rirs=``)."""
+        return self.reverb_plan.cpu().numpy().view(REVERB_PLAN_DTYPE).reshape(self.B)
+
+    def reverb_records_numpy(self):
+        return self.reverb_records.cpu().numpy().view(REVERB_RECORD_DTYPE).reshape(self.B)
 
     # ---- drawing ----------------------------------------------------------------------------------------------------
     def _rows(self, t, what):
@@ -219,12 +408,32 @@ class BatchSource:
                 self.seed_step.data_ptr(), int(bool(advance)), self.plan.data_ptr(), _stream_ptr()))
         return self.plan
 
-    def draw(self, clips=None, plan=None, out=None, passes=7):
+    def draw_reverb_plan(self):
+        """Fills ``self.reverb_plan`` for the current (seed, step); the step word is read, never moved (so this goes
+        before ``draw_plan``)."""
+        import torch
+        with torch.cuda.device(self.device):
+            _check(lib().gtcrn_batch_reverb_plan(self.rirs.n, self.p_reverb, self.B, self.item0, self.seed_step.data_ptr(),
+                                                 self.reverb_plan.data_ptr(), _stream_ptr()))
+        return self.reverb_plan
+
+    def draw(self, clips=None, plan=None, out=None, passes=7, reverb_plan=None):
         """-> (noisy, clean), (B, L) float32: ``self.noisy`` / ``self.clean`` or the pair given as ``out`` (row strides
         >= L).  plan: a (B, 8) int32 device tensor of gtcrn_batch_item rows to use instead of drawing one (the step word
-        then stays).  Asynchronous on the current stream, allocates nothing, capturable.  passes: measurement hook of
-        the mix form (gtcrn_batch_mix)."""
+        then stays).  reverb_plan (a source with ``rirs=``): a (B, 2) int32 device tensor of gtcrn_reverb_item rows to use
+        instead of drawing one.  Asynchronous on the current stream, allocates nothing, capturable.  passes: measurement
+        hook of the mix form (gtcrn_batch_mix)."""
         import torch
+        rp = None
+        if reverb_plan is not None:
+            if self.rirs is None:
+                raise GtcrnError("reverb_plan= needs a source with rirs=")
+            rp = reverb_plan
+            if (not isinstance(rp, torch.Tensor) or rp.device != self.device or rp.dtype != torch.int32
+                    or tuple(rp.shape) != (self.B, 2) or not rp.is_contiguous()):
+                raise GtcrnError(f"reverb_plan must be a contiguous ({self.B}, 2) int32 tensor on {self.device}")
+        elif self.rirs is not None:
+            rp = self.draw_reverb_plan()                 # before the batch plan: that one moves the step word
         if plan is None:
             p = self.draw_plan(clips)
         else:
@@ -240,7 +449,16 @@ class BatchSource:
         with torch.cuda.device(self.device):
             if self.noise is not None:
                 nz = self.noise
-                _check(lib().gtcrn_batch_mix(sp.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n, nz.pcm.data_ptr(), nz.offsets.data_ptr(),
+                s_pcm, s_off, s_n = sp.pcm, sp.offsets, sp.n
+                if rp is not None:                       # the speech side of the mix becomes the staged corpus
+                    rb = self.rirs
+                    _check(lib().gtcrn_batch_reverb(
+                        sp.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n, rb.taps.data_ptr(), rb.offsets.data_ptr(), rb.n,
+                        rb.table.data_ptr(), rb.table.numel(), p.data_ptr(), rp.data_ptr(), self.B, self.L,
+                        self.staged.data_ptr(), self.staged_stride, self.staged_offsets.data_ptr(), self.staged_plan.data_ptr(),
+                        self.reverb_records.data_ptr(), self._rws.data_ptr(), self.reverb_form, _stream_ptr()))
+                    s_pcm, s_off, s_n, p = self.staged, self.staged_offsets, self.B, self.staged_plan
+                _check(lib().gtcrn_batch_mix(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(), nz.offsets.data_ptr(),
                                              nz.n, p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
                                              self.records.data_ptr(), self._ws.data_ptr(), int(passes), _stream_ptr()))
             else:

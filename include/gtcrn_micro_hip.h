@@ -887,8 +887,9 @@ int gtcrn_score_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap
  *
  * Output rows are float32 with noisy_stride / clean_stride >= L floats between them.  Everything is asynchronous on `stream`,
  * allocates nothing and is capturable.  B <= 0, L <= 0 or L >= 2^31, an empty corpus, a null table or buffer, granule < 1,
- * hi < lo and a stride below L return GTCRN_ERR_ARG before anything is enqueued.  Out of scope: room impulse responses,
- * active-speech levels (a VAD), other sample rates, float corpora, streaming a corpus larger than device memory from disk. */
+ * hi < lo and a stride below L return GTCRN_ERR_ARG before anything is enqueued.  Out of scope: active-speech levels (a VAD),
+ * other sample rates, float corpora, streaming a corpus larger than device memory from disk.  (Room impulse responses: the
+ * next section.) */
 typedef struct { int sclip, sstart, nclip, nstart; float snr_db, snr_amp, lvl_db, lvl_amp; } gtcrn_batch_item;   /* 32 bytes */
 typedef struct { long long Ss, Sn, Ssn; float gn, Gf, peak; int flags; } gtcrn_batch_record;                   /* 40 bytes */
 int gtcrn_batch_plan(const long long *d_speech_offsets, int n_speech, const long long *d_noise_offsets, int n_noise, int B,
@@ -905,6 +906,69 @@ int gtcrn_batch_mix(const short *d_speech_pcm, const long long *d_speech_offsets
                     const long long *d_noise_offsets, int n_noise, const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy,
                     long noisy_stride, float *d_clean, long clean_stride, gtcrn_batch_record *d_records, void *d_workspace,
                     int passes, void *stream);
+
+/* ---- reverberant speech: exact RIR convolution ----------------------------------------------------------------------------
+ * The DNS noisy files the reference trains on were synthesised from REVERBERANT speech; a dynamic mix of dry speech is not
+ * that data.  gtcrn_batch_reverb convolves each row's speech window with a room impulse response before the mix, in exact
+ * integer arithmetic: the result is a function of its inputs, not of a summation order.  Additions only; no handle, no host
+ * state, caller-owned buffers, everything asynchronous on `stream`, capturable, nothing allocated.
+ *
+ * RIR bank: shaped like a corpus.  taps: int16 Q15 (32768 = 1.0), all responses back to back; offsets: int64 [n + 1].  Every
+ * response holds 1 .. GTCRN_REVERB_MAX_TAPS taps (1.024 s) and every tap lies in -GTCRN_REVERB_TAP_MAX .. GTCRN_REVERB_TAP_MAX
+ * (+-32639 = 127 * 256 + 127: both balanced int8 digits of a tap then fit; a tap outside gives wrong audio).  Speech is NOT
+ * restricted: -32768 and 32767 are exact.  A response whose offsets give another length counts as absent (its rows stay dry).
+ *
+ * Reverb plan: one 8-byte gtcrn_reverb_item per row, drawn by gtcrn_batch_reverb_plan or written by the caller; rir < 0: the
+ * row stays dry.  The batch plan's Philox4x32-10, same key and counter, block k = 2 gives t0..t3 (k = 0, 1 are the batch
+ * plan's, so no existing plan changes):  rir = mulhi(t1, n_rir) if u(t0) < p_reverb, else -1; reserved = 0.  p_reverb = 0
+ * never reverberates a row, 1 always does.  The function READS d_seed_step and never advances it: launch it BEFORE
+ * gtcrn_batch_plan in the stream, it then sees the step that plan is about to use.  gtcrn_batch_reverb_plan_host is the same
+ * function body on host pointers.
+ *
+ * gtcrn_batch_reverb, per row b with c = plan[b].sclip, s0 = plan[b].sstart, response h of K taps:
+ *   acc[i] = sum_{k=0}^{K-1} h[k] * x[s0 + i - k],  i = 0 .. L - 1, a 64-bit integer, exact;
+ *   x[j]   = clip c's sample j for 0 <= j < len_c, else 0 (true history before the window; zeros before the clip and behind it);
+ *   wet[i] = clamp((acc[i] + 16384) >> 15, -32768, 32767), an arithmetic shift;  a dry row: wet[i] = x[s0 + i].
+ *   d_staged[b * staged_stride + i] = wet[i] (int16; samples L .. staged_stride - 1 of a row are not touched);
+ *   d_staged_offsets[b] = b * staged_stride for b = 0 .. B (B + 1 entries): with d_staged a corpus of B clips, of which only
+ *   the first L samples are read;  d_staged_plan[b] = d_plan[b] with sclip = b, sstart = 0.  gtcrn_batch_mix then runs
+ *   UNCHANGED on (d_staged, d_staged_offsets, B, d_staged_plan): its clean output is the reverberant speech, the target of a
+ *   model that does not dereverberate.  With every row dry the draw is bit-identical to the draw without this call.
+ *   d_records[b] = {rir (as used: clamped, -1 for a dry row), ntaps, saturated = the number of clamped samples, 0}.
+ *   A plan entry outside its table is clamped into it (sclip, rir > n_rir - 1; sstart < 0 counts as 0): a wrong plan gives wrong
+ *   audio, never an access outside a buffer.  Given the plans the output is defined bit for bit, in both forms:
+ *   form 1, plain: one thread per output sample, the sum as written above.  form 2, matrix: int16 operands as two int8 digits
+ *   (tap = 256 * hi + lo, both in -127 .. 127; sample = 256 * (x >> 8) + ((x & 255) - 128) + 128, zero padding stored as the
+ *   digits of 0, so the + 128 adds 128 * sum(h) per output), digit products on v_mfma_i32_16x16x64_i8 into int32 (below
+ *   2^31 for 16384 + 255 terms), recombined in int64; a workgroup takes 8192 output samples of a row if B rows of such blocks
+ *   make 256 workgroups, else 2048; forms 3 and 4 pin the small and the large block (the A/B switch of tests and
+ *   measurements).  form 0: the library chooses (form 2).  The matrix form reads a table derived from the bank:
+ *   gtcrn_batch_reverb_table_bytes(host offsets, n) bytes, 16-byte aligned, filled once per bank by
+ *   gtcrn_batch_reverb_prepare (16 bytes per tap and digit, taps padded to whole 256); form 1 takes d_table = NULL.  A table of another bank
+ *   gives wrong audio (rows whose entry does not lie inside table_bytes stay dry), never an access outside it.
+ *   d_workspace: gtcrn_batch_reverb_workspace_bytes(B, L) bytes, 4-byte aligned (per-workgroup clamp counts; integers, so the
+ *   total is order-free).  Two launches: the convolution over a (row, block) grid, then records / offsets / plan.
+ * B <= 0, L <= 0 or L >= 2^31, an empty corpus or bank, a null or misaligned buffer, a stride below L, p_reverb outside 0 .. 1,
+ * an unknown form and a matrix form without its table return GTCRN_ERR_ARG before anything is enqueued.  Out of scope:
+ * early-reflection or dry targets (the clean output is the full reverberant speech), responses longer than 16384 taps,
+ * multichannel responses. */
+#define GTCRN_REVERB_MAX_TAPS 16384
+#define GTCRN_REVERB_TAP_MAX 32639
+typedef struct { int rir, reserved; } gtcrn_reverb_item;                        /* 8 bytes */
+typedef struct { int rir, ntaps, saturated, reserved; } gtcrn_reverb_record;    /* 16 bytes */
+int gtcrn_batch_reverb_plan(int n_rir, float p_reverb, int B, long item0, const unsigned long long *d_seed_step,
+                            gtcrn_reverb_item *d_rplan, void *stream);
+int gtcrn_batch_reverb_plan_host(int n_rir, float p_reverb, int B, long item0, const unsigned long long *h_seed_step,
+                                 gtcrn_reverb_item *h_rplan);
+size_t gtcrn_batch_reverb_table_bytes(const long long *h_rir_offsets, int n_rir);   /* 0 (and GTCRN_ERR_ARG recorded) for a bad bank */
+int gtcrn_batch_reverb_prepare(const short *d_taps, const long long *d_rir_offsets, int n_rir, void *d_table, size_t table_bytes,
+                               void *stream);
+size_t gtcrn_batch_reverb_workspace_bytes(int B, long L);                           /* 0 (and GTCRN_ERR_ARG recorded) for a bad shape */
+int gtcrn_batch_reverb(const short *d_speech_pcm, const long long *d_speech_offsets, int n_speech, const short *d_taps,
+                       const long long *d_rir_offsets, int n_rir, const void *d_table, size_t table_bytes,
+                       const gtcrn_batch_item *d_plan, const gtcrn_reverb_item *d_rplan, int B, long L, short *d_staged,
+                       long staged_stride, long long *d_staged_offsets, gtcrn_batch_item *d_staged_plan,
+                       gtcrn_reverb_record *d_records, void *d_workspace, int form, void *stream);
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
@@ -976,6 +1040,9 @@ long gtcrn_debug_stamps(gtcrn_model *m, int kernel, unsigned long long *h_dst, l
 int gtcrn_pcm16_to_f32(int device, const short *d_pcm, float *d_wave, long n, void *stream);
 int gtcrn_f32_to_pcm16(int device, const float *d_wave, short *d_pcm, long n, void *stream);
 int gtcrn_selftest_mfma(int device);
+/* The same for v_mfma_i32_16x16x64_i8, the instruction of gtcrn_batch_reverb's matrix form: asymmetric full-range int8
+ * operands and a non-zero C, every element of D compared with the integer product.  0 = as assumed. */
+int gtcrn_selftest_mfma_i8(int device);
 /* The exact three-way bf16 split the dense 3x3 runs on (kernels.hip split3 / join3 / split_mm6), on caller-chosen
  * values: h_x[n] (n a multiple of 4) -> h_planes[3][n] (hi, mid, lo as floats) and h_joined[n] (= h_x bit for bit
  * wherever all three planes are normal numbers); optionally h_A (16x32, row major) * h_B (32x16) -> h_D (16x16)
