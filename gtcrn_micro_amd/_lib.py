@@ -245,6 +245,16 @@ def lib():
         L.gtcrn_batch_reverb.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, ctypes.c_size_t, _vp, _vp, ci, cl, _vp, cl, _vp, _vp,
                                          _vp, _vp, ci, _vp]
         L.gtcrn_selftest_mfma_i8.argtypes = [ci]
+    # dereverberation targets: the split convolution and the mix with a target corpus
+    if hasattr(L, "gtcrn_batch_reverb_split"):
+        L.gtcrn_batch_reverb_split_table_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_reverb_split_table_bytes.argtypes = [_vp, _vp, ci]
+        L.gtcrn_batch_reverb_split_prepare.argtypes = [_vp, _vp, _vp, ci, _vp, ctypes.c_size_t, _vp]
+        L.gtcrn_batch_reverb_split_workspace_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_reverb_split_workspace_bytes.argtypes = [ci, cl]
+        L.gtcrn_batch_reverb_split.argtypes = [_vp, _vp, ci, _vp, _vp, _vp, ci, _vp, ctypes.c_size_t, _vp, _vp, ci, cl, _vp, _vp, cl,
+                                               _vp, _vp, _vp, _vp, ci, _vp]
+        L.gtcrn_batch_mix_target.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, _vp, ci, cl, _vp, cl, _vp, cl, _vp, _vp, ci, _vp]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

@@ -115,5 +115,8 @@ int launch_plan(const PlanArgs& a, unsigned long long* d_seed_step, int advance,
 int launch_pairs(const DrawArgs& d, hipStream_t s);
 // The three launches of a mix draw, in stream order: passes = 7; a subset (1 sums, 2 peak, 4 write) launches only those.
 int launch_mix(const DrawArgs& d, int passes, hipStream_t s);
+// The same with the clean rows cut from d_target, a corpus under the speech offsets table: passes 1 and 2 are launch_mix's
+// kernels, pass 3 is a write kernel of its own.
+int launch_mix_target(const DrawArgs& d, const short* d_target, int passes, hipStream_t s);
 
 }  // namespace gtb

@@ -285,6 +285,49 @@ __global__ __launch_bounds__(THREADS) void k_batch_write(DrawArgs d, int chunks,
     }
 }
 
+// pass 3 of the mix with a target: k_batch_write, but the clean row is the gained window of a target corpus that lies under
+// the speech offsets table (three 16-byte loads and four 16-byte stores per 8 samples).  Sums, gains, peak, record and noisy
+// are the speech side's: with target == the speech corpus this writes what k_batch_write writes, bit for bit.
+__global__ __launch_bounds__(THREADS) void k_batch_write_target(DrawArgs d, const short* target, int chunks, long ch, bool vec) {
+    __shared__ long long sm[THREADS / 64];
+    __shared__ float smf[THREADS / 64];
+    const int b = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const View v = view_of(d, b, false);
+    const short* tg = target + (v.s - d.a.pcm);        // the same clip of the parallel corpus
+    const Sums s = item_sums(d.sums + (long)b * chunks * 3, chunks, sm);
+    const float peak = block_all<float, true>((int)threadIdx.x < chunks ? d.peaks[(long)b * chunks + threadIdx.x] : 0.0f, smf);
+    int flags = 0;
+    const float gn = noise_gain(s, v.snr_amp, &flags);
+    const float Gf = level_gain(s, gn, peak, v.lvl_amp, d.L, &flags);
+    if (c == 0 && threadIdx.x == 0) {
+        Record r;
+        r.Ss = s.ss; r.Sn = s.sn; r.Ssn = s.ssn;
+        r.gn = gn; r.Gf = Gf; r.peak = peak; r.flags = flags;
+        d.rec[b] = r;
+    }
+    float* noisy = d.noisy + (long)b * d.noisy_stride;
+    float* clean = d.clean + (long)b * d.clean_stride;
+    const long lo = (long)c * ch, hi = lo + ch < d.L ? lo + ch : d.L;
+    for (long i0 = lo + (long)threadIdx.x * GROUP; i0 < hi; i0 += TILE) {
+        const int cnt = hi - i0 < GROUP ? (int)(hi - i0) : GROUP;
+        int x[GROUP], z[GROUP], t[GROUP];
+        load_clip8(v.s, v.len_s, v.sstart + i0, cnt, x);
+        load_wrap8(v.n, v.len_n, wrap_index(v, i0), cnt, z);
+        load_clip8(tg, v.len_s, v.sstart + i0, cnt, t);
+        float yn[GROUP], yc[GROUP];
+#pragma unroll
+        for (int k = 0; k < GROUP; ++k) {
+            const float sf = (float)x[k] * kScale;
+            const float gz = gn * ((float)z[k] * kScale);
+            const float m = sf + gz;
+            yn[k] = Gf * m;
+            yc[k] = Gf * ((float)t[k] * kScale);
+        }
+        store8(noisy, i0, cnt, vec, yn);
+        store8(clean, i0, cnt, vec, yc);
+    }
+}
+
 bool rows_take_16_bytes(const DrawArgs& d) {
     return (reinterpret_cast<uintptr_t>(d.noisy) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.clean) & 15) == 0 &&
            d.noisy_stride % 4 == 0 && d.clean_stride % 4 == 0;
@@ -311,6 +354,16 @@ int launch_mix(const DrawArgs& d, int passes, hipStream_t s) {
     if (passes & 1) hipLaunchKernelGGL(k_batch_sums, grid, block, 0, s, d, chunks, ch);
     if (passes & 2) hipLaunchKernelGGL(k_batch_peak, grid, block, 0, s, d, chunks, ch);
     if (passes & 4) hipLaunchKernelGGL(k_batch_write, grid, block, 0, s, d, chunks, ch, rows_take_16_bytes(d));
+    return (int)hipGetLastError();
+}
+
+int launch_mix_target(const DrawArgs& d, const short* d_target, int passes, hipStream_t s) {
+    const int chunks = chunks_of(d.L);
+    const long ch = chunk_samples(d.L);
+    const dim3 grid((unsigned)((long)d.B * chunks)), block(THREADS);
+    if (passes & 1) hipLaunchKernelGGL(k_batch_sums, grid, block, 0, s, d, chunks, ch);
+    if (passes & 2) hipLaunchKernelGGL(k_batch_peak, grid, block, 0, s, d, chunks, ch);
+    if (passes & 4) hipLaunchKernelGGL(k_batch_write_target, grid, block, 0, s, d, d_target, chunks, ch, rows_take_16_bytes(d));
     return (int)hipGetLastError();
 }
 

@@ -111,16 +111,19 @@ int gtcrn_batch_pairs(const short* d_noisy_pcm, const short* d_clean_pcm, const 
     return 0;
 }
 
-int gtcrn_batch_mix(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_noise_pcm,
-                    const long long* d_noise_offsets, int n_noise, const gtcrn_batch_item* d_plan, int B, long L, float* d_noisy,
-                    long noisy_stride, float* d_clean, long clean_stride, gtcrn_batch_record* d_records, void* d_workspace,
-                    int passes, void* stream) {
-    const std::string w("gtcrn_batch_mix");
+namespace {
+
+// gtcrn_batch_mix (d_target_pcm null) and gtcrn_batch_mix_target: one set of checks, two launch sequences
+int mix_call(const std::string& w, const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech,
+             const short* d_noise_pcm, const long long* d_noise_offsets, int n_noise, const short* d_target_pcm, bool with_target,
+             const gtcrn_batch_item* d_plan, int B, long L, float* d_noisy, long noisy_stride, float* d_clean, long clean_stride,
+             gtcrn_batch_record* d_records, void* d_workspace, int passes, void* stream) {
     gtb::DrawArgs d;
     const int rc = draw_args(w, d_speech_pcm, d_noise_pcm, d_speech_offsets, n_speech, d_noise_offsets, n_noise, d_plan, B, L, d_noisy,
                              noisy_stride, d_clean, clean_stride, &d);
     if (rc != 0) return rc;
-    if (!d_records || !d_workspace) return bfail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (!d_records || !d_workspace || (with_target && !d_target_pcm)) return bfail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (with_target && (reinterpret_cast<uintptr_t>(d_target_pcm) & 1)) return bfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
     if ((reinterpret_cast<uintptr_t>(d_records) & 7) || (reinterpret_cast<uintptr_t>(d_workspace) & 15))
         return bfail(GTCRN_ERR_ARG, w + ": the records must be 8-byte, the workspace 16-byte aligned");
     if (passes < 1 || passes > 7) return bfail(GTCRN_ERR_ARG, w + ": `passes` is a sum of 1 (sums), 2 (peak) and 4 (write); 7 is a draw");
@@ -129,7 +132,27 @@ int gtcrn_batch_mix(const short* d_speech_pcm, const long long* d_speech_offsets
     d.rec = reinterpret_cast<gtb::Record*>(d_records);
     d.sums = static_cast<long long*>(d_workspace);
     d.peaks = reinterpret_cast<float*>(d.sums + 3 * cells);
-    const int e = gtb::launch_mix(d, passes, static_cast<hipStream_t>(stream));
+    const int e = with_target ? gtb::launch_mix_target(d, d_target_pcm, passes, static_cast<hipStream_t>(stream))
+                              : gtb::launch_mix(d, passes, static_cast<hipStream_t>(stream));
     if (e != 0) return bfail(GTCRN_ERR_HIP, w + ": " + hipGetErrorString(static_cast<hipError_t>(e)));
     return 0;
+}
+
+}  // namespace
+
+int gtcrn_batch_mix(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_noise_pcm,
+                    const long long* d_noise_offsets, int n_noise, const gtcrn_batch_item* d_plan, int B, long L, float* d_noisy,
+                    long noisy_stride, float* d_clean, long clean_stride, gtcrn_batch_record* d_records, void* d_workspace,
+                    int passes, void* stream) {
+    return mix_call("gtcrn_batch_mix", d_speech_pcm, d_speech_offsets, n_speech, d_noise_pcm, d_noise_offsets, n_noise, nullptr, false,
+                    d_plan, B, L, d_noisy, noisy_stride, d_clean, clean_stride, d_records, d_workspace, passes, stream);
+}
+
+int gtcrn_batch_mix_target(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_noise_pcm,
+                           const long long* d_noise_offsets, int n_noise, const short* d_target_pcm, const gtcrn_batch_item* d_plan,
+                           int B, long L, float* d_noisy, long noisy_stride, float* d_clean, long clean_stride,
+                           gtcrn_batch_record* d_records, void* d_workspace, int passes, void* stream) {
+    return mix_call("gtcrn_batch_mix_target", d_speech_pcm, d_speech_offsets, n_speech, d_noise_pcm, d_noise_offsets, n_noise,
+                    d_target_pcm, true, d_plan, B, L, d_noisy, noisy_stride, d_clean, clean_stride, d_records, d_workspace, passes,
+                    stream);
 }

@@ -1,7 +1,8 @@
 // reverb.h -- reverberant speech for resident-corpus batches ("reverberant speech: exact RIR convolution" in
 // include/gtcrn_micro_hip.h): the reverb plan's arithmetic as one __host__ __device__ body
 // (reverb.hip runs it per row on the device, reverb_host.cpp on the host), the digit scheme and the table geometry both
-// files share, and the launch interface of reverb.hip.
+// files share, and the launch interface of reverb.hip; behind them the geometry of the split table and the launch interface
+// of the split convolution ("dereverberation targets: early or direct clean").
 #pragma once
 #include "batch.h"
 
@@ -70,7 +71,30 @@ struct ReverbArgs {
     int blocks = 0;
 };
 
+// ---- the split convolution ("dereverberation targets: early or direct clean" in the header) ----------
+struct SRecord { int rir, ntaps, saturated, split, target_saturated, r0, r1, r2; };   // == gtcrn_reverb_split_record, 32 bytes
+
+// Split of a response of K taps (K >= 1): any value is clamped into 1 .. K.
+__host__ __device__ inline int split_of(int e, int K) { return e < 1 ? 1 : e > K ? K : e; }
+// The split table of a response: its early segment, taps 0 .. E - 1 in the tile format above (groups_of(E) groups), then its
+// rest segment, groups rest_first(E) .. groups_of(K) - 1 of the response with the taps below E stored as zero -- absent when
+// E == K.  Both are whole fours of 64-tap chunks, and they are contiguous.
+__host__ __device__ inline int rest_first(int E) { return 16 * (E / 256); }
+__host__ __device__ inline int rest_groups(int E, int K) { return E >= K ? 0 : groups_of(K) - rest_first(E); }
+// header: per response {int64 byte offset of its groups, int64 sum of its taps below E, int64 sum of its taps, int64 E}
+__host__ __device__ inline long long split_header_bytes(int n) { return ((long long)n * 32 + 255) & ~255LL; }
+
+struct SplitArgs {
+    ReverbArgs r;                              // r.staged: the wet rows; r.rec is not used; r.partial: [2][B][blocks]
+    const int* split = nullptr;                // [n_rir]
+    short* target = nullptr;                   // [B][r.stride]
+    SRecord* srec = nullptr;                   // [B]
+};
+
 // Every launch_* returns 0 or a hipError_t.
+int launch_split_prepare(const short* d_taps, const long long* d_roff, const int* d_split, int n_rir, unsigned char* d_table,
+                         long long table_bytes, hipStream_t s);
+int launch_split(SplitArgs a, int form, hipStream_t s);     // forms as launch_reverb; sets a.r.blocks
 int launch_reverb_plan(int n_rir, float p_reverb, int B, long item0, const unsigned long long* d_seed_step, RItem* d_rplan,
                        hipStream_t s);
 int launch_reverb_prepare(const short* d_taps, const long long* d_roff, int n_rir, unsigned char* d_table, long long table_bytes,

@@ -1,6 +1,7 @@
 // reverb_host.cpp -- the "reverberant speech: exact RIR convolution" section of include/gtcrn_micro_hip.h: argument checks,
 // launch sequencing, gtcrn_batch_reverb_plan_host (the reverb plan's own function body, reverb.h, run on the host) and the
-// host side of gtcrn_selftest_mfma_i8.  The kernels are in reverb.hip.  Compiled with -ffp-contract=off like batch_host.cpp.
+// host side of gtcrn_selftest_mfma_i8; behind them the "dereverberation targets: early or direct clean" section (the split
+// convolution).  The kernels are in reverb.hip.  Compiled with -ffp-contract=off like batch_host.cpp.
 #include "../../include/gtcrn_micro_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@ extern "C" void gtcrn_set_error_(const char* msg);   // api.cpp: thread-local la
 
 static_assert(sizeof(gtcrn_reverb_item) == 8 && sizeof(gtr::RItem) == 8, "the reverb plan item is 8 bytes");
 static_assert(sizeof(gtcrn_reverb_record) == 16 && sizeof(gtr::RRecord) == 16, "the reverb record is 16 bytes");
+static_assert(sizeof(gtcrn_reverb_split_record) == 32 && sizeof(gtr::SRecord) == 32, "the split record is 32 bytes");
 static_assert(GTCRN_REVERB_MAX_TAPS == gtr::MAX_TAPS && GTCRN_REVERB_TAP_MAX == gtr::TAP_MAX, "the header states the bank's bounds");
 
 namespace {
@@ -112,24 +114,26 @@ size_t gtcrn_batch_reverb_workspace_bytes(int B, long L) {
     return ((size_t)B * (size_t)blocks_of(L) * sizeof(int) + 15) & ~(size_t)15;
 }
 
-int gtcrn_batch_reverb(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_taps,
-                       const long long* d_rir_offsets, int n_rir, const void* d_table, size_t table_bytes,
-                       const gtcrn_batch_item* d_plan, const gtcrn_reverb_item* d_rplan, int B, long L, short* d_staged,
-                       long staged_stride, long long* d_staged_offsets, gtcrn_batch_item* d_staged_plan,
-                       gtcrn_reverb_record* d_records, void* d_workspace, int form, void* stream) {
-    const std::string w("gtcrn_batch_reverb");
+namespace {
+
+// the checks gtcrn_batch_reverb and gtcrn_batch_reverb_split share; fills `a` (but a.rec) and resolves form 0
+int reverb_args(const std::string& w, const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_taps,
+                const long long* d_rir_offsets, int n_rir, const void* d_table, size_t table_bytes, long long header,
+                const gtcrn_batch_item* d_plan, const gtcrn_reverb_item* d_rplan, int B, long L, short* d_staged, long staged_stride,
+                long long* d_staged_offsets, gtcrn_batch_item* d_staged_plan, const void* d_records, void* d_workspace, int* form,
+                gtr::ReverbArgs* a) {
     if (B <= 0 || L <= 0 || L > gtb::MAX_L) return rfail(GTCRN_ERR_ARG, w + ": B and L must be positive (L below 2^31)");
     if (!d_speech_pcm || !d_speech_offsets || !d_taps || !d_rir_offsets || !d_plan || !d_rplan || !d_staged || !d_staged_offsets ||
         !d_staged_plan || !d_records || !d_workspace)
         return rfail(GTCRN_ERR_ARG, w + ": null pointer");
     if (n_speech <= 0 || n_rir <= 0) return rfail(GTCRN_ERR_ARG, w + ": the corpus or the bank is empty");
     if (staged_stride < L) return rfail(GTCRN_ERR_ARG, w + ": the staged stride is shorter than its row");
-    if (form < 0 || form > 4)
+    if (*form < 0 || *form > 4)
         return rfail(GTCRN_ERR_ARG, w + ": form is 0 (the library chooses), 1 (plain), 2 (matrix) or 3 / 4 (matrix, block pinned)");
-    if (form == 0) form = 2;                          // the matrix form is the faster wherever both were measured
-    if (form >= 2) {
-        if (!d_table) return rfail(GTCRN_ERR_ARG, w + ": the matrix form needs the table of gtcrn_batch_reverb_prepare");
-        if ((reinterpret_cast<uintptr_t>(d_table) & 15) || (long long)table_bytes < gtr::header_bytes(n_rir))
+    if (*form == 0) *form = 2;                        // the matrix form is the faster wherever both were measured
+    if (*form >= 2) {
+        if (!d_table) return rfail(GTCRN_ERR_ARG, w + ": the matrix form needs its table");
+        if ((reinterpret_cast<uintptr_t>(d_table) & 15) || (long long)table_bytes < header)
             return rfail(GTCRN_ERR_ARG, w + ": the table must be 16-byte aligned and hold its header");
     }
     if ((reinterpret_cast<uintptr_t>(d_plan) & 3) || (reinterpret_cast<uintptr_t>(d_rplan) & 3) ||
@@ -138,19 +142,102 @@ int gtcrn_batch_reverb(const short* d_speech_pcm, const long long* d_speech_offs
         (reinterpret_cast<uintptr_t>(d_staged) & 1))
         return rfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
     if ((long long)B * blocks_of(L) > kMaxGrid) return rfail(GTCRN_ERR_ARG, w + ": B * L is too large for one launch");
+    a->speech.pcm = d_speech_pcm; a->speech.off = d_speech_offsets; a->speech.n = n_speech;
+    a->taps = d_taps; a->roff = d_rir_offsets; a->n_rir = n_rir;
+    a->table = static_cast<const unsigned char*>(d_table); a->table_bytes = (long long)table_bytes;
+    a->plan = reinterpret_cast<const gtb::Item*>(d_plan);
+    a->rplan = reinterpret_cast<const gtr::RItem*>(d_rplan);
+    a->B = B; a->L = L;
+    a->staged = d_staged; a->stride = staged_stride; a->soffsets = d_staged_offsets;
+    a->splan = reinterpret_cast<gtb::Item*>(d_staged_plan);
+    a->partial = static_cast<int*>(d_workspace);
+    a->blocks = 0;                                    // (launch_reverb / launch_split: the form's own block)
+    return 0;
+}
+
+}  // namespace
+
+int gtcrn_batch_reverb(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_taps,
+                       const long long* d_rir_offsets, int n_rir, const void* d_table, size_t table_bytes,
+                       const gtcrn_batch_item* d_plan, const gtcrn_reverb_item* d_rplan, int B, long L, short* d_staged,
+                       long staged_stride, long long* d_staged_offsets, gtcrn_batch_item* d_staged_plan,
+                       gtcrn_reverb_record* d_records, void* d_workspace, int form, void* stream) {
+    const std::string w("gtcrn_batch_reverb");
     gtr::ReverbArgs a;
-    a.speech.pcm = d_speech_pcm; a.speech.off = d_speech_offsets; a.speech.n = n_speech;
-    a.taps = d_taps; a.roff = d_rir_offsets; a.n_rir = n_rir;
-    a.table = static_cast<const unsigned char*>(d_table); a.table_bytes = (long long)table_bytes;
-    a.plan = reinterpret_cast<const gtb::Item*>(d_plan);
-    a.rplan = reinterpret_cast<const gtr::RItem*>(d_rplan);
-    a.B = B; a.L = L;
-    a.staged = d_staged; a.stride = staged_stride; a.soffsets = d_staged_offsets;
-    a.splan = reinterpret_cast<gtb::Item*>(d_staged_plan);
+    const int rc = reverb_args(w, d_speech_pcm, d_speech_offsets, n_speech, d_taps, d_rir_offsets, n_rir, d_table, table_bytes,
+                               gtr::header_bytes(n_rir), d_plan, d_rplan, B, L, d_staged, staged_stride, d_staged_offsets,
+                               d_staged_plan, d_records, d_workspace, &form, &a);
+    if (rc != 0) return rc;
     a.rec = reinterpret_cast<gtr::RRecord*>(d_records);
-    a.partial = static_cast<int*>(d_workspace);
-    a.blocks = 0;                                     // (launch_reverb: the form's own block)
     const int e = gtr::launch_reverb(a, form, static_cast<hipStream_t>(stream));
+    if (e != 0) return rfail(GTCRN_ERR_HIP, w + ": " + hipGetErrorString(static_cast<hipError_t>(e)));
+    return 0;
+}
+
+// ---- dereverberation targets: the split convolution ---------------------------------------------------------------------------
+size_t gtcrn_batch_reverb_split_table_bytes(const long long* h_rir_offsets, const int* h_split, int n_rir) {
+    const std::string w("gtcrn_batch_reverb_split_table_bytes");
+    if (!h_rir_offsets || !h_split || n_rir <= 0) {
+        rfail(GTCRN_ERR_ARG, w + ": host offsets and splits of a bank that is not empty");
+        return 0;
+    }
+    long long bytes = gtr::split_header_bytes(n_rir);
+    for (int r = 0; r < n_rir; ++r) {
+        const long long len = h_rir_offsets[r + 1] - h_rir_offsets[r];
+        if (len < 1 || len > gtr::MAX_TAPS) {
+            rfail(GTCRN_ERR_ARG, w + ": response " + std::to_string(r) + " has " + std::to_string(len) + " taps; 1 .. 16384 are allowed");
+            return 0;
+        }
+        const int E = gtr::split_of(h_split[r], (int)len);
+        bytes += (long long)(gtr::groups_of(E) + gtr::rest_groups(E, (int)len)) * gtr::GROUP_BYTES;
+    }
+    return (size_t)bytes;
+}
+
+int gtcrn_batch_reverb_split_prepare(const short* d_taps, const long long* d_rir_offsets, const int* d_split, int n_rir, void* d_table,
+                                     size_t table_bytes, void* stream) {
+    const std::string w("gtcrn_batch_reverb_split_prepare");
+    if (!d_taps || !d_rir_offsets || !d_split || !d_table) return rfail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (n_rir <= 0) return rfail(GTCRN_ERR_ARG, w + ": the bank is empty");
+    if (reinterpret_cast<uintptr_t>(d_table) & 15) return rfail(GTCRN_ERR_ARG, w + ": the table must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_split) & 3) return rfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
+    const long long least = gtr::split_header_bytes(n_rir) + (long long)n_rir * gtr::groups_of(1) * gtr::GROUP_BYTES;
+    const long long groups = ((long long)table_bytes - gtr::split_header_bytes(n_rir)) / gtr::GROUP_BYTES;
+    if ((long long)table_bytes < least || groups > kMaxGrid)
+        return rfail(GTCRN_ERR_ARG, w + ": table_bytes is not gtcrn_batch_reverb_split_table_bytes of a bank of this size");
+    const int e = gtr::launch_split_prepare(d_taps, d_rir_offsets, d_split, n_rir, static_cast<unsigned char*>(d_table),
+                                            (long long)table_bytes, static_cast<hipStream_t>(stream));
+    if (e != 0) return rfail(GTCRN_ERR_HIP, w + ": " + hipGetErrorString(static_cast<hipError_t>(e)));
+    return 0;
+}
+
+size_t gtcrn_batch_reverb_split_workspace_bytes(int B, long L) {
+    if (B <= 0 || L <= 0 || L > gtb::MAX_L || (long long)B * blocks_of(L) > kMaxGrid) {
+        rfail(GTCRN_ERR_ARG, "gtcrn_batch_reverb_split_workspace_bytes: B and L must be positive, L below 2^31, B * blocks below 2^31");
+        return 0;
+    }
+    return (2 * (size_t)B * (size_t)blocks_of(L) * sizeof(int) + 15) & ~(size_t)15;
+}
+
+int gtcrn_batch_reverb_split(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_taps,
+                             const long long* d_rir_offsets, const int* d_split, int n_rir, const void* d_table, size_t table_bytes,
+                             const gtcrn_batch_item* d_plan, const gtcrn_reverb_item* d_rplan, int B, long L, short* d_staged,
+                             short* d_staged_target, long staged_stride, long long* d_staged_offsets,
+                             gtcrn_batch_item* d_staged_plan, gtcrn_reverb_split_record* d_records, void* d_workspace, int form,
+                             void* stream) {
+    const std::string w("gtcrn_batch_reverb_split");
+    gtr::SplitArgs a;
+    const int rc = reverb_args(w, d_speech_pcm, d_speech_offsets, n_speech, d_taps, d_rir_offsets, n_rir, d_table, table_bytes,
+                               gtr::split_header_bytes(n_rir), d_plan, d_rplan, B, L, d_staged, staged_stride, d_staged_offsets,
+                               d_staged_plan, d_records, d_workspace, &form, &a.r);
+    if (rc != 0) return rc;
+    if (!d_split || !d_staged_target) return rfail(GTCRN_ERR_ARG, w + ": null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_split) & 3) || (reinterpret_cast<uintptr_t>(d_staged_target) & 1))
+        return rfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
+    a.split = d_split;
+    a.target = d_staged_target;
+    a.srec = reinterpret_cast<gtr::SRecord*>(d_records);
+    const int e = gtr::launch_split(a, form, static_cast<hipStream_t>(stream));
     if (e != 0) return rfail(GTCRN_ERR_HIP, w + ": " + hipGetErrorString(static_cast<hipError_t>(e)));
     return 0;
 }

@@ -8,11 +8,14 @@ captured graph if the caller wants.  Nothing here falls back to the CPU; the ari
 
 With a ``RirBank`` (``rirs=``, ``p_reverb=``) a drawn share of the rows is convolved with a room impulse response before
 the mix -- the DNS noisy files were synthesised from reverberant speech -- in exact integer arithmetic (csrc/reverb.hip;
-"reverberant speech: exact RIR convolution" in the header).
+"reverberant speech: exact RIR convolution" in the header).  With ``target_ms=`` the same pass also
+writes the row convolved with the early part of its response -- the direct path plus ``target_ms`` milliseconds -- and ``clean``
+is that: a dereverberation target ("dereverberation targets: early or direct clean").  ``target=`` mixes
+noise into a caller's own paired (degraded, target) speech.
 
 Out of scope: active-speech levels (a VAD), sample rates other than 16 kHz, float corpora, streaming a corpus larger than
-device memory from disk; for the reverberation: early-reflection or dry targets, responses longer than 16384 taps, and
-multichannel responses.
+device memory from disk; for the reverberation: targets that need a response of their own (a shortened-decay tail), responses
+longer than 16384 taps, and multichannel responses.
 """
 import numpy as np
 
@@ -25,6 +28,8 @@ RECORD_DTYPE = np.dtype([("Ss", "<i8"), ("Sn", "<i8"), ("Ssn", "<i8"), ("gn", "<
 FLAG_NOISE_ZERO, FLAG_SPEECH_ZERO, FLAG_MIX_ZERO, FLAG_LIMITED = 1, 2, 4, 8
 REVERB_PLAN_DTYPE = np.dtype([("rir", "<i4"), ("reserved", "<i4")])
 REVERB_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("reserved", "<i4")])
+REVERB_SPLIT_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("split", "<i4"),
+                                      ("target_saturated", "<i4"), ("reserved", "<i4", (3,))])
 REVERB_MAX_TAPS = 16384        # GTCRN_REVERB_MAX_TAPS
 REVERB_TAP_MAX = 32639         # GTCRN_REVERB_TAP_MAX
 _U64 = (1 << 64) - 1
@@ -97,6 +102,36 @@ def reverb_workspace_bytes(B, L):
     if n == 0:
         raise GtcrnError(lib().gtcrn_last_error().decode())
     return n
+
+
+def _split_lib():
+    L = _reverb_lib()
+    if not hasattr(L, "gtcrn_batch_reverb_split"):
+        raise GtcrnError("this library has no dereverberation targets (gtcrn_batch_reverb_split, gtcrn_batch_mix_target)")
+    return L
+
+
+def reverb_split_workspace_bytes(B, L):
+    n = int(_split_lib().gtcrn_batch_reverb_split_workspace_bytes(int(B), int(L)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+def split_for(responses, target_ms):
+    """The split of each int16 response for a target of the direct path plus ``target_ms`` milliseconds:
+    E_r = min(K_r, d_r + 1 + rint(16 * target_ms)), d_r the first tap of the largest magnitude (0 for a bank made with
+    trim_direct=True).  target_ms = 0: the direct path alone.  -> int32 array."""
+    t = float(target_ms)
+    if not np.isfinite(t) or t < 0.0:
+        raise GtcrnError("target_ms must be finite and not negative")
+    more = int(np.rint(16.0 * t))
+    out = np.zeros(len(responses), np.int32)
+    for r, h in enumerate(responses):
+        h = np.asarray(h)
+        d = int(np.argmax(np.abs(h.astype(np.int64))))
+        out[r] = min(h.size, d + 1 + more)
+    return out
 
 
 def plan_to_device(plan, device):
@@ -244,6 +279,7 @@ class RirBank:
         if int(used.min()) < -REVERB_TAP_MAX or int(used.max()) > REVERB_TAP_MAX:
             raise GtcrnError(f"every tap must lie in +-{REVERB_TAP_MAX}")
         self.taps, self.offsets, self.n = taps, offsets, n
+        self._host_offsets, self._split_tables = off.astype(np.int64), {}
         nbytes = int(L.gtcrn_batch_reverb_table_bytes(off.ctypes.data, n))
         if nbytes == 0:
             raise GtcrnError(lib().gtcrn_last_error().decode())
@@ -254,6 +290,35 @@ class RirBank:
     @property
     def device(self):
         return self.taps.device
+
+    def split_for(self, target_ms):
+        """int32 [n]: per response the number of leading taps that make a target of the direct path plus ``target_ms``
+        milliseconds (``data.split_for`` on this bank's taps; reads them back once per call)."""
+        taps, off = self.taps.cpu().numpy(), self._host_offsets
+        return split_for([taps[int(off[r]):int(off[r + 1])] for r in range(self.n)], target_ms)
+
+    def split_table(self, split):
+        """-> (split, table): the int32 device split and the split table of gtcrn_batch_reverb_split_prepare for it, made
+        once per split and kept.  A value outside 1 .. K_r is clamped into it, as the library does."""
+        import torch
+        L = _split_lib()
+        sp = np.ascontiguousarray(split, np.int32)
+        if sp.ndim != 1 or sp.size != self.n:
+            raise GtcrnError(f"split must hold {self.n} entries")
+        lens = (self._host_offsets[1:] - self._host_offsets[:-1]).astype(np.int64)
+        sp = np.clip(sp, 1, lens).astype(np.int32)
+        key = sp.tobytes()
+        if key not in self._split_tables:
+            nbytes = int(L.gtcrn_batch_reverb_split_table_bytes(self._host_offsets.ctypes.data, sp.ctypes.data, self.n))
+            if nbytes == 0:
+                raise GtcrnError(lib().gtcrn_last_error().decode())
+            d_split = torch.from_numpy(sp).to(self.device)
+            table = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+            with torch.cuda.device(self.device):
+                _check(L.gtcrn_batch_reverb_split_prepare(self.taps.data_ptr(), self.offsets.data_ptr(), d_split.data_ptr(), self.n,
+                                                          table.data_ptr(), nbytes, _stream_ptr()))
+            self._split_tables[key] = (d_split, table)
+        return self._split_tables[key]
 
     @classmethod
     def from_tensors(cls, taps, offsets):
@@ -304,10 +369,16 @@ class BatchSource:
     ``rirs=`` a RirBank (mix form only): each row is reverberant with probability ``p_reverb`` -- its speech window, with
     its true history, convolved with a drawn response (gtcrn_batch_reverb) -- and ``clean`` is then the reverberant
     speech.  With p_reverb = 0 every draw is bit-identical to the source without ``rirs=``.  ``reverb_form``: gtcrn_batch_reverb's
-    `form` (0: the library chooses; 1 plain, 2 matrix, 3 / 4 matrix with the block pinned: bit-identical, for measurements)."""
+    `form` (0: the library chooses; 1 plain, 2 matrix, 3 / 4 matrix with the block pinned: bit-identical, for measurements).
+    ``target_ms=`` a number (with ``rirs=``): ``clean`` is the speech convolved with the early part of the row's response, the
+    direct path plus ``target_ms`` milliseconds (0: the direct path alone; ``RirBank.split_for``), written by the same pass as
+    the wet row (gtcrn_batch_reverb_split, gtcrn_batch_mix_target); ``noisy``, its SNR and its level are those of the fully
+    reverberant speech.  None: the draw above, call for call.
+    ``target=`` a Corpus under ``speech``'s offsets table (mix form, without ``rirs=``): ``clean`` is cut from it instead of
+    from ``speech`` -- noise mixed on the device into a caller's own paired (degraded, target) speech."""
 
     def __init__(self, speech, noise=None, paired_clean=None, B=1, L=64000, seed=0, snr_db=(-5.0, 20.0), level_db=(-35.0, -15.0),
-                 granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0):
+                 granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0, target_ms=None, target=None):
         import torch
         _batch_lib()
         if (noise is None) == (paired_clean is None):
@@ -338,6 +409,17 @@ class BatchSource:
         self.clean = torch.empty((B, L), device=dev, dtype=torch.float32)
         self._ws = torch.empty(workspace_bytes(B, L), device=dev, dtype=torch.uint8) if noise is not None else None
         self.rirs, self.p_reverb, self.reverb_form = rirs, float(p_reverb), int(reverb_form)
+        self.target, self.target_ms = target, None if target_ms is None else float(target_ms)
+        if target is not None:
+            _split_lib()
+            if noise is None or rirs is not None:
+                raise GtcrnError("target= goes with noise= (the mix) and without rirs= or paired_clean=")
+            if not isinstance(target, Corpus) or target.device != speech.device:
+                raise GtcrnError("target must be a data.Corpus on the corpora's device")
+            if target.n != speech.n or not torch.equal(target.offsets, speech.offsets):
+                raise GtcrnError("target and speech must share one offsets table")
+        if target_ms is not None and rirs is None:
+            raise GtcrnError("target_ms needs rirs=")
         if rirs is not None:
             _reverb_lib()
             if paired_clean is not None:
@@ -355,6 +437,12 @@ class BatchSource:
             self.reverb_plan = torch.full((B, 2), -1, device=dev, dtype=torch.int32)   # gtcrn_reverb_item rows
             self.reverb_records = torch.zeros((B, 4), device=dev, dtype=torch.int32)   # gtcrn_reverb_record rows
             self._rws = torch.empty(reverb_workspace_bytes(B, L), device=dev, dtype=torch.uint8)
+            if target_ms is not None:
+                _split_lib()
+                self.split, self.split_table = rirs.split_table(rirs.split_for(self.target_ms))
+                self.staged_target = torch.zeros(B * self.staged_stride, device=dev, dtype=torch.int16)
+                self.split_records = torch.zeros((B, 8), device=dev, dtype=torch.int32)   # gtcrn_reverb_split_record rows
+                self._rws = torch.empty(reverb_split_workspace_bytes(B, L), device=dev, dtype=torch.uint8)
         elif self.p_reverb != 0.0:
             raise GtcrnError("p_reverb needs rirs=")
 
@@ -378,7 +466,16 @@ class BatchSource:
         return self.reverb_plan.cpu().numpy().view(REVERB_PLAN_DTYPE).reshape(self.B)
 
     def reverb_records_numpy(self):
+        if self.target_ms is not None:                   # the split records' first three fields are these records'
+            s, out = self.split_records_numpy(), np.zeros(self.B, REVERB_RECORD_DTYPE)
+            for f in ("rir", "ntaps", "saturated"):
+                out[f] = s[f]
+            return out
         return self.reverb_records.cpu().numpy().view(REVERB_RECORD_DTYPE).reshape(self.B)
+
+    def split_records_numpy(self):
+        """The split records of the most recent draw (a source with ``target_ms=``)."""
+        return self.split_records.cpu().numpy().view(REVERB_SPLIT_RECORD_DTYPE).reshape(self.B)
 
     # ---- drawing ----------------------------------------------------------------------------------------------------
     def _rows(self, t, what):
@@ -450,7 +547,17 @@ class BatchSource:
             if self.noise is not None:
                 nz = self.noise
                 s_pcm, s_off, s_n = sp.pcm, sp.offsets, sp.n
-                if rp is not None:                       # the speech side of the mix becomes the staged corpus
+                t_pcm = self.target.pcm if self.target is not None else None
+                if rp is not None and self.target_ms is not None:      # one pass, two staged corpora: wet speech and its target
+                    rb = self.rirs
+                    _check(lib().gtcrn_batch_reverb_split(
+                        sp.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n, rb.taps.data_ptr(), rb.offsets.data_ptr(),
+                        self.split.data_ptr(), rb.n, self.split_table.data_ptr(), self.split_table.numel(), p.data_ptr(),
+                        rp.data_ptr(), self.B, self.L, self.staged.data_ptr(), self.staged_target.data_ptr(), self.staged_stride,
+                        self.staged_offsets.data_ptr(), self.staged_plan.data_ptr(), self.split_records.data_ptr(),
+                        self._rws.data_ptr(), self.reverb_form, _stream_ptr()))
+                    s_pcm, s_off, s_n, p, t_pcm = self.staged, self.staged_offsets, self.B, self.staged_plan, self.staged_target
+                elif rp is not None:                     # the speech side of the mix becomes the staged corpus
                     rb = self.rirs
                     _check(lib().gtcrn_batch_reverb(
                         sp.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n, rb.taps.data_ptr(), rb.offsets.data_ptr(), rb.n,
@@ -458,9 +565,15 @@ class BatchSource:
                         self.staged.data_ptr(), self.staged_stride, self.staged_offsets.data_ptr(), self.staged_plan.data_ptr(),
                         self.reverb_records.data_ptr(), self._rws.data_ptr(), self.reverb_form, _stream_ptr()))
                     s_pcm, s_off, s_n, p = self.staged, self.staged_offsets, self.B, self.staged_plan
-                _check(lib().gtcrn_batch_mix(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(), nz.offsets.data_ptr(),
-                                             nz.n, p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
-                                             self.records.data_ptr(), self._ws.data_ptr(), int(passes), _stream_ptr()))
+                if t_pcm is not None:
+                    _check(lib().gtcrn_batch_mix_target(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(),
+                                                        nz.offsets.data_ptr(), nz.n, t_pcm.data_ptr(), p.data_ptr(), self.B, self.L,
+                                                        noisy.data_ptr(), ns, clean.data_ptr(), cs, self.records.data_ptr(),
+                                                        self._ws.data_ptr(), int(passes), _stream_ptr()))
+                else:
+                    _check(lib().gtcrn_batch_mix(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(), nz.offsets.data_ptr(),
+                                                 nz.n, p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
+                                                 self.records.data_ptr(), self._ws.data_ptr(), int(passes), _stream_ptr()))
             else:
                 _check(lib().gtcrn_batch_pairs(sp.pcm.data_ptr(), self.paired_clean.pcm.data_ptr(), sp.offsets.data_ptr(), sp.n,
                                                p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,

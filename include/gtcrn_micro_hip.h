@@ -950,8 +950,7 @@ int gtcrn_batch_mix(const short *d_speech_pcm, const long long *d_speech_offsets
  *   total is order-free).  Two launches: the convolution over a (row, block) grid, then records / offsets / plan.
  * B <= 0, L <= 0 or L >= 2^31, an empty corpus or bank, a null or misaligned buffer, a stride below L, p_reverb outside 0 .. 1,
  * an unknown form and a matrix form without its table return GTCRN_ERR_ARG before anything is enqueued.  Out of scope:
- * early-reflection or dry targets (the clean output is the full reverberant speech), responses longer than 16384 taps,
- * multichannel responses. */
+ * responses longer than 16384 taps, multichannel responses.  (Early-reflection or direct-path targets: the next section.) */
 #define GTCRN_REVERB_MAX_TAPS 16384
 #define GTCRN_REVERB_TAP_MAX 32639
 typedef struct { int rir, reserved; } gtcrn_reverb_item;                        /* 8 bytes */
@@ -969,6 +968,67 @@ int gtcrn_batch_reverb(const short *d_speech_pcm, const long long *d_speech_offs
                        const gtcrn_batch_item *d_plan, const gtcrn_reverb_item *d_rplan, int B, long L, short *d_staged,
                        long staged_stride, long long *d_staged_offsets, gtcrn_batch_item *d_staged_plan,
                        gtcrn_reverb_record *d_records, void *d_workspace, int form, void *stream);
+
+/* ---- dereverberation targets: early or direct clean ---------------------------------------------------------------------------
+ * The clean output of the section above is the full reverberant speech: a model trained from it learns to denoise.  To train
+ * it to remove the late tail the target is the early part of the response, or the direct path alone.  The convolution is
+ * linear, so after the first E taps its accumulators ARE that target: gtcrn_batch_reverb_split writes them out and walks on
+ * into the tail -- one pass over the speech, two staged corpora, still exact integers.  gtcrn_batch_mix_target then takes its
+ * clean rows from the second.  Additions only: nothing above changes.
+ *
+ * Split: d_split, int32 [n_rir], E_r in 1 .. K_r, the number of leading taps of response r that make the target (E_r = K_r:
+ * the target is the wet row).  A value outside 1 .. K_r is clamped into it: a wrong value gives wrong audio, never an access
+ * outside a buffer.
+ *
+ * gtcrn_batch_reverb_split, per wet row b with h, K, s0 and x[] exactly as in gtcrn_batch_reverb and E = split[rir]:
+ *   early[i] = sum_{k<E} h[k] * x[s0 + i - k];   acc[i] = early[i] + sum_{k>=E} h[k] * x[s0 + i - k]     (64-bit integers, exact)
+ *   d_staged_target[b * staged_stride + i] = clamp((early[i] + 16384) >> 15);   d_staged[b * staged_stride + i] =
+ *   clamp((acc[i] + 16384) >> 15): the latter is gtcrn_batch_reverb's wet row, bit for bit, for any split.  A dry row copies x
+ *   into both.  The two staged buffers share staged_stride, d_staged_offsets and d_staged_plan (written as above): the target
+ *   is a corpus parallel to the wet one under one offsets table.
+ *   d_records[b] = {rir, ntaps, saturated (as above), split = E as used (0 for a dry row), target_saturated = the clamped
+ *   samples of the target row, 0, 0, 0}: 32 bytes.
+ *   d_workspace: gtcrn_batch_reverb_split_workspace_bytes(B, L) bytes, 4-byte aligned: two per-workgroup clamp counts.
+ *   Forms: the numbering above, and all agree on every bit.  1, plain: one thread per output sample, two accumulators, the sums
+ *   as written.  2, matrix (0: the library chooses it); 3 / 4 pin the 2048 / 8192 block, the block rule is the one above.  The
+ *   matrix form runs the chunks of the early taps, the epilogue into the target row with bias 128 * sum(h[:E]), does NOT reset
+ *   its accumulators, runs the chunks of the rest and the epilogue into the wet row with bias 128 * sum(h).  Padding taps are
+ *   stored as zero and add zero products, so every int32 accumulator holds a subset of the terms it holds in
+ *   gtcrn_batch_reverb: the bound above (below 2^31 for 16384 + 255 terms) covers both epilogues.
+ *   Split table (matrix form): gtcrn_batch_reverb_split_table_bytes(host offsets, host split, n) bytes, 16-byte aligned,
+ *   filled once per (bank, split) by gtcrn_batch_reverb_split_prepare.  Header: 32 bytes per response {int64 byte offset,
+ *   int64 sum(h[:E]), int64 sum(h), int64 E}, padded to whole 256 bytes.  Per response two contiguous segments in the tile
+ *   format above: taps 0 .. E - 1 padded with zeros to 16 * ceil((E + 15) / 256) groups, then -- absent when E == K -- groups
+ *   16 * floor(E / 256) .. of the response with its taps below E stored as zero (the 256-tap block that holds E is there
+ *   twice, cut at E; one block more than gtcrn_batch_reverb's table, two when E mod 256 > 241).
+ *   The matrix form takes E from the table's header (clamped as a split is) and checks that both segments lie inside
+ *   table_bytes -- a row whose entry does not stays dry in both outputs; the plain form and the record take E from d_split.  A
+ *   table prepared from another split or bank gives wrong audio, never an access outside a buffer.
+ * Argument errors as for gtcrn_batch_reverb; a null d_split or d_staged_target is one too.  Refused before anything is enqueued.
+ *
+ * gtcrn_batch_mix_target: gtcrn_batch_mix with one more corpus, d_target_pcm, under the SPEECH offsets table (as the two
+ * sides of gtcrn_batch_pairs).  Everything is as in the mix contract but the clean output: clean[b][i] = Gf * tf_i, tf_i =
+ * float(t_i) / 32768, t_i = target[offsets[sclip] + sstart + i] inside the clip, else 0.  The sums, both gains, the peak, the
+ * limiter, the record and noisy come from the speech side: the SNR is that of the speech the model hears.  Passes 1 and 2 are
+ * gtcrn_batch_mix's launches, pass 3 a write kernel of its own.  With d_target_pcm == d_speech_pcm the call is bit-identical
+ * to gtcrn_batch_mix.  After gtcrn_batch_reverb_split: speech = d_staged, target = d_staged_target, plan = d_staged_plan.  A
+ * caller who owns paired (degraded, target) speech mixes noise in on the device with the same call.
+ * Out of scope: targets that need a response of their own (a shortened-decay tail), responses longer than 16384 taps. */
+typedef struct { int rir, ntaps, saturated, split, target_saturated, reserved[3]; } gtcrn_reverb_split_record;   /* 32 bytes */
+size_t gtcrn_batch_reverb_split_table_bytes(const long long *h_rir_offsets, const int *h_split, int n_rir);   /* 0 for a bad bank */
+int gtcrn_batch_reverb_split_prepare(const short *d_taps, const long long *d_rir_offsets, const int *d_split, int n_rir,
+                                     void *d_table, size_t table_bytes, void *stream);
+size_t gtcrn_batch_reverb_split_workspace_bytes(int B, long L);                               /* 0 for a bad shape */
+int gtcrn_batch_reverb_split(const short *d_speech_pcm, const long long *d_speech_offsets, int n_speech, const short *d_taps,
+                             const long long *d_rir_offsets, const int *d_split, int n_rir, const void *d_table,
+                             size_t table_bytes, const gtcrn_batch_item *d_plan, const gtcrn_reverb_item *d_rplan, int B, long L,
+                             short *d_staged, short *d_staged_target, long staged_stride, long long *d_staged_offsets,
+                             gtcrn_batch_item *d_staged_plan, gtcrn_reverb_split_record *d_records, void *d_workspace, int form,
+                             void *stream);
+int gtcrn_batch_mix_target(const short *d_speech_pcm, const long long *d_speech_offsets, int n_speech, const short *d_noise_pcm,
+                           const long long *d_noise_offsets, int n_noise, const short *d_target_pcm,
+                           const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy, long noisy_stride, float *d_clean,
+                           long clean_stride, gtcrn_batch_record *d_records, void *d_workspace, int passes, void *stream);
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
