@@ -1311,6 +1311,10 @@ class Engine:
         _check(lib().gtcrn_stream_form(self._h, int(form)))
 
     def tap(self, name, b, T):
+        """Stage tap of clip b of the most recent forward, (C,T,F) float32: en0..en4, gtcn1, gtcn2 (fp32 forwards
+        only), sum4 (gtcn2 + en4 as stored: the decoder's first input), and -- with debug_enable before the forward --
+        de0..de4.  After a quant forward (which needs debug_enable for every tap) the values are the fp16 records,
+        widened."""
         F = {"en0": 65, "de3": 65}.get(name, 33)
         shape = (2, T, 129) if name == "de4" else (16, T, F)
         dst = np.empty(shape, np.float32)

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -100,6 +101,7 @@ struct gtcrn_model {
     int stamps_cap_b = 0;
     float** d_ptr8 = nullptr;  // device table of 8 tcn cache pointers
     bool last_quant = false;       // the last forward was the fp16 variant: the hand-off buffers hold fp16 records
+    bool last_quant_taps = false;  // ... and ran with the stage taps enabled (gtcrn_debug_enable 1): gtcrn_debug_tap serves it
     bool last_fused_stream = false;  // the last forward was the single-launch streaming step: no hand-off tensors exist
     bool timing = false;
     int timing_only = -1;          // >= 0: record events around this kernel only (two events per call)
@@ -235,6 +237,7 @@ int run_model(gtcrn_model* m, const float* spec_in, long isb, long isf, long ist
     const float* pf = q ? m->d_pfq : m->d_pf;
     const bool offline = !state;
     m->last_quant = q != nullptr;
+    m->last_quant_taps = q != nullptr && m->debug;
     m->last_fused_stream = false;
     if (offline) {
         // offline: the frame-independent front end runs as a throughput kernel (fused with the STFT by
@@ -287,7 +290,7 @@ int run_model(gtcrn_model* m, const float* spec_in, long isb, long isf, long ist
     tm.begin(K_DECODER);
     LAUNCH_TRY(gtk::launch_decoder(m->d_g2, m->d_en0, m->d_en[0], m->d_en[1], m->d_en[2], m->d_en[3], spec_in, isb, isf,
                                    ist, spec_out, osb, osf, ost, B, T, lens, pf, m->d_pi, state,
-                                   m->debug && !q ? m->d_dbg : nullptr, stp ? stp + 3 * sst : nullptr, s, q, pref));
+                                   m->debug ? m->d_dbg : nullptr, stp ? stp + 3 * sst : nullptr, s, q, pref));
     tm.end();
     m->last_B = B;
     m->last_T = T;
@@ -1745,21 +1748,33 @@ int gtcrn_stream_form(gtcrn_model* m, int form) {
     return 0;
 }
 
+// binary16 bits -> float, exact (the fp16 hand-off records of the int8/fp16 variant, read back for the stage taps)
+static float half_bits_to_float(uint16_t h) {
+    const int e = (h >> 10) & 31, f = h & 1023;
+    float v;
+    if (e == 0) v = std::ldexp((float)f, -24);
+    else if (e == 31) v = f ? std::numeric_limits<float>::quiet_NaN() : std::numeric_limits<float>::infinity();
+    else v = std::ldexp((float)(f | 1024), e - 25);
+    return (h & 0x8000) ? -v : v;
+}
+
 long gtcrn_debug_tap(gtcrn_model* m, const char* name, int b, float* h_dst, long cap) {
     int rc = check_model(m);
     if (rc) return rc;
     if (!name || !h_dst) return fail(GTCRN_ERR_ARG, "null argument");
     const int B = m->last_B, T = m->last_T;
     if (B < 1 || b < 0 || b >= B) return fail(GTCRN_ERR_ARG, "no forward recorded or batch index out of range");
-    if (m->last_quant)
-        return fail(GTCRN_ERR_STATE, "the last forward was the int8/fp16 variant: its hand-off tensors are fp16 records, "
-                                     "the stage taps read fp32");
     if (m->last_fused_stream)
         return fail(GTCRN_ERR_STATE, "the last forward was a single-launch streaming step, which keeps no hand-off "
                                      "tensors: enable debug before the step to run the three-launch form");
+    const bool q = m->last_quant;       // the hand-off tensors are fp16 records (HandOff<true>): same element offsets
+    if (q && !m->last_quant_taps)
+        return fail(GTCRN_ERR_STATE, "the last forward was the int8/fp16 variant without the stage taps: its hand-off tensors "
+                                     "are fp16 records, read only after gtcrn_debug_enable(m,1) before the forward");
     const std::string nm(name);
     const long bt = (long)B * T;
     const float* src = nullptr;
+    bool handoff = true;                // false: a decoder tap in d_dbg, fp32 in either variant
     int F = 33, perm = -1;
     if (nm == "en0") { src = m->d_en0; F = 65; perm = 0; }
     else if (nm == "en1") { src = m->d_en[0]; perm = 1; }
@@ -1767,10 +1782,17 @@ long gtcrn_debug_tap(gtcrn_model* m, const char* name, int b, float* h_dst, long
     else if (nm == "en3") { src = m->d_en[2]; perm = 3; }
     else if (nm == "en4") { src = m->d_en[3]; perm = 4; }
     else if (nm == "gtcn1") { src = m->d_g1; perm = 4; }
-    else if (nm == "gtcn2") { src = m->d_g2; perm = 4; }
+    else if (nm == "gtcn2") {
+        if (q)
+            return fail(GTCRN_ERR_STATE, "the last forward was the int8/fp16 variant: it stores gtcn2(x) + en4 rounded to "
+                                         "fp16, which cannot be un-added -- tap \"sum4\" instead");
+        src = m->d_g2; perm = 4;
+    }
+    else if (nm == "sum4") { src = m->d_g2; perm = 4; }           // gtcn2(x) + en4 as stored: the decoder's first input
     else if (nm == "de0" || nm == "de1" || nm == "de2" || nm == "de3" || nm == "de4") {
         if (!m->debug || !m->d_dbg || m->dbg_cap_bt < bt)
             return fail(GTCRN_ERR_STATE, "decoder taps need gtcrn_debug_enable(m,1) before the forward");
+        handoff = false;
         const int j = nm[2] - '0';
         if (j < 3) { src = m->d_dbg + (long)j * bt * 528; perm = 5 + j; }
         else if (j == 3) { src = m->d_dbg + 3 * bt * 528; F = 65; perm = 8; }
@@ -1790,10 +1812,17 @@ long gtcrn_debug_tap(gtcrn_model* m, const char* name, int b, float* h_dst, long
     if (cap < nel) return fail(GTCRN_ERR_ARG, "destination too small");
     std::vector<float> tmp(nel);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(tmp.data(), src + (long)b * T * F * 16, sizeof(float) * nel, hipMemcpyDeviceToHost));
+    if (q && handoff) {
+        std::vector<uint16_t> hb(nel);
+        HIP_TRY(hipMemcpy(hb.data(), reinterpret_cast<const uint16_t*>(src) + (long)b * nel, sizeof(uint16_t) * nel,
+                          hipMemcpyDeviceToHost));
+        for (long i = 0; i < nel; ++i) tmp[i] = half_bits_to_float(hb[i]);
+    } else {
+        HIP_TRY(hipMemcpy(tmp.data(), src + (long)b * nel, sizeof(float) * nel, hipMemcpyDeviceToHost));
+    }
     if (nm == "gtcn2") {  // stored as gtcn2(x) + en4: recover the stage output for the tap
         std::vector<float> e4(nel);
-        HIP_TRY(hipMemcpy(e4.data(), m->d_en[3] + (long)b * T * F * 16, sizeof(float) * nel, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(e4.data(), m->d_en[3] + (long)b * nel, sizeof(float) * nel, hipMemcpyDeviceToHost));
         for (long i = 0; i < nel; ++i) tmp[i] -= e4[i];
     }
     const int* pm = m->h_pi.data() + gtl::I_PERM + perm * 16;

@@ -171,15 +171,46 @@ __device__ __forceinline__ h16x4 to_h4(const f32x4 v) {
 __device__ __forceinline__ f32x4 mfma_h(h16x4 a, h16x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
 }
+// rq / rq1: the contract's rounding of an activation, fp32 -> fp16 (RNE) -> fp32.  The fp32 value goes through an empty
+// asm first: a multiply-add feeding the conversion is otherwise fused into v_fma_mixlo_f16, which rounds the exact
+// sum ONCE to fp16 -- not the contract's fp32 sum rounded to fp16 (they differ where the fp32 sum is an fp16 tie: one
+// element in ~10^4; tests/test_gpu_quant_stages.py holds the output stage to equality).
+__device__ __forceinline__ float as_fp32_value(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
 template <bool Q>
 __device__ __forceinline__ float rq1(float v) {
-    if constexpr (Q) return (float)(_Float16)v;
+    if constexpr (Q) return (float)(_Float16)as_fp32_value(v);
     else return v;
+}
+// The PReLU argument of prelu4q: the slope itself in the Q variant, slope - 1 otherwise (prelu4).
+template <bool Q>
+__device__ __forceinline__ float slope_arg(float slope) {
+    if constexpr (Q) return slope;
+    else return slope - 1.0f;
+}
+// Q: max(x, 0) + a * min(x, 0) -- a * x rounded once for x < 0, as the contract's checker forms it.  prelu4's
+// x + (a - 1) * min(x, 0) rounds a - 1 first: a relative error of 2^-25 / a in the negative branch, harmless in fp32
+// but enough, for a trained slope of a few 1e-3, to move one negative value in a hundred to the next fp16 number.
+template <bool Q>
+__device__ __forceinline__ f32x4 prelu4q(f32x4 v, float a) {
+    if constexpr (Q) {
+        f32x4 r;
+        r[0] = fmaf(a, fminf(v[0], 0.f), fmaxf(v[0], 0.f));
+        r[1] = fmaf(a, fminf(v[1], 0.f), fmaxf(v[1], 0.f));
+        r[2] = fmaf(a, fminf(v[2], 0.f), fmaxf(v[2], 0.f));
+        r[3] = fmaf(a, fminf(v[3], 0.f), fmaxf(v[3], 0.f));
+        return r;
+    } else {
+        return prelu4(v, a);
+    }
 }
 template <bool Q>
 __device__ __forceinline__ f32x4 rq(const f32x4 v) {
     if constexpr (Q) {
-        const h16x4 h = to_h4(v);
+        const f32x4 w = {as_fp32_value(v[0]), as_fp32_value(v[1]), as_fp32_value(v[2]), as_fp32_value(v[3])};
+        const h16x4 h = to_h4(w);
         f32x4 r = {(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
         return r;
     } else {
@@ -1186,7 +1217,7 @@ __device__ __forceinline__ void gtconv_block(f32x4 (&x)[TPW], const Tiles<TPW>& 
     if constexpr (!MS) {
         if (c.sHtop) ring_to_image<RS, PT, FMT>(c.sW, c.sHtop, L.tid);
     }
-    const float a1 = c.pb[GB_SLOPE] - 1.0f, a2 = c.pb[GB_SLOPE + 1] - 1.0f;
+    const float a1 = slope_arg<Q>(c.pb[GB_SLOPE]), a2 = slope_arg<Q>(c.pb[GB_SLOPE + 1]);
     // ---- point_conv1 + BN + PReLU; h lives only in the LDS image from here on (its centre tap and the
     //      ring update re-read it: one ds_read_b128 each instead of 12 registers held across the phase) ----
     {
@@ -1197,7 +1228,7 @@ __device__ __forceinline__ void gtconv_block(f32x4 (&x)[TPW], const Tiles<TPW>& 
         mm16<TPW, Q>(A, x, h);
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
-            const f32x4 hv = rq<Q>(prelu4(h[i], a1));
+            const f32x4 hv = rq<Q>(prelu4q<Q>(h[i], a1));
             if constexpr (SPLIT) { if (in_image(i)) st_split(c.sW, b0s[i] - 4 * g, g, hv); }
             else if constexpr (HALF) st_half(c.sW, b0s[i] - 4 * g, g, hv);
             else if (in_image(i)) st4(c.sW + b0s[i], hv);
@@ -1246,7 +1277,7 @@ __device__ __forceinline__ void gtconv_block(f32x4 (&x)[TPW], const Tiles<TPW>& 
             }
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                acc[i] = rq<Q>(prelu4(acc[i], a2));
+                acc[i] = rq<Q>(prelu4q<Q>(acc[i], a2));
                 x[i] = keep * x[i] + B2;
             }
             mm16<TPW, Q>(A2, acc, x);                         // point_conv2: the tiles' chains interleaved
@@ -1331,7 +1362,7 @@ __device__ __forceinline__ void gtconv_block(f32x4 (&x)[TPW], const Tiles<TPW>& 
             }
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                acc[i] = rq<Q>(prelu4(acc[i], a2));
+                acc[i] = rq<Q>(prelu4q<Q>(acc[i], a2));
                 x[i] = keep * x[i] + B2;
             }
             mm16<TPW, Q>(A2, acc, x);
@@ -1366,7 +1397,7 @@ __device__ __forceinline__ void gtconv_block(f32x4 (&x)[TPW], const Tiles<TPW>& 
             }
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                acc[i] = rq<Q>(prelu4(acc[i], a2));
+                acc[i] = rq<Q>(prelu4q<Q>(acc[i], a2));
                 x[i] = keep * x[i] + B2;
             }
             mm16<TPW, Q>(A2, acc, x);                         // point_conv2: the tiles' chains interleaved
@@ -1980,7 +2011,7 @@ segment_top:
         // ---- C: en_convs.0 = Conv2d(3,16,(1,5),stride (1,2),pad (0,2)) + BN + PReLU --------------
         {
             const f32x4 A = ld4(sP + E_EN0_A + arow(n, g)), Bv = ld4(sP + E_EN0_B + 4 * g);
-            const float a = sP[E_EN0_S] - 1.0f;
+            const float a = slope_arg<Q>(sP[E_EN0_S]);
             int off[4];
             int go = g;
             asm volatile("" : "+v"(go));   // recompute the im2col offsets per chunk instead of spilling them
@@ -2000,7 +2031,7 @@ segment_top:
 #pragma unroll
                 for (int s = 0; s < 4; ++s) bv[s] = sF0[off[s] + tl * F0_ROW + 2 * fo];
                 f32x4 acc = mm1<Q>(A, bv, Bv);
-                acc = rq<Q>(prelu4(acc, a));
+                acc = rq<Q>(prelu4q<Q>(acc, a));
                 st4(sE0 + pl(tl * ENC_E0_ROW + 2 + fo, g), acc);
                 if (q < nfr * F1) stx<Q>(en0h + (long)t0 * (F1 * 16) + (unsigned)(q * 16 + 4 * g), acc);
             }
@@ -2010,7 +2041,7 @@ segment_top:
         // ---- D: en_convs.1 = Conv2d(16,16,(1,5),stride (1,2),pad (0,2)) + BN + PReLU -------------
         {
             const f32x4 Bv = ld4(sP + E_EN1_B + 4 * g);
-            const float a = sP[E_EN1_S] - 1.0f;
+            const float a = slope_arg<Q>(sP[E_EN1_S]);
             const int* ix = sI + I_ENST - ENC_I_SKIP + 0 * 16 + 4 * g;
             // tap major: each of the five 16x16 slot matrices is read from LDS once per wave, one MFMA chain per tile
 #pragma unroll
@@ -2026,7 +2057,7 @@ segment_top:
             }
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                x[i] = rq<Q>(prelu4(x[i], a));
+                x[i] = rq<Q>(prelu4q<Q>(x[i], a));
                 {   // en1 in the slot order of its decoder consumer; scratch: this tile's records of F0/EB (dead)
                     const f32x4 y = permute_via_lds(sEB + tt.pp(i) * 16, ix, g, x[i]);
                     if (tt.pp(i) < nfr * 33 && t0 + tt.tl[i] >= wlo) stx<Q>(en1h + (long)t0 * 528 + (unsigned)(tt.pp(i) * 16 + 4 * g), y);
@@ -2331,7 +2362,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
             // ---- C: en_convs.0: 65 positions = 5 tiles (the last one holds a single valid position) ---------------
             {
                 const f32x4 Am = ld4(sP + E_EN0_A + arow(n, g)), Bv = ld4(sP + E_EN0_B + 4 * g);
-                const float a = sP[E_EN0_S] - 1.0f;
+                const float a = slope_arg<Q>(sP[E_EN0_S]);
                 int off[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
@@ -2347,7 +2378,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
 #pragma unroll
                     for (int s = 0; s < 4; ++s) bv[s] = sF0[off[s] + 2 * fo];
                     f32x4 acc = mm1<Q>(Am, bv, Bv);
-                    acc = rq<Q>(prelu4(acc, a));
+                    acc = rq<Q>(prelu4q<Q>(acc, a));
                     if (q < F1) {
                         st4(sE0 + pl(2 + fo, g), acc);
                         stx<Q>(reinterpret_cast<ht*>(en0c + (rec_off + (unsigned)(tile * 256) * EB)), acc);
@@ -2358,7 +2389,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
             // ---- D: en_convs.1: 33 positions = 3 tiles; stored in both slot orders ---------------------------------
             {
                 const f32x4 Bv = ld4(sP + E_EN1_B + 4 * g);
-                const float a = sP[E_EN1_S] - 1.0f;
+                const float a = slope_arg<Q>(sP[E_EN1_S]);
                 const int* ix = sI + 128 + 4 * g;
                 char* en1pc = reinterpret_cast<char*>(reinterpret_cast<ht*>(en1p) + fr * 528);
                 f32x4 x[3];
@@ -2385,7 +2416,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
                         po[i] = (i * 16 + n) * PERM_RS;
-                        x[i] = rq<Q>(prelu4(x[i], a));
+                        x[i] = rq<Q>(prelu4q<Q>(x[i], a));
                     }
                     permute_tiles_via_lds<3>(sE0, po, ix, g, x, y);     // E0's taps are consumed: X region
 #pragma unroll
@@ -2669,7 +2700,7 @@ __device__ __forceinline__ void tcn_block_band(f32x4 (&x)[TPW], const float* pk,
         mm16<TPW, Q>(A, x, acc);
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
-            y1[i] = rq<Q>(prelu4(acc[i], a1));
+            y1[i] = rq<Q>(prelu4q<Q>(acc[i], a1));
             st4(cw + i * 16 * RS + n * RS + 4 * g, y1[i]);
         }
     }
@@ -2692,12 +2723,12 @@ __device__ __forceinline__ void tcn_block_band(f32x4 (&x)[TPW], const float* pk,
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
             const f32x4 p1 = ld4(cw + b1 + i * s1), p2 = ld4(cw + b2 + i * s2);
-            y2[i] = rq<Q>(prelu4(B2 + w0 * p2 + w1 * p1 + w2 * y1[i], a2));
+            y2[i] = rq<Q>(prelu4q<Q>(B2 + w0 * p2 + w1 * p1 + w2 * y1[i], a2));
             acc[i] = B3 + x[i];
         }
         mm16<TPW, Q>(A, y2, acc);
 #pragma unroll
-        for (int i = 0; i < TPW; ++i) x[i] = rq<Q>(prelu4(acc[i], a3));
+        for (int i = 0; i < TPW; ++i) x[i] = rq<Q>(prelu4q<Q>(acc[i], a3));
     }
     // ring update: the last 2d frames of the chunk (every live lane for the final, partial chunk is fine:
     // later frames overwrite earlier ones of the same row only in program order of a single lane set)
@@ -2742,7 +2773,7 @@ __global__ __launch_bounds__(NTHR) void k_gtcn_band(const float* __restrict__ xi
     auto slopes = [&](const float* pk, float (&a)[3]) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const float v = pk[TCN_SLOPE + j] - 1.0f;
+            const float v = slope_arg<Q>(pk[TCN_SLOPE + j]);
             a[j] = SPANS ? v : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
         }
     };
@@ -3192,13 +3223,13 @@ segment_top:
         f32x4 ze[TPW], zo[TPW];
         {
             const f32x4 Bv = ld4(sP + dl(D_DE3_B) + 4 * g);
-            const float a = sP[dl(D_DE3_S)] - 1.0f;
+            const float a = slope_arg<Q>(sP[dl(D_DE3_S)]);
             f32x4 ae[TPW], ao[TPW];
             de_conv3_tiles<TPW, SPLIT3, Q, RS>(sW, rec3, x, sP + DL_DE3M, Bv, n, g, ae, ao);
             const f32x4 A4 = ld4(sP + dl(D_DE4_A) + arow(n, g));
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
-                f32x4 e2 = rq<Q>(prelu4(ae[i], a)), o2 = rq<Q>(prelu4(ao[i], a));
+                f32x4 e2 = rq<Q>(prelu4q<Q>(ae[i], a)), o2 = rq<Q>(prelu4q<Q>(ao[i], a));
                 if (DBG && tt.pp(i) < npos && t0 + tt.tl[i] >= wlo) {
                     float* d3 = dbg + 3 * nbt * 528 + ((ob + t0 + tt.tl[i]) * F1) * 16 + 4 * g;
                     st4(d3 + (2 * tt.ff[i]) * 16, e2);
@@ -4687,7 +4718,8 @@ int configure_kernels() {
                          reinterpret_cast<const void*>(k_decoder<true, 1, false, false>),
                          reinterpret_cast<const void*>(k_decoder<false, 2, false, false>),
                          reinterpret_cast<const void*>(k_decoder<true, 2, false, false>),
-                         reinterpret_cast<const void*>(k_decoder<false, TPW, false, true>)};
+                         reinterpret_cast<const void*>(k_decoder<false, TPW, false, true>),
+                         reinterpret_cast<const void*>(k_decoder<true, TPW, false, true>)};
     for (const void* f : dec) {
         e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, DEC_LDS_FLOATS * 4);
         if (e != hipSuccess) return (int)e;
@@ -4854,9 +4886,15 @@ int launch_decoder(const float* xg, const float* en0, const float* en1, const fl
                        en2, en3, en4, spec, sb, sf, st, out, osb, osf, ost, T, lens, B, 0.f, 0.f, PF, PI, state, dbg,   \
                        stamps)
     if (q) {
-        hipLaunchKernelGGL((k_decoder<false, TPW, false, true>), dim3(B), dim3(NTHR), DEC_LDS_FLOATS * 4, s, xg, en0, en1,
-                           en2, en3, en4, spec, sb, sf, st, out, osb, osf, ost, T, lens, B, q->in_step, q->out_step, PF,
-                           PI, (float*)nullptr, (float*)nullptr, stamps);
+        // (dbg: the stage-tap instantiation, de0..de4 as fp32 copies of the fp16-valued registers)
+        if (dbg)
+            hipLaunchKernelGGL((k_decoder<true, TPW, false, true>), dim3(B), dim3(NTHR), DEC_LDS_FLOATS * 4, s, xg, en0, en1,
+                               en2, en3, en4, spec, sb, sf, st, out, osb, osf, ost, T, lens, B, q->in_step, q->out_step, PF,
+                               PI, (float*)nullptr, dbg, stamps);
+        else
+            hipLaunchKernelGGL((k_decoder<false, TPW, false, true>), dim3(B), dim3(NTHR), DEC_LDS_FLOATS * 4, s, xg, en0, en1,
+                               en2, en3, en4, spec, sb, sf, st, out, osb, osf, ost, T, lens, B, q->in_step, q->out_step, PF,
+                               PI, (float*)nullptr, (float*)nullptr, stamps);
     } else if (!dbg && use_multi_stream(T, state, sb) && use_multi_stream(T, state, osb)) {
         const int grid = (B + MS_STREAMS - 1) / MS_STREAMS;
         hipLaunchKernelGGL((k_decoder<false, 1, true, false>), dim3(grid), dim3(NTHR), DEC_MS_LDS_FLOATS * 4, s, xg, en0,

@@ -116,8 +116,27 @@ int gtcrn_forward_wave_var(gtcrn_model *m, const float *d_wave, float *d_wave_ou
  *                x_q = clip(round(x / (scale/255)), -128, 127), x = x_q * scale/255 (tflite_infer.py:79-92 with zero
  *                point 0; the calibration convention x/scale + 0.5 in [0,1] of utils/calibration_data.py:97-106 is
  *                this quantiser, scale = 19.944473 in streaming/tflite/calib_scale.txt).  0 = fp16 boundary.
+ *   functions    PReLU(x) = max(x, 0) + a * min(x, 0) (a * x rounded once); magnitude = sqrt(re^2 + im^2 + 1e-12)
+ *                (__builtin_amdgcn_sqrtf, 1 ulp); TRA gate sigmoid(z) = __frcp_rn(1 + __expf(-z)); mask
+ *                tanh(x) = 1 - 2 * __frcp_rn(__expf(2x) + 1) -- absolute error ~1e-7, i.e. a LARGE relative error of a
+ *                small mask value, which the fp16 rounding behind it then shows; each is rounded to fp16 like any
+ *                other activation, as an fp32 value (never a fused multiply-add rounded straight to fp16)
  * Same shapes/strides as gtcrn_forward_spec / gtcrn_forward_wave (STFT and iSTFT stay fp32: they are the caller's
- * torch.stft / torch.istft around the tflite interpreter, tflite_infer.py:63-101).  Offline only. */
+ * torch.stft / torch.istft around the tflite interpreter, tflite_infer.py:63-101).  Offline only.
+ *
+ * Stage taps (gtcrn_debug_tap after a _quant forward that ran with gtcrn_debug_enable(m, 1); without it every tap is
+ * refused with GTCRN_ERR_STATE, as the fp32 stage taps do not read fp16 records; tests/test_gpu_quant_stages.py pins a
+ * float64 checker of this contract to them, stage by stage).  Every tap comes back as float in the fp32 taps' (C,T,F) layout and holds fp16
+ * numbers only:
+ *   en0 .. en4   the encoder's hand-off tensors, fp16 records (same element offsets as the fp32 ones, half the bytes),
+ *                widened on the host
+ *   gtcn1        the first GTCN stack's output, likewise
+ *   sum4         what the second stack stores: fp16(gtcn2(x) + en4), the decoder's first input.  "gtcn2" is REFUSED
+ *                after a _quant forward (GTCRN_ERR_STATE): the rounded sum cannot be un-added (after an fp32 forward
+ *                "gtcn2" is sum4 - en4 as before, and "sum4" the stored sum)
+ *   de0 .. de2   the decoder blocks' outputs before the skip sum; de3; de4 = the tanh mask (2,T,129): fp32 copies
+ *                written by the stage-tap build of the decoder, whose output is bit-identical to the plain build's
+ * The taps follow the variant of the most recent forward. */
 int gtcrn_forward_spec_quant(gtcrn_model *m, const float *d_spec_in, long isb, long isf, long ist,
                              float *d_spec_out, long osb, long osf, long ost, int B, int T, float in_scale,
                              float out_scale, void *stream);

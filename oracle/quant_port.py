@@ -21,8 +21,22 @@ float32 sums, the default) rounds to fp16.  split=True forms every conv / linear
 halves of its reduction, added: a third order.  The distance between two of them is the flip-noise floor of the contract
 (tests/quant_cases.py); the kernels' MFMA k-order is one more draw of the same noise.
 
-Mutants.  QuantPort(..., mutate=name) seeds ONE bug in ONE place (MUTANTS below): what a checker of this variant has to
-reject.  They exist for tests/test_quant_checker.py only.
+Transcendentals.  fn="aten" (default) calls ATen's sqrt / sigmoid / tanh in self.dt.  fn="kernel" evaluates, in float32,
+the forms the header names for the kernels: sigmoid(z) = 1 / (1 + exp(-z)), tanh(x) = 1 - 2 / (exp(2x) + 1) (sqrt is the
+float32 square root either way).  The second tanh form cancels for small |x| (absolute error ~1e-7, a large relative
+error of a small mask value that is about to be rounded to fp16): one more stand-in for the floors of the stages that
+hold such a function (tests/quant_cases.py: TRANSCENDENTAL_STAGES).
+
+Stage taps and pins.  forward(..., pins=, taps=) works at the 13 boundaries STAGES: en0..en4 (encoder outputs), gtcn1
+(first stack), sum4 (h16(gtcn2(x) + en4), the decoder's first input -- what the kernels store), de0..de2 (block
+outputs BEFORE the skip sum, which belongs to the next stage), de3, de4 (the tanh mask, (B,2,T,129)) and out (the
+result).  `taps` (a dict) receives the checker's own float32 value at each boundary, (B,C,T,F); `pins` (a dict, any
+subset) replaces it with the given one before anything downstream reads it -- the skip connections included.  Pinned to
+a device's taps, every stage is evaluated from the device's own stage inputs: differences no longer avalanche past one
+stage (tests/quant_cases.py: accept_stages).  With neither argument nothing changes, bit for bit.
+
+Mutants.  QuantPort(..., mutate=name) seeds ONE bug in ONE place (MUTANTS below: name -> (stage it is seeded in, what
+it is)): what a checker of this variant has to reject.  They exist for tests/test_quant_checker.py only.
 """
 import numpy as np
 import torch
@@ -63,25 +77,38 @@ def quant_per_out_channel(w, out_dim=0, per_tensor=False):
     return h16((q * scale).float())
 
 
-# name -> the one place the bug is seeded in
+STAGES = ("en0", "en1", "en2", "en3", "en4", "gtcn1", "sum4", "de0", "de1", "de2", "de3", "de4", "out")
+
+# name -> (the stage the bug is seeded in, the one place).  The two boundary mutants change the quantised spectrogram,
+# which the first stage AND the mask product of the last one read (BOUNDARY_MUTANTS: also seen in "out").
 MUTANTS = {
-    "drop_tap": "encoder.en_convs.3.depth_conv: tap (current frame, centre bin) of channel 0 set to 0",
-    "drop_tcn_tap": "gtcn2.blocks.3.conv2 (d = 8): the oldest tap (16 frames back) set to 0",
-    "no_round": "decoder.de_convs.1.point_conv2: its fp16 rounding skipped",
-    "per_tensor_scale": "encoder.en_convs.2.point_conv2: one weight scale for the tensor, not one per output channel",
-    "clamp127": "input boundary clamped to -127 .. 127",
-    "ties_away": "input and output boundary round half away from zero",
-    "tra_hist": "encoder.en_convs.4.tra: one frame of energy history instead of two",
-    "skip_unrounded": "decoder.de_convs.1: its skip sum x + skips[3] left unrounded",
-    "stale_hist_16": "encoder.en_convs.2.depth_conv: the two history rows zero at every frame = 0 mod 16",
+    "drop_tap": ("en3", "encoder.en_convs.3.depth_conv: tap (current frame, centre bin) of channel 0 set to 0"),
+    "drop_tcn_tap": ("sum4", "gtcn2.blocks.3.conv2 (d = 8): the oldest tap (16 frames back) set to 0"),
+    "no_round": ("de1", "decoder.de_convs.1.point_conv2: its fp16 rounding skipped"),
+    "per_tensor_scale": ("en2", "encoder.en_convs.2.point_conv2: one weight scale for the tensor, not one per output channel"),
+    "clamp127": ("en0", "input boundary clamped to -127 .. 127"),
+    "ties_away": ("en0", "input and output boundary round half away from zero"),
+    "tra_hist": ("en4", "encoder.en_convs.4.tra: one frame of energy history instead of two"),
+    "skip_unrounded": ("de1", "decoder.de_convs.1: its skip sum x + skips[3] left unrounded"),
+    "stale_hist_16": ("en2", "encoder.en_convs.2.depth_conv: the two history rows zero at every frame = 0 mod 16"),
+    # one missed rounding each: invisible at the output once the flip noise has saturated, plain under pins
+    "mag_unrounded": ("en0", "the magnitude sqrt(re^2 + im^2 + 1e-12): its fp16 rounding skipped"),
+    "en1_unrounded": ("en1", "encoder.en_convs.1: the fp16 rounding of its PReLU output skipped"),
+    "tcn1_act2_unrounded": ("gtcn1", "gtcn1.blocks.2.act2: its fp16 rounding skipped"),
+    "tcn2_act3_unrounded": ("sum4", "gtcn2.blocks.0.act3: its fp16 rounding skipped"),
+    "gate_unrounded": ("en3", "encoder.en_convs.3.tra: the sigmoid gate left unrounded"),
+    "de3_unrounded": ("de3", "decoder.de_convs.3: the fp16 rounding of its PReLU output skipped"),
+    "ierb_unrounded": ("out", "the inverse-ERB sum of the mask: its fp16 rounding skipped"),
 }
+BOUNDARY_MUTANTS = ("clamp127", "ties_away")
 
 
 class QuantPort:
-    def __init__(self, blob, acc="f32", mutate=None, split=False):
+    def __init__(self, blob, acc="f32", mutate=None, split=False, fn="aten"):
         assert acc in ("f32", "f64") and (mutate is None or mutate in MUTANTS) and not (split and acc != "f32")
+        assert fn in ("aten", "kernel") and not (fn == "kernel" and acc != "f32")
         self.dt = torch.float64 if acc == "f64" else torch.float32
-        self.mutate, self.split = mutate, split
+        self.mutate, self.split, self.fn = mutate, split, fn
         p = {k: v.double() for k, v in blob_to_dict(blob).items()}
         self.p = p
         self.w, self.b = {}, {}
@@ -136,11 +163,22 @@ class QuantPort:
             y = y + b.view([1, -1] + [1] * (y.dim() - 2)) if fn is not F.linear else y + b
         return y
 
+    def _rnd(self, x, site):
+        """h16, unless the mutant is the missed rounding at `site`."""
+        return x if site is not None and self.mutate == site else h16(x)
+
+    def _sigmoid(self, z):
+        return torch.reciprocal(1.0 + torch.exp(-z)) if self.fn == "kernel" else torch.sigmoid(z)
+
+    def _tanh(self, x):
+        return 1.0 - 2.0 * torch.reciprocal(torch.exp(2.0 * x) + 1.0) if self.fn == "kernel" else torch.tanh(x)
+
     def _tra(self, v, pre):
         f = self.f
         e = (v * v).mean(dim=3)
         y = self._sum(F.conv1d, F.pad(e, [2, 0]), self.w[pre + ".depth_conv"], f[pre + ".depth_conv.bias"], groups=8)
-        g = h16(torch.sigmoid(self._sum(F.conv1d, y, self.w[pre + ".point_conv"], f[pre + ".point_conv.bias"])))
+        g = self._sigmoid(self._sum(F.conv1d, y, self.w[pre + ".point_conv"], f[pre + ".point_conv.bias"]))
+        g = self._rnd(g, "gate_unrounded" if pre == "encoder.en_convs.3.tra" else None)
         return h16(v * g.unsqueeze(-1))
 
     def _gtconv(self, x, pre, deconv):
@@ -169,49 +207,65 @@ class QuantPort:
         f, w, b = self.f, self.w, self.b
         y = h16(F.prelu(self._sum(F.conv2d, x, w[pre + ".conv1"], b[pre + ".conv1"]), f[pre + ".act1.weight"]))
         y = self._sum(F.conv2d, F.pad(y, [0, 0, 2 * d, 0]), w[pre + ".conv2"], b[pre + ".conv2"], dilation=(d, 1), groups=16)
-        y = h16(F.prelu(y, f[pre + ".act2.weight"]))
+        y = self._rnd(F.prelu(y, f[pre + ".act2.weight"]), "tcn1_act2_unrounded" if pre == "gtcn1.blocks.2" else None)
         y = self._sum(F.conv2d, y, w[pre + ".conv3"], b[pre + ".conv3"])
-        return h16(F.prelu(y + x, f[pre + ".act3.weight"]))
+        return self._rnd(F.prelu(y + x, f[pre + ".act3.weight"]), "tcn2_act3_unrounded" if pre == "gtcn2.blocks.0" else None)
 
     def _skip(self, x, skips, i):
         s = x + skips[i]
         return s if self.mutate == "skip_unrounded" and i == 3 else h16(s)
 
     @torch.inference_mode()
-    def forward(self, spec, in_scale=0.0, out_scale=0.0):
+    def forward(self, spec, in_scale=0.0, out_scale=0.0, pins=None, taps=None):
         f, w, b = self.f, self.w, self.b
         away = self.mutate == "ties_away"
+
+        def stage(name, x):
+            """A stage boundary: hand the checker's value to `taps`, go on with the pinned one if there is one."""
+            if taps is not None:
+                taps[name] = x.float().contiguous().numpy().copy()
+            if pins is not None and name in pins:
+                x = torch.as_tensor(np.asarray(pins[name], np.float32)).to(self.dt)
+            return x
         spec = torch.as_tensor(spec, dtype=torch.float32)
         if in_scale > 0:
             spec = int8_boundary(spec, in_scale, -127 if self.mutate == "clamp127" else -128, away)
         spec = h16(spec).to(self.dt)
         re, im = spec[..., 0].permute(0, 2, 1), spec[..., 1].permute(0, 2, 1)
-        feat = torch.stack([h16(torch.sqrt(re * re + im * im + 1e-12)), re, im], dim=1)
+        feat = torch.stack([self._rnd(torch.sqrt(re * re + im * im + 1e-12), "mag_unrounded"), re, im], dim=1)
         feat = torch.cat([feat[..., :65], h16(self._sum(F.linear, feat[..., 65:], w["erb"]))], dim=-1)
         x = h16(self._sum(F.conv2d, feat, w["sfe"], padding=(0, 1), groups=3))
         skips = []
         for i in range(2):
             pre = f"encoder.en_convs.{i}"
             x = self._sum(F.conv2d, x, w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
-            x = h16(F.prelu(x, f[pre + ".act.weight"]))
+            x = self._rnd(F.prelu(x, f[pre + ".act.weight"]), "en1_unrounded" if i == 1 else None)
+            x = stage(f"en{i}", x)
             skips.append(x)
         for i in range(2, 5):
-            x = self._gtconv(x, f"encoder.en_convs.{i}", False)
+            x = stage(f"en{i}", self._gtconv(x, f"encoder.en_convs.{i}", False))
             skips.append(x)
         for g in (1, 2):
             for k in range(4):
                 x = self._tcn(x, f"gtcn{g}.blocks.{k}", 1 << k)
+            if g == 1:
+                x = stage("gtcn1", x)
+        x = stage("sum4", self._skip(x, skips, 4))
         for i in range(3):
-            x = self._gtconv(self._skip(x, skips, 4 - i), f"decoder.de_convs.{i}", True)
+            x = stage(f"de{i}", self._gtconv(x, f"decoder.de_convs.{i}", True))
+            x = self._skip(x, skips, 3 - i)
         pre = "decoder.de_convs.3"
-        x = self._sum(F.conv_transpose2d, self._skip(x, skips, 1), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
-        x = h16(F.prelu(x, f[pre + ".act.weight"]))
+        x = self._sum(F.conv_transpose2d, x, w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
+        x = stage("de3", self._rnd(F.prelu(x, f[pre + ".act.weight"]), "de3_unrounded"))
         pre = "decoder.de_convs.4"
         m = self._sum(F.conv_transpose2d, self._skip(x, skips, 0), w[pre + ".conv"], b[pre + ".conv"], stride=(1, 2), padding=(0, 2))
-        m = h16(torch.tanh(m))
-        m = torch.cat([m[..., :65], h16(self._sum(F.linear, m[..., 65:], w["ierb"]))], dim=-1)
+        m = stage("de4", h16(self._tanh(m)))
+        m = torch.cat([m[..., :65], self._rnd(self._sum(F.linear, m[..., 65:], w["ierb"]), "ierb_unrounded")], dim=-1)
         out = torch.stack([h16(re * m[:, 0] - im * m[:, 1]), h16(im * m[:, 0] + re * m[:, 1])], dim=-1).permute(0, 2, 1, 3)
         out = out.float()
         if out_scale > 0:
             out = int8_boundary(out, out_scale, ties_away=away)
-        return out.contiguous().numpy()
+        out = out.contiguous().numpy()
+        if taps is not None:
+            taps["out"] = out.copy()
+        return out
