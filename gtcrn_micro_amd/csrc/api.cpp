@@ -1227,6 +1227,9 @@ struct PkGeom {
     int n16 = 0, g = 0, hmax = 0;   // packet at 16 kHz; gcd(n16, 256); the most hops one call steps
     int d_in = 0, d_out = 0;        // the two causal stages' delays in 16 kHz samples (0 at 16 kHz)
     RsDesign in, out;               // (no taps) fs -> 16000 and 16000 -> fs; ntp = 0 at 16 kHz
+    // the per-stream state row (floats): [inbound FIFO | outbound FIFO | inbound stage history | outbound stage history]
+    int hist_off() const { return 2 * gtk::PK_FIFO + in.ntp; }        // to the outbound stage's history
+    long ps_stride() const { return hist_off() + out.ntp; }
 };
 
 bool pk_rate_ok(int fs) {
@@ -1329,7 +1332,7 @@ int gtcrn_packet_stream_latency16(int fs, int n) {
 size_t gtcrn_packet_stream_state_bytes(int fs, int n) {
     PkGeom p;
     if (!pk_geometry(fs, n, &p)) { (void)fail(GTCRN_ERR_ARG, std::string("gtcrn_packet_stream_state_bytes") + kPkBad); return 0; }
-    return sizeof(float) * (size_t)(2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp);
+    return sizeof(float) * (size_t)p.ps_stride();
 }
 int gtcrn_packet_stream_schedule(int fs, int n, int phase, int* next_phase) {
     PkGeom p;
@@ -1408,87 +1411,19 @@ int gtcrn_packet_stream_reset(gtcrn_packet_stream* ps, void* d_state, void* d_ws
     if (int rc = gtcrn_wave_stream_reset(ps->m, d_state, d_wstate, nstreams, stream)) return rc;
     // zeros ARE the pre-roll: the FIFO levels follow from the handle's phase, so a stream reset at phase z holds z zeros
     // inbound and 256 - g - z zeros outbound
-    HIP_TRY(hipMemsetAsync(d_pstate, 0, gtcrn_packet_stream_state_bytes(ps->fs, ps->n) * nstreams, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(d_pstate, 0, sizeof(float) * (size_t)ps->p.ps_stride() * nstreams, (hipStream_t)stream));
     return 0;
-}
-
-extern "C++" template <typename S>
-static int packet_stream_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
-                              const S* d_in, long in_stride, S* d_out, long out_stride, int nstreams, const float* d_win,
-                              void* stream, const PkHb* hb = nullptr) {
-    const std::string w(who);
-    if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
-    if (!d_state || !d_wstate || !d_pstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (nstreams < 1 || nstreams > ps->max_streams)
-        return fail(GTCRN_ERR_ARG, w + ": nstreams must be >= 1 and at most the handle's max_streams");
-    if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_pstate})) return rc0;
-    int l16 = 0, lat = 0;
-    if (hb)
-        if (int rc0 = packet_hb_args(w, ps, hb, d_in, in_stride, d_out, out_stride, nstreams, &l16, &lat)) return rc0;
-    gtcrn_model* m = ps->m;
-    int rc = check_model(m);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const PkGeom& p = ps->p;
-    const int phi = ps->phase, h = (phi + p.n16) / 256, lvl = 256 - p.g - phi;
-    const long row = 256L * h, ps_stride = 2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp;
-    float* pst = static_cast<float*>(d_pstate);
-    if (h && (rc = ensure_workspace(m, nstreams, h, s))) return rc;       // (create reserved max_streams x hmax)
-    Timer tm(m, s);
-    tm.begin(K_PACKET_IN);
-    LAUNCH_TRY(gtk::launch_packet_in<S>(d_in, in_stride, ps->n, ps->d_a, row, pst, ps_stride, nstreams, phi, p.n16, h, p.in.up,
-                                        p.in.down, p.in.ntp, ps->in ? ps->in->d_taps : nullptr, s));
-    tm.end();
-    if (h) {
-        rc = wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, ps->d_a, row, ps->d_b, row, nstreams, h, false, 0,
-                              ps->d_gain, d_win, {}, stream);
-        if (rc) return rc;
-    }
-    tm.begin(K_PACKET_OUT);                 // (the high-band kernel is timed in the row of the kernel it stands in for)
-    if constexpr (std::is_same<S, float>::value || std::is_same<S, short>::value) {
-        if (hb)
-            LAUNCH_TRY(gtk::launch_packet_out_hb<S>(ps->d_b, ps->d_a, row, d_in, in_stride, d_out, out_stride, ps->n, pst, ps_stride,
-                                                    2 * gtk::PK_FIFO + p.in.ntp, static_cast<float*>(hb->d_hbstate),
-                                                    pk_hb_stride(l16, lat), hb->d_gain, l16, lat, nstreams, phi, p.n16, h,
-                                                    p.out.up, p.out.down, p.out.ntp, ps->out->d_taps, s));
-    }
-    if (!hb)
-        LAUNCH_TRY(gtk::launch_packet_out<S>(ps->d_b, row, d_out, out_stride, ps->n, pst, ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
-                                             nstreams, lvl, p.n16, h, p.out.up, p.out.down, p.out.ntp,
-                                             ps->out ? ps->out->d_taps : nullptr, s));
-    tm.end();
-    ps->phase = (phi + p.n16) % 256;
-    ps->last_h = h;
-    ps->last_n = nstreams;
-    return 0;
-}
-int gtcrn_packet_stream_step(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const float* d_in,
-                             long in_stride, float* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
-    return packet_stream_impl<float>("gtcrn_packet_stream_step", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
-                                     out_stride, nstreams, d_win, stream);
-}
-int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const short* d_in,
-                                   long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
-    return packet_stream_impl<short>("gtcrn_packet_stream_step_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
-                                     out_stride, nstreams, d_win, stream);
-}
-// G.711 rows: the same call with the law as the sample type (gtk::g711u / g711a); the strides are in bytes = samples
-int gtcrn_packet_stream_step_g711(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
-                                  const unsigned char* d_in, long in_stride, unsigned char* d_out, long out_stride, int nstreams,
-                                  int law, const float* d_win, void* stream) {
-    const char* who = "gtcrn_packet_stream_step_g711";
-    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
-    if (law == 0)
-        return packet_stream_impl<gtk::g711u>(who, ps, d_state, d_wstate, d_pstate, reinterpret_cast<const gtk::g711u*>(d_in),
-                                              in_stride, reinterpret_cast<gtk::g711u*>(d_out), out_stride, nstreams, d_win, stream);
-    return packet_stream_impl<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, reinterpret_cast<const gtk::g711a*>(d_in),
-                                          in_stride, reinterpret_cast<gtk::g711a*>(d_out), out_stride, nstreams, d_win, stream);
 }
 
 // ---- packet stream slots (contract: include/gtcrn_micro_hip.h): the phase is one device word per slot, and a call is
 // plan -> k_packet_in_slots -> hmax rounds of the indexed wave step -> k_packet_out_slots whatever the phases are.
 namespace {
+// the slot arguments of a packet step (null: the contiguous call, whose phase is the handle's)
+struct PkSlots {
+    int* d_phase = nullptr;
+    const int* d_slots = nullptr;
+    const int* d_count = nullptr;
+};
 int packet_slots_args(const std::string& w, gtcrn_packet_stream* ps, const void* d_state, const void* d_wstate,
                       const void* d_pstate, const int* d_phase, const int* d_slots, int max_active) {
     if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
@@ -1500,6 +1435,108 @@ int packet_slots_args(const std::string& w, gtcrn_packet_stream* ps, const void*
 }
 }  // namespace
 
+// One packet step, every entry point's: checks, (slots) the plan, the inbound launch, the wave step, the outbound launch.
+// nrows: nstreams, or with `sl` the call's max_active.  Each form refuses in the order its contract states.
+extern "C++" template <typename S>
+static int packet_step(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const PkSlots* sl,
+                       int nrows, const S* d_in, long in_stride, S* d_out, long out_stride, const float* d_win, void* stream,
+                       const PkHb* hb = nullptr) {
+    const std::string w(who);
+    if (sl) {
+        if (int rc0 = packet_slots_args(w, ps, d_state, d_wstate, d_pstate, sl->d_phase, sl->d_slots, nrows)) return rc0;
+        if (!d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+    } else {
+        if (!ps) return fail(GTCRN_ERR_ARG, w + ": null handle");
+        if (!d_state || !d_wstate || !d_pstate || !d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
+        if (nrows < 1 || nrows > ps->max_streams)
+            return fail(GTCRN_ERR_ARG, w + ": nstreams must be >= 1 and at most the handle's max_streams");
+    }
+    if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
+    if (!sl)
+        if (int rc0 = check_state_alignment(w, {d_state, d_wstate, d_pstate})) return rc0;
+    int l16 = 0, lat = 0;
+    if (hb)
+        if (int rc0 = packet_hb_args(w, ps, hb, d_in, in_stride, d_out, out_stride, nrows, &l16, &lat)) return rc0;
+    gtcrn_model* m = ps->m;
+    int rc = check_model(m);
+    if (rc) return rc;
+    if (sl && (rc = refuse_three_launch_form(w, m))) return rc;           // (before the plan: nothing runs on a refusal)
+    hipStream_t s = (hipStream_t)stream;
+    const PkGeom& p = ps->p;
+    // contiguous: h hops of every row at the handle's phase (possibly none); slots: hmax one-hop rounds of the rows the plan names
+    const int phi = sl ? 0 : ps->phase, h = sl ? 1 : (phi + p.n16) / 256, M = ps->max_streams;
+    if (h && (rc = ensure_workspace(m, nrows, h, s))) return rc;          // (create reserved max_streams x hmax)
+    const gtk::PkPacket pk{ps->n, p.n16, p.g};
+    const gtk::PkState st{static_cast<float*>(d_pstate), p.ps_stride(), p.hist_off()};
+    gtk::PkRows rw;
+    rw.N = nrows;
+    if (sl) { rw.rows = gtk::Rows{sl->d_slots, sl->d_count}; rw.phi_rec = ps->phi_rec(); rw.pos = ps->pos(); rw.M = M; }
+    else { rw.phi = phi; rw.hand_stride = 256L * h; }
+    Timer tm(m, s);
+    if (sl) {
+        tm.begin(K_PACKET_PLAN);
+        LAUNCH_TRY(gtk::launch_packet_plan(sl->d_slots, sl->d_count, nrows, sl->d_phase, p.n16, p.hmax, M, ps->tab(0), ps->pos(),
+                                           ps->phi_rec(), ps->cnts(), s));
+        tm.end();
+    }
+    tm.begin(sl ? K_PACKET_IN_SLOTS : K_PACKET_IN);
+    LAUNCH_TRY(gtk::launch_packet_in<S>(d_in, in_stride, ps->d_a, pk, st, rw,
+                                        {p.in.up, p.in.down, p.in.ntp, ps->in ? ps->in->d_taps : nullptr}, s));
+    tm.end();
+    if (sl) {
+        const long block = 256L * M;
+        for (int r = 0; r < p.hmax; ++r) {
+            // round r: one hop of the rows that have more than r ready; an empty round's workgroups return at once
+            rc = wave_step<float>(who, m, d_state, d_wstate, ps->d_a + block * r, 256, ps->d_b + block * r, 256, nrows, 1, false, 0,
+                                  ps->d_gain, d_win, gtk::Rows{ps->tab(r), ps->cnts() + r}, stream);
+            if (rc) return rc;
+        }
+    } else if (h) {
+        rc = wave_step<float>("gtcrn_wave_stream_step", m, d_state, d_wstate, ps->d_a, rw.hand_stride, ps->d_b, rw.hand_stride,
+                              nrows, h, false, 0, ps->d_gain, d_win, {}, stream);
+        if (rc) return rc;
+    }
+    gtk::PkHighBand band;
+    if (hb) band = {ps->d_a, static_cast<float*>(hb->d_hbstate), pk_hb_stride(l16, lat), hb->d_gain, l16, lat};
+    tm.begin(sl ? K_PACKET_OUT_SLOTS : K_PACKET_OUT);   // (the high-band kernel is timed in the row of the kernel it stands in for)
+    LAUNCH_TRY(gtk::launch_packet_out<S>(ps->d_b, d_in, in_stride, d_out, out_stride, pk, st, rw,
+                                         {p.out.up, p.out.down, p.out.ntp, ps->out ? ps->out->d_taps : nullptr}, hb ? &band : nullptr,
+                                         s));
+    tm.end();
+    if (!sl) ps->phase = (phi + p.n16) % 256;
+    // (a slot call leaves no contiguous hand-off to copy: gtcrn_packet_stream_debug_handoff is out of scope for it)
+    ps->last_h = sl ? 0 : h;
+    ps->last_n = sl ? 0 : nrows;
+    return 0;
+}
+// G.711 rows: the same step with the law as the sample type (gtk::g711u / g711a); the strides are in bytes = samples
+static int packet_step_g711(const char* who, int law, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
+                            const PkSlots* sl, int nrows, const unsigned char* d_in, long in_stride, unsigned char* d_out,
+                            long out_stride, const float* d_win, void* stream) {
+    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
+    if (law == 0)
+        return packet_step<gtk::g711u>(who, ps, d_state, d_wstate, d_pstate, sl, nrows, reinterpret_cast<const gtk::g711u*>(d_in),
+                                       in_stride, reinterpret_cast<gtk::g711u*>(d_out), out_stride, d_win, stream);
+    return packet_step<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, sl, nrows, reinterpret_cast<const gtk::g711a*>(d_in),
+                                   in_stride, reinterpret_cast<gtk::g711a*>(d_out), out_stride, d_win, stream);
+}
+int gtcrn_packet_stream_step(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const float* d_in,
+                             long in_stride, float* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return packet_step<float>("gtcrn_packet_stream_step", ps, d_state, d_wstate, d_pstate, nullptr, nstreams, d_in, in_stride,
+                              d_out, out_stride, d_win, stream);
+}
+int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const short* d_in,
+                                   long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win, void* stream) {
+    return packet_step<short>("gtcrn_packet_stream_step_pcm16", ps, d_state, d_wstate, d_pstate, nullptr, nstreams, d_in,
+                              in_stride, d_out, out_stride, d_win, stream);
+}
+int gtcrn_packet_stream_step_g711(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
+                                  const unsigned char* d_in, long in_stride, unsigned char* d_out, long out_stride, int nstreams,
+                                  int law, const float* d_win, void* stream) {
+    return packet_step_g711("gtcrn_packet_stream_step_g711", law, ps, d_state, d_wstate, d_pstate, nullptr, nstreams, d_in,
+                            in_stride, d_out, out_stride, d_win, stream);
+}
+
 int gtcrn_packet_stream_reset_slots(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                     const int* d_slots, const int* d_count, int max_active, void* stream) {
     const std::string w("gtcrn_packet_stream_reset_slots");
@@ -1508,93 +1545,32 @@ int gtcrn_packet_stream_reset_slots(gtcrn_packet_stream* ps, void* d_state, void
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     LAUNCH_TRY(gtk::launch_reset_slots(static_cast<float*>(d_state), static_cast<float*>(d_wstate), d_slots, d_count, max_active, s));
-    LAUNCH_TRY(gtk::launch_packet_reset_slots(static_cast<float*>(d_pstate), (long)(gtcrn_packet_stream_state_bytes(ps->fs, ps->n) / sizeof(float)),
-                                              d_phase, d_slots, d_count, max_active, s));
+    LAUNCH_TRY(gtk::launch_packet_reset_slots(static_cast<float*>(d_pstate), ps->p.ps_stride(), d_phase, d_slots, d_count,
+                                              max_active, s));
     return 0;
 }
 
-extern "C++" template <typename S>
-static int packet_slots_impl(const char* who, gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate,
-                             int* d_phase, const int* d_slots, const int* d_count, int max_active, const S* d_in,
-                             long in_stride, S* d_out, long out_stride, const float* d_win, void* stream,
-                             const PkHb* hb = nullptr) {
-    const std::string w(who);
-    if (int rc0 = packet_slots_args(w, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, max_active)) return rc0;
-    if (!d_in || !d_out || !d_win) return fail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (in_stride < ps->n || out_stride < ps->n) return fail(GTCRN_ERR_ARG, w + ": a stride is shorter than its row");
-    int l16 = 0, lat = 0;
-    if (hb)
-        if (int rc0 = packet_hb_args(w, ps, hb, d_in, in_stride, d_out, out_stride, max_active, &l16, &lat)) return rc0;
-    gtcrn_model* m = ps->m;
-    int rc = check_model(m);
-    if (rc) return rc;
-    if ((rc = refuse_three_launch_form(w, m))) return rc;                 // (before the plan: nothing runs on a refusal)
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = ensure_workspace(m, max_active, 1, s))) return rc;          // (create reserved max_streams x hmax)
-    const PkGeom& p = ps->p;
-    const int M = ps->max_streams;
-    const long ps_stride = 2 * gtk::PK_FIFO + p.in.ntp + p.out.ntp, block = 256L * M;
-    float* pst = static_cast<float*>(d_pstate);
-    Timer tm(m, s);
-    tm.begin(K_PACKET_PLAN);
-    LAUNCH_TRY(gtk::launch_packet_plan(d_slots, d_count, max_active, d_phase, p.n16, p.hmax, M, ps->tab(0), ps->pos(),
-                                       ps->phi_rec(), ps->cnts(), s));
-    tm.end();
-    tm.begin(K_PACKET_IN_SLOTS);
-    LAUNCH_TRY(gtk::launch_packet_in_slots<S>(d_in, in_stride, ps->n, ps->d_a, M, pst, ps_stride, d_slots, d_count, max_active,
-                                              ps->phi_rec(), ps->pos(), p.n16, p.in.up, p.in.down, p.in.ntp,
-                                              ps->in ? ps->in->d_taps : nullptr, s));
-    tm.end();
-    for (int r = 0; r < p.hmax; ++r) {
-        // round r: one hop of the rows that have more than r ready; an empty round's workgroups return at once
-        rc = wave_step<float>(who, m, d_state, d_wstate, ps->d_a + block * r, 256, ps->d_b + block * r, 256, max_active, 1, false,
-                              0, ps->d_gain, d_win, gtk::Rows{ps->tab(r), ps->cnts() + r}, stream);
-        if (rc) return rc;
-    }
-    tm.begin(K_PACKET_OUT_SLOTS);
-    if constexpr (std::is_same<S, float>::value || std::is_same<S, short>::value) {
-        if (hb)
-            LAUNCH_TRY(gtk::launch_packet_out_slots_hb<S>(ps->d_b, ps->d_a, M, d_in, in_stride, d_out, out_stride, ps->n, pst,
-                                                          ps_stride, 2 * gtk::PK_FIFO + p.in.ntp,
-                                                          static_cast<float*>(hb->d_hbstate), pk_hb_stride(l16, lat), hb->d_gain,
-                                                          l16, lat, d_slots, d_count, max_active, ps->phi_rec(), ps->pos(), p.g,
-                                                          p.n16, p.out.up, p.out.down, p.out.ntp, ps->out->d_taps, s));
-    }
-    if (!hb)
-        LAUNCH_TRY(gtk::launch_packet_out_slots<S>(ps->d_b, M, d_out, out_stride, ps->n, pst, ps_stride,
-                                                   2 * gtk::PK_FIFO + p.in.ntp, d_slots, d_count, max_active, ps->phi_rec(),
-                                                   ps->pos(), p.g, p.n16, p.out.up, p.out.down, p.out.ntp,
-                                                   ps->out ? ps->out->d_taps : nullptr, s));
-    tm.end();
-    ps->last_h = 0;     // (no contiguous hand-off to copy: gtcrn_packet_stream_debug_handoff is out of scope for slot calls)
-    ps->last_n = 0;
-    return 0;
-}
 int gtcrn_packet_stream_step_slots(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                    const int* d_slots, const int* d_count, int max_active, const float* d_in, long in_stride,
                                    float* d_out, long out_stride, const float* d_win, void* stream) {
-    return packet_slots_impl<float>("gtcrn_packet_stream_step_slots", ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count,
-                                    max_active, d_in, in_stride, d_out, out_stride, d_win, stream);
+    const PkSlots sl{d_phase, d_slots, d_count};
+    return packet_step<float>("gtcrn_packet_stream_step_slots", ps, d_state, d_wstate, d_pstate, &sl, max_active, d_in, in_stride,
+                              d_out, out_stride, d_win, stream);
 }
 int gtcrn_packet_stream_step_slots_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                          const int* d_slots, const int* d_count, int max_active, const short* d_in,
                                          long in_stride, short* d_out, long out_stride, const float* d_win, void* stream) {
-    return packet_slots_impl<short>("gtcrn_packet_stream_step_slots_pcm16", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
-                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream);
+    const PkSlots sl{d_phase, d_slots, d_count};
+    return packet_step<short>("gtcrn_packet_stream_step_slots_pcm16", ps, d_state, d_wstate, d_pstate, &sl, max_active, d_in,
+                              in_stride, d_out, out_stride, d_win, stream);
 }
 int gtcrn_packet_stream_step_slots_g711(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                         const int* d_slots, const int* d_count, int max_active, const unsigned char* d_in,
                                         long in_stride, unsigned char* d_out, long out_stride, int law, const float* d_win,
                                         void* stream) {
-    const char* who = "gtcrn_packet_stream_step_slots_g711";
-    if (law != 0 && law != 1) return fail(GTCRN_ERR_ARG, std::string(who) + ": law must be 0 (mu-law) or 1 (A-law)");
-    if (law == 0)
-        return packet_slots_impl<gtk::g711u>(who, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count, max_active,
-                                             reinterpret_cast<const gtk::g711u*>(d_in), in_stride,
-                                             reinterpret_cast<gtk::g711u*>(d_out), out_stride, d_win, stream);
-    return packet_slots_impl<gtk::g711a>(who, ps, d_state, d_wstate, d_pstate, d_phase, d_slots, d_count, max_active,
-                                         reinterpret_cast<const gtk::g711a*>(d_in), in_stride,
-                                         reinterpret_cast<gtk::g711a*>(d_out), out_stride, d_win, stream);
+    const PkSlots sl{d_phase, d_slots, d_count};
+    return packet_step_g711("gtcrn_packet_stream_step_slots_g711", law, ps, d_state, d_wstate, d_pstate, &sl, max_active, d_in,
+                            in_stride, d_out, out_stride, d_win, stream);
 }
 
 // ---- high band on the packet forms: the plain launch sequences with k_packet_out_hb / k_packet_out_slots_hb as the last launch
@@ -1641,31 +1617,33 @@ int gtcrn_packet_stream_step_hb(gtcrn_packet_stream* ps, void* d_state, void* d_
                                 long in_stride, float* d_out, long out_stride, int nstreams, const float* d_win, void* d_hbstate,
                                 const float* d_hb_gain, void* stream) {
     const PkHb hb{d_hbstate, d_hb_gain};
-    return packet_stream_impl<float>("gtcrn_packet_stream_step_hb", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
-                                     out_stride, nstreams, d_win, stream, &hb);
+    return packet_step<float>("gtcrn_packet_stream_step_hb", ps, d_state, d_wstate, d_pstate, nullptr, nstreams, d_in, in_stride,
+                              d_out, out_stride, d_win, stream, &hb);
 }
 int gtcrn_packet_stream_step_hb_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, const short* d_in,
                                       long in_stride, short* d_out, long out_stride, int nstreams, const float* d_win,
                                       void* d_hbstate, const float* d_hb_gain, void* stream) {
     const PkHb hb{d_hbstate, d_hb_gain};
-    return packet_stream_impl<short>("gtcrn_packet_stream_step_hb_pcm16", ps, d_state, d_wstate, d_pstate, d_in, in_stride, d_out,
-                                     out_stride, nstreams, d_win, stream, &hb);
+    return packet_step<short>("gtcrn_packet_stream_step_hb_pcm16", ps, d_state, d_wstate, d_pstate, nullptr, nstreams, d_in,
+                              in_stride, d_out, out_stride, d_win, stream, &hb);
 }
 int gtcrn_packet_stream_step_slots_hb(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                       const int* d_slots, const int* d_count, int max_active, const float* d_in, long in_stride,
                                       float* d_out, long out_stride, const float* d_win, void* d_hbstate, const float* d_hb_gain,
                                       void* stream) {
     const PkHb hb{d_hbstate, d_hb_gain};
-    return packet_slots_impl<float>("gtcrn_packet_stream_step_slots_hb", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
-                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream, &hb);
+    const PkSlots sl{d_phase, d_slots, d_count};
+    return packet_step<float>("gtcrn_packet_stream_step_slots_hb", ps, d_state, d_wstate, d_pstate, &sl, max_active, d_in,
+                              in_stride, d_out, out_stride, d_win, stream, &hb);
 }
 int gtcrn_packet_stream_step_slots_hb_pcm16(gtcrn_packet_stream* ps, void* d_state, void* d_wstate, void* d_pstate, int* d_phase,
                                             const int* d_slots, const int* d_count, int max_active, const short* d_in,
                                             long in_stride, short* d_out, long out_stride, const float* d_win, void* d_hbstate,
                                             const float* d_hb_gain, void* stream) {
     const PkHb hb{d_hbstate, d_hb_gain};
-    return packet_slots_impl<short>("gtcrn_packet_stream_step_slots_hb_pcm16", ps, d_state, d_wstate, d_pstate, d_phase, d_slots,
-                                    d_count, max_active, d_in, in_stride, d_out, out_stride, d_win, stream, &hb);
+    const PkSlots sl{d_phase, d_slots, d_count};
+    return packet_step<short>("gtcrn_packet_stream_step_slots_hb_pcm16", ps, d_state, d_wstate, d_pstate, &sl, max_active, d_in,
+                              in_stride, d_out, out_stride, d_win, stream, &hb);
 }
 
 long gtcrn_packet_stream_debug_handoff(gtcrn_packet_stream* ps, int which, float* d_dst, long n, void* stream) {

@@ -161,53 +161,65 @@ constexpr int PK_SEQ = PK_FIFO + PK_MAX16;       // LDS: a FIFO's content ++ wha
 constexpr int PK_HIST = 256;                     // LDS in front of the outbound sequence: the outbound stage's history (<= 132)
 constexpr int PK_TILE = 256;                     // outputs per staging round of the inbound stage
 constexpr int PK_SPAN = 1024;                    // floats of input one round stages: 48 -> 16 kHz needs 3 * 255 + 196 + 1
-// in: N packets (n samples, S) + the inbound FIFOs (phi samples each) -> h = (phi + n16) / 256 hops per stream in `hand`
-// (row stride hand_stride >= 256 h), the remainder back in the FIFO.  ntp == 0: no stage (16 kHz, n == n16).
+// The step launchers take their arguments as records, so that no two neighbouring ints can change places unnoticed.
+struct PkStage {                                 // a causal resampling stage; ntp == 0: none (16 kHz)
+    int up = 1, down = 1, ntp = 0;
+    const float* taps = nullptr;
+};
+struct PkState {                                 // the state rows: ps_stride floats apart, the outbound stage's history
+    float* pstate = nullptr;                     // hist_off floats into the row
+    long ps_stride = 0;
+    int hist_off = 0;
+};
+struct PkPacket {                                // n samples at the caller's rate = n16 at 16 kHz; g = gcd(n16, 256)
+    int n = 0, n16 = 0, g = 0;
+};
+// Which rows a launch steps and where their hops sit in the hand-off buffer(s).  rows.slots == nullptr: the contiguous form,
+// rows 0 .. N-1 at the group's phase phi (the phase BEFORE the call), hop r of row i at hand + i hand_stride + 256 r.
+// Otherwise the indexed form of the _slots calls: N = max_active rows named by `rows`, the old phase of row i in phi_rec[i]
+// and hop r of it at row pos[r M + i] of round r's block of M rows of 256 floats (what launch_packet_plan wrote).
+struct PkRows {
+    Rows rows;
+    int N = 0;
+    int phi = 0;                                 // contiguous
+    long hand_stride = 0;
+    const int* phi_rec = nullptr;                // indexed
+    const int* pos = nullptr;
+    int M = 0;
+};
+// in: N packets (n samples, S) + the inbound FIFOs (phi samples each) -> h = (phi + n16) / 256 hops per stream in `hand`,
+// the remainder back in the FIFO.
 template <typename S>
-int launch_packet_in(const S* in, long in_stride, int n, float* hand, long hand_stride, float* pstate, long ps_stride, int N,
-                     int phi, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s);
-// out: the outbound FIFOs (lvl samples each) ++ the 256 h samples of the wave step -> n16 popped, resampled to n samples
-// (S) per stream, the remainder back in the FIFO.  hist_off: floats from the row's start to the outbound stage's history.
+int launch_packet_in(const S* in, long in_stride, float* hand, PkPacket pk, PkState st, PkRows rw, PkStage sg, hipStream_t s);
+// high band (gtcrn_packet_stream_step_hb / _step_slots_hb; fs = 24000, 32000, 48000; S = float or short): fl(P - fl(gam
+// A[t - l16])) staged in the place of the n16 popped samples and fl(gam in[m - lat]) added at the store, gam = gain[stream or
+// slot].  hand_a: the inbound hand-off of the same call (rows as `hand`).  hbstate + stream * hb_stride = [the last l16 =
+// 512 - g samples of A | the last lat input samples] as floats, read and advanced.  in and out rows must not overlap.
+constexpr int PKHB_A = 512;                      // floats of LDS for A's line: l16 <= 511
+constexpr int PKHB_DELAY = 1728;                 // the longest input delay line: (511 + 64) * 3 = 1725 samples at 48 kHz
+struct PkHighBand {
+    const float* hand_a = nullptr;
+    float* hbstate = nullptr;
+    long hb_stride = 0;
+    const float* gain = nullptr;
+    int l16 = 0, lat = 0;
+};
+// out: the outbound FIFOs (lvl = 256 - g - phi samples each) ++ the 256 h samples of the wave step -> n16 popped, resampled
+// to n samples (S) per stream, the remainder back in the FIFO.  hb (nullptr: the plain kernels) adds the high band and reads
+// the call's input rows `in`.
 template <typename S>
-int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stride, int n, float* pstate, long ps_stride,
-                      int hist_off, int N, int lvl, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s);
+int launch_packet_out(const float* hand, const S* in, long in_stride, S* out, long out_stride, PkPacket pk, PkState st,
+                      PkRows rw, PkStage sg, const PkHighBand* hb, hipStream_t s);
 // packet stream slots (gtcrn_packet_stream_*_slots): the phase is one device word per slot.  plan: for the rows the call
 // names (slots / cnt / max_active as in Rows) reads phase[slot], writes per round r < hmax the table tab + r M (the slots
 // with more than r hops ready, in row order) and its count cnts[r], per row the record phi_rec[i] (the old phase) and
 // pos[r M + i] (the row's place in round r's table, or -1), and advances phase[slot].  M: the row capacity of every array
-// and of a round's block of the hand-off buffers (M rows of 256 floats).  in / out: launch_packet_in / _out per row, the state
-// at the slot, phi / h / lvl from the record, hop r of a row at row pos[r M + i] of round r's block.
+// and of a round's block of the hand-off buffers (M rows of 256 floats).  The step launchers read the record (PkRows).
 int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* phase, int n16, int hmax, int M, int* tab,
                        int* pos, int* phi_rec, int* cnts, hipStream_t s);
-template <typename S>
-int launch_packet_in_slots(const S* in, long in_stride, int n, float* hand, int M, float* pstate, long ps_stride,
-                           const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos, int n16, int up,
-                           int down, int ntp, const float* taps, hipStream_t s);
-template <typename S>
-int launch_packet_out_slots(const float* hand, int M, S* out, long out_stride, int n, float* pstate, long ps_stride,
-                            int hist_off, const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos,
-                            int g, int n16, int up, int down, int ntp, const float* taps, hipStream_t s);
 // zeroes the packet state rows (ps_stride floats) and the phase words of the listed slots (k_packet_reset_slots)
 int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const int* slots, const int* cnt, int max_active,
                               hipStream_t s);
-// high band on the packet forms (gtcrn_packet_stream_step_hb / _step_slots_hb; fs = 24000, 32000, 48000): launch_packet_out /
-// _out_slots with fl(P - fl(gam A[t - l16])) staged in the place of the n16 popped samples and fl(gam in[m - lat]) added at the
-// store, gam = hb_gain[stream or slot].  hand_a: the inbound hand-off of the same call (rows as `hand`), phi: the phase before
-// the call (lvl = l16 - 256 - phi).  hbstate + stream * hb_stride = [the last l16 = 512 - g samples of A | the last lat input
-// samples] as floats, read and advanced.  in and out rows must not overlap.
-constexpr int PKHB_A = 512;                      // floats of LDS for A's line: l16 <= 511
-constexpr int PKHB_DELAY = 1728;                 // the longest input delay line: (511 + 64) * 3 = 1725 samples at 48 kHz
-template <typename S>
-int launch_packet_out_hb(const float* hand, const float* hand_a, long hand_stride, const S* in, long in_stride, S* out,
-                         long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate, long hb_stride,
-                         const float* hb_gain, int l16, int lat, int N, int phi, int n16, int h, int up, int down, int ntp,
-                         const float* taps, hipStream_t s);
-template <typename S>
-int launch_packet_out_slots_hb(const float* hand, const float* hand_a, int M, const S* in, long in_stride, S* out,
-                               long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate,
-                               long hb_stride, const float* hb_gain, int l16, int lat, const int* slots, const int* cnt,
-                               int max_active, const int* phi_rec, const int* pos, int g, int n16, int up, int down, int ntp,
-                               const float* taps, hipStream_t s);
 // zeroes the high-band rows (hb_stride floats) of the listed slots (k_packet_hb_reset_slots)
 int launch_packet_hb_reset_slots(float* hbstate, long hb_stride, const int* slots, const int* cnt, int max_active,
                                  hipStream_t s);

@@ -5363,17 +5363,161 @@ int launch_resample_hb(const float* wet, long wet_stride, const float* dry, long
 // kHz) are read from global memory, as k_resample does.
 // One workgroup per stream.  Every global word of the state row is read into LDS before the barrier and written after it
 // by the thread that owns its index; nothing is read back.
+// Where sample i of a call's row (hop i >> 8, place i & 255) sits in a hand-off buffer.  Contiguous: row-major, `stride`
+// floats apart.  Indexed: round-major, block r is M rows of 256 floats and hop r of a row is row pos[r M + row] of it.
+// (RS_THREADS == 256: a thread's hop index i >> 8 is workgroup uniform in every pass of a loop over i.)
+template <bool IDX>
+struct PkHand {
+    long stride;          // contiguous
+    const int* pos;       // indexed
+    int M;
+    __device__ __forceinline__ long at(long row, int i) const {
+        if constexpr (IDX) return ((long)(i >> 8) * M + pos[(long)(i >> 8) * M + row]) * 256 + (i & 255);
+        else return row * stride + i;
+    }
+};
+
+// The inbound stage and FIFO of one stream: ONE statement for k_packet_in and k_packet_in_slots, which resolve srow (the
+// stream's row of pstate: the call's row, or its slot) and phi / h (the group's, or the row's from the plan record).
+template <bool IDX, typename S>
+__device__ __forceinline__ void packet_in_body(const S* __restrict__ in, long in_stride, int n, float* __restrict__ hand,
+                                               PkHand<IDX> hd, float* __restrict__ pstate, long ps_stride, long srow, int phi,
+                                               int n16, int h, int up, int down, int ntp, const float* __restrict__ taps) {
+    __shared__ __attribute__((aligned(16))) float s_a[PK_SEQ];       // the FIFO's phi samples ++ this packet at 16 kHz
+    __shared__ __attribute__((aligned(16))) float s_x[PK_SPAN];
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const S* x = in + row * in_stride;
+    float* ps = pstate + srow * ps_stride;
+    for (int i = tid; i < phi; i += RS_THREADS) s_a[i] = ps[i];
+    if (ntp == 0) {                                                  // 16 kHz: the packet as it is
+        for (int m = tid; m < n16; m += RS_THREADS) s_a[phi + m] = wave_ld<S>(x + m);
+        __syncthreads();
+    } else {
+        float* hist = ps + 2 * PK_FIFO;
+        const float* tp = rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS);
+        for (int m0 = 0; m0 < n16; m0 += PK_TILE) {
+            const int m1 = m0 + PK_TILE < n16 ? m0 + PK_TILE : n16;
+            const int lo = (m0 * down) / up - (ntp - 1), cnt = ((m1 - 1) * down) / up - lo + 1;   // <= PK_SPAN (launch check)
+            for (int i = tid; i < cnt; i += RS_THREADS) {
+                const int g = lo + i;                                // >= 1 - ntp; < n
+                s_x[i] = g >= 0 ? wave_ld<S>(x + g) : hist[ntp + g];
+            }
+            __syncthreads();
+            for (int m = m0 + tid; m < m1; m += RS_THREADS) {
+                const int num = m * down, ih = num / up, k0 = num - ih * up;
+                const float* xs = s_x + (ih - lo);
+                s_a[phi + m] = tp ? rs_dot(tp + k0 * ntp, ntp, xs) : rs_dot(taps + (long)k0 * ntp, ntp, xs);
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = wave_ld<S>(x + n - ntp + i);        // (ntp <= n)
+    }
+    const int whole = 256 * h, rem = phi + n16 - whole;              // rem < 256: the next call's phi
+    for (int i = tid; i < whole; i += RS_THREADS) hand[hd.at(row, i)] = s_a[i];
+    for (int i = tid; i < rem; i += RS_THREADS) ps[i] = s_a[whole + i];
+}
+
+// What the high-band kernels take beyond the plain outbound ones (an empty record in the plain kernels, never read).
+template <typename S>
+struct PkHbArgs {
+    const float* hand_a = nullptr;    // the inbound hand-off of the same call, read only
+    const S* in = nullptr;            // the call's input rows
+    long in_stride = 0;
+    float* hbstate = nullptr;
+    long hb_stride = 0;
+    const float* hb_gain = nullptr;
+    int l16 = 0, lat = 0, phi = 0;    // phi: the phase BEFORE this call's inbound stage
+};
+
+// The outbound FIFO and stage of one stream: ONE statement for k_packet_out, k_packet_out_slots and (HB) their high-band
+// forms; the kernels resolve srow, lvl and h as the inbound ones do.
+// HB carries the band above 8 kHz around the model.  With gam = hb_gain[srow], A the stream's inbound 16 kHz sequence and P
+// what the outbound FIFO pops (both counted from the stream's reset), l16 = 512 - g and lat the form's latency at fs:
+//     s[t] = fl(P[t] - fl(gam A[t - l16]))   staged in the place of the n16 popped samples (the remainder that returns to the
+//                                            FIFO stays raw P; the outbound history then holds s)
+//     out[m] = fl(stage(s)[m] + fl(gam x[m - lat]))
+// High-band state row (floats, hb_stride apart): [the last l16 samples of A | the last lat input samples], zeros after a
+// reset.  This call's n16 new samples of A are where k_packet_in left them: index phi + k of "old inbound FIFO ++ packet" lies
+// in hop (phi + k) >> 8 of the inbound hand-off while below 256 h, else in the inbound FIFO of the packet state (neither is
+// written here; the wave step writes the other hand-off).  The HB form assumes a stage (ntp > 0) whose table fits LDS: the
+// launcher checks both.
+// Every word of the state rows is read into LDS before the barrier and written after it by the thread that owns its index:
+// with n < lat most of the delay line survives a call and moves.
+template <bool IDX, bool HB, typename S>
+__device__ __forceinline__ void packet_out_body(const float* __restrict__ hand, PkHand<IDX> hd, S* __restrict__ out,
+                                                long out_stride, int n, float* __restrict__ pstate, long ps_stride, int hist_off,
+                                                long srow, int lvl, int n16, int h, int up, int down, int ntp,
+                                                const float* __restrict__ taps, const PkHbArgs<S> hb) {
+    __shared__ __attribute__((aligned(16))) float s_q[PK_HIST + PK_SEQ];   // [stage history | the FIFO's lvl samples ++ 256 h new]
+    __shared__ __attribute__((aligned(16))) float s_t[RS_LDS_TAPS];
+    [[maybe_unused]] __shared__ float s_sa[HB ? PKHB_A : 1];           // the last l16 samples of A
+    [[maybe_unused]] __shared__ float s_dl[HB ? PKHB_DELAY : 1];       // the last lat input samples
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    float* ps = pstate + srow * ps_stride;
+    float* fo = ps + PK_FIFO;
+    float* hist = ps + hist_off;
+    float* q = s_q + PK_HIST;
+    const int whole = 256 * h;
+    [[maybe_unused]] const float gam = HB ? hb.hb_gain[srow] : 0.f;
+    [[maybe_unused]] float* const sa = hb.hbstate + srow * hb.hb_stride;
+    [[maybe_unused]] float* const dl = sa + hb.l16;
+    [[maybe_unused]] const S* const x = hb.in + row * hb.in_stride;
+    // new sample k < n16 of A (this call's)
+    [[maybe_unused]] const auto new_a = [&](int k) -> float {
+        const int i = hb.phi + k;
+        return i >= whole ? ps[i - whole] : hb.hand_a[hd.at(row, i)];
+    };
+    // what is staged for popped sample m of this call: P[m], less gam A[t - l16] (the state's, then this call's own) in HB
+    const auto staged = [&](int m, float p) -> float {
+        if constexpr (HB) {
+            if (m < n16) return __fsub_rn(p, __fmul_rn(gam, m < hb.l16 ? sa[m] : new_a(m - hb.l16)));
+        }
+        return p;
+    };
+    for (int i = tid; i < lvl; i += RS_THREADS) q[i] = staged(i, fo[i]);
+    for (int i = tid; i < whole; i += RS_THREADS) q[lvl + i] = staged(lvl + i, hand[hd.at(row, i)]);
+    for (int i = tid; i < ntp; i += RS_THREADS) q[i - ntp] = hist[i];
+    if constexpr (HB) {
+        for (int i = tid; i < hb.l16; i += RS_THREADS) s_sa[i] = sa[i];
+        for (int i = tid; i < hb.lat; i += RS_THREADS) s_dl[i] = dl[i];
+    }
+    const float* tp = HB || ntp ? rs_stage_taps(taps, up * ntp, s_t, tid, RS_THREADS) : nullptr;   // (HB: never nullptr)
+    __syncthreads();
+    S* o = out + row * out_stride;
+    if (!HB && ntp == 0) {
+        for (int m = tid; m < n; m += RS_THREADS) wave_st<S>(o + m, q[m]);
+    } else {
+        for (int m = tid; m < n; m += RS_THREADS) {
+            const int num = m * down, ih = num / up, k0 = num - ih * up;       // ih < n16
+            const float y = HB || tp ? rs_dot(tp + k0 * ntp, ntp, q + ih) : rs_dot(taps + (long)k0 * ntp, ntp, q + ih);
+            if constexpr (HB) {
+                const float xd = m >= hb.lat ? wave_ld<S>(x + (m - hb.lat)) : s_dl[m];
+                wave_st<S>(o + m, __fadd_rn(y, __fmul_rn(gam, xd)));
+            } else {
+                wave_st<S>(o + m, y);
+            }
+        }
+        for (int i = tid; i < ntp; i += RS_THREADS) hist[i] = q[n16 - ntp + i];
+    }
+    const int rem = lvl + whole - n16;                               // < 256: the next call's lvl
+    for (int i = tid; i < rem; i += RS_THREADS) fo[i] = q[n16 + i];
+    if constexpr (HB) {
+        // both delay lines advance: the last l16 of (A's line ++ n16 new), the last lat of (x's line ++ the packet)
+        for (int i = tid; i < hb.l16; i += RS_THREADS) sa[i] = n16 + i < hb.l16 ? s_sa[n16 + i] : new_a(n16 + i - hb.l16);
+        for (int i = tid; i < hb.lat; i += RS_THREADS) dl[i] = n + i < hb.lat ? s_dl[n + i] : wave_ld<S>(x + (n + i - hb.lat));
+    }
+}
+
 template <typename S>
 __global__ __launch_bounds__(RS_THREADS) void k_packet_in(const S* __restrict__ in, long in_stride, int n, float* __restrict__ hand,
                                                           long hand_stride, float* __restrict__ pstate, long ps_stride, int phi,
                                                           int n16, int h, int up, int down, int ntp,
                                                           const float* __restrict__ taps) {
-    const long srow = blockIdx.x;
-    [[maybe_unused]] const int* const pos = nullptr;                 // (the indexed kernel's; see packet_in_body.inc)
-    [[maybe_unused]] constexpr int M = 0;
-#define GT_PK_IDX false
-#include "packet_in_body.inc"
-#undef GT_PK_IDX
+    packet_in_body<false, S>(in, in_stride, n, hand, {hand_stride, nullptr, 0}, pstate, ps_stride, blockIdx.x, phi, n16, h, up,
+                             down, ntp, taps);
 }
 
 template <typename S>
@@ -5381,12 +5525,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_out(const float* __restri
                                                            long out_stride, int n, float* __restrict__ pstate, long ps_stride,
                                                            int hist_off, int lvl, int n16, int h, int up, int down, int ntp,
                                                            const float* __restrict__ taps) {
-    const long srow = blockIdx.x;
-    [[maybe_unused]] const int* const pos = nullptr;
-    [[maybe_unused]] constexpr int M = 0;
-#define GT_PK_IDX false
-#include "packet_out_body.inc"
-#undef GT_PK_IDX
+    packet_out_body<false, false, S>(hand, {hand_stride, nullptr, 0}, out, out_stride, n, pstate, ps_stride, hist_off, blockIdx.x,
+                                     lvl, n16, h, up, down, ntp, taps, {});
 }
 
 // ---- packet stream slots (gtcrn_packet_stream_*_slots): the packet form for the resident streams a call names.  The phase
@@ -5449,10 +5589,10 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_packet_plan(const int* __restr
     if (tid < hmax) cnts[tid] = s_base[tid];
 }
 
-// k_packet_in_slots / k_packet_out_slots: the contiguous kernels' bodies (packet_*_body.inc) with the state row taken at the
-// slot, phi / h / lvl per row from the plan record, and hop r of a row at row pos[r M + row] of round r's block of the
-// hand-off buffer (round-major: block r is M rows of 256 floats).  A workgroup at or beyond the count returns before its
-// first barrier and state access.
+// k_packet_in_slots / k_packet_out_slots: packet_in_body / packet_out_body with the state row taken at the slot, phi / h /
+// lvl per row from the plan record, and the hand-off addressed through PkHand<true> (round-major: hop r of a row is row
+// pos[r M + row] of round r's block of M rows of 256 floats).  A workgroup at or beyond the count returns before its first
+// barrier and state access.
 template <typename S>
 __global__ __launch_bounds__(RS_THREADS) void k_packet_in_slots(const S* __restrict__ in, long in_stride, int n,
                                                                 float* __restrict__ hand, int M, float* __restrict__ pstate,
@@ -5462,12 +5602,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_in_slots(const S* __restr
                                                                 int n16, int up, int down, int ntp,
                                                                 const float* __restrict__ taps) {
     if ((int)blockIdx.x >= slot_count(count, max_active)) return;
-    const long srow = slots[blockIdx.x];
-    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8;
-    [[maybe_unused]] constexpr long hand_stride = 0;                 // (the contiguous kernel's)
-#define GT_PK_IDX true
-#include "packet_in_body.inc"
-#undef GT_PK_IDX
+    const int phi = phi_rec[blockIdx.x];
+    packet_in_body<true, S>(in, in_stride, n, hand, {0, pos, M}, pstate, ps_stride, slots[blockIdx.x], phi, n16, (phi + n16) >> 8,
+                            up, down, ntp, taps);
 }
 
 template <typename S>
@@ -5479,12 +5616,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_out_slots(const float* __
                                                                  int g, int n16, int up, int down, int ntp,
                                                                  const float* __restrict__ taps) {
     if ((int)blockIdx.x >= slot_count(count, max_active)) return;
-    const long srow = slots[blockIdx.x];
-    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8, lvl = 256 - g - phi;
-    [[maybe_unused]] constexpr long hand_stride = 0;
-#define GT_PK_IDX true
-#include "packet_out_body.inc"
-#undef GT_PK_IDX
+    const int phi = phi_rec[blockIdx.x];
+    packet_out_body<true, false, S>(hand, {0, pos, M}, out, out_stride, n, pstate, ps_stride, hist_off, slots[blockIdx.x],
+                                    256 - g - phi, n16, (phi + n16) >> 8, up, down, ntp, taps, {});
 }
 
 // zeroes the packet state rows and the phase words of the listed slots (with k_reset_slots: gtcrn_packet_stream_reset_slots)
@@ -5499,7 +5633,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_reset_slots(float* __rest
 }
 
 // ---- high band on the packet forms (gtcrn_packet_stream_step_hb, _step_slots_hb): k_packet_out / k_packet_out_slots with
-// the band above 8 kHz carried around the model (packet_out_hb_body.inc states the arithmetic and the state row).  They take
+// the band above 8 kHz carried around the model (packet_out_body<IDX, true> states the arithmetic and the state row).  They take
 // BOTH hand-offs (hand_a: what the inbound kernel produced, read only), the call's input rows, the old inbound phase and
 // the high-band state and gains; the gain and the state row are the stream's (by row, or by slot).
 template <typename S>
@@ -5511,12 +5645,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_out_hb(const float* __res
                                                               const float* __restrict__ hb_gain, int l16, int lat, int phi,
                                                               int lvl, int n16, int h, int up, int down, int ntp,
                                                               const float* __restrict__ taps) {
-    const long srow = blockIdx.x;
-    [[maybe_unused]] const int* const pos = nullptr;
-    [[maybe_unused]] constexpr int M = 0;
-#define GT_PK_IDX false
-#include "packet_out_hb_body.inc"
-#undef GT_PK_IDX
+    packet_out_body<false, true, S>(hand, {hand_stride, nullptr, 0}, out, out_stride, n, pstate, ps_stride, hist_off, blockIdx.x,
+                                    lvl, n16, h, up, down, ntp, taps,
+                                    {hand_a, in, in_stride, hbstate, hb_stride, hb_gain, l16, lat, phi});
 }
 
 template <typename S>
@@ -5531,12 +5662,10 @@ __global__ __launch_bounds__(RS_THREADS) void k_packet_out_slots_hb(const float*
                                                                     const int* __restrict__ pos, int g, int n16, int up,
                                                                     int down, int ntp, const float* __restrict__ taps) {
     if ((int)blockIdx.x >= slot_count(count, max_active)) return;
-    const long srow = slots[blockIdx.x];
-    const int phi = phi_rec[blockIdx.x], h = (phi + n16) >> 8, lvl = 256 - g - phi;
-    [[maybe_unused]] constexpr long hand_stride = 0;
-#define GT_PK_IDX true
-#include "packet_out_hb_body.inc"
-#undef GT_PK_IDX
+    const int phi = phi_rec[blockIdx.x];
+    packet_out_body<true, true, S>(hand, {0, pos, M}, out, out_stride, n, pstate, ps_stride, hist_off, slots[blockIdx.x],
+                                   256 - g - phi, n16, (phi + n16) >> 8, up, down, ntp, taps,
+                                   {hand_a, in, in_stride, hbstate, hb_stride, hb_gain, l16, lat, phi});
 }
 
 // zeroes the high-band rows of the listed slots (gtcrn_packet_stream_hb_reset_slots)
@@ -5553,38 +5682,77 @@ static bool packet_stage_ok(int n_in, int n_out, int up, int down, int ntp, cons
     return taps && !(reinterpret_cast<uintptr_t>(taps) & 15) && up >= 1 && down >= 1 && (long)n_in * up == (long)n_out * down &&
            !(ntp & 3) && ntp <= n_in;
 }
+// what both step launchers check: the packet, the rows of the form, and the phase the contiguous form is given
+static bool packet_rows_ok(const PkPacket& pk, const PkRows& rw) {
+    if (pk.n16 < 1 || pk.n16 > PK_MAX16) return false;
+    if (rw.rows.slots) return rw.N >= 1 && rw.N <= rw.M;
+    return rw.phi >= 0 && rw.phi < 256 && rw.hand_stride >= 256L * ((rw.phi + pk.n16) / 256);
+}
 template <typename S>
-int launch_packet_in(const S* in, long in_stride, int n, float* hand, long hand_stride, float* pstate, long ps_stride, int N,
-                     int phi, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s) {
-    if (phi < 0 || phi >= 256 || n16 < 1 || n16 > PK_MAX16 || h != (phi + n16) / 256 || hand_stride < 256L * h ||
-        ps_stride < 2 * PK_FIFO + ntp || !packet_stage_ok(n, n16, up, down, ntp, taps) ||
-        (ntp && ((PK_TILE - 1) * down) / up + ntp + 1 > PK_SPAN))
+int launch_packet_in(const S* in, long in_stride, float* hand, PkPacket pk, PkState st, PkRows rw, PkStage sg, hipStream_t s) {
+    if (!packet_rows_ok(pk, rw) || st.ps_stride < 2 * PK_FIFO + sg.ntp ||
+        !packet_stage_ok(pk.n, pk.n16, sg.up, sg.down, sg.ntp, sg.taps) ||
+        (sg.ntp && ((PK_TILE - 1) * sg.down) / sg.up + sg.ntp + 1 > PK_SPAN))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_in<S>), dim3(N), dim3(RS_THREADS), 0, s, in, in_stride, n, hand, hand_stride, pstate, ps_stride,
-                       phi, n16, h, up, down, ntp, taps);
+    if (rw.rows.slots) {
+        hipLaunchKernelGGL((k_packet_in_slots<S>), dim3(rw.N), dim3(RS_THREADS), 0, s, in, in_stride, pk.n, hand, rw.M, st.pstate,
+                           st.ps_stride, rw.rows.slots, rw.rows.cnt, rw.N, rw.phi_rec, rw.pos, pk.n16, sg.up, sg.down, sg.ntp,
+                           sg.taps);
+    } else {
+        hipLaunchKernelGGL((k_packet_in<S>), dim3(rw.N), dim3(RS_THREADS), 0, s, in, in_stride, pk.n, hand, rw.hand_stride,
+                           st.pstate, st.ps_stride, rw.phi, pk.n16, (rw.phi + pk.n16) / 256, sg.up, sg.down, sg.ntp, sg.taps);
+    }
     GT_LAUNCH_CHECK();
     return 0;
 }
 template <typename S>
-int launch_packet_out(const float* hand, long hand_stride, S* out, long out_stride, int n, float* pstate, long ps_stride,
-                      int hist_off, int N, int lvl, int n16, int h, int up, int down, int ntp, const float* taps, hipStream_t s) {
-    const int rem = lvl + 256 * h - n16;
-    if (lvl < 0 || lvl >= 256 || n16 < 1 || n16 > PK_MAX16 || h < 0 || rem < 0 || rem >= 256 || hand_stride < 256L * h ||
-        hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST || !packet_stage_ok(n16, n, up, down, ntp, taps))
+int launch_packet_out(const float* hand, const S* in, long in_stride, S* out, long out_stride, PkPacket pk, PkState st,
+                      PkRows rw, PkStage sg, const PkHighBand* hb, hipStream_t s) {
+    constexpr bool kHb = std::is_same<S, float>::value || std::is_same<S, short>::value;   // (no G.711 high-band kernel exists)
+    // contiguous: the hops and both FIFO levels follow from the group's phase, a multiple of g on every schedule
+    const int h = (rw.phi + pk.n16) / 256, lvl = 256 - pk.g - rw.phi, rem = lvl + 256 * h - pk.n16;
+    if (!packet_rows_ok(pk, rw) || pk.g < 1 || pk.g > 256 || 256 % pk.g || pk.n16 % pk.g || st.hist_off < 2 * PK_FIFO ||
+        st.ps_stride < st.hist_off + sg.ntp || sg.ntp > PK_HIST || !packet_stage_ok(pk.n16, pk.n, sg.up, sg.down, sg.ntp, sg.taps))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_out<S>), dim3(N), dim3(RS_THREADS), 0, s, hand, hand_stride, out, out_stride, n, pstate,
-                       ps_stride, hist_off, lvl, n16, h, up, down, ntp, taps);
+    if (!rw.rows.slots && (lvl < 0 || rem < 0)) return (int)hipErrorInvalidValue;
+    // the high band: the stage exists (ntp > 0) and its table sits in LDS
+    if (hb && (!kHb || !hb->hand_a || !in || !hb->hbstate || !hb->gain || hb->l16 != 512 - pk.g || hb->l16 < 256 ||
+               hb->l16 > PKHB_A || hb->lat < 1 || hb->lat > PKHB_DELAY || hb->hb_stride < hb->l16 + hb->lat || sg.ntp <= 0 ||
+               sg.up * sg.ntp > RS_LDS_TAPS))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(rw.N), block(RS_THREADS);
+    if (hb) {
+        if constexpr (kHb) {
+            if (rw.rows.slots) {
+                hipLaunchKernelGGL((k_packet_out_slots_hb<S>), grid, block, 0, s, hand, hb->hand_a, rw.M, in, in_stride, out,
+                                   out_stride, pk.n, st.pstate, st.ps_stride, st.hist_off, hb->hbstate, hb->hb_stride, hb->gain,
+                                   hb->l16, hb->lat, rw.rows.slots, rw.rows.cnt, rw.N, rw.phi_rec, rw.pos, pk.g, pk.n16, sg.up,
+                                   sg.down, sg.ntp, sg.taps);
+            } else {
+                hipLaunchKernelGGL((k_packet_out_hb<S>), grid, block, 0, s, hand, hb->hand_a, rw.hand_stride, in, in_stride, out,
+                                   out_stride, pk.n, st.pstate, st.ps_stride, st.hist_off, hb->hbstate, hb->hb_stride, hb->gain,
+                                   hb->l16, hb->lat, rw.phi, lvl, pk.n16, h, sg.up, sg.down, sg.ntp, sg.taps);
+            }
+        }
+    } else if (rw.rows.slots) {
+        hipLaunchKernelGGL((k_packet_out_slots<S>), grid, block, 0, s, hand, rw.M, out, out_stride, pk.n, st.pstate, st.ps_stride,
+                           st.hist_off, rw.rows.slots, rw.rows.cnt, rw.N, rw.phi_rec, rw.pos, pk.g, pk.n16, sg.up, sg.down,
+                           sg.ntp, sg.taps);
+    } else {
+        hipLaunchKernelGGL((k_packet_out<S>), grid, block, 0, s, hand, rw.hand_stride, out, out_stride, pk.n, st.pstate,
+                           st.ps_stride, st.hist_off, lvl, pk.n16, h, sg.up, sg.down, sg.ntp, sg.taps);
+    }
     GT_LAUNCH_CHECK();
     return 0;
 }
-template int launch_packet_in<float>(const float*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in<short>(const short*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in<g711u>(const g711u*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in<g711a>(const g711a*, long, int, float*, long, float*, long, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out<float>(const float*, long, float*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out<short>(const float*, long, short*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out<g711u>(const float*, long, g711u*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out<g711a>(const float*, long, g711a*, long, int, float*, long, int, int, int, int, int, int, int, int, const float*, hipStream_t);
+template int launch_packet_in<float>(const float*, long, float*, PkPacket, PkState, PkRows, PkStage, hipStream_t);
+template int launch_packet_in<short>(const short*, long, float*, PkPacket, PkState, PkRows, PkStage, hipStream_t);
+template int launch_packet_in<g711u>(const g711u*, long, float*, PkPacket, PkState, PkRows, PkStage, hipStream_t);
+template int launch_packet_in<g711a>(const g711a*, long, float*, PkPacket, PkState, PkRows, PkStage, hipStream_t);
+template int launch_packet_out<float>(const float*, const float*, long, float*, long, PkPacket, PkState, PkRows, PkStage, const PkHighBand*, hipStream_t);
+template int launch_packet_out<short>(const float*, const short*, long, short*, long, PkPacket, PkState, PkRows, PkStage, const PkHighBand*, hipStream_t);
+template int launch_packet_out<g711u>(const float*, const g711u*, long, g711u*, long, PkPacket, PkState, PkRows, PkStage, const PkHighBand*, hipStream_t);
+template int launch_packet_out<g711a>(const float*, const g711a*, long, g711a*, long, PkPacket, PkState, PkRows, PkStage, const PkHighBand*, hipStream_t);
 
 // ---- packet stream slots: the launch sequence of a call depends on (fs, n, max_active) alone
 int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* phase, int n16, int hmax, int M, int* tab,
@@ -5597,73 +5765,11 @@ int launch_packet_plan(const int* slots, const int* cnt, int max_active, int* ph
     GT_LAUNCH_CHECK();
     return 0;
 }
-template <typename S>
-int launch_packet_in_slots(const S* in, long in_stride, int n, float* hand, int M, float* pstate, long ps_stride,
-                           const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos, int n16, int up,
-                           int down, int ntp, const float* taps, hipStream_t s) {
-    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || ps_stride < 2 * PK_FIFO + ntp ||
-        !packet_stage_ok(n, n16, up, down, ntp, taps) || (ntp && ((PK_TILE - 1) * down) / up + ntp + 1 > PK_SPAN))
-        return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_in_slots<S>), dim3(max_active), dim3(RS_THREADS), 0, s, in, in_stride, n, hand, M, pstate,
-                       ps_stride, slots, cnt, max_active, phi_rec, pos, n16, up, down, ntp, taps);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-template <typename S>
-int launch_packet_out_slots(const float* hand, int M, S* out, long out_stride, int n, float* pstate, long ps_stride,
-                            int hist_off, const int* slots, const int* cnt, int max_active, const int* phi_rec, const int* pos,
-                            int g, int n16, int up, int down, int ntp, const float* taps, hipStream_t s) {
-    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || g < 1 || g > 256 || 256 % g || n16 % g ||
-        hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST || !packet_stage_ok(n16, n, up, down, ntp, taps))
-        return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_out_slots<S>), dim3(max_active), dim3(RS_THREADS), 0, s, hand, M, out, out_stride, n, pstate,
-                       ps_stride, hist_off, slots, cnt, max_active, phi_rec, pos, g, n16, up, down, ntp, taps);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
 int launch_packet_reset_slots(float* pstate, long ps_stride, int* phase, const int* slots, const int* cnt, int max_active,
                               hipStream_t s) {
     if (!pstate || !phase || !slots || max_active < 1 || ps_stride < 2 * PK_FIFO) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_packet_reset_slots, dim3(max_active), dim3(RS_THREADS), 0, s, pstate, ps_stride, phase, slots, cnt,
                        max_active);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-// high band: the two outbound launchers with the extra rows; the stage exists (ntp > 0) and its table sits in LDS
-static bool packet_hb_ok(const float* hand_a, const void* in, float* hbstate, long hb_stride, const float* hb_gain, int l16,
-                         int lat, int up, int ntp) {
-    return hand_a && in && hbstate && hb_gain && l16 >= 256 && l16 <= PKHB_A && lat >= 1 && lat <= PKHB_DELAY &&
-           hb_stride >= l16 + lat && ntp > 0 && up * ntp <= RS_LDS_TAPS;
-}
-template <typename S>
-int launch_packet_out_hb(const float* hand, const float* hand_a, long hand_stride, const S* in, long in_stride, S* out,
-                         long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate, long hb_stride,
-                         const float* hb_gain, int l16, int lat, int N, int phi, int n16, int h, int up, int down, int ntp,
-                         const float* taps, hipStream_t s) {
-    const int lvl = l16 - 256 - phi, rem = lvl + 256 * h - n16;
-    if (phi < 0 || phi >= 256 || lvl < 0 || lvl >= 256 || n16 < 1 || n16 > PK_MAX16 || h != (phi + n16) / 256 || rem < 0 ||
-        rem >= 256 || hand_stride < 256L * h || hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST ||
-        !packet_stage_ok(n16, n, up, down, ntp, taps) || !packet_hb_ok(hand_a, in, hbstate, hb_stride, hb_gain, l16, lat, up, ntp))
-        return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_out_hb<S>), dim3(N), dim3(RS_THREADS), 0, s, hand, hand_a, hand_stride, in, in_stride, out,
-                       out_stride, n, pstate, ps_stride, hist_off, hbstate, hb_stride, hb_gain, l16, lat, phi, lvl, n16, h, up,
-                       down, ntp, taps);
-    GT_LAUNCH_CHECK();
-    return 0;
-}
-template <typename S>
-int launch_packet_out_slots_hb(const float* hand, const float* hand_a, int M, const S* in, long in_stride, S* out,
-                               long out_stride, int n, float* pstate, long ps_stride, int hist_off, float* hbstate,
-                               long hb_stride, const float* hb_gain, int l16, int lat, const int* slots, const int* cnt,
-                               int max_active, const int* phi_rec, const int* pos, int g, int n16, int up, int down, int ntp,
-                               const float* taps, hipStream_t s) {
-    if (!slots || max_active < 1 || max_active > M || n16 < 1 || n16 > PK_MAX16 || g < 1 || g > 256 || 256 % g || n16 % g ||
-        l16 != 512 - g || hist_off < 2 * PK_FIFO || ps_stride < hist_off + ntp || ntp > PK_HIST ||
-        !packet_stage_ok(n16, n, up, down, ntp, taps) || !packet_hb_ok(hand_a, in, hbstate, hb_stride, hb_gain, l16, lat, up, ntp))
-        return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_packet_out_slots_hb<S>), dim3(max_active), dim3(RS_THREADS), 0, s, hand, hand_a, M, in, in_stride, out,
-                       out_stride, n, pstate, ps_stride, hist_off, hbstate, hb_stride, hb_gain, l16, lat, slots, cnt, max_active,
-                       phi_rec, pos, g, n16, up, down, ntp, taps);
     GT_LAUNCH_CHECK();
     return 0;
 }
@@ -5675,17 +5781,5 @@ int launch_packet_hb_reset_slots(float* hbstate, long hb_stride, const int* slot
     GT_LAUNCH_CHECK();
     return 0;
 }
-template int launch_packet_out_hb<float>(const float*, const float*, long, const float*, long, float*, long, int, float*, long, int, float*, long, const float*, int, int, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_hb<short>(const float*, const float*, long, const short*, long, short*, long, int, float*, long, int, float*, long, const float*, int, int, int, int, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots_hb<float>(const float*, const float*, int, const float*, long, float*, long, int, float*, long, int, float*, long, const float*, int, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots_hb<short>(const float*, const float*, int, const short*, long, short*, long, int, float*, long, int, float*, long, const float*, int, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in_slots<float>(const float*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in_slots<short>(const short*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in_slots<g711u>(const g711u*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_in_slots<g711a>(const g711a*, long, int, float*, int, float*, long, const int*, const int*, int, const int*, const int*, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots<float>(const float*, int, float*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots<short>(const float*, int, short*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots<g711u>(const float*, int, g711u*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
-template int launch_packet_out_slots<g711a>(const float*, int, g711a*, long, int, float*, long, int, const int*, const int*, int, const int*, const int*, int, int, int, int, int, const float*, hipStream_t);
 
 }  // namespace gtk
