@@ -255,6 +255,12 @@ def lib():
         L.gtcrn_batch_reverb_split.argtypes = [_vp, _vp, ci, _vp, _vp, _vp, ci, _vp, ctypes.c_size_t, _vp, _vp, ci, cl, _vp, _vp, cl,
                                                _vp, _vp, _vp, _vp, ci, _vp]
         L.gtcrn_batch_mix_target.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, _vp, ci, cl, _vp, cl, _vp, cl, _vp, _vp, ci, _vp]
+    # the mix at an SNR of active levels
+    if hasattr(L, "gtcrn_batch_mix_active"):
+        L.gtcrn_batch_active_workspace_bytes.restype = ctypes.c_size_t
+        L.gtcrn_batch_active_workspace_bytes.argtypes = [ci, cl, ci]
+        L.gtcrn_batch_mix_active.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, _vp, ci, cl, _vp, cl, _vp, cl, ci, ctypes.c_longlong,
+                                             _vp, _vp, ci, _vp]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

@@ -21,7 +21,15 @@ struct Record {                        // == gtcrn_batch_record, 40 bytes
     int flags;
 };
 
-enum { FLAG_NOISE_ZERO = 1, FLAG_SPEECH_ZERO = 2, FLAG_MIX_ZERO = 4, FLAG_LIMITED = 8 };
+struct ActiveRecord {                  // == gtcrn_batch_active_record, 64 bytes; As, An, Ns, Nn as used (after the fallback)
+    long long Ss, Sn, Ssn, As, An;
+    int Ns, Nn;
+    float gn, Gf, peak;
+    int flags;
+};
+
+enum { FLAG_NOISE_ZERO = 1, FLAG_SPEECH_ZERO = 2, FLAG_MIX_ZERO = 4, FLAG_LIMITED = 8, FLAG_SPEECH_INACTIVE = 16,
+       FLAG_NOISE_INACTIVE = 32 };
 
 constexpr int THREADS = 256;           // four waves
 constexpr int GROUP = 8;               // samples a thread handles at a time: 16 bytes in, 2 x 16 bytes out
@@ -37,6 +45,22 @@ __host__ __device__ inline long chunk_samples(long L) {
     return ch;
 }
 __host__ __device__ inline int chunks_of(long L) { return (int)((L + chunk_samples(L) - 1) / chunk_samples(L)); }
+
+// "active levels": the same cut for a row that is judged in windows of W samples (a multiple of GROUP).  A chunk is a whole
+// number of windows: as few as cover two tiles, or what keeps an item within MAX_CHUNKS chunks.  W = 1600: 3 windows, 4800 samples.
+constexpr int MIN_WINDOW = GROUP, MAX_WINDOW = 1 << 20;
+constexpr long long MAX_THRESHOLD = 1LL << 30;
+constexpr int ACTIVE_PARTS = 7;        // a chunk's partials: Ss, Sn, Ssn, As, Ns, An, Nn
+__host__ __device__ inline long active_chunk_windows(long L, int W) {
+    long k = (2 * TILE + W - 1) / W;
+    const long windows = (L + W - 1) / W;
+    const long need = (windows + MAX_CHUNKS - 1) / MAX_CHUNKS;
+    return need > k ? need : k;
+}
+__host__ __device__ inline long active_chunk_samples(long L, int W) { return active_chunk_windows(L, W) * W; }
+__host__ __device__ inline int active_chunks_of(long L, int W) {
+    return (int)((L + active_chunk_samples(L, W) - 1) / active_chunk_samples(L, W));
+}
 
 struct PlanArgs {
     const long long* soff = nullptr;   // [n_speech + 1]
@@ -118,5 +142,8 @@ int launch_mix(const DrawArgs& d, int passes, hipStream_t s);
 // The same with the clean rows cut from d_target, a corpus under the speech offsets table: passes 1 and 2 are launch_mix's
 // kernels, pass 3 is a write kernel of its own.
 int launch_mix_target(const DrawArgs& d, const short* d_target, int passes, hipStream_t s);
+// The mix at an SNR of active levels ("active levels"): three kernels of its own over the active_* geometry.  d.sums holds
+// [B][chunks][ACTIVE_PARTS], d.rec is not used (the records are `rec`), d_target may be null (clean is cut from the speech).
+int launch_mix_active(const DrawArgs& d, const short* d_target, ActiveRecord* rec, int W, long long thr, int passes, hipStream_t s);
 
 }  // namespace gtb

@@ -1,5 +1,6 @@
 // batch.hip -- training batches from a resident corpus: the plan, the pairs draw and the three passes of the mix draw
-// (contract: include/gtcrn_micro_hip.h, "training batches from a resident corpus").
+// (contract: include/gtcrn_micro_hip.h, "training batches from a resident corpus"), and the three
+// passes of the mix at an SNR of active levels ("active levels"; section 7o) behind them.
 //
 // Compiled with -ffp-contract=off: every float and double operation below rounds once, as the contract states it, so
 // numpy restates the output bit for bit.  The three sums of an item are 64-bit integers over its int16 samples: exact,
@@ -328,6 +329,220 @@ __global__ __launch_bounds__(THREADS) void k_batch_write_target(DrawArgs d, cons
     }
 }
 
+// ---- active levels: the mix at an SNR of the levels over active windows ("active levels" in the header) ----
+// A row is judged in windows of W samples (a multiple of GROUP, so a thread's 16-byte group never straddles a window); a chunk
+// is a whole number of windows (batch.h).  A window's energy is an exact 64-bit integer and its activity an integer
+// comparison, so the four active sums are as order-free as the three plain ones.
+
+// N sums of a workgroup at once, returned to every thread.  sm: (THREADS / 64) * N values.
+template <int N>
+__device__ inline void block_sums(long long* v, long long* sm) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) sm[(threadIdx.x >> 6) * N + j] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        long long r = sm[j];
+#pragma unroll
+        for (int k = 1; k < THREADS / 64; ++k) r += sm[k * N + j];
+        v[j] = r;
+    }
+}
+
+struct ActiveSums {
+    Sums s;                    // the whole row's, as in the plain mix
+    long long As, An;          // energy over the active windows of each side
+    long long Ns, Nn;          // samples in them (at most L)
+};
+
+// an item's seven sums from its chunks' partials (chunks <= THREADS)
+__device__ inline ActiveSums active_item_sums(const long long* part, int chunks, long long* sm) {
+    long long p[ACTIVE_PARTS];
+#pragma unroll
+    for (int j = 0; j < ACTIVE_PARTS; ++j) p[j] = (int)threadIdx.x < chunks ? part[ACTIVE_PARTS * threadIdx.x + j] : 0;
+    block_sums<ACTIVE_PARTS>(p, sm);
+    ActiveSums a;
+    a.s.ss = p[0]; a.s.sn = p[1]; a.s.ssn = p[2];
+    a.As = p[3]; a.Ns = p[4]; a.An = p[5]; a.Nn = p[6];
+    return a;
+}
+
+// The fallback (a side without an active window is levelled over the whole row), then gn in the contract's operation order.
+__device__ inline float noise_gain_active(ActiveSums* a, float snr_amp, long L, int* flags) {
+    if (a->Ns == 0) { a->As = a->s.ss; a->Ns = L; *flags |= FLAG_SPEECH_INACTIVE; }
+    if (a->Nn == 0) { a->An = a->s.sn; a->Nn = L; *flags |= FLAG_NOISE_INACTIVE; }
+    if (a->An == 0) { *flags |= FLAG_NOISE_ZERO; return 0.0f; }
+    if (a->As == 0) { *flags |= FLAG_SPEECH_ZERO; return 1.0f; }
+    double r = (double)a->As / (double)a->An;
+    if (a->Ns != a->Nn) r = r * ((double)a->Nn / (double)a->Ns);
+    return (float)(sqrt(r) * (double)snr_amp);
+}
+
+// a value every lane of the wave holds, moved into scalar registers: what is added up per window then costs no vector register
+__device__ inline long long wave_uniform(long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// pass 1: one wave per window.  Its lanes stride the window's groups, both energies are reduced across the wave and every
+// lane then holds the window's two decisions; the chunk's seven partials -> sums[b][c][0..6]
+__global__ __launch_bounds__(THREADS) void k_batch_active_sums(DrawArgs d, int W, long long thr, int chunks, long ch) {
+    __shared__ long long sm[(THREADS / 64) * ACTIVE_PARTS];
+    const int b = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const View v = view_of(d, b, false);
+    const long lo = (long)c * ch, hi = lo + ch < d.L ? lo + ch : d.L;
+    long long ss = 0, sn = 0, ssn = 0, as = 0, ns = 0, an = 0, nn = 0;      // ssn per lane, the others per wave
+#pragma unroll 1
+    for (long w0 = lo + (long)wave * W; w0 < hi; w0 += (long)(THREADS / 64) * W) {
+        const long w1 = w0 + W < hi ? w0 + W : hi;
+        long long es = 0, en = 0;
+        // A window of whole groups that lies inside the speech clip and does not wrap the noise (all but a few of a batch):
+        // four 16-byte loads per side and lane are in flight at once, a lane past the window's end reads its last group and
+        // counts zeros.  Any other window goes group by group through the checked loads.
+        const unsigned j0 = wrap_index(v, w0);
+        const int ng = (int)((w1 - w0) / GROUP);
+        const bool inside = (w1 - w0) % GROUP == 0 && v.sstart + w1 <= v.len_s && (unsigned long long)j0 + (unsigned long long)(w1 - w0) <= v.len_n;
+        const short* ps = v.s + (v.sstart + w0);
+        const short* pn = v.n + j0;
+#pragma unroll 1
+        for (int g0 = lane; inside && g0 - lane < ng; g0 += 4 * 64) {
+            short ts[4][GROUP], tn[4][GROUP];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int g = g0 + 64 * u < ng ? g0 + 64 * u : ng - 1;
+                __builtin_memcpy(ts[u], ps + (long)g * GROUP, sizeof(ts[u]));
+                __builtin_memcpy(tn[u], pn + (long)g * GROUP, sizeof(tn[u]));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool on = g0 + 64 * u < ng;
+#pragma unroll
+                for (int k = 0; k < GROUP; ++k) {
+                    const int x = on ? (int)ts[u][k] : 0, z = on ? (int)tn[u][k] : 0;
+                    es += (long long)(x * x);
+                    en += (long long)(z * z);
+                    ssn += (long long)(x * z);
+                }
+            }
+        }
+#pragma unroll 1
+        for (long i0 = w0 + (long)lane * GROUP; !inside && i0 < w1; i0 += 64 * GROUP) {
+            const int cnt = w1 - i0 < GROUP ? (int)(w1 - i0) : GROUP;
+            int x[GROUP], z[GROUP];
+            load_clip8(v.s, v.len_s, v.sstart + i0, cnt, x);
+            load_wrap8(v.n, v.len_n, wrap_index(v, i0), cnt, z);
+#pragma unroll
+            for (int k = 0; k < GROUP; ++k) {
+                es += (long long)(x[k] * x[k]);
+                en += (long long)(z[k] * z[k]);
+                ssn += (long long)(x[k] * z[k]);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            es += __shfl_xor(es, o, 64);
+            en += __shfl_xor(en, o, 64);
+        }
+        es = wave_uniform(es);
+        en = wave_uniform(en);
+        const long long bar = thr * (long long)(w1 - w0);
+        ss += es;
+        sn += en;
+        if (es > bar) { as += es; ns += w1 - w0; }
+        if (en > bar) { an += en; nn += w1 - w0; }
+    }
+    const bool first = lane == 0;
+    long long p[ACTIVE_PARTS] = {first ? ss : 0, first ? sn : 0, ssn, first ? as : 0, first ? ns : 0, first ? an : 0, first ? nn : 0};
+    block_sums<ACTIVE_PARTS>(p, sm);
+    if (threadIdx.x == 0) {
+        long long* out = d.sums + ((long)b * chunks + c) * ACTIVE_PARTS;
+#pragma unroll
+        for (int j = 0; j < ACTIVE_PARTS; ++j) out[j] = p[j];
+    }
+}
+
+// pass 2: k_batch_peak with the item's seven sums and the active gain
+__global__ __launch_bounds__(THREADS) void k_batch_active_peak(DrawArgs d, int chunks, long ch) {
+    __shared__ long long sm[(THREADS / 64) * ACTIVE_PARTS];
+    __shared__ float smf[THREADS / 64];
+    const int b = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const View v = view_of(d, b, false);
+    ActiveSums a = active_item_sums(d.sums + (long)b * chunks * ACTIVE_PARTS, chunks, sm);
+    int flags = 0;
+    const float gn = noise_gain_active(&a, v.snr_amp, d.L, &flags);
+    const long lo = (long)c * ch, hi = lo + ch < d.L ? lo + ch : d.L;
+    float pk = 0.0f;
+    for (long i0 = lo + (long)threadIdx.x * GROUP; i0 < hi; i0 += TILE) {
+        const int cnt = hi - i0 < GROUP ? (int)(hi - i0) : GROUP;
+        int x[GROUP], z[GROUP];
+        load_clip8(v.s, v.len_s, v.sstart + i0, cnt, x);
+        load_wrap8(v.n, v.len_n, wrap_index(v, i0), cnt, z);
+#pragma unroll
+        for (int k = 0; k < GROUP; ++k) {
+            const float gz = gn * ((float)z[k] * kScale);
+            const float m = (float)x[k] * kScale + gz;
+            pk = fmaxf(pk, fabsf(m));
+        }
+    }
+    pk = block_all<float, true>(pk, smf);
+    if (threadIdx.x == 0) d.peaks[(long)b * chunks + c] = pk;
+}
+
+// pass 3: k_batch_write (TARGET: k_batch_write_target; `target` is not read otherwise) with the item's seven sums, the active
+// gain and the 64-byte record
+template <bool TARGET>
+__global__ __launch_bounds__(THREADS) void k_batch_active_write(DrawArgs d, const short* target, ActiveRecord* rec, int chunks, long ch,
+                                                                bool vec) {
+    __shared__ long long sm[(THREADS / 64) * ACTIVE_PARTS];
+    __shared__ float smf[THREADS / 64];
+    const int b = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const View v = view_of(d, b, false);
+    const short* tg = TARGET ? target + (v.s - d.a.pcm) : v.s;          // the same clip of the parallel corpus
+    ActiveSums a = active_item_sums(d.sums + (long)b * chunks * ACTIVE_PARTS, chunks, sm);
+    const float peak = block_all<float, true>((int)threadIdx.x < chunks ? d.peaks[(long)b * chunks + threadIdx.x] : 0.0f, smf);
+    int flags = 0;
+    const float gn = noise_gain_active(&a, v.snr_amp, d.L, &flags);
+    const float Gf = level_gain(a.s, gn, peak, v.lvl_amp, d.L, &flags);
+    if (c == 0 && threadIdx.x == 0) {
+        ActiveRecord r;
+        r.Ss = a.s.ss; r.Sn = a.s.sn; r.Ssn = a.s.ssn; r.As = a.As; r.An = a.An;
+        r.Ns = (int)a.Ns; r.Nn = (int)a.Nn;
+        r.gn = gn; r.Gf = Gf; r.peak = peak; r.flags = flags;
+        rec[b] = r;
+    }
+    float* noisy = d.noisy + (long)b * d.noisy_stride;
+    float* clean = d.clean + (long)b * d.clean_stride;
+    const long lo = (long)c * ch, hi = lo + ch < d.L ? lo + ch : d.L;
+    for (long i0 = lo + (long)threadIdx.x * GROUP; i0 < hi; i0 += TILE) {
+        const int cnt = hi - i0 < GROUP ? (int)(hi - i0) : GROUP;
+        int x[GROUP], z[GROUP], t[GROUP];
+        load_clip8(v.s, v.len_s, v.sstart + i0, cnt, x);
+        load_wrap8(v.n, v.len_n, wrap_index(v, i0), cnt, z);
+        if (TARGET) load_clip8(tg, v.len_s, v.sstart + i0, cnt, t);
+        float yn[GROUP], yc[GROUP];
+#pragma unroll
+        for (int k = 0; k < GROUP; ++k) {
+            const float sf = (float)x[k] * kScale;
+            const float gz = gn * ((float)z[k] * kScale);
+            const float m = sf + gz;
+            yn[k] = Gf * m;
+            yc[k] = Gf * (TARGET ? (float)t[k] * kScale : sf);
+        }
+        store8(noisy, i0, cnt, vec, yn);
+        store8(clean, i0, cnt, vec, yc);
+    }
+}
+
 bool rows_take_16_bytes(const DrawArgs& d) {
     return (reinterpret_cast<uintptr_t>(d.noisy) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.clean) & 15) == 0 &&
            d.noisy_stride % 4 == 0 && d.clean_stride % 4 == 0;
@@ -364,6 +579,20 @@ int launch_mix_target(const DrawArgs& d, const short* d_target, int passes, hipS
     if (passes & 1) hipLaunchKernelGGL(k_batch_sums, grid, block, 0, s, d, chunks, ch);
     if (passes & 2) hipLaunchKernelGGL(k_batch_peak, grid, block, 0, s, d, chunks, ch);
     if (passes & 4) hipLaunchKernelGGL(k_batch_write_target, grid, block, 0, s, d, d_target, chunks, ch, rows_take_16_bytes(d));
+    return (int)hipGetLastError();
+}
+
+int launch_mix_active(const DrawArgs& d, const short* d_target, ActiveRecord* rec, int W, long long thr, int passes, hipStream_t s) {
+    const int chunks = active_chunks_of(d.L, W);
+    const long ch = active_chunk_samples(d.L, W);
+    const dim3 grid((unsigned)((long)d.B * chunks)), block(THREADS);
+    const bool vec = rows_take_16_bytes(d);
+    if (passes & 1) hipLaunchKernelGGL(k_batch_active_sums, grid, block, 0, s, d, W, thr, chunks, ch);
+    if (passes & 2) hipLaunchKernelGGL(k_batch_active_peak, grid, block, 0, s, d, chunks, ch);
+    if (passes & 4) {
+        if (d_target) hipLaunchKernelGGL(k_batch_active_write<true>, grid, block, 0, s, d, d_target, rec, chunks, ch, vec);
+        else hipLaunchKernelGGL(k_batch_active_write<false>, grid, block, 0, s, d, d_target, rec, chunks, ch, vec);
+    }
     return (int)hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// batch_host.cpp -- the "training batches from a resident corpus" section of include/gtcrn_micro_hip.h: argument checks,
+// batch_host.cpp -- the "training batches from a resident corpus" and "active levels" sections of include/gtcrn_micro_hip.h: argument checks,
 // launch sequencing and gtcrn_batch_plan_host, the plan's own function body (batch.h) run on the host.  The kernels are in
 // batch.hip.  Compiled with -ffp-contract=off like them.
 #include "../../include/gtcrn_micro_hip.h"
@@ -113,6 +113,17 @@ int gtcrn_batch_pairs(const short* d_noisy_pcm, const short* d_clean_pcm, const 
 
 namespace {
 
+// what every mix entry point checks after draw_args: the records, the workspace, the target corpus if one is given, `passes`
+int mix_buffers(const std::string& w, const void* d_records, const void* d_workspace, const short* d_target_pcm, bool target_needed,
+                int passes) {
+    if (!d_records || !d_workspace || (target_needed && !d_target_pcm)) return bfail(GTCRN_ERR_ARG, w + ": null pointer");
+    if (d_target_pcm && (reinterpret_cast<uintptr_t>(d_target_pcm) & 1)) return bfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
+    if ((reinterpret_cast<uintptr_t>(d_records) & 7) || (reinterpret_cast<uintptr_t>(d_workspace) & 15))
+        return bfail(GTCRN_ERR_ARG, w + ": the records must be 8-byte, the workspace 16-byte aligned");
+    if (passes < 1 || passes > 7) return bfail(GTCRN_ERR_ARG, w + ": `passes` is a sum of 1 (sums), 2 (peak) and 4 (write); 7 is a draw");
+    return 0;
+}
+
 // gtcrn_batch_mix (d_target_pcm null) and gtcrn_batch_mix_target: one set of checks, two launch sequences
 int mix_call(const std::string& w, const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech,
              const short* d_noise_pcm, const long long* d_noise_offsets, int n_noise, const short* d_target_pcm, bool with_target,
@@ -122,11 +133,8 @@ int mix_call(const std::string& w, const short* d_speech_pcm, const long long* d
     const int rc = draw_args(w, d_speech_pcm, d_noise_pcm, d_speech_offsets, n_speech, d_noise_offsets, n_noise, d_plan, B, L, d_noisy,
                              noisy_stride, d_clean, clean_stride, &d);
     if (rc != 0) return rc;
-    if (!d_records || !d_workspace || (with_target && !d_target_pcm)) return bfail(GTCRN_ERR_ARG, w + ": null pointer");
-    if (with_target && (reinterpret_cast<uintptr_t>(d_target_pcm) & 1)) return bfail(GTCRN_ERR_ARG, w + ": misaligned pointer");
-    if ((reinterpret_cast<uintptr_t>(d_records) & 7) || (reinterpret_cast<uintptr_t>(d_workspace) & 15))
-        return bfail(GTCRN_ERR_ARG, w + ": the records must be 8-byte, the workspace 16-byte aligned");
-    if (passes < 1 || passes > 7) return bfail(GTCRN_ERR_ARG, w + ": `passes` is a sum of 1 (sums), 2 (peak) and 4 (write); 7 is a draw");
+    const int rb = mix_buffers(w, d_records, d_workspace, d_target_pcm, with_target, passes);
+    if (rb != 0) return rb;
     const long long cells = (long long)B * gtb::chunks_of(L);
     if (cells > kMaxGrid) return bfail(GTCRN_ERR_ARG, w + ": B * L is too large for one launch");
     d.rec = reinterpret_cast<gtb::Record*>(d_records);
@@ -155,4 +163,47 @@ int gtcrn_batch_mix_target(const short* d_speech_pcm, const long long* d_speech_
     return mix_call("gtcrn_batch_mix_target", d_speech_pcm, d_speech_offsets, n_speech, d_noise_pcm, d_noise_offsets, n_noise,
                     d_target_pcm, true, d_plan, B, L, d_noisy, noisy_stride, d_clean, clean_stride, d_records, d_workspace, passes,
                     stream);
+}
+
+// ---- active levels ------------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(gtcrn_batch_active_record) == 64 && sizeof(gtb::ActiveRecord) == 64, "the active record is 64 bytes");
+
+namespace {
+
+bool window_ok(int window) { return window >= gtb::MIN_WINDOW && window <= gtb::MAX_WINDOW && window % gtb::GROUP == 0; }
+
+}  // namespace
+
+size_t gtcrn_batch_active_workspace_bytes(int B, long L, int window) {
+    if (B <= 0 || L <= 0 || L > gtb::MAX_L || !window_ok(window) || (long long)B * gtb::active_chunks_of(L, window) > kMaxGrid) {
+        bfail(GTCRN_ERR_ARG, "gtcrn_batch_active_workspace_bytes: B and L must be positive, L below 2^31, window a multiple of 8 in "
+                             "8 .. 2^20, B * chunks below 2^31");
+        return 0;
+    }
+    const size_t cells = (size_t)B * (size_t)gtb::active_chunks_of(L, window);
+    return (cells * (gtb::ACTIVE_PARTS * sizeof(long long) + sizeof(float)) + 15) & ~(size_t)15;
+}
+
+int gtcrn_batch_mix_active(const short* d_speech_pcm, const long long* d_speech_offsets, int n_speech, const short* d_noise_pcm,
+                           const long long* d_noise_offsets, int n_noise, const short* d_target_pcm, const gtcrn_batch_item* d_plan,
+                           int B, long L, float* d_noisy, long noisy_stride, float* d_clean, long clean_stride, int window,
+                           long long threshold, gtcrn_batch_active_record* d_records, void* d_workspace, int passes, void* stream) {
+    const std::string w("gtcrn_batch_mix_active");
+    gtb::DrawArgs d;
+    const int rc = draw_args(w, d_speech_pcm, d_noise_pcm, d_speech_offsets, n_speech, d_noise_offsets, n_noise, d_plan, B, L, d_noisy,
+                             noisy_stride, d_clean, clean_stride, &d);
+    if (rc != 0) return rc;
+    const int rb = mix_buffers(w, d_records, d_workspace, d_target_pcm, false, passes);
+    if (rb != 0) return rb;
+    if (!window_ok(window)) return bfail(GTCRN_ERR_ARG, w + ": `window` is a multiple of 8 samples in 8 .. 2^20");
+    if (threshold < 0 || threshold > gtb::MAX_THRESHOLD) return bfail(GTCRN_ERR_ARG, w + ": `threshold` lies in 0 .. 2^30");
+    const long long cells = (long long)B * gtb::active_chunks_of(L, window);
+    if (cells > kMaxGrid) return bfail(GTCRN_ERR_ARG, w + ": B * L is too large for one launch");
+    d.sums = static_cast<long long*>(d_workspace);
+    d.peaks = reinterpret_cast<float*>(d.sums + gtb::ACTIVE_PARTS * cells);
+    const int e = gtb::launch_mix_active(d, d_target_pcm, reinterpret_cast<gtb::ActiveRecord*>(d_records), window, threshold, passes,
+                                         static_cast<hipStream_t>(stream));
+    if (e != 0) return bfail(GTCRN_ERR_HIP, w + ": " + hipGetErrorString(static_cast<hipError_t>(e)));
+    return 0;
 }

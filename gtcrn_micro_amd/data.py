@@ -13,9 +13,14 @@ writes the row convolved with the early part of its response -- the direct path 
 is that: a dereverberation target ("dereverberation targets: early or direct clean").  ``target=`` mixes
 noise into a caller's own paired (degraded, target) speech.
 
-Out of scope: active-speech levels (a VAD), sample rates other than 16 kHz, float corpora, streaming a corpus larger than
-device memory from disk; for the reverberation: targets that need a response of their own (a shortened-decay tail), responses
-longer than 16384 taps, and multichannel responses.
+With ``active_db=`` the noise is scaled to the drawn SNR of the levels over each side's active 100 ms windows -- a short clip,
+pauses and a reverberant tail no longer dilute the speech level -- by exact integer window energies (gtcrn_batch_mix_active;
+"active levels" in the header).
+
+Out of scope: sample rates other than 16 kHz, float corpora, streaming a corpus larger than device memory from disk; for the
+active levels: an active-level ``level_db`` (the level stays the mixture's plain RMS), a threshold relative to the clip, hangover
+smoothing and P.56-style envelope followers, activity labels as an output; for the reverberation: targets that need a response
+of their own (a shortened-decay tail), responses longer than 16384 taps, and multichannel responses.
 """
 import numpy as np
 
@@ -26,6 +31,11 @@ PLAN_DTYPE = np.dtype([("sclip", "<i4"), ("sstart", "<i4"), ("nclip", "<i4"), ("
 RECORD_DTYPE = np.dtype([("Ss", "<i8"), ("Sn", "<i8"), ("Ssn", "<i8"), ("gn", "<f4"), ("Gf", "<f4"), ("peak", "<f4"),
                          ("flags", "<i4")])
 FLAG_NOISE_ZERO, FLAG_SPEECH_ZERO, FLAG_MIX_ZERO, FLAG_LIMITED = 1, 2, 4, 8
+ACTIVE_RECORD_DTYPE = np.dtype([("Ss", "<i8"), ("Sn", "<i8"), ("Ssn", "<i8"), ("As", "<i8"), ("An", "<i8"), ("Ns", "<i4"),
+                                ("Nn", "<i4"), ("gn", "<f4"), ("Gf", "<f4"), ("peak", "<f4"), ("flags", "<i4")])
+FLAG_SPEECH_INACTIVE, FLAG_NOISE_INACTIVE = 16, 32
+ACTIVE_WINDOW_MAX = 1 << 20    # samples; a window is a multiple of 8 in 8 .. this
+ACTIVE_THRESHOLD_MAX = 1 << 30
 REVERB_PLAN_DTYPE = np.dtype([("rir", "<i4"), ("reserved", "<i4")])
 REVERB_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("reserved", "<i4")])
 REVERB_SPLIT_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("split", "<i4"),
@@ -53,6 +63,52 @@ def workspace_bytes(B, L):
     if n == 0:
         raise GtcrnError(lib().gtcrn_last_error().decode())
     return n
+
+
+def _active_lib():
+    L = _batch_lib()
+    if not hasattr(L, "gtcrn_batch_mix_active"):
+        raise GtcrnError("this library has no active levels (gtcrn_batch_mix_active)")
+    return L
+
+
+def _active_window(window):
+    w = int(window)
+    if w != window or w < 8 or w > ACTIVE_WINDOW_MAX or w % 8:
+        raise GtcrnError(f"active_window must be a multiple of 8 samples in 8 .. {ACTIVE_WINDOW_MAX}, got {window!r}")
+    return w
+
+
+def active_threshold(db):
+    """The integer threshold of gtcrn_batch_mix_active for a mean-square level of ``db`` dB re full scale:
+    floor(2^30 * 10^(db / 10)), computed here in double (-50 dB -> 10737).  The threshold is absolute."""
+    db = float(db)
+    if np.isnan(db) or db > 0.0:
+        raise GtcrnError("active_db is a level re full scale: at most 0 dB")
+    return int(np.floor(float(ACTIVE_THRESHOLD_MAX) * 10.0 ** (db / 10.0)))
+
+
+def active_workspace_bytes(B, L, window=1600):
+    n = int(_active_lib().gtcrn_batch_active_workspace_bytes(int(B), int(L), int(window)))
+    if n == 0:
+        raise GtcrnError(lib().gtcrn_last_error().decode())
+    return n
+
+
+def achieved_snr_db(records):
+    """-> (active, plain), float64 [B], from an ACTIVE_RECORD_DTYPE array: the SNR of the mixture over each side's active
+    windows, 10 log10((As / Ns) / (gn^2 An / Nn)) -- what ``snr_db`` of the plan asks for --, and over the whole row,
+    10 log10(Ss / (gn^2 Sn)).  NaN where the row has flag 1 or 2 (a side is all zero: there is no SNR)."""
+    r = np.asarray(records)
+    if r.dtype != ACTIVE_RECORD_DTYPE:
+        raise GtcrnError("achieved_snr_db takes ACTIVE_RECORD_DTYPE records (a source with active_db=)")
+    ok = (r["flags"] & (FLAG_NOISE_ZERO | FLAG_SPEECH_ZERO)) == 0
+    g2 = r["gn"].astype(np.float64) ** 2
+    active, plain = np.full(r.shape, np.nan), np.full(r.shape, np.nan)
+    f = lambda k: r[k][ok].astype(np.float64)      # noqa: E731
+    active[ok] = 10.0 * np.log10((f("As") / f("Ns")) / (g2[ok] * f("An") / f("Nn")))
+    plain[ok] = 10.0 * np.log10(f("Ss") / (g2[ok] * f("Sn")))
+    return active, plain
 
 
 def plan_host(speech_offsets, noise_offsets, B, L, seed, step, item0=0, granule=1, snr_db=(-5.0, 20.0),
@@ -375,14 +431,27 @@ class BatchSource:
     the wet row (gtcrn_batch_reverb_split, gtcrn_batch_mix_target); ``noisy``, its SNR and its level are those of the fully
     reverberant speech.  None: the draw above, call for call.
     ``target=`` a Corpus under ``speech``'s offsets table (mix form, without ``rirs=``): ``clean`` is cut from it instead of
-    from ``speech`` -- noise mixed on the device into a caller's own paired (degraded, target) speech."""
+    from ``speech`` -- noise mixed on the device into a caller's own paired (degraded, target) speech.
+    ``active_db=`` a level in dB re full scale (mix form; -50 is the usual choice): the drawn SNR is that of the levels over the
+    windows of ``active_window`` samples (1600: 100 ms) whose mean square exceeds it, each side by its own activity
+    (gtcrn_batch_mix_active in place of the two mix calls above, in every combination with ``rirs=``, ``target_ms=`` and
+    ``target=``).  ``records`` is then (B, 16) int32, ``records_numpy()`` ACTIVE_RECORD_DTYPE, ``active_threshold`` the integer
+    threshold; ``achieved_snr_db`` reads the SNR back.  None: the draw above, call for call."""
 
     def __init__(self, speech, noise=None, paired_clean=None, B=1, L=64000, seed=0, snr_db=(-5.0, 20.0), level_db=(-35.0, -15.0),
-                 granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0, target_ms=None, target=None):
+                 granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0, target_ms=None, target=None, active_db=None,
+                 active_window=1600):
         import torch
         _batch_lib()
         if (noise is None) == (paired_clean is None):
             raise GtcrnError("give exactly one of noise= (mix) and paired_clean= (pairs)")
+        self.active_db, self.active_window, self.active_threshold = None, None, None
+        if active_db is not None:                        # decided on the arguments alone, before any corpus is looked at
+            _active_lib()
+            if paired_clean is not None:
+                raise GtcrnError("active_db= goes with noise= (the mix): a paired corpus is not mixed, so it has no SNR to set")
+            self.active_window = _active_window(active_window)
+            self.active_db, self.active_threshold = float(active_db), active_threshold(active_db)
         other = noise if noise is not None else paired_clean
         if not isinstance(speech, Corpus) or not isinstance(other, Corpus) or other.device != speech.device:
             raise GtcrnError("the corpora must be data.Corpus objects on one device")
@@ -408,6 +477,9 @@ class BatchSource:
         self.noisy = torch.empty((B, L), device=dev, dtype=torch.float32)
         self.clean = torch.empty((B, L), device=dev, dtype=torch.float32)
         self._ws = torch.empty(workspace_bytes(B, L), device=dev, dtype=torch.uint8) if noise is not None else None
+        if self.active_db is not None:
+            self.records = torch.zeros((B, 16), device=dev, dtype=torch.int32)  # gtcrn_batch_active_record rows
+            self._ws = torch.empty(active_workspace_bytes(B, L, self.active_window), device=dev, dtype=torch.uint8)
         self.rirs, self.p_reverb, self.reverb_form = rirs, float(p_reverb), int(reverb_form)
         self.target, self.target_ms = target, None if target_ms is None else float(target_ms)
         if target is not None:
@@ -459,7 +531,8 @@ class BatchSource:
         return self.plan.cpu().numpy().view(PLAN_DTYPE).reshape(self.B)
 
     def records_numpy(self):
-        return self.records.cpu().numpy().view(RECORD_DTYPE).reshape(self.B)
+        """The mix records of the most recent draw: RECORD_DTYPE, or ACTIVE_RECORD_DTYPE for a source with ``active_db=``."""
+        return self.records.cpu().numpy().view(RECORD_DTYPE if self.active_db is None else ACTIVE_RECORD_DTYPE).reshape(self.B)
 
     def reverb_plan_numpy(self):
         """The reverb plan of the most recent draw (a source with ``rirs=``)."""
@@ -565,7 +638,13 @@ class BatchSource:
                         self.staged.data_ptr(), self.staged_stride, self.staged_offsets.data_ptr(), self.staged_plan.data_ptr(),
                         self.reverb_records.data_ptr(), self._rws.data_ptr(), self.reverb_form, _stream_ptr()))
                     s_pcm, s_off, s_n, p = self.staged, self.staged_offsets, self.B, self.staged_plan
-                if t_pcm is not None:
+                if self.active_db is not None:           # one entry point for the plain and the target form
+                    _check(lib().gtcrn_batch_mix_active(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(),
+                                                        nz.offsets.data_ptr(), nz.n, t_pcm.data_ptr() if t_pcm is not None else None,
+                                                        p.data_ptr(), self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
+                                                        self.active_window, self.active_threshold, self.records.data_ptr(),
+                                                        self._ws.data_ptr(), int(passes), _stream_ptr()))
+                elif t_pcm is not None:
                     _check(lib().gtcrn_batch_mix_target(s_pcm.data_ptr(), s_off.data_ptr(), s_n, nz.pcm.data_ptr(),
                                                         nz.offsets.data_ptr(), nz.n, t_pcm.data_ptr(), p.data_ptr(), self.B, self.L,
                                                         noisy.data_ptr(), ns, clean.data_ptr(), cs, self.records.data_ptr(),

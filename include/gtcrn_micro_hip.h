@@ -906,9 +906,9 @@ int gtcrn_score_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap
  *
  * Output rows are float32 with noisy_stride / clean_stride >= L floats between them.  Everything is asynchronous on `stream`,
  * allocates nothing and is capturable.  B <= 0, L <= 0 or L >= 2^31, an empty corpus, a null table or buffer, granule < 1,
- * hi < lo and a stride below L return GTCRN_ERR_ARG before anything is enqueued.  Out of scope: active-speech levels (a VAD),
- * other sample rates, float corpora, streaming a corpus larger than device memory from disk.  (Room impulse responses: the
- * next section.) */
+ * hi < lo and a stride below L return GTCRN_ERR_ARG before anything is enqueued.  Out of scope: other sample rates, float
+ * corpora, streaming a corpus larger than device memory from disk.  (Room impulse responses: the next section; levels over
+ * active windows instead of the plain RMS: "active levels".) */
 typedef struct { int sclip, sstart, nclip, nstart; float snr_db, snr_amp, lvl_db, lvl_amp; } gtcrn_batch_item;   /* 32 bytes */
 typedef struct { long long Ss, Sn, Ssn; float gn, Gf, peak; int flags; } gtcrn_batch_record;                   /* 40 bytes */
 int gtcrn_batch_plan(const long long *d_speech_offsets, int n_speech, const long long *d_noise_offsets, int n_noise, int B,
@@ -1048,6 +1048,46 @@ int gtcrn_batch_mix_target(const short *d_speech_pcm, const long long *d_speech_
                            const long long *d_noise_offsets, int n_noise, const short *d_target_pcm,
                            const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy, long noisy_stride, float *d_clean,
                            long clean_stride, gtcrn_batch_record *d_records, void *d_workspace, int passes, void *stream);
+
+/* ---- active levels: the mix at an SNR of the levels while each side is active ------------------------------------------------
+ * gtcrn_batch_mix levels speech and noise by their plain RMS over the row.  A clip shorter than the row, pauses, and the build-up
+ * and tail of a reverberant row put samples without speech into that mean: the noise is scaled too low and the SNR while
+ * somebody speaks is higher than the drawn one (a 2 s utterance in a 4 s row: 3 dB).  gtcrn_batch_mix_active levels each side
+ * over its ACTIVE windows.  The rule is the familiar one of DNS-style synthesizers -- fixed windows, an energy threshold, each
+ * side judged by its own activity -- but the threshold is absolute, not applied after a normalisation: the contract is this
+ * library's own and no parity with an outside tool is claimed.
+ *
+ * Inputs as gtcrn_batch_mix_target, with d_target_pcm NULLABLE (null: clean is cut from the speech side, as gtcrn_batch_mix), plus
+ *   window W in samples, a multiple of 8, 8 <= W <= 2^20 (production: 1600, 100 ms), and
+ *   threshold thr, an integer mean-square level in int16^2 units, 0 <= thr <= 2^30 (floor(2^30 * 10^(dB / 10)) re full scale,
+ *   computed by the caller: -50 dB -> 10737).
+ * Window w of a row covers row samples [w W, min((w + 1) W, L)), n_w its length (the last one may be short); windows are aligned
+ * to the row, not to the clip.  Per side, E_w = the 64-bit sum of squares of the int16 samples AS MIXED (the speech window with
+ * zeros past the clip's end; the wrapped noise window; the staged wet speech of a reverberant row).  Window w is active on that
+ * side iff E_w > thr * n_w: an int64 comparison (both sides below 2^51), equality is inactive.
+ *   As = sum E_w, Ns = sum n_w over the speech-active windows; An, Nn likewise over the noise-active windows;
+ *   Ss, Sn, Ssn: the whole-row sums of gtcrn_batch_mix.
+ *   Fallback: Ns == 0 -> As = Ss, Ns = L, flag 16 (SPEECH_INACTIVE);  Nn == 0 -> An = Sn, Nn = L, flag 32 (NOISE_INACTIVE).
+ *   gn = 0 and flag 1 if An == 0; else 1 and flag 2 if As == 0; else
+ *     r = double(As) / double(An);  if (Ns != Nn) r = r * (double(Nn) / double(Ns));  gn = float(sqrt(r) * double(snr_amp)):
+ *     every conversion and operation rounds once, in double, in this order.
+ * Everything after gn is gtcrn_batch_mix, unchanged: m_i, the peak, Gf from the PLAIN mixture RMS over L (what the level range
+ * describes), the 0.99 limiter, noisy, clean (or the target row), flags 1, 2, 4, 8.  When every window of both sides is active
+ * (Ns == Nn == L) the output and the shared record fields equal gtcrn_batch_mix's bit for bit.
+ * d_records[b] = {Ss, Sn, Ssn, As, An, Ns, Nn, gn, Gf, peak, flags}; As, An, Ns, Nn as USED, i.e. after the fallback.
+ * Energies and decisions are exact integers, so the output is defined bit for bit given a plan and does not depend on how a row
+ * is cut over workgroups.  Three launches as gtcrn_batch_mix's, kernels of their own; a chunk is a whole number of windows.
+ * d_workspace: gtcrn_batch_active_workspace_bytes(B, L, window) bytes, 16-byte aligned; `passes` as gtcrn_batch_mix.
+ * Argument errors as gtcrn_batch_mix_target's, then a bad window, then a bad threshold: GTCRN_ERR_ARG before anything is
+ * enqueued.  Out of scope: an active-level lvl_db, a threshold relative to the clip, hangover smoothing and P.56-style
+ * envelope followers, activity labels as an output. */
+typedef struct { long long Ss, Sn, Ssn, As, An; int Ns, Nn; float gn, Gf, peak; int flags; } gtcrn_batch_active_record;   /* 64 bytes */
+size_t gtcrn_batch_active_workspace_bytes(int B, long L, int window);   /* 0 (and GTCRN_ERR_ARG recorded) for a bad shape */
+int gtcrn_batch_mix_active(const short *d_speech_pcm, const long long *d_speech_offsets, int n_speech, const short *d_noise_pcm,
+                           const long long *d_noise_offsets, int n_noise, const short *d_target_pcm,
+                           const gtcrn_batch_item *d_plan, int B, long L, float *d_noisy, long noisy_stride, float *d_clean,
+                           long clean_stride, int window, long long threshold, gtcrn_batch_active_record *d_records,
+                           void *d_workspace, int passes, void *stream);
 
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward

@@ -33,7 +33,8 @@ def kernels(path):
 
 def demangled(names):
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-    return [re.sub(r"\(.*$", "", d) for d in r.stdout.splitlines()]
+    # (batch.hip keeps its kernels in an unnamed namespace: that bracket is part of the name, not an argument list)
+    return [re.sub(r"\(.*$", "", d.replace("(anonymous namespace)", "{anonymous}")) for d in r.stdout.splitlines()]
 
 
 def main():

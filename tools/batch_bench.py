@@ -13,6 +13,10 @@ For B = 512 and B = 8 rows of 4 s (L = 64000), from a synthetic corpus of at lea
 and the two ratios draw / train step and draw / copy.
 
     python tools/batch_bench.py [--out profiles/batch_bench.json] [--iters 100] [--gigabytes 2.0]
+
+--active measures only the draw at an SNR of active levels (BatchSource(active_db=-50), 100 ms windows) beside the plain mix
+draw, from the same corpora in the same run: the whole draw and each pass of both, repeated `--reps` times, and the ratios
+active / plain with their spread between repetitions (profiles/batch_active_bench.json).
 """
 import argparse
 import json
@@ -63,15 +67,71 @@ def synthetic_corpus(samples, seed, device="cuda"):
     return Corpus.from_tensors(pcm, off)
 
 
+def mix_times(src, iters):
+    """A mix source's whole draw and each launch's share, as main() takes them: from draws cut short after the plan, the sums
+    and the peak pass, every one of which draws a new plan first."""
+    draw = median_ms(lambda: src.draw(), iters)
+    cum = {"plan": median_ms(lambda: src.draw_plan(), iters),
+           "plan_sums": median_ms(lambda: src.draw(passes=1), iters),
+           "plan_sums_peak": median_ms(lambda: src.draw(passes=3), iters)}
+    return {"draw_ms": draw, "cumulative_ms": cum,
+            "launch_ms": {"plan": cum["plan"][0], "sums": cum["plan_sums"][0] - cum["plan"][0],
+                          "peak": cum["plan_sums_peak"][0] - cum["plan_sums"][0], "write": draw[0] - cum["plan_sums_peak"][0]}}
+
+
+def active_leg(a, speech, noise, L, res):
+    """--active: the draw at an SNR of active levels (100 ms windows, -50 dB) beside the plain mix draw of the same run, B = 512:
+    `reps` repetitions of both, interleaved; the ratios active / plain of the draw and of pass 1 per repetition, and the spread
+    between repetitions they are to be read against."""
+    from gtcrn_micro_amd.data import BatchSource, achieved_snr_db
+    B, W, db = a.active_batch, 1600, -50.0
+    plain = BatchSource(speech, noise=noise, B=B, L=L, seed=1)
+    act = BatchSource(speech, noise=noise, B=B, L=L, seed=1, active_db=db, active_window=W)
+    reps = []
+    for _ in range(a.reps):
+        reps.append({"plain": mix_times(plain, a.iters), "active": mix_times(act, a.iters)})
+    col = lambda side, f: [f(r[side]) for r in reps]      # noqa: E731
+    span = lambda v: {"median": statistics.median(v), "min": min(v), "max": max(v)}      # noqa: E731
+    summary = {}
+    for side in ("plain", "active"):
+        summary[side] = {"draw_ms": span(col(side, lambda t: t["draw_ms"][0]))}
+        for k in ("plan", "sums", "peak", "write"):
+            summary[side][k + "_ms"] = span(col(side, lambda t, k=k: t["launch_ms"][k]))
+    ratio = lambda f: span([f(r["active"]) / f(r["plain"]) for r in reps])      # noqa: E731
+    summary["active_over_plain"] = {"draw": ratio(lambda t: t["draw_ms"][0])}
+    for k in ("sums", "peak", "write"):
+        summary["active_over_plain"][k] = ratio(lambda t, k=k: t["launch_ms"][k])
+    act.draw()                                           # a whole draw last: the records below belong to the plan below
+    rec = act.records_numpy()
+    snr_active, snr_plain = achieved_snr_db(rec)
+    res.update({"B": B, "window": W, "active_db": db, "threshold": act.active_threshold, "reps": reps, "summary": summary,
+                "bytes_compulsory": 12 * B * L,
+                "last_batch": {"flags_seen": sorted(set(int(v) for v in rec["flags"])),
+                               "speech_active_share": float((rec["Ns"] / L).mean()), "noise_active_share": float((rec["Nn"] / L).mean()),
+                               "snr_error_db_max": float(np.nanmax(np.abs(snr_active - act.plan_numpy()["snr_db"]))),
+                               "plain_minus_active_snr_db_max": float(np.nanmax(np.abs(snr_plain - snr_active)))}})
+    s = summary
+    print(f"B={B} W={W} {db} dB: active draw {s['active']['draw_ms']['median']:.4f} ms (sums {s['active']['sums_ms']['median']:.4f}, "
+          f"peak {s['active']['peak_ms']['median']:.4f}, write {s['active']['write_ms']['median']:.4f}); plain draw "
+          f"{s['plain']['draw_ms']['median']:.4f} ms (sums {s['plain']['sums_ms']['median']:.4f}, peak "
+          f"{s['plain']['peak_ms']['median']:.4f}, write {s['plain']['write_ms']['median']:.4f}); active / plain: draw "
+          f"{s['active_over_plain']['draw']['median']:.3f}, sums {s['active_over_plain']['sums']['median']:.3f}", flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.json"))
+    ap.add_argument("--active", action="store_true", help="only the active-level leg (default --out: profiles/batch_active_bench.json)")
+    ap.add_argument("--active-batch", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=5, help="repetitions of the active leg")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--train-iters", type=int, default=12)
     ap.add_argument("--gigabytes", type=float, default=2.0, help="least size of each side of the corpus")
     ap.add_argument("--batches", default="512,8")
     ap.add_argument("--samples", type=int, default=64000)
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "batch_active_bench.json" if a.active else "batch_bench.json")
     import torch
     from gtcrn_micro_amd.data import BatchSource, Corpus
     from gtcrn_micro_amd.train import make_training, train_step
@@ -90,6 +150,14 @@ def main(argv=None):
            "timing": "median (min, max) in ms over %d windows of 4 calls (train step: %d windows of 1), device events, warmed, "
                      "one process" % (a.iters, a.train_iters),
            "batches": {}}
+    if a.active:
+        del res["batches"]
+        res["timing"] = "median (min, max) in ms over %d windows of 4 calls, device events, warmed, one process" % a.iters
+        active_leg(a, speech, noise, L, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+        print("wrote", a.out)
+        return
     for B in (int(v) for v in a.batches.split(",")):
         mix = BatchSource(speech, noise=noise, B=B, L=L, seed=1)
         prs = BatchSource(paired_noisy, paired_clean=paired_clean, B=B, L=L, seed=1)
