@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgtcrn_micro_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["kernels.hip", "api.cpp", "pack.cpp", "train_kernels.hip", "train.cpp", "metrics.hip", "metrics_host.cpp", "batch.hip", "batch_host.cpp", "reverb.hip", "reverb_host.cpp"]
-HEADERS = ["kernels.h", "stream_ms_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", "batch.h", "reverb.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
+HEADERS = ["kernels.h", "fft256.h", "stream_ms_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", "batch.h", "reverb.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
 
 
 def _stale(target, deps):

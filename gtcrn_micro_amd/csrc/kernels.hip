@@ -19,10 +19,12 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "fft256.h"
 #include "kernels.h"
 #include "layout.h"
 
 using namespace gtl;
+using namespace gtfft;
 
 namespace gtk {
 
@@ -82,13 +84,7 @@ __device__ __forceinline__ void lds_dma_group(const DmaSeg (&seg)[NSEG], const f
 // fence, which on gfx950 drains vmcnt: every barrier would then wait for all global loads and
 // stores in flight (prefetches, skip-tensor stores).  Waves of a workgroup exchange data only
 // through LDS here, so waiting for this wave's LDS operations (lgkmcnt) is sufficient.
-// Ordering for LDS data that only the lanes of ONE wave exchange: LDS operations of a wave complete in
-// issue order, so it is enough to keep the compiler from reordering across this point.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// (LDS data that only the lanes of ONE wave exchange: wave_lds_sync, fft256.h)
 __device__ __forceinline__ void wg_barrier() {
 #ifdef GT_EXP_NOBARRIER      // timing experiment only (results are wrong): what the barrier skew costs
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -417,48 +413,7 @@ __device__ __forceinline__ Lane lane_info() {
 // torch.stft(x,512,256,512,win,center=True,reflect,onesided) (infer.py:60-67): frame t =
 // reflect_pad(x,256)[256t : 256t+512] * win, unnormalised rFFT.  One wave per frame: the 512 real
 // samples are packed as 256 complex, radix-4 Stockham FFT in LDS, then the real-FFT split.
-__device__ __forceinline__ long reflect_idx(long i, long L) {
-    long j = i - 256;
-    j = j < 0 ? -j : j;
-    return j >= L ? 2 * (L - 1) - j : j;
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// 256-point complex FFT of one wave's buffer (ping-pong a -> b ...), DIR = -1 forward, +1 inverse
-// (unnormalised).  tw[k] = exp(-2 pi i k / 256).  Result ends in `a` (4 stages).
-template <int DIR>
-__device__ __forceinline__ void fft256(float2* a, float2* b, const float2* tw, int lane) {
-    float2* src = a;
-    float2* dst = b;
-#pragma unroll
-    for (int stage = 0; stage < 4; ++stage) {
-        const int Ns = 1 << (2 * stage);
-        const int k = lane & (Ns - 1);
-        const int tstep = k * (64 / Ns);
-        float2 v0 = src[lane], v1 = src[lane + 64], v2 = src[lane + 128], v3 = src[lane + 192];
-        if (stage > 0) {
-            float2 w1 = tw[tstep], w2 = tw[2 * tstep], w3 = tw[3 * tstep];
-            if (DIR > 0) { w1.y = -w1.y; w2.y = -w2.y; w3.y = -w3.y; }
-            v1 = cmul(v1, w1); v2 = cmul(v2, w2); v3 = cmul(v3, w3);
-        }
-        const float2 s0 = make_float2(v0.x + v2.x, v0.y + v2.y), s1 = make_float2(v0.x - v2.x, v0.y - v2.y);
-        const float2 s2 = make_float2(v1.x + v3.x, v1.y + v3.y);
-        const float2 dd = make_float2(v1.x - v3.x, v1.y - v3.y);
-        // (v1 - v3) * (i * DIR): forward multiplies by -i, inverse by +i
-        const float2 s3 = DIR < 0 ? make_float2(dd.y, -dd.x) : make_float2(-dd.y, dd.x);
-        const int j0 = ((lane - k) << 2) + k;
-        dst[j0] = make_float2(s0.x + s2.x, s0.y + s2.y);
-        dst[j0 + Ns] = make_float2(s1.x + s3.x, s1.y + s3.y);
-        dst[j0 + 2 * Ns] = make_float2(s0.x - s2.x, s0.y - s2.y);
-        dst[j0 + 3 * Ns] = make_float2(s1.x - s3.x, s1.y - s3.y);
-        wave_lds_sync();   // each wave transforms its own frame in its own buffers
-        float2* t = src; src = dst; dst = t;
-    }
-}
-
+// The stage itself (tables, window, fft256, split, merge, envelope, frame fetch) is fft256.h.
 constexpr int FFT_WAVES = 4;
 
 // ADJ = true: the adjoint of k_istft's linear map (the backward of torch.istft, used by the fused HybridLoss):
@@ -475,13 +430,11 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_stft(const float* __restrict
     __shared__ float s_win[512];
     __shared__ float2 s_buf[FFT_WAVES][2][256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
-    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    fft_tables_load(s_tw, s_tw512, s_win, twid, win, tid, FFT_WAVES * 64);
     __syncthreads();
     const long nframes = (long)B * T;
     const long base = (long)blockIdx.x * (FFT_WAVES * FRAMES_PER_WAVE);
-    // samples of a frame: lane holds the pairs (2m, 2m+1), m = lane + 64 q.  Interior frames read them as one
-    // 8-byte load each; only the first and the last two frames of an utterance touch the reflected edges.
+    // samples of a frame (frame_fetch): only the first and the last two frames of an utterance touch the edges.
     // lens (optional): utterance b holds lens[b] <= L samples in its row of L (variable-length batch); its frames
     // t >= 1 + lens[b]/256 do not exist (nothing is stored for them) and its reflected edge is its own
     auto fetch = [&](long fr, float2 (&v)[4]) {
@@ -491,19 +444,19 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_stft(const float* __restrict
         const float* x = wave + (long)b * L;
         const long Lb = lens ? (long)lens[b] : L;
         if (t > (int)(Lb >> 8)) t = 0;                        // a frame past the utterance's end: not live, reads frame 0
-        const long lo = 256L * t - 256;                       // first sample of the frame in the unpadded signal
-        if (lo >= 0 && lo + 512 <= Lb && ((reinterpret_cast<uintptr_t>(x + lo) & 7) == 0)) {
+        if constexpr (!ADJ) {
+            frame_fetch(x, t, Lb, lane, v);
+        } else {                                              // frame_fetch's two paths, zeros where it reflects
+            const long lo = 256L * t - 256;
+            if (lo >= 0 && lo + 512 <= Lb && ((reinterpret_cast<uintptr_t>(x + lo) & 7) == 0)) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float2*>(x + lo + 2 * (lane + 64 * q));
-        } else {
+                for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float2*>(x + lo + 2 * (lane + 64 * q));
+            } else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const long i0 = 256L * t + 2 * (lane + 64 * q);
-                if (ADJ) {
+                for (int q = 0; q < 4; ++q) {
+                    const long i0 = 256L * t + 2 * (lane + 64 * q);
                     const long j0 = i0 - 256, j1 = j0 + 1;
                     v[q] = make_float2(j0 >= 0 && j0 < Lb ? x[j0] : 0.f, j1 >= 0 && j1 < Lb ? x[j1] : 0.f);
-                } else {
-                    v[q] = make_float2(x[reflect_idx(i0, Lb)], x[reflect_idx(i0 + 1, Lb)]);
                 }
             }
         }
@@ -523,9 +476,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_stft(const float* __restrict
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int m = lane + 64 * q;
-            float2 v;
-            v.x = cur[q].x * s_win[2 * m];
-            v.y = cur[q].y * s_win[2 * m + 1];
+            const float2 v = frame_window(cur[q], s_win, m);
             A[m] = v;
             if (frames_out && live) {
                 frames_out[fr * 512 + 2 * m] = v.x;
@@ -534,29 +485,23 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_stft(const float* __restrict
         }
         wave_lds_sync();
         fft256<-1>(A, Bf, s_tw, lane);
-        // real-FFT split: X[k] = Ze + exp(-2 pi i k/512) Zo, Ze = (Z[k]+conj(Z[256-k]))/2,
-        // Zo = (Z[k]-conj(Z[256-k]))/(2i)
         if (live && spec) {
             float* o = spec + (long)b * sb + (long)t * st;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int k = lane + 64 * q;
-                const float2 zk = A[k], zm = A[(256 - k) & 255];
-                const float2 ze = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-                const float2 zo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                const float2 r = cmul(s_tw512[k], zo);
+                const float2 zk = A[k], X = rfft_bin(A, s_tw512, k, zk);
                 // the re/im pair is contiguous and 8-byte aligned (even strides): one 8-byte store
                 float2* ok = reinterpret_cast<float2*>(o + (long)k * sf);
                 float2* on = reinterpret_cast<float2*>(o + 256L * sf);
                 if (ADJ) {
                     const float ck = (k == 0 ? 1.0f : 2.0f) / 512.0f;
                     const float2 old = *ok;
-                    *ok = make_float2(old.x + ck * (ze.x + r.x), old.y + (k == 0 ? 0.f : ck * (ze.y + r.y)));
-                    if (k == 0) { const float2 o2 = *on; *on = make_float2(o2.x + (zk.x - zk.y) * (1.0f / 512.0f), o2.y); }
+                    *ok = make_float2(old.x + ck * X.x, old.y + (k == 0 ? 0.f : ck * X.y));
+                    if (k == 0) { const float2 o2 = *on; *on = make_float2(o2.x + rfft_nyquist(zk).x * (1.0f / 512.0f), o2.y); }
                 } else {
-                    *ok = make_float2(ze.x + r.x, ze.y + r.y);
-                    if (k == 0)  // Nyquist bin: X[256] = Re Z[0] - Im Z[0]
-                        *on = make_float2(zk.x - zk.y, 0.f);
+                    *ok = X;
+                    if (k == 0) *on = rfft_nyquist(zk);
                 }
             }
         }
@@ -597,8 +542,7 @@ __device__ __forceinline__ void istft_body(const float* __restrict__ spec, long 
     float (*s_fr)[512] = reinterpret_cast<float (*)[512]>(&s_fa[0][0]);
     static_assert(ISTFT_BLOCKS + 1 <= 2 * FFT_WAVES, "one buffer per frame of the two rounds");
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
-    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    fft_tables_load(s_tw, s_tw512, s_win, twid, win, tid, FFT_WAVES * 64);
     __syncthreads();
     const int groups = (T - 1 + ISTFT_BLOCKS - 1) / ISTFT_BLOCKS;
     const int b = blockIdx.x / groups, grp = blockIdx.x - b * groups;
@@ -634,20 +578,10 @@ __device__ __forceinline__ void istft_body(const float* __restrict__ spec, long 
         float2* A = s_fa[fi < ISTFT_BLOCKS + 1 ? fi : ISTFT_BLOCKS];
         float2* Bf = s_fb[wv];
         if (it + 1 < ROUNDS) fetch(it + 1, nk, nm);
-        // merge: Z[k] = Xe + i Xo, Xe = (X[k]+conj(X[256-k]))/2, Xo = (X[k]-conj(X[256-k]))/2 * exp(+2 pi i k/512);
-        // c2r semantics: the imaginary parts of DC and Nyquist are ignored.
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k = lane + 64 * q;
-            float2 xk = ck[q];
-            float2 xm = cm[q];
-            xm.y = -xm.y;
-            if (k == 0) { xk.y = 0.f; xm.y = 0.f; }
-            const float2 xe = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y + xm.y));
-            float2 w = s_tw512[k];
-            w.y = -w.y;
-            const float2 xo = cmul(make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y - xm.y)), w);
-            A[k] = make_float2(xe.x - xo.y, xe.y + xo.x);
+            A[k] = irfft_bin(ck[q], cm[q], s_tw512, k);
         }
         wave_lds_sync();
         fft256<1>(A, Bf, s_tw, lane);
@@ -655,9 +589,9 @@ __device__ __forceinline__ void istft_body(const float* __restrict__ spec, long 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int m = lane + 64 * q;
-                const float2 z = A[m];
-                s_fr[fi][2 * m] = (z.x * (1.0f / 256.0f)) * s_win[2 * m];
-                s_fr[fi][2 * m + 1] = (z.y * (1.0f / 256.0f)) * s_win[2 * m + 1];
+                const float2 f = irfft_window(A[m], s_win, m);
+                s_fr[fi][2 * m] = f.x;
+                s_fr[fi][2 * m + 1] = f.y;
             }
         }
         wave_lds_sync();
@@ -669,20 +603,19 @@ __device__ __forceinline__ void istft_body(const float* __restrict__ spec, long 
     float* o = wave + (long)b * 256 * (T - 1);                // rows of 256 (T - 1) samples
     if constexpr (MIX) {
         const float g = gain[b];
-        const float env = s_win[256 + tid] * s_win[256 + tid] + s_win[tid] * s_win[tid];
+        const float env = ola_env(s_win, tid);
 #pragma unroll
         for (int jb = 0; jb < ISTFT_BLOCKS; ++jb) {
             if (jb >= nfr - 1) break;
             const float acc = s_fr[jb][256 + tid] + s_fr[jb + 1][tid];
-            o[(long)(j0 + jb) * 256 + tid] = wave_mix(g, dv[jb], env > 1e-11f ? acc / env : acc);
+            o[(long)(j0 + jb) * 256 + tid] = wave_mix(g, dv[jb], ola_div(acc, env));
         }
         return;
     }
     for (int idx = tid; idx < (nfr - 1) * 256; idx += FFT_WAVES * 64) {
         const int jb = idx >> 8, i = idx & 255;
         const float acc = s_fr[jb][256 + i] + s_fr[jb + 1][i];
-        const float env = s_win[256 + i] * s_win[256 + i] + s_win[i] * s_win[i];
-        o[(long)(j0 + jb) * 256 + i] = env > 1e-11f ? acc / env : acc;
+        o[(long)(j0 + jb) * 256 + i] = ola_div(acc, ola_env(s_win, i));
     }
 }
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_istft(const float* __restrict__ spec, long sb, long sf, long st,
@@ -720,10 +653,10 @@ constexpr int SLOT_WORDS = 8;
 // gtcrn_wave_stream_step).  Frame t of torch.stft(center=True) is x[256t-256 : 256t+256]: at call k the library
 // frames hop k (with hop k-1 from the stream's input ring), the model steps it, and the synthesis emits hop block k-1
 // = second half of frame k-1 (the stored tail) + first half of frame k, / env.  Frame 0 is the start-reflected hop 0
-// whose one future sample, x[256], meets win[0] == 0 (it is read as 0).  The arithmetic is k_stft / k_front's (window
-// product, fft256<-1>, real split, Nyquist bin) and k_istft's (merge, fft256<1>, (z / 256) * win, acc / env)
-// expression for expression, so the stream equals gtcrn_forward_wave one hop late, bit for bit.
-// Samples are float or int16 (widened as / 32768, stored as clip(rint(y * 32768)): the PCM16 kernels' expressions).
+// whose one future sample, x[256], meets win[0] == 0 (it is read as 0).  The arithmetic is k_stft / k_front's and
+// k_istft's because it is the same functions (fft256.h: frame_window, fft256<-1>, rfft_bin, rfft_nyquist; irfft_bin,
+// fft256<1>, irfft_window, ola_div), so the stream equals gtcrn_forward_wave one hop late, bit for bit.
+// Samples are float or int16 (pcm16_widen / pcm16_round, which the PCM16 kernels call too).
 // FLUSH: the stream's last frame from the ring and r < 256 extra samples, end-reflected as reflect_idx does.
 // The packet kernels also take G.711 codes (g711u / g711a, kernels.h): read as D_law[c] / 32768, stored as E_law of the
 // int16 the PCM16 store would have written -- integer arithmetic in registers, no table.
@@ -731,15 +664,14 @@ template <typename S>
 inline constexpr bool is_g711 = std::is_same<S, g711u>::value || std::is_same<S, g711a>::value;
 template <typename S>
 __device__ __forceinline__ float wave_ld(const S* p) {
-    if constexpr (std::is_same<S, short>::value) return (float)*p * (1.0f / 32768.0f);
-    else if constexpr (is_g711<S>) return (float)g711_decode(S::law, p->code) * (1.0f / 32768.0f);
+    if constexpr (std::is_same<S, short>::value) return pcm16_widen(*p);
+    else if constexpr (is_g711<S>) return pcm16_widen(g711_decode(S::law, p->code));
     else return *p;
 }
 template <typename S>
 __device__ __forceinline__ void wave_st(S* p, float y) {
-    if constexpr (std::is_same<S, short>::value) *p = (short)(int)fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f);
-    else if constexpr (is_g711<S>)
-        p->code = (unsigned char)g711_encode(S::law, (int)fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f));
+    if constexpr (std::is_same<S, short>::value) *p = (short)pcm16_round(y);
+    else if constexpr (is_g711<S>) p->code = (unsigned char)g711_encode(S::law, pcm16_round(y));
     else *p = y;
 }
 
@@ -760,8 +692,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
     __shared__ float s_win[512];
     __shared__ float2 s_buf[FFT_WAVES][2][256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
-    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    fft_tables_load(s_tw, s_tw512, s_win, twid, win, tid, FFT_WAVES * 64);
     __syncthreads();
     const long nframes = (long)N * nhops;
     const long base = (long)blockIdx.x * (FFT_WAVES * WAVE_FRAMES);
@@ -803,10 +734,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
             } else {
                 c = make_float2(wave_ld(x + 256L * h + 2 * m - 256), wave_ld(x + 256L * h + 2 * m - 255));
             }
-            float2 v;
-            v.x = c.x * s_win[2 * m];
-            v.y = c.y * s_win[2 * m + 1];
-            A[m] = v;
+            A[m] = frame_window(c, s_win, m);
         }
         wave_lds_sync();
         fft256<-1>(A, Bf, s_tw, lane);
@@ -814,13 +742,9 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k = lane + 64 * q;
-            const float2 zk = A[k], zm = A[(256 - k) & 255];
-            const float2 ze = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-            const float2 zo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-            const float2 rr = cmul(s_tw512[k], zo);
-            *reinterpret_cast<float2*>(o + 2 * k) = make_float2(ze.x + rr.x, ze.y + rr.y);
-            if (k == 0)  // Nyquist bin: X[256] = Re Z[0] - Im Z[0]
-                *reinterpret_cast<float2*>(o + 512) = make_float2(zk.x - zk.y, 0.f);
+            const float2 zk = A[k];
+            *reinterpret_cast<float2*>(o + 2 * k) = rfft_bin(A, s_tw512, k, zk);
+            if (k == 0) *reinterpret_cast<float2*>(o + 512) = rfft_nyquist(zk);
         }
         wave_lds_sync();
     }
@@ -867,8 +791,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     __shared__ float s_win[512];
     __shared__ float2 s_buf[FFT_WAVES][2][256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < 256; i += FFT_WAVES * 64) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
-    for (int i = tid; i < 512; i += FFT_WAVES * 64) s_win[i] = win[i];
+    fft_tables_load(s_tw, s_tw512, s_win, twid, win, tid, FFT_WAVES * 64);
     __syncthreads();
     const int n = blockIdx.x * FFT_WAVES + wv;
     if (n >= N) return;
@@ -885,8 +808,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const int i = 2 * (lane + 64 * q) + e;
-            env[q][e] = s_win[256 + i] * s_win[256 + i] + s_win[i] * s_win[i];
+            env[q][e] = ola_env(s_win, 2 * (lane + 64 * q) + e);
         }
     float2* A = s_buf[wv][0];
     float2* Bf = s_buf[wv][1];
@@ -908,19 +830,11 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     }
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
-        // merge: Z[k] = Xe + i Xo (k_istft); the imaginary parts of DC and Nyquist are ignored
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k = lane + 64 * q;
-            float2 xk = *reinterpret_cast<const float2*>(x + 2 * k);
-            float2 xm = *reinterpret_cast<const float2*>(x + 2 * (256 - k));
-            xm.y = -xm.y;
-            if (k == 0) { xk.y = 0.f; xm.y = 0.f; }
-            const float2 xe = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y + xm.y));
-            float2 w = s_tw512[k];
-            w.y = -w.y;
-            const float2 xo = cmul(make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y - xm.y)), w);
-            A[k] = make_float2(xe.x - xo.y, xe.y + xo.x);
+            A[k] = irfft_bin(*reinterpret_cast<const float2*>(x + 2 * k), *reinterpret_cast<const float2*>(x + 2 * (256 - k)),
+                             s_tw512, k);
         }
         wave_lds_sync();
         fft256<1>(A, Bf, s_tw, lane);
@@ -928,9 +842,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int m = lane + 64 * q;
-            const float2 z = A[m];
-            f[q].x = (z.x * (1.0f / 256.0f)) * s_win[2 * m];
-            f[q].y = (z.y * (1.0f / 256.0f)) * s_win[2 * m + 1];
+            f[q] = irfft_window(A[m], s_win, m);
         }
         wave_lds_sync();     // A is rewritten by the next hop's merge
         const bool zero = none || c0 + h == 0;     // call 0 of a stream emits zeros (the one-hop delay)
@@ -945,7 +857,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                     const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
                     d = make_float2(wave_ld(xd), wave_ld(xd + 1));
                 }
-                const float w0 = env[q][0] > 1e-11f ? a0 / env[q][0] : a0, w1 = env[q][1] > 1e-11f ? a1 / env[q][1] : a1;
+                const float w0 = ola_div(a0, env[q][0]), w1 = ola_div(a1, env[q][1]);
                 // (without gains the plain sample itself: wave_mix(0, x, w) is not w for a non-finite x)
                 const float y0 = zero ? 0.f : (gain ? wave_mix(g, d.x, w0) : w0);
                 const float y1 = zero ? 0.f : (gain ? wave_mix(g, d.y, w1) : w1);
@@ -961,11 +873,12 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                     const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
                     d = make_float2(wave_ld(xd), wave_ld(xd + 1));
                 }
-                wave_st(o + 256L * h + 2 * m, zero ? 0.f : wave_mix(g, d.x, env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
-                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : wave_mix(g, d.y, env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
-            } else {
-                wave_st(o + 256L * h + 2 * m, zero ? 0.f : (env[q][0] > 1e-11f ? a0 / env[q][0] : a0));
-                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : (env[q][1] > 1e-11f ? a1 / env[q][1] : a1));
+                wave_st(o + 256L * h + 2 * m, zero ? 0.f : wave_mix(g, d.x, ola_div(a0, env[q][0])));
+                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : wave_mix(g, d.y, ola_div(a1, env[q][1])));
+            } else {      // (the sample first: the zero then selects between two values, no branch around the division)
+                const float w0 = ola_div(a0, env[q][0]), w1 = ola_div(a1, env[q][1]);
+                wave_st(o + 256L * h + 2 * m, zero ? 0.f : w0);
+                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : w1);
             }
             prev[q] = f[q + 2];
         }
@@ -2205,10 +2118,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
     copy_params(sP, PF + P_ENC, E_BLK, tid, FR_NT);
     for (int i = tid; i < 128; i += FR_NT) sI[i] = PI[I_ERB_LO + i];
     if (tid < 16) sI[128 + tid] = PI[I_ENST + tid];
-    if (WAVE_IN) {
-        for (int i = tid; i < 256; i += FR_NT) { s_tw[i] = twid[i]; s_tw512[i] = twid[256 + i]; }
-        for (int i = tid; i < 512; i += FR_NT) s_win[i] = win[i];
-    }
+    if (WAVE_IN) fft_tables_load(s_tw, s_tw512, s_win, twid, win, tid, FR_NT);
     __syncthreads();          // the only workgroup barrier: from here on every wave works on its own frames
     const long nframes = (long)B * T, stride = (long)gridDim.x * FR_WAVES;
     long fr = (long)blockIdx.x * FR_WAVES + wv;
@@ -2220,20 +2130,9 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
     const int step_b = (int)(stride / T), step_t = (int)(stride - (long)step_b * T);
     int b_len = -1;                            // the utterance Lb belongs to
     long Lb = L;
-    auto fetch = [&](int b, int t, long Lb, float2 (&v)[4]) {
-        const float* x = in + (long)b * L;
-        const long lo = 256L * t - 256;
-        if (lo >= 0 && lo + 512 <= Lb && ((reinterpret_cast<uintptr_t>(x + lo) & 7) == 0)) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float2*>(x + lo + 2 * (lane + 64 * q));
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const long i0 = 256L * t + 2 * (lane + 64 * q);
-                v[q] = make_float2(x[reflect_idx(i0, Lb)], x[reflect_idx(i0 + 1, Lb)]);
-            }
-        }
-    };
+    // (a lambda, as the fetch always was: it is inlined after the frame loop is simplified, not ahead of it as a forced
+    // inline in the loop would be, and the kernel's instructions stay what they were)
+    auto fetch = [&](int b, int t, long Lb, float2 (&v)[4]) { frame_fetch(in + (long)b * L, t, Lb, lane, v); };
     // bin k of the frame -> the LDS images: low bins straight to their place in EB (ERB.bm passes them through),
     // high bins as (re, im) pairs for the band filters; the magnitude of a high bin is formed where it is used
     auto quant_in = [&](float2 v) -> float2 {
@@ -2279,10 +2178,7 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int m = lane + 64 * q;
-                    float2 v;
-                    v.x = cur[q].x * s_win[2 * m];
-                    v.y = cur[q].y * s_win[2 * m + 1];
-                    A[m] = v;
+                    A[m] = frame_window(cur[q], s_win, m);
                 }
                 wave_lds_sync();
                 fft256<-1>(A, Bf, s_tw, lane);
@@ -2291,12 +2187,9 @@ __global__ __launch_bounds__(FR_NT, 4) void k_front(const float* __restrict__ in
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int k = lane + 64 * q;
-                    const float2 zk = A[k], zm = A[(256 - k) & 255];
-                    const float2 ze = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-                    const float2 zo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-                    const float2 r = cmul(s_tw512[k], zo);
-                    X[q] = make_float2(ze.x + r.x, ze.y + r.y);
-                    if (k == 0) XN = make_float2(zk.x - zk.y, 0.f);   // Nyquist bin: X[256] = Re Z[0] - Im Z[0]
+                    const float2 zk = A[k];
+                    X[q] = rfft_bin(A, s_tw512, k, zk);
+                    if (k == 0) XN = rfft_nyquist(zk);
                 }
                 wave_lds_sync();                                  // every lane has read A and Bf is free: stage
 #pragma unroll
@@ -4482,7 +4375,7 @@ __global__ __launch_bounds__(256) void k_pcm16_to_f32(const i16x8* __restrict__ 
         const i16x8 v = __builtin_nontemporal_load(src + i);
         f32x4 a, b;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { a[k] = (float)v[k] * (1.0f / 32768.0f); b[k] = (float)v[4 + k] * (1.0f / 32768.0f); }
+        for (int k = 0; k < 4; ++k) { a[k] = pcm16_widen(v[k]); b[k] = pcm16_widen(v[4 + k]); }
         dst[2 * i] = a;
         dst[2 * i + 1] = b;
     }
@@ -4494,8 +4387,8 @@ __global__ __launch_bounds__(256) void k_f32_to_pcm16(const f32x4* __restrict__ 
         i16x8 v;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            v[k] = (short)(int)fminf(fmaxf(__builtin_rintf(a[k] * 32768.0f), -32768.0f), 32767.0f);
-            v[4 + k] = (short)(int)fminf(fmaxf(__builtin_rintf(b[k] * 32768.0f), -32768.0f), 32767.0f);
+            v[k] = (short)pcm16_round(a[k]);
+            v[4 + k] = (short)pcm16_round(b[k]);
         }
         dst[i] = v;
     }
@@ -4524,7 +4417,7 @@ __global__ __launch_bounds__(256) void k_g711_to_f32(const u32x4* __restrict__ s
         for (int w = 0; w < 4; ++w) {
             f32x4 a;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = (float)g711_decode(LAW, (v[w] >> (8 * k)) & 0xFFu) * (1.0f / 32768.0f);
+            for (int k = 0; k < 4; ++k) a[k] = pcm16_widen(g711_decode(LAW, (v[w] >> (8 * k)) & 0xFFu));
             dst[4 * i + w] = a;
         }
     }
@@ -4539,8 +4432,7 @@ __global__ __launch_bounds__(256) void k_f32_to_g711(const f32x4* __restrict__ s
             const f32x4 a = __builtin_nontemporal_load(src + 4 * i + w);
             unsigned word = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                word |= g711_encode(LAW, (int)fminf(fmaxf(__builtin_rintf(a[k] * 32768.0f), -32768.0f), 32767.0f)) << (8 * k);
+            for (int k = 0; k < 4; ++k) word |= g711_encode(LAW, pcm16_round(a[k])) << (8 * k);
             v[w] = word;
         }
         dst[i] = v;

@@ -17,18 +17,16 @@
 
 #include <cfloat>
 
+#include "fft256.h"
+
 namespace gtm {
 
 namespace {
 
+using namespace gtfft;
+
 constexpr int TH = 256;
 constexpr double SC_EPS = 2.220446049250313e-16;   // 2^-52
-
-__device__ __forceinline__ void wave_lds_sync() {   // LDS data exchanged between the lanes of ONE wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ int clip_len(const ScorePlan& p, int b) {
     long n = p.lens ? (long)p.lens[b] : p.L;
@@ -185,35 +183,8 @@ __global__ __launch_bounds__(TH) void k_score_mask(ScorePlan p) {
 
 // ---- band envelopes.  Frame m of the overlap-added signal is gathered from the kept frames m - 1, m, m + 1 of the
 // 10 kHz signal; 512 real samples (the upper 256 zero) are packed as 256 complex, radix-4 Stockham FFT in LDS (one wave
-// per frame, the scheme of k_stft), real split, |X|^2, and one lane per band sums its bins in ascending order.
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-__device__ __forceinline__ void fft256_fwd(float2* a, float2* b, const float2* tw, int lane) {   // result ends in `a`
-    float2* src = a;
-    float2* dst = b;
-#pragma unroll
-    for (int stage = 0; stage < 4; ++stage) {
-        const int Ns = 1 << (2 * stage);
-        const int k = lane & (Ns - 1);
-        const int tstep = k * (64 / Ns);
-        float2 v0 = src[lane], v1 = src[lane + 64], v2 = src[lane + 128], v3 = src[lane + 192];
-        if (stage > 0) {
-            v1 = cmul(v1, tw[tstep]); v2 = cmul(v2, tw[2 * tstep]); v3 = cmul(v3, tw[3 * tstep]);
-        }
-        const float2 s0 = make_float2(v0.x + v2.x, v0.y + v2.y), s1 = make_float2(v0.x - v2.x, v0.y - v2.y);
-        const float2 s2 = make_float2(v1.x + v3.x, v1.y + v3.y);
-        const float2 dd = make_float2(v1.x - v3.x, v1.y - v3.y);
-        const float2 s3 = make_float2(dd.y, -dd.x);              // (v1 - v3) * -i
-        const int j0 = ((lane - k) << 2) + k;
-        dst[j0] = make_float2(s0.x + s2.x, s0.y + s2.y);
-        dst[j0 + Ns] = make_float2(s1.x + s3.x, s1.y + s3.y);
-        dst[j0 + 2 * Ns] = make_float2(s0.x - s2.x, s0.y - s2.y);
-        dst[j0 + 3 * Ns] = make_float2(s1.x - s3.x, s1.y - s3.y);
-        wave_lds_sync();
-        float2* t = src; src = dst; dst = t;
-    }
-}
-
+// per frame) and real split -- fft256<-1> and rfft_bin of fft256.h, which k_stft calls too -- then |X|^2, and one lane per
+// band sums its bins in ascending order.
 constexpr int ENV_WAVES = 4;
 __global__ __launch_bounds__(ENV_WAVES * 64) void k_score_env(ScorePlan p) {
     __shared__ float2 s_tw[256];
@@ -252,18 +223,13 @@ __global__ __launch_bounds__(ENV_WAVES * 64) void k_score_env(ScorePlan p) {
         A[n + 128] = make_float2(0.0f, 0.0f);
     }
     wave_lds_sync();
-    fft256_fwd(A, Bf, s_tw, lane);
-    // X[k] = Ze + exp(-2 pi i k / 512) Zo, Ze = (Z[k] + conj(Z[256 - k])) / 2, Zo = (Z[k] - conj(Z[256 - k])) / (2 i)
+    fft256<-1>(A, Bf, s_tw, lane);
     float* P = reinterpret_cast<float*>(Bf);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int k = lane + 64 * q;
-        const float2 zk = A[k], zm = A[(256 - k) & 255];
-        const float2 ze = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 zo = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-        const float2 r = cmul(s_tw512[k], zo);
-        const float re = ze.x + r.x, im = ze.y + r.y;
-        P[k] = re * re + im * im;
+        const float2 X = rfft_bin(A, s_tw512, k, A[k]);
+        P[k] = X.x * X.x + X.y * X.y;
     }
     wave_lds_sync();
     if (lane < SC_BANDS) {
