@@ -8,6 +8,8 @@
 // Reference semantics are cited per kernel (paths relative to the reference repo).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "train_kernels.h"
 
 namespace gtt {
@@ -4444,6 +4446,46 @@ __global__ __launch_bounds__(ADAM_NT) void k_adam_flat(float* __restrict__ p, fl
 
 int check() { return (int)hipGetLastError(); }
 
+// One launch: the kernel named once, its arguments once.
+template <class... P, class... A>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+}
+
+// Run-time value -> template argument (the integer twin of with_flags in kernels.hip): calls f with the
+// std::integral_constant of the admitted value that equals v.  False when v is none of them: nothing was launched and
+// the launcher refuses the call.
+template <auto... Vs, class V, class F>
+bool dispatch(V v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+}
+// ... and a pair of values -> one of the listed Case<A, B>s.  Pairs are ENUMERATED, never the cross-product of two
+// dispatches: only the listed instantiations exist in the code object (no kernel stores bf16 gradients next to fp32
+// activations, none recomputes x without a riding reduction).
+template <auto A, auto B> struct Case { static constexpr auto a = A; static constexpr auto b = B; };
+template <class... Cs, class VA, class VB, class F>
+bool dispatch_case(VA a, VB b, F&& f) {
+    return ((a == Cs::a && b == Cs::b ? (f(Cs{}), true) : false) || ...);
+}
+// storage format of one tensor where the kernel has a general form for everything but fp32 / bf16: that form's argument
+inline int fmt_or(int bf, int other) { return bf == 0 || bf == 1 ? bf : other; }
+// formats of a kernel's input and output tensor (.a, .b): fp32 / bf16 each, all four
+template <class F>
+bool with_io_fmt(int in_bf, int out_bf, F&& f) {
+    return dispatch_case<Case<0, 0>, Case<1, 1>, Case<0, 1>, Case<1, 0>>(in_bf, out_bf, f);
+}
+// formats of a unit backward's saved activations and of the gradients handed between units (.a, .b): bf16 gradients go
+// with bf16 activations only
+template <class F>
+bool with_grad_fmt(int bf, int gbf, F&& f) {
+    return dispatch_case<Case<0, 0>, Case<1, 1>, Case<1, 0>>(bf, gbf ? 1 : 0, f);
+}
+// riding reduction of the unit in front (.a) and recomputation of x from that unit's y (.b), which needs the former
+template <class F>
+bool with_riding(bool nxt, bool xr, F&& f) {
+    return dispatch_case<Case<false, false>, Case<true, false>, Case<true, true>>(nxt, xr, f);
+}
+
 // ---- in-launch finish: host side.  The trainer hands over its group-sum / counter buffers per call (thread local: one
 // caller thread per trainer); `on` = fusion bit 10.
 struct FinCtx { bool on = false; double* gpart = nullptr; unsigned* ctr = nullptr; };
@@ -4527,22 +4569,22 @@ void set_column_form(bool on) { g_col_form = on; }
 static void launch_bn_bwd_reduce4(int grid, hipStream_t s, const float* da, const float* y, long total, int C,
                                   const float* stats, const float* gamma, const float* beta, const float* res, int act,
                                   const float* slope, double* partial, int bf, int ybf, const FinArgs& fa, int gbf = 0) {
-#define GT_RED(F, A, GF_) hipLaunchKernelGGL((k_bn_bwd_reduce<4, F, A, GF_>), dim3(grid), dim3(NT), 0, s, da, y, total, C, stats, \
-                                             gamma, beta, res, act, slope, partial, bf, ybf, fa)
+    // FA: formats (.a; 0: all fp32, 5: bf16 activations, bf16 conv outputs) and activation (.b) as compile-time
+    // constants, -1 where the kernel reads them at run time
+    auto run = [&](auto FA, auto GF) {
+        launch(k_bn_bwd_reduce<4, FA.a, FA.b, GF.value>, dim3(grid), dim3(NT), 0, s, da, y, total, C, stats, gamma, beta, res,
+               act, slope, partial, bf, ybf, fa);
+    };
     const int f = bf * 4 + ybf;
     if (gbf) {                                                       // bf16 gradient hand-offs (storage mode 5)
-        if (f == 5 && act == ACT_PRELU) GT_RED(5, ACT_PRELU, 1);
-        else if (f == 5 && act == ACT_NONE) GT_RED(5, ACT_NONE, 1);
-        else GT_RED(-1, -1, 1);
+        auto run1 = [&](auto FA) { run(FA, std::integral_constant<int, 1>{}); };
+        if (!dispatch_case<Case<5, ACT_PRELU>, Case<5, ACT_NONE>>(f, act, run1)) run1(Case<-1, -1>{});
+    } else {
+        auto run0 = [&](auto FA) { run(FA, std::integral_constant<int, 0>{}); };
+        if (!dispatch_case<Case<0, ACT_PRELU>, Case<0, ACT_NONE>, Case<5, ACT_PRELU>, Case<5, ACT_NONE>>(f, act, run0) &&
+            !dispatch_case<Case<0, -1>, Case<5, -1>>(f, -1, run0))
+            run0(Case<-1, -1>{});
     }
-    else if (f == 0 && act == ACT_PRELU) GT_RED(0, ACT_PRELU, 0);
-    else if (f == 0 && act == ACT_NONE) GT_RED(0, ACT_NONE, 0);
-    else if (f == 5 && act == ACT_PRELU) GT_RED(5, ACT_PRELU, 0);      // bf16 activations, bf16 conv outputs
-    else if (f == 5 && act == ACT_NONE) GT_RED(5, ACT_NONE, 0);
-    else if (f == 0) GT_RED(0, -1, 0);
-    else if (f == 5) GT_RED(5, -1, 0);
-    else GT_RED(-1, -1, 0);
-#undef GT_RED
 }
 
 static int red_grid(long units) {
@@ -4576,7 +4618,29 @@ static int bwd_first_pass(int have_parts, hipStream_t s, const float* da, const 
 static FinArgs next_fin(bool nxt, const DwUnitNext* next, double* dscratch, int slot) {
     return nxt ? fin_bwd(next->n, 16, red_slot(dscratch, 1 - slot), next->dgamma, next->dbeta, next->dslope) : fin_off();
 }
-static int next_parts_value(const FinArgs& nfa, int slot, int grid) { return nfa.kind ? -1 - (1 - slot) : grid; }
+// ... and what the launcher reports for it (the have_parts of that unit's backward): the slot, or `grid` partial sums
+static void set_next_parts(int* next_parts, bool nxt, const FinArgs& nfa, int slot, int grid) {
+    if (nxt && next_parts) *next_parts = nfa.kind ? -1 - (1 - slot) : grid;
+}
+// the riding reduction's view of the unit in front: its y and BatchNorm / PReLU constants (nothing without one).  res,
+// xround and yfmt differ between the kernels: their launchers fill them.
+static NextRedArgs next_args(bool nxt, const DwUnitNext* next) {
+    NextRedArgs nx{};
+    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope};
+    return nx;
+}
+// the weight-gradient finish of a fused unit backward whose partial sums are `nparts` rows of `part`: recorded for
+// the batch when they sit in a region of the deferral pool (fusion bit 15), launched now when in the caller's scratch
+static void finish_wgrad(bool deferred, const ConvGeom& g, const float* part, int nparts, float* dw, float* dbias, hipStream_t s) {
+    const int K = g.nkt * g.nkf * 256 + 16;
+    if (deferred) wdefer_conv(g, part, nparts, dw, dbias);
+    else launch(k_wgrad_mfma_finish, dim3((K + 63) / 64), dim3(1024), 0, s, g, part, nparts, dw, dbias);
+}
+static void finish_wgrad(bool deferred, const DwGeom& g, const double* part, int nparts, float* dw, float* dbias, hipStream_t s) {
+    const int K = (g.nkt * g.nkf + 1) * 16;
+    if (deferred) wdefer_dw(g, part, nparts, dw, dbias);
+    else launch(k_dw_wgrad_finish2, dim3((K + 63) / 64), dim3(1024), 0, s, g, part, nparts, dw, dbias);
+}
 
 static bool mfma_ok(const ConvGeom& g) {
     return (g.Cin % 4) == 0 && (g.Cout % 4) == 0 && (g.CinT % 4) == 0 && (g.CoutT % 4) == 0 && (g.cin_off % 4) == 0 &&
@@ -4599,11 +4663,6 @@ static bool win_wgrad_ok(const ConvGeom& g) {
     return g.Cout * g.nkf <= 16 && g.CoutT == g.Cout && g.cout_off == 0 && g.Cin == 16 && g.CinT == 16 && g.cin_off == 0;
 }
 
-static NextRedArgs next_args(const DwUnitNext* next, int yfmt) {
-    NextRedArgs nx{};
-    if (next) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, nullptr, 0, yfmt};
-    return nx;
-}
 int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bias, float* out, hipStream_t s,
              double* stat_partial, int* stat_parts, const float* shift, const BnPre* pre, const DwUnitNext* next,
              int next_yfmt, const StatFin* sf) {
@@ -4628,13 +4687,15 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
         if (waves > ntiles) waves = ntiles;
         const long tpw = (ntiles + waves - 1) / waves;
         const int grid = (int)((ntiles + tpw * 4 - 1) / (tpw * 4));
-        const NextRedArgs nx = next_args(next, next_yfmt);
+        NextRedArgs nx = next_args(true, next);
+        nx.yfmt = next_yfmt;
         if (next_yfmt < 0 || next_yfmt > 1) return (int)hipErrorInvalidValue;
-#define GT_CN(KT, KF, NX) hipLaunchKernelGGL((k_conv_mfma<KT, KF, 0, false, false, NX>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, \
-                                             out, tpw, stat_partial, shift, nopre, nx, fa)
-        if (g.nkt == 3) { if (next_yfmt) GT_CN(3, 3, 2); else GT_CN(3, 3, 1); }
-        else { if (next_yfmt) GT_CN(1, 5, 2); else GT_CN(1, 5, 1); }
-#undef GT_CN
+        dispatch_case<Case<3, 3>, Case<1, 5>>(g.nkt, g.nkf, [&](auto K) {
+            dispatch<0, 1>(next_yfmt, [&](auto YF) {
+                launch(k_conv_mfma<K.a, K.b, 0, false, false, 1 + YF.value>, dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw,
+                       stat_partial, shift, nopre, nx, fa);
+            });
+        });
         *stat_parts = fa.kind ? -1 : grid;           // (folded: that unit's means are in slot 0)
         return check();
     }
@@ -4648,8 +4709,9 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
         const int tiles_t = (g.Tout + F33_TF - 1) / F33_TF;
         const long ntiles = (long)g.B * tiles_t;
         const int gridt = (int)(ntiles < MAX_PARTIALS ? ntiles : MAX_PARTIALS);
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_dense33_fwd_pre<0>), dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
-        else hipLaunchKernelGGL((k_dense33_fwd_pre<1>), dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
+        dispatch<0, 1>(g.in_bf, [&](auto FI) {
+            launch(k_dense33_fwd_pre<FI.value>, dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
+        });
         *stat_parts = fa.kind ? -gridt : gridt;
         return check();
     }
@@ -4663,9 +4725,9 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
         const int g16 = grid_for(units, sp ? MAX_PARTIALS : 16384);
         const StrideIter it = stride_iter((long)g16 * NT / 4, g.Fout, g.Tout);
         const FinArgs fw = sp ? fa : fin_off();
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_conv_win_fma<0>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, fw);
-        else if (g.in_bf == 1) hipLaunchKernelGGL((k_conv_win_fma<1>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, fw);
-        else hipLaunchKernelGGL((k_conv_win_fma<2>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, fw);
+        dispatch<0, 1, 2>(fmt_or(g.in_bf, 2), [&](auto FI) {
+            launch(k_conv_win_fma<FI.value>, dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, fw);
+        });
         if (sp) *stat_parts = fw.kind ? -g16 : g16;
         return check();
     }
@@ -4679,12 +4741,6 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
         double* sp = (stat_partial && stat_parts && grid <= MAX_PARTIALS && g.cout_off == 0 && g.Cout == g.CoutT &&
                       !g.accumulate) ? stat_partial : nullptr;
         const FinArgs fm = sp ? fa : fin_off();
-#define GT_CM(KT, KF)                                                                                                  \
-    do {                                                                                                               \
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_conv_mfma<KT, KF, 0>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm); \
-        else if (g.in_bf == 1) hipLaunchKernelGGL((k_conv_mfma<KT, KF, 1>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm); \
-        else hipLaunchKernelGGL((k_conv_mfma<KT, KF, 2>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm); \
-    } while (0)
         // the dedicated pointwise form (see k_pw_fwd): a pure 1x1 conv over flat positions, whole output tensor, 0 / bf16 formats
         const bool pw = !win && g.nkt == 1 && g.nkf == 1 && g.t_off[0] == 0 && g.Tin == g.Tout && g.Fin == g.Fout && g.sf == 1 &&
                         g.pf == 0 && g.f_mode == 0 && !g.accumulate && g.cout_off == 0 && g.Cout == g.CoutT && g.in_bf <= 1 && g.out_bf <= 1 &&
@@ -4698,44 +4754,37 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
                          (long)g.B * g.Tout * 65 * 16 < (1L << 31);
         if (c15) {
             const long npos = (long)g.B * g.Tout * g.Fout;
-#define GT_C5(FI_, FO_, TR_) hipLaunchKernelGGL((k_c15_fwd<FI_, FO_, TR_>), dim3(grid), dim3(NT), 0, s, npos, g.w_co, g.w_ci, in, w, bias, out, \
-                                                tpw, sp, shift, fm)
-#define GT_C52(TR_) do { if (g.in_bf == 0 && g.out_bf == 0) GT_C5(0, 0, TR_); else if (g.in_bf == 1 && g.out_bf == 1) GT_C5(1, 1, TR_); \
-                         else if (g.in_bf == 0) GT_C5(0, 1, TR_); else GT_C5(1, 0, TR_); } while (0)
-            if (g.f_mode) GT_C52(true); else GT_C52(false);
-#undef GT_C52
-#undef GT_C5
-            if (sp) *stat_parts = fm.kind ? -grid : grid;
-            return check();
-        }
-        if (pw) {
+            with_io_fmt(g.in_bf, g.out_bf, [&](auto IO) {
+                dispatch<false, true>(g.f_mode != 0, [&](auto TR) {
+                    launch(k_c15_fwd<IO.a, IO.b, TR.value>, dim3(grid), dim3(NT), 0, s, npos, g.w_co, g.w_ci, in, w, bias, out,
+                           tpw, sp, shift, fm);
+                });
+            });
+        } else if (pw) {
             const long npos = (long)g.B * g.Tout * g.Fout;
-#define GT_PW(FI, FO, PR, RS) hipLaunchKernelGGL((k_pw_fwd<FI, FO, PR, RS>), dim3(grid), dim3(NT), 0, s, npos, g.Cin, g.CinT, g.cin_off, \
-                                                 g.Cout, g.w_co, g.w_ci, in, w, bias, out, tpw, sp, shift, pre ? *pre : nopre, fm)
-#define GT_PW2(PR, RS) do { if (g.in_bf == 0 && g.out_bf == 0) GT_PW(0, 0, PR, RS); else if (g.in_bf == 1 && g.out_bf == 1) GT_PW(1, 1, PR, RS); \
-                            else if (g.in_bf == 0) GT_PW(0, 1, PR, RS); else GT_PW(1, 0, PR, RS); } while (0)
-            if (pre && pre->res) GT_PW2(true, true);
-            else if (pre) GT_PW2(true, false);
-            else GT_PW2(false, false);
-#undef GT_PW2
-#undef GT_PW
-            if (sp) *stat_parts = fm.kind ? -grid : grid;
-            return check();
+            // PR (.a): behind a deferred unit; RS (.b): that unit has a residual input
+            dispatch_case<Case<true, true>, Case<true, false>, Case<false, false>>(pre != nullptr, pre && pre->res, [&](auto PR) {
+                with_io_fmt(g.in_bf, g.out_bf, [&](auto IO) {
+                    launch(k_pw_fwd<IO.a, IO.b, PR.a, PR.b>, dim3(grid), dim3(NT), 0, s, npos, g.Cin, g.CinT, g.cin_off,
+                           g.Cout, g.w_co, g.w_ci, in, w, bias, out, tpw, sp, shift, pre ? *pre : nopre, fm);
+                });
+            });
+        } else {
+            // the general kernel: its (1, 1) form behind a deferred unit or as the window form, else by the layer's taps
+            dispatch<0, 1, 2>(fmt_or(g.in_bf, 2), [&](auto FI) {
+                if (pre)
+                    launch(k_conv_mfma<1, 1, FI.value, false, true>, dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift,
+                           *pre, nonx, fm);
+                else if (win)
+                    launch(k_conv_mfma<1, 1, FI.value, true>, dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre,
+                           nonx, fm);
+                else
+                    dispatch_case<Case<3, 3>, Case<1, 5>, Case<1, 1>>(g.nkt, g.nkf, [&](auto K) {
+                        launch(k_conv_mfma<K.a, K.b, FI.value>, dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift,
+                               nopre, nonx, fm);
+                    });
+            });
         }
-        if (pre) {
-            if (g.in_bf == 0) hipLaunchKernelGGL((k_conv_mfma<1, 1, 0, false, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, *pre, nonx, fm);
-            else if (g.in_bf == 1) hipLaunchKernelGGL((k_conv_mfma<1, 1, 1, false, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, *pre, nonx, fm);
-            else hipLaunchKernelGGL((k_conv_mfma<1, 1, 2, false, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, *pre, nonx, fm);
-        }
-        else if (win) {
-            if (g.in_bf == 0) hipLaunchKernelGGL((k_conv_mfma<1, 1, 0, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm);
-            else if (g.in_bf == 1) hipLaunchKernelGGL((k_conv_mfma<1, 1, 1, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm);
-            else hipLaunchKernelGGL((k_conv_mfma<1, 1, 2, true>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, tpw, sp, shift, nopre, nonx, fm);
-        }
-        else if (g.nkt == 3) GT_CM(3, 3);
-        else if (g.nkf == 5) GT_CM(1, 5);
-        else GT_CM(1, 1);
-#undef GT_CM
         if (sp) *stat_parts = fm.kind ? -grid : grid;
         return check();
     }
@@ -4747,24 +4796,20 @@ int conv_fwd(const ConvGeom& g, const float* in, const float* w, const float* bi
         g.w_kf == 1 && g.Tin == g.Tout && g.t_off[0] == 0 && g.in_bf <= 1 && g.out_bf <= 1) {
         const long nrows = (long)g.B * g.Tout;
         const int gt = grid_for((nrows + 3) / 4 * NT, 2048);
-#define GT_TT(CO_, FI_, FO_) hipLaunchKernelGGL((k_thin_tr_fm<CO_, FI_, FO_>), dim3(gt), dim3(NT), 0, s, nrows, g.w_co, g.w_ci, in, w, bias, \
-                                                shift, out)
-#define GT_TT2(CO_) do { if (g.in_bf == 0 && g.out_bf == 0) GT_TT(CO_, 0, 0); else if (g.in_bf == 1 && g.out_bf == 1) GT_TT(CO_, 1, 1); \
-                         else if (g.in_bf == 0) GT_TT(CO_, 0, 1); else GT_TT(CO_, 1, 0); } while (0)
-        if (g.Cout == 2) GT_TT2(2); else GT_TT2(3);
-#undef GT_TT2
-#undef GT_TT
+        dispatch<2, 3>(g.Cout, [&](auto CO) {
+            with_io_fmt(g.in_bf, g.out_bf, [&](auto IO) {
+                launch(k_thin_tr_fm<CO.value, IO.a, IO.b>, dim3(gt), dim3(NT), 0, s, nrows, g.w_co, g.w_ci, in, w, bias, shift, out);
+            });
+        });
         return check();
     }
-#define GT_CONV_CASE(CI, CO)                                                                      \
-    if (g.Cin == CI && g.Cout == CO) {                                                            \
-        hipLaunchKernelGGL((k_conv<CI, CO>), dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, shift); \
-        return check();                                                                           \
-    }
-    GT_CONV_CASE(3, 16) GT_CONV_CASE(16, 3) GT_CONV_CASE(16, 16) GT_CONV_CASE(8, 16) GT_CONV_CASE(16, 8)
-    GT_CONV_CASE(16, 2) GT_CONV_CASE(2, 16)
-#undef GT_CONV_CASE
-    return (int)hipErrorInvalidValue;
+    // the direct form: the channel counts (.a in, .b out) of this model's thin layers
+    if (!dispatch_case<Case<3, 16>, Case<16, 3>, Case<16, 16>, Case<8, 16>, Case<16, 8>, Case<16, 2>, Case<2, 16>>(
+            g.Cin, g.Cout, [&](auto C) {
+                launch(k_conv<C.a, C.b>, dim3(grid), dim3(NT), 0, s, g, in, w, bias, out, shift);
+            }))
+        return (int)hipErrorInvalidValue;
+    return check();
 }
 
 int conv_wgrad(const ConvGeom& g, const float* in, const float* dout, float* dw, float* dbias, float* scratch,
@@ -4777,12 +4822,11 @@ int conv_wgrad(const ConvGeom& g, const float* in, const float* dout, float* dw,
         long gpw = (ngroups + waves - 1) / waves;
         gpw = (gpw + 3) & ~3L;                           // whole 16-position tiles per wave
         const int grid = (int)((ngroups + gpw * WG_WAVES - 1) / (gpw * WG_WAVES));
-#define GT_WW(F) do { if (wide_in) hipLaunchKernelGGL((k_wgrad_win<F, true>), dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw); \
-                      else hipLaunchKernelGGL((k_wgrad_win<F, false>), dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw); } while (0)
-        if (g.in_bf == 0) GT_WW(0);
-        else if (g.in_bf == 1) GT_WW(1);
-        else GT_WW(2);
-#undef GT_WW
+        dispatch<0, 1, 2>(fmt_or(g.in_bf, 2), [&](auto FI) {
+            dispatch<false, true>(wide_in, [&](auto WIDE) {
+                launch(k_wgrad_win<FI.value, WIDE.value>, dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw);
+            });
+        });
         hipLaunchKernelGGL(k_wgrad_win_finish, dim3(5), dim3(1024), 0, s, g, scratch, grid, dw, dbias, wide_in ? 1 : 0);
         return check();
     }
@@ -4796,22 +4840,12 @@ int conv_wgrad(const ConvGeom& g, const float* in, const float* dout, float* dw,
         // 16-byte operand loads through wave-private LDS tiles when the channel counts allow them (all MFMA layers of
         // this model); the 4-byte form otherwise
         const bool wide = mfma_ok(g);     // channel counts / offsets in multiples of four: 16-byte operand loads
-#define GT_WG1(K_, KT, KF)                                                                                             \
-    do {                                                                                                               \
-        if (g.in_bf == 0) hipLaunchKernelGGL((K_<KT, KF, 0>), dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw); \
-        else if (g.in_bf == 1) hipLaunchKernelGGL((K_<KT, KF, 1>), dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw); \
-        else hipLaunchKernelGGL((K_<KT, KF, 2>), dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw); \
-    } while (0)
-#define GT_WG(KT, KF)                                                                                                  \
-    do {                                                                                                               \
-        if (wide) GT_WG1(k_conv_wgrad_lds, KT, KF);                                                                    \
-        else GT_WG1(k_conv_wgrad_mfma, KT, KF);                                                                        \
-    } while (0)
-        if (g.nkt == 3) GT_WG(3, 3);
-        else if (g.nkf == 5) GT_WG(1, 5);
-        else GT_WG(1, 1);
-#undef GT_WG
-#undef GT_WG1
+        dispatch_case<Case<3, 3>, Case<1, 5>, Case<1, 1>>(g.nkt, g.nkf, [&](auto K) {
+            dispatch<0, 1, 2>(fmt_or(g.in_bf, 2), [&](auto FI) {
+                if (wide) launch(k_conv_wgrad_lds<K.a, K.b, FI.value>, dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw);
+                else launch(k_conv_wgrad_mfma<K.a, K.b, FI.value>, dim3(grid), dim3(WG_WAVES * 64), 0, s, g, in, dout, scratch, gpw);
+            });
+        });
         hipLaunchKernelGGL(k_wgrad_mfma_finish, dim3((K + 63) / 64), dim3(1024), 0, s, g, scratch, grid, dw, dbias);
         return check();
     }
@@ -4836,12 +4870,12 @@ int dw_fwd(const DwGeom& g, const float* in, const float* w, const float* bias, 
         const int g16 = grid_for((long)g.B * g.Tout * g.F * 4, MAX_PARTIALS);
         const StrideIter it = stride_iter((long)g16 * NT / 4, g.F, g.Tout);
         if (next_yfmt < 0 || next_yfmt > 1) return (int)hipErrorInvalidValue;
-        if (next_yfmt)
-            hipLaunchKernelGGL((k_dw16<3, 3, 0, false, 2>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, it,
-                               shift, nopre, next_args(next, next_yfmt), fa);
-        else
-            hipLaunchKernelGGL((k_dw16<3, 3, 0, false, 1>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, it,
-                               shift, nopre, next_args(next, next_yfmt), fa);
+        NextRedArgs nx = next_args(true, next);
+        nx.yfmt = next_yfmt;
+        dispatch<0, 1>(next_yfmt, [&](auto YF) {
+            launch(k_dw16<3, 3, 0, false, 1 + YF.value>, dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, it, shift,
+                   nopre, nx, fa);
+        });
         *stat_parts = fa.kind ? -1 : g16;
         return check();
     }
@@ -4854,8 +4888,9 @@ int dw_fwd(const DwGeom& g, const float* in, const float* w, const float* bias, 
         const int tiles_t = (g.Tout + F33_TF - 1) / F33_TF;
         const long ntiles = (long)g.B * tiles_t;
         const int gridt = (int)(ntiles < MAX_PARTIALS ? ntiles : MAX_PARTIALS);
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_dw33_fwd_pre<0>), dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
-        else hipLaunchKernelGGL((k_dw33_fwd_pre<1>), dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
+        dispatch<0, 1>(g.in_bf, [&](auto FI) {
+            launch(k_dw33_fwd_pre<FI.value>, dim3(gridt), dim3(NT), 0, s, g, in, w, bias, out, stat_partial, shift, *pre, tiles_t, fa);
+        });
         *stat_parts = fa.kind ? -gridt : gridt;
         return check();
     }
@@ -4869,12 +4904,6 @@ int dw_fwd(const DwGeom& g, const float* in, const float* w, const float* bias, 
         const int g16 = grid_for((long)g.B * g.Tout * g.F * 4, sp ? MAX_PARTIALS : 16384);
         if (g.Tin != g.Tout) return (int)hipErrorInvalidValue;
         const StrideIter it = stride_iter((long)g16 * NT / 4, g.F, g.Tout);
-#define GT_DW(KT, KF)                                                                                                   \
-    do {                                                                                                               \
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_dw16<KT, KF, 0>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd); \
-        else if (g.in_bf == 1) hipLaunchKernelGGL((k_dw16<KT, KF, 1>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd); \
-        else hipLaunchKernelGGL((k_dw16<KT, KF, -1>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd); \
-    } while (0)
         // the column form (see k_dw31_col): the TCN's dilated (3,1) conv behind its deferred unit, fusion bit 14
         const int dil = -g.t_off[1];
         if (pre && g_col_form && sp && dil >= 1 && g.t_off[0] == -2 * dil && g.w_kf == 1 && !pre->exact && pre->bf == g.in_bf &&
@@ -4882,25 +4911,28 @@ int dw_fwd(const DwGeom& g, const float* in, const float* w, const float* bias, 
             const int cj = g.in_bf ? DcChunk<1>::J : DcChunk<0>::J;
             const long items = (long)g.B * dil * (((g.Tout + dil - 1) / dil + cj - 1) / cj) * g.F * 4;
             const int gc = grid_for(items, MAX_PARTIALS);
-#define GT_DC(FI, FO) hipLaunchKernelGGL((k_dw31_col<FI, FO>), dim3(gc), dim3(NT), 0, s, g.B, g.Tout, g.F, dil, g.w_c, g.w_kt, in, w, bias, \
-                                         out, sp, shift, *pre, fd)
-            if (g.in_bf == 0 && g.out_bf == 0) GT_DC(0, 0);
-            else if (g.in_bf == 1 && g.out_bf == 1) GT_DC(1, 1);
-            else if (g.in_bf == 0) GT_DC(0, 1);
-            else GT_DC(1, 0);
-#undef GT_DC
+            with_io_fmt(g.in_bf, g.out_bf, [&](auto IO) {
+                launch(k_dw31_col<IO.a, IO.b>, dim3(gc), dim3(NT), 0, s, g.B, g.Tout, g.F, dil, g.w_c, g.w_kt, in, w, bias, out, sp,
+                       shift, *pre, fd);
+            });
             *stat_parts = fd.kind ? -gc : gc;
             return check();
         }
-        if (pre) {
-            if (g.in_bf == 0) hipLaunchKernelGGL((k_dw16<3, 1, 0, true>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, *pre, nonx, fd);
-            else hipLaunchKernelGGL((k_dw16<3, 1, 1, true>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, *pre, nonx, fd);
-        }
-        else if (g.nkt == 3 && g.nkf == 3) GT_DW(3, 3);
-        else if (g.nkt == 3 && g.nkf == 1) GT_DW(3, 1);
-#undef GT_DW
+        // (3, 1) behind a deferred unit, the (3, 3) / (3, 1) forms with the input format at compile time (-1: read at
+        // run time), or the form for any taps
+        const bool taps3 = g.nkt == 3 && (g.nkf == 3 || g.nkf == 1);
+        if (pre)
+            dispatch<0, 1>(g.in_bf, [&](auto FI) {
+                launch(k_dw16<3, 1, FI.value, true>, dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, *pre, nonx, fd);
+            });
+        else if (taps3)
+            dispatch<3, 1>(g.nkf, [&](auto KF) {
+                dispatch<0, 1, -1>(fmt_or(g.in_bf, -1), [&](auto FI) {
+                    launch(k_dw16<3, KF.value, FI.value>, dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd);
+                });
+            });
         else
-            hipLaunchKernelGGL((k_dw16<0, 0>), dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd);
+            launch(k_dw16<0, 0>, dim3(g16), dim3(NT), 0, s, g, in, w, bias, out, sp, it, shift, nopre, nonx, fd);
         if (sp) *stat_parts = fd.kind ? -g16 : g16;
         return check();
     }
@@ -4917,15 +4949,11 @@ int dw_wgrad(const DwGeom& g, const float* in, const float* dout, float* dw, flo
         const int K = (g.nkt * g.nkf + 1) * 16;
         if (g.Tin != g.Tout) return (int)hipErrorInvalidValue;
         const StrideIter it = stride_iter((long)grid * NT / 4, g.F, g.Tout);
-#define GT_DWG(KF)                                                                                                      \
-    do {                                                                                                               \
-        if (g.in_bf == 0) hipLaunchKernelGGL((k_dw_wgrad_stream<3, KF, 0>), dim3(grid), dim3(NT), 0, s, g, in, dout, part, it); \
-        else if (g.in_bf == 1) hipLaunchKernelGGL((k_dw_wgrad_stream<3, KF, 1>), dim3(grid), dim3(NT), 0, s, g, in, dout, part, it); \
-        else hipLaunchKernelGGL((k_dw_wgrad_stream<3, KF, -1>), dim3(grid), dim3(NT), 0, s, g, in, dout, part, it); \
-    } while (0)
-        if (g.nkf == 3) GT_DWG(3);
-        else GT_DWG(1);
-#undef GT_DWG
+        dispatch<3, 1>(g.nkf, [&](auto KF) {
+            dispatch<0, 1, -1>(fmt_or(g.in_bf, -1), [&](auto FI) {
+                launch(k_dw_wgrad_stream<3, KF.value, FI.value>, dim3(grid), dim3(NT), 0, s, g, in, dout, part, it);
+            });
+        });
         hipLaunchKernelGGL(k_dw_wgrad_finish2, dim3((K + 63) / 64), dim3(1024), 0, s, g, part, grid, dw, dbias);
         return check();
     }
@@ -4951,19 +4979,12 @@ int bn_stats(const float* y, long n, int C, float* stats, float* running_mean, f
     }
     const StatFin sf{n, C, stats, running_mean, running_var, shifted, stats_b};
     const FinArgs fa = fin_stats(&sf);
-    if (C % 4 == 0) {
-        const int grid = red_grid(total / 4);
-        hipLaunchKernelGGL((k_bn_stats<4>), dim3(grid), dim3(NT), 0, s, y, total, C, scratch, bf, fa);
-        if (!fa.kind)
-            hipLaunchKernelGGL(k_bn_stats_finish, dim3(1), dim3(1024), 0, s, scratch, grid, n, C, stats, running_mean,
-                               running_var, shifted, stats_b);
-    } else {
-        const int grid = red_grid(total);
-        hipLaunchKernelGGL((k_bn_stats<1>), dim3(grid), dim3(NT), 0, s, y, total, C, scratch, bf, fa);
-        if (!fa.kind)
-            hipLaunchKernelGGL(k_bn_stats_finish, dim3(1), dim3(1024), 0, s, scratch, grid, n, C, stats, running_mean,
-                               running_var, shifted, stats_b);
-    }
+    const int vec = C % 4 == 0 ? 4 : 1;      // elements per thread and load
+    const int grid = red_grid(total / vec);
+    dispatch<4, 1>(vec, [&](auto V) { launch(k_bn_stats<V.value>, dim3(grid), dim3(NT), 0, s, y, total, C, scratch, bf, fa); });
+    if (!fa.kind)
+        hipLaunchKernelGGL(k_bn_stats_finish, dim3(1), dim3(1024), 0, s, scratch, grid, n, C, stats, running_mean,
+                           running_var, shifted, stats_b);
     return check();
 }
 
@@ -5032,38 +5053,32 @@ int dwunit_bwd(const DwGeom& g, const float* x, const float* y, const float* da,
     if (dpool) fscratch = dpool;
     double* wpart = reinterpret_cast<double*>(fscratch);      // [grid][64]
     BnBwdArgs bn{stats, gamma, beta, slope, red, ACT_PRELU};
-    NextRedArgs nx{};
-    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, nullptr, next->recompute_x == 2};
+    NextRedArgs nx = next_args(nxt, next);
+    if (nxt) nx.xround = next->recompute_x == 2;
     const FinArgs nfa = next_fin(nxt, next, dscratch, slot);
+    int nparts = grid;
     if (g_col_form && nxt && total < (1L << 31)) {       // the column form (see k_dwunit31_col), fusion bit 14
         const int dil = -g.t_off[1];
         const int cj = (bf && gbf) ? DcBwdChunk<1, 1>::J : DcBwdChunk<0, 0>::J;
         const long items = (long)g.B * dil * (((g.Tout + dil - 1) / dil + cj - 1) / cj) * g.F * 4;
         const int gc = (int)((items + NT - 1) / NT < DC_BWD_GRID ? (items + NT - 1) / NT : DC_BWD_GRID);
-#define GT_DCB(FX_, GF_, XR_) hipLaunchKernelGGL((k_dwunit31_col<FX_, GF_, XR_>), dim3(gc), dim3(NT), 0, s, g.B, g.Tout, g.F, dil, g.w_c, g.w_kt, \
-                                               x, y, da, bn, w, dx, wpart, nx, dscratch, nfa)
-        if (bf == 0) { if (xr) GT_DCB(0, 0, true); else GT_DCB(0, 0, false); }
-        else if (gbf) { if (xr) GT_DCB(1, 1, true); else GT_DCB(1, 1, false); }
-        else { if (xr) GT_DCB(1, 0, true); else GT_DCB(1, 0, false); }
-#undef GT_DCB
-        if (dpool) wdefer_dw(g, wpart, gc, dw, dbias);
-        else hipLaunchKernelGGL(k_dw_wgrad_finish2, dim3(1), dim3(1024), 0, s, g, wpart, gc, dw, dbias);
-        if (next_parts) *next_parts = next_parts_value(nfa, slot, gc);
-        return check();
+        with_grad_fmt(bf, gbf, [&](auto FMT) {
+            dispatch<false, true>(xr, [&](auto XR) {
+                launch(k_dwunit31_col<FMT.a, FMT.b, XR.value>, dim3(gc), dim3(NT), 0, s, g.B, g.Tout, g.F, dil, g.w_c, g.w_kt, x, y,
+                       da, bn, w, dx, wpart, nx, dscratch, nfa);
+            });
+        });
+        nparts = gc;
+    } else {
+        with_grad_fmt(bf, gbf, [&](auto FMT) {
+            with_riding(nxt, xr, [&](auto RIDE) {
+                launch(k_dwunit31_bwd<FMT.a, FMT.a, RIDE.a, RIDE.b, FMT.b>, dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx,
+                       wpart, nx, dscratch, it, nfa);
+            });
+        });
     }
-#define GT_DU(F, GF_)                                                                                                   \
-    do {                                                                                                               \
-        if (xr) hipLaunchKernelGGL((k_dwunit31_bwd<F, F, true, true, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, it, nfa); \
-        else if (nxt) hipLaunchKernelGGL((k_dwunit31_bwd<F, F, true, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, it, nfa); \
-        else hipLaunchKernelGGL((k_dwunit31_bwd<F, F, false, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, it, nfa); \
-    } while (0)
-    if (bf == 0) GT_DU(0, 0);
-    else if (gbf) GT_DU(1, 1);
-    else GT_DU(1, 0);
-#undef GT_DU
-    if (dpool) wdefer_dw(g, wpart, grid, dw, dbias);
-    else hipLaunchKernelGGL(k_dw_wgrad_finish2, dim3(1), dim3(1024), 0, s, g, wpart, grid, dw, dbias);
-    if (nxt && next_parts) *next_parts = next_parts_value(nfa, slot, grid);
+    finish_wgrad(dpool != nullptr, g, wpart, nparts, dw, dbias, s);
+    set_next_parts(next_parts, nxt, nfa, slot, nparts);
     return check();
 }
 
@@ -5092,22 +5107,17 @@ int dwunit33_bwd(const DwGeom& g, const float* x, const float* y, const float* d
     if (dpool) fscratch = dpool;
     double* wpart = reinterpret_cast<double*>(fscratch);      // [grid][160]
     BnBwdArgs bn{stats, gamma, beta, slope, red, ACT_PRELU};
-    NextRedArgs nx{};
-    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, nullptr, next->recompute_x == 2, ybf};
+    NextRedArgs nx = next_args(nxt, next);
+    if (nxt) { nx.xround = next->recompute_x == 2; nx.yfmt = ybf; }
     const FinArgs nfa = next_fin(nxt, next, dscratch, slot);
-#define GT_D33(F, GF_)                                                                                                  \
-    do {                                                                                                               \
-        if (xr) hipLaunchKernelGGL((k_dwunit33_bwd<F, F, true, true, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, tiles_t, nfa); \
-        else if (nxt) hipLaunchKernelGGL((k_dwunit33_bwd<F, F, true, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, tiles_t, nfa); \
-        else hipLaunchKernelGGL((k_dwunit33_bwd<F, F, false, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart, nx, dscratch, tiles_t, nfa); \
-    } while (0)
-    if (bf == 0) GT_D33(0, 0);
-    else if (gbf) GT_D33(1, 1);
-    else GT_D33(1, 0);
-#undef GT_D33
-    if (dpool) wdefer_dw(g, wpart, grid, dw, dbias);
-    else hipLaunchKernelGGL(k_dw_wgrad_finish2, dim3((160 + 63) / 64), dim3(1024), 0, s, g, wpart, grid, dw, dbias);
-    if (nxt && next_parts) *next_parts = next_parts_value(nfa, slot, grid);
+    with_grad_fmt(bf, gbf, [&](auto FMT) {
+        with_riding(nxt, xr, [&](auto RIDE) {
+            launch(k_dwunit33_bwd<FMT.a, FMT.a, RIDE.a, RIDE.b, FMT.b>, dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, wpart,
+                   nx, dscratch, tiles_t, nfa);
+        });
+    });
+    finish_wgrad(dpool != nullptr, g, wpart, grid, dw, dbias, s);
+    set_next_parts(next_parts, nxt, nfa, slot, grid);
     return check();
 }
 
@@ -5130,32 +5140,29 @@ int dense33_bwd(const ConvGeom& g, const float* x, const float* y, const float* 
     const long ntiles = (long)g.B * tiles_t;
     const int grid = (int)(ntiles < 512 ? ntiles : 512);           // 72 KB of LDS: two workgroups per CU, all resident
     BnBwdArgs bn{stats, gamma, beta, slope, red, ACT_PRELU};
-    NextRedArgs nx{};
     const bool nxt = next && next->slope && !next->res;
     const bool xr = nxt && next->recompute_x;
     if (!x && !xr) return (int)hipErrorInvalidValue;
-    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, nullptr, next->recompute_x == 2, ybf};
+    NextRedArgs nx = next_args(nxt, next);
+    if (nxt) { nx.xround = next->recompute_x == 2; nx.yfmt = ybf; }
     const FinArgs nfa = next_fin(nxt, next, dscratch, slot);
     float* const dpool = wdefer_take((size_t)grid * (9 * 256 + 16));
     if (dpool) fscratch = dpool;
     // (the attribute belongs to the current device's copy of the kernel: set on every launch -- a host-side table lookup --
     // rather than remembered per process, which would miss a second device)
-#define GT_D9(F, NXV, XRV, GF_)                                                                                         \
-    do {                                                                                                               \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(k_dense33_bwd<F, F, NXV, XRV, GF_>),          \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, D9_LDS_FLOATS * 4);             \
-        if (e_ != hipSuccess) return (int)e_;                                                                          \
-        hipLaunchKernelGGL((k_dense33_bwd<F, F, NXV, XRV, GF_>), dim3(grid), dim3(NT), D9_LDS_FLOATS * 4, s, g, x, y, da, bn, w, dx, \
-                           fscratch, nx, dscratch, tiles_t, nfa);                                                      \
-    } while (0)
-    if (bf == 0) { if (xr) GT_D9(0, true, true, 0); else if (nxt) GT_D9(0, true, false, 0); else GT_D9(0, false, false, 0); }
-    else if (gbf) { if (xr) GT_D9(1, true, true, 1); else if (nxt) GT_D9(1, true, false, 1); else GT_D9(1, false, false, 1); }
-    else { if (xr) GT_D9(1, true, true, 0); else if (nxt) GT_D9(1, true, false, 0); else GT_D9(1, false, false, 0); }
-#undef GT_D9
-    const int K = 9 * 256 + 16;
-    if (dpool) wdefer_conv(g, fscratch, grid, dw, dbias);
-    else hipLaunchKernelGGL(k_wgrad_mfma_finish, dim3((K + 63) / 64), dim3(1024), 0, s, g, fscratch, grid, dw, dbias);
-    if (nxt && next_parts) *next_parts = next_parts_value(nfa, slot, grid);
+    hipError_t e = hipSuccess;
+    with_grad_fmt(bf, gbf, [&](auto FMT) {
+        with_riding(nxt, xr, [&](auto RIDE) {
+            const auto kernel = k_dense33_bwd<FMT.a, FMT.a, RIDE.a, RIDE.b, FMT.b>;
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    D9_LDS_FLOATS * 4);
+            if (e == hipSuccess)
+                launch(kernel, dim3(grid), dim3(NT), D9_LDS_FLOATS * 4, s, g, x, y, da, bn, w, dx, fscratch, nx, dscratch, tiles_t, nfa);
+        });
+    });
+    if (e != hipSuccess) return (int)e;
+    finish_wgrad(dpool != nullptr, g, fscratch, grid, dw, dbias, s);
+    set_next_parts(next_parts, nxt, nfa, slot, grid);
     return check();
 }
 
@@ -5178,23 +5185,22 @@ int conv15_bwd(const ConvGeom& g, const float* x, const float* y, const float* d
     const long ntiles = (long)g.B * tiles_t;
     const int grid = (int)(ntiles < 512 ? ntiles : 512);           // 61 KB of LDS: two workgroups per CU, all resident
     BnBwdArgs bn{stats, gamma, beta, slope, red, ACT_PRELU};
-    NextRedArgs nx{};
     const bool nxt = next && next->slope && !next->res;
-    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, nullptr, 0, ybf};
+    NextRedArgs nx = next_args(nxt, next);
+    if (nxt) nx.yfmt = ybf;
     const FinArgs nfa = next_fin(nxt, next, dscratch, slot);
     float* const dpool = wdefer_take((size_t)grid * (5 * 256 + 16));
     if (dpool) fscratch = dpool;
-#define GT_C15(DW_, F, NXV, GF_)                                                                                        \
-    hipLaunchKernelGGL((k_conv15_bwd<DW_, F, F, NXV, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w, dx, dx_acc, fscratch, nx, \
-                       dscratch, tiles_t, nfa)
-    if (dyw) { if (bf == 0) GT_C15(true, 0, 0, 0); else if (gbf) GT_C15(true, 1, 0, 1); else GT_C15(true, 1, 0, 0); }
-    else if (nxt) { if (bf == 0) GT_C15(false, 0, 1, 0); else if (gbf) GT_C15(false, 1, 2, 1); else GT_C15(false, 1, 2, 0); }
-    else { if (bf == 0) GT_C15(false, 0, 0, 0); else if (gbf) GT_C15(false, 1, 0, 1); else GT_C15(false, 1, 0, 0); }
-#undef GT_C15
-    const int K = 5 * 256 + 16;
-    if (dpool) wdefer_conv(g, fscratch, grid, dw, dbias);
-    else hipLaunchKernelGGL(k_wgrad_mfma_finish, dim3((K + 63) / 64), dim3(1024), 0, s, g, fscratch, grid, dw, dbias);
-    if (nxt && next_parts) *next_parts = next_parts_value(nfa, slot, grid);
+    // the wide-output direction (.a), or the narrow one with or without a riding reduction (.b; refused above for the
+    // wide one): the kernel's NEXT is 1 + the format of that unit's y
+    dispatch_case<Case<true, false>, Case<false, true>, Case<false, false>>(dyw, nxt, [&](auto FORM) {
+        with_grad_fmt(bf, gbf, [&](auto FMT) {
+            launch(k_conv15_bwd<FORM.a, FMT.a, FMT.a, FORM.b ? 1 + FMT.a : 0, FMT.b>, dim3(grid), dim3(NT), 0, s, g, x, y, da, bn, w,
+                   dx, dx_acc, fscratch, nx, dscratch, tiles_t, nfa);
+        });
+    });
+    finish_wgrad(dpool != nullptr, g, fscratch, grid, dw, dbias, s);
+    set_next_parts(next_parts, nxt, nfa, slot, grid);
     return check();
 }
 
@@ -5218,49 +5224,51 @@ int unit1x1_bwd(const ConvGeom& g, const float* x, const float* y, const float* 
     // unit's, which the finish kernel above has consumed, in dscratch)
     const bool nxt = next && next->slope && dx && g.Cin == 16 && g.CinT == 16 && g.cin_off == 0 && bf == ybf;
     // (the recomputing form needs 120 VGPRs: four workgroups per CU, 1024 resident)
-    const bool xr_ = nxt && next->recompute_x;
-    long waves = (long)(nxt && !xr_ ? NEXT_GRID : MAX_PARTIALS) * (NT / 64);
+    const bool xr = nxt && next->recompute_x;
+    long waves = (long)(nxt && !xr ? NEXT_GRID : MAX_PARTIALS) * (NT / 64);
     if (waves > ntiles) waves = ntiles;
     const long tpw = (ntiles + waves - 1) / waves;
     const int grid = (int)((ntiles + tpw * (NT / 64) - 1) / (tpw * (NT / 64)));
     BnBwdArgs bn{stats, gamma, beta, slope, red, act};
-    NextRedArgs nx{};
-    const bool xr = nxt && next->recompute_x;
     if (!x && !xr) return (int)hipErrorInvalidValue;
-    if (nxt) nx = NextRedArgs{next->y, next->stats, next->gamma, next->beta, next->slope, next->res, next->recompute_x == 2};
+    NextRedArgs nx = next_args(nxt, next);
+    if (nxt) { nx.res = next->res; nx.xround = next->recompute_x == 2; }
     const FinArgs nfa = next_fin(nxt, next, dscratch, slot);
     float* const dpool = wdefer_take((size_t)grid * (256 + 16));      // (fusion bit 15: the finish is recorded, not launched)
     if (dpool) fscratch = dpool;
-#define GT_U1(F, Y, GF_)                                                                                                \
-    do {                                                                                                               \
-        if (xr) hipLaunchKernelGGL((k_unit1x1_bwd<F, Y, true, true, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, res, bn, w, dx, dx_acc, \
-                                   dres, dres_acc, fscratch, tpw, nx, dscratch, nfa);                                   \
-        else if (nxt) hipLaunchKernelGGL((k_unit1x1_bwd<F, Y, true, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, res, bn, w, dx, dx_acc, \
-                                    dres, dres_acc, fscratch, tpw, nx, dscratch, nfa);                                  \
-        else hipLaunchKernelGGL((k_unit1x1_bwd<F, Y, false, false, GF_>), dim3(grid), dim3(NT), 0, s, g, x, y, da, res, bn, w, dx, dx_acc, \
-                                dres, dres_acc, fscratch, tpw, nx, dscratch, nfa);                                      \
-    } while (0)
-    if (bf == 0 && ybf == 0) GT_U1(0, 0, 0);
-    else if (bf == 1 && ybf == 1) { if (gbf) GT_U1(1, 1, 1); else GT_U1(1, 1, 0); }
-    else return (int)hipErrorInvalidValue;
-#undef GT_U1
-    if (nxt && next_parts) *next_parts = next_parts_value(nfa, slot, grid);
-    if (dpool) wdefer_conv(g, fscratch, grid, dw, dbias);
-    else hipLaunchKernelGGL(k_wgrad_mfma_finish, dim3((256 + 16 + 63) / 64), dim3(1024), 0, s, g, fscratch, grid, dw, dbias);
+    // x / res and y in one format, fp32 or bf16
+    if (bf != ybf || !with_grad_fmt(bf, gbf, [&](auto FMT) {
+            with_riding(nxt, xr, [&](auto RIDE) {
+                launch(k_unit1x1_bwd<FMT.a, FMT.a, RIDE.a, RIDE.b, FMT.b>, dim3(grid), dim3(NT), 0, s, g, x, y, da, res, bn, w, dx,
+                       dx_acc, dres, dres_acc, fscratch, tpw, nx, dscratch, nfa);
+            });
+        }))
+        return (int)hipErrorInvalidValue;
+    finish_wgrad(dpool != nullptr, g, fscratch, grid, dw, dbias, s);
+    set_next_parts(next_parts, nxt, nfa, slot, grid);
     return check();
 }
 
+// Layouts of a (B, 257, T, 2) spectrogram given by its strides in floats.  The two special forms make 8-byte (re, im)
+// accesses: even strides and an 8-byte aligned base, which is what a complex tensor viewed as real has; anything else
+// takes the generic form.
+static bool pair_ok(const float* p, long sb, long sf, long st) {
+    return ((sb | sf | st) & 1) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0;
+}
+static long ab(long v) { return v < 0 ? -v : v; }
+// dense frame-major: LDS-staged frames
+static bool frame_major(const float* p, long sb, long sf, long st, int T) {
+    return sf == 2 && st == 514 && sb == (long)T * 514 && pair_ok(p, sb, sf, st);
+}
+// frame axis fastest (torch.stft's layout): tiles of TT frames, lanes along t
+static bool time_major(const float* p, long sb, long sf, long st) { return ab(st) < ab(sf) && pair_ok(p, sb, sf, st); }
+
 int feat_fwd(const float* spec, long sb, long sf, long st, int B, int T, const float* erb_w, float* eb,
              hipStream_t s, int bf, float* eb2, int eb2_bf) {
-    // frame axis fastest (torch.stft's layout): tiles of TT frames, lanes along t (8-byte (re, im) accesses: even strides
-    // and an 8-byte aligned base, which is what a complex tensor viewed as real has; anything else takes the generic form)
-    auto pair_ok = [](const float* p, long a, long b2, long c) {
-        return ((a | b2 | c) & 1) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0;
-    };
-    if (sf == 2 && st == 514 && sb == (long)T * 514 && pair_ok(spec, sb, sf, st))      // dense frame-major: LDS-staged frames
+    if (frame_major(spec, sb, sf, st, T))
         hipLaunchKernelGGL(k_feat_fm, dim3(grid_for(((long)B * T + FM_NF - 1) / FM_NF * NT, 2048)), dim3(NT), 0, s, spec, (long)B * T,
                            erb_w, eb, bf, eb2, eb2_bf);
-    else if ((st < 0 ? -st : st) < (sf < 0 ? -sf : sf) && pair_ok(spec, sb, sf, st))
+    else if (time_major(spec, sb, sf, st))
         hipLaunchKernelGGL(k_feat_t, dim3(B * ((T + TT - 1) / TT)), dim3(NT), 0, s, spec, sb, sf, st, B, T, erb_w, eb, bf,
                            eb2, eb2_bf);
     else
@@ -5270,15 +5278,10 @@ int feat_fwd(const float* spec, long sb, long sf, long st, int B, int T, const f
 }
 int bs_mask_fwd(const float* m, const float* spec, long sb, long sf, long st, int B, int T, const float* ierb_w,
                 float* out, long ob, long of, long ot, hipStream_t s, int bf) {
-    auto ab = [](long v) { return v < 0 ? -v : v; };
-    auto pair_ok = [](const float* p, long a, long b2, long c) {
-        return ((a | b2 | c) & 1) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0;
-    };
-    if (sf == 2 && st == 514 && sb == (long)T * 514 && of == 2 && ot == 514 && ob == (long)T * 514 && pair_ok(spec, sb, sf, st) &&
-        pair_ok(out, ob, of, ot))
+    if (frame_major(spec, sb, sf, st, T) && frame_major(out, ob, of, ot, T))
         hipLaunchKernelGGL(k_bs_mask_fm, dim3(grid_for(((long)B * T + FM_NF - 1) / FM_NF * NT, 2048)), dim3(NT), 0, s, m, spec,
                            (long)B * T, ierb_w, out, bf);
-    else if (ab(st) < ab(sf) && ab(ot) < ab(of) && pair_ok(spec, sb, sf, st) && pair_ok(out, ob, of, ot))
+    else if (time_major(spec, sb, sf, st) && time_major(out, ob, of, ot))
         hipLaunchKernelGGL(k_bs_mask_t, dim3(B * ((T + TT - 1) / TT)), dim3(NT), 0, s, m, spec, sb, sf, st, B, T, ierb_w,
                            out, ob, of, ot, bf);
     else
@@ -5288,15 +5291,10 @@ int bs_mask_fwd(const float* m, const float* spec, long sb, long sf, long st, in
 }
 int bs_mask_bwd(const float* dout, long ob, long of, long ot, const float* spec, long sb, long sf, long st, int B,
                 int T, const float* ierb_w, float* dm, hipStream_t s) {
-    auto ab = [](long v) { return v < 0 ? -v : v; };
-    auto pair_ok = [](const float* p, long a, long b2, long c) {
-        return ((a | b2 | c) & 1) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0;
-    };
-    if (sf == 2 && st == 514 && sb == (long)T * 514 && of == 2 && ot == 514 && ob == (long)T * 514 && pair_ok(spec, sb, sf, st) &&
-        pair_ok(dout, ob, of, ot))
+    if (frame_major(spec, sb, sf, st, T) && frame_major(dout, ob, of, ot, T))
         hipLaunchKernelGGL(k_bs_mask_bwd_fm, dim3(grid_for(((long)B * T + FM_NF - 1) / FM_NF * NT, 2048)), dim3(NT), 0, s, dout, spec,
                            (long)B * T, ierb_w, dm);
-    else if (ab(st) < ab(sf) && ab(ot) < ab(of) && pair_ok(spec, sb, sf, st) && pair_ok(dout, ob, of, ot))
+    else if (time_major(spec, sb, sf, st) && time_major(dout, ob, of, ot))
         hipLaunchKernelGGL(k_bs_mask_bwd_t, dim3(B * ((T + TT - 1) / TT)), dim3(NT), 0, s, dout, ob, of, ot, spec, sb, sf,
                            st, B, T, ierb_w, dm);
     else
@@ -5347,12 +5345,9 @@ int hybrid_loss_spec(const float* pred, long pb, long pf, long pt, const float* 
                      int T, float* grad, long gb, long gf, long gt, double* partial, int* parts, hipStream_t s) {
     const int grid = red_grid((long)B * 257 * T);
     if ((long)B * 257 * T >= (1L << 31)) return (int)hipErrorInvalidValue;       // (k_hloss_spec divides in 32 bits)
-    if ((pt < 0 ? -pt : pt) > (pf < 0 ? -pf : pf))
-        hipLaunchKernelGGL(k_hloss_spec<true>, dim3(grid), dim3(NT), 0, s, pred, pb, pf, pt, tru, tb, tf, tt, B, T, grad, gb, gf, gt,
-                           partial);
-    else
-        hipLaunchKernelGGL(k_hloss_spec<false>, dim3(grid), dim3(NT), 0, s, pred, pb, pf, pt, tru, tb, tf, tt, B, T, grad, gb, gf, gt,
-                           partial);
+    dispatch<false, true>(ab(pt) > ab(pf), [&](auto FM) {
+        launch(k_hloss_spec<FM.value>, dim3(grid), dim3(NT), 0, s, pred, pb, pf, pt, tru, tb, tf, tt, B, T, grad, gb, gf, gt, partial);
+    });
     *parts = grid;
     return check();
 }

@@ -1,7 +1,9 @@
-"""Compares the gfx950 device assembly of kernels.hip between two source trees, kernel by kernel.
+"""Compares the gfx950 device assembly of one .hip file of gtcrn_micro_amd/csrc (kernels.hip, train_kernels.hip,
+metrics.hip, batch.hip, reverb.hip) between two source trees, kernel by kernel.
 
-    hipcc --offload-arch=gfx950 <the flags of gtcrn_micro_amd/build.py for kernels.hip> --cuda-device-only -S \
-          OLD/gtcrn_micro_amd/csrc/kernels.hip -o old.s        (and the same for the new tree -> new.s)
+    hipcc --offload-arch=gfx950 <the flags gtcrn_micro_amd/build.py gives that file: the common ones and its per_file
+          entry, if it has one> --cuda-device-only -S OLD/gtcrn_micro_amd/csrc/FILE.hip -o old.s
+          (and the same for the new tree -> new.s)
     python tools/asm_compare.py old.s new.s [--drop-arg false]
 
 A kernel is its instruction lines in order: comments and assembler directives dropped, branch labels renumbered by

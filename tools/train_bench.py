@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Train-step throughput (BASELINE config 4 shape: synthetic DNS-style mixes, 4 s clips, Adam, clip 3.0).
 
-    python tools/train_bench.py --batch 512 --steps 5 --warmup 2 [--profile]
+    python tools/train_bench.py --batch 512 --steps 5 --warmup 2 [--storage bf16]
 
-fp32 end to end (the reference trains in fp32; config 4 asks for bf16, which this path does not use).
+fp32 end to end by default (the reference trains in fp32); --storage: the saved activations in another storage mode
+(Trainer.set_storage).
 Prints one JSON line: frames/s of full train steps (STFT x2, forward, HybridLoss, backward, clip, Adam)
 and the split model-forward / model-backward / rest measured with HIP events."""
 import argparse
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--storage", default="f32")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -32,10 +34,12 @@ def main():
     torch.manual_seed(43)
     model, opt, sched, loss_func = make_training(device="cuda")
     model.train()
+    if a.storage != "f32":
+        model.set_activation_storage(a.storage)
     L = int(a.seconds * 16000)
     noisy, clean = synthetic_mix(a.batch, samples=L, seed=43)
     T = 1 + L // 256
-    ws = G.Trainer.workspace_bytes(a.batch, T)
+    ws = G.Trainer.workspace_bytes(a.batch, T, a.storage)
     for _ in range(a.warmup):
         train_step(model, opt, sched, loss_func, noisy, clean)
     torch.cuda.synchronize()
@@ -56,8 +60,8 @@ def main():
     print(json.dumps({
         "metric": "train frames/sec (STFT x2 -> forward -> HybridLoss -> backward -> clip -> Adam)",
         "value": round(a.batch * T / el, 1), "unit": "frames/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(el * 1e3, 3), "dtype": "f32", "data": "synthetic DNS-style mixes",
-        "config": {"workload": f"train step, B={a.batch} clips x {a.seconds:g} s (T={T}), fp32, Adam, clip 3.0"},
+        "ms_per_step": round(el * 1e3, 3), "dtype": a.storage, "data": "synthetic DNS-style mixes",
+        "config": {"workload": f"train step, B={a.batch} clips x {a.seconds:g} s (T={T}), {a.storage} storage, Adam, clip 3.0"},
         "model_forward_ms": round(ev[0].elapsed_time(ev[1]), 3), "model_backward_ms": round(ev[1].elapsed_time(ev[2]), 3),
         "workspace_GB": round(ws / 2 ** 30, 2), "loss": float(loss), "grad_norm": float(gn)}))
 
