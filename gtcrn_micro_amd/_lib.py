@@ -261,6 +261,14 @@ def lib():
         L.gtcrn_batch_active_workspace_bytes.argtypes = [ci, cl, ci]
         L.gtcrn_batch_mix_active.argtypes = [_vp, _vp, ci, _vp, _vp, ci, _vp, _vp, ci, cl, _vp, cl, _vp, cl, ci, ctypes.c_longlong,
                                              _vp, _vp, ci, _vp]
+    # telephone-channel rows: the 8 kHz band and G.711 as a post-pass over drawn rows
+    if hasattr(L, "gtcrn_batch_phone"):
+        L.gtcrn_batch_phone_taps.argtypes = [_vp]
+        L.gtcrn_batch_phone_chunk.argtypes = []
+        L.gtcrn_batch_phone_plan.argtypes = [cf, ci, ci, cl, _vp, _vp, _vp]
+        L.gtcrn_batch_phone_plan_host.argtypes = [cf, ci, ci, cl, _vp, _vp]
+        L.gtcrn_batch_phone.argtypes = [_vp, cl, _vp, cl, _vp, ci, cl, _vp, cl, _vp, cl, ci, _vp, _vp]
+        L.gtcrn_batch_phone_host.argtypes = [_vp, cl, _vp, cl, _vp, ci, cl, _vp, cl, _vp, cl, ci, _vp]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

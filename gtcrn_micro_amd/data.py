@@ -17,7 +17,15 @@ With ``active_db=`` the noise is scaled to the drawn SNR of the levels over each
 pauses and a reverberant tail no longer dilute the speech level -- by exact integer window energies (gtcrn_batch_mix_active;
 "active levels" in the header).
 
+With ``p_phone=`` a drawn share of the rows of a finished batch goes through a telephone channel: band-limited to 4 kHz by an
+exact integer FIR pair (16 kHz -> 8 kHz -> 16 kHz) and, per row, through linear 8 kHz PCM, mu-law or A-law G.711 in between --
+what the 8 kHz and G.711 live forms hand the model (csrc/phone.hip, a post-pass over the rows any draw form has written;
+"telephone-channel rows: exact 8 kHz band + G.711" in the header).  ``phone_channel`` is the same pass for
+a caller's own tensors.
+
 Out of scope: sample rates other than 16 kHz, float corpora, streaming a corpus larger than device memory from disk; for the
+telephone channel: a 300 Hz high-pass or an IRS send / receive characteristic, other codecs, packet loss and jitter, a channel in
+front of the mix (speech through the phone, noise added after), corpora at 8 kHz, a per-row target; for the
 active levels: an active-level ``level_db`` (the level stays the mixture's plain RMS), a threshold relative to the clip, hangover
 smoothing and P.56-style envelope followers, activity labels as an output; for the reverberation: targets that need a response
 of their own (a shortened-decay tail), responses longer than 16384 taps, and multichannel responses.
@@ -40,6 +48,10 @@ REVERB_PLAN_DTYPE = np.dtype([("rir", "<i4"), ("reserved", "<i4")])
 REVERB_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("reserved", "<i4")])
 REVERB_SPLIT_RECORD_DTYPE = np.dtype([("rir", "<i4"), ("ntaps", "<i4"), ("saturated", "<i4"), ("split", "<i4"),
                                       ("target_saturated", "<i4"), ("reserved", "<i4", (3,))])
+PHONE_PLAN_DTYPE = np.dtype([("codec", "<i4"), ("reserved", "<i4")])
+PHONE_RECORD_DTYPE = np.dtype([("codec", "<i4"), ("saturated_down", "<i4"), ("saturated_up", "<i4"), ("reserved", "<i4")])
+PHONE_CODECS = {"pcm": 0, "ulaw": 1, "alaw": 2}      # gtcrn_phone_item.codec; -1: a wide-band row
+PHONE_TARGETS = {"narrow": 0, "wide": 1}
 REVERB_MAX_TAPS = 16384        # GTCRN_REVERB_MAX_TAPS
 REVERB_TAP_MAX = 32639         # GTCRN_REVERB_TAP_MAX
 _U64 = (1 << 64) - 1
@@ -195,6 +207,143 @@ def plan_to_device(plan, device):
     import torch
     p = np.ascontiguousarray(plan, PLAN_DTYPE)
     return torch.from_numpy(p.view(np.int32).reshape(p.size, 8).copy()).to(device)
+
+
+def _phone_lib():
+    L = _batch_lib()
+    if not hasattr(L, "gtcrn_batch_phone"):
+        raise GtcrnError("this library has no telephone-channel rows (gtcrn_batch_phone*)")
+    return L
+
+
+def _phone_mask(codecs):
+    """Codec names -> gtcrn_batch_phone_plan's codec_mask."""
+    names = (codecs,) if isinstance(codecs, str) else tuple(codecs)
+    if not names or any(c not in PHONE_CODECS for c in names):
+        raise GtcrnError(f"phone_codecs holds one or more of {tuple(PHONE_CODECS)}, got {codecs!r}")
+    mask = 0
+    for c in names:
+        mask |= 1 << PHONE_CODECS[c]
+    return mask
+
+
+def _phone_target(target):
+    if target not in PHONE_TARGETS:
+        raise GtcrnError(f'phone_target is "narrow" or "wide", got {target!r}')
+    return PHONE_TARGETS[target]
+
+
+def phone_taps():
+    """gtcrn_batch_phone_taps: the 129 integer taps of the channel's filter pair, exactly as the kernel uses them (int32)."""
+    t = np.zeros(129, np.int32)
+    if _check(_phone_lib().gtcrn_batch_phone_taps(t.ctypes.data)) != 129:
+        raise GtcrnError("gtcrn_batch_phone_taps did not return 129 taps")
+    return t
+
+
+def phone_chunk():
+    """gtcrn_batch_phone_chunk: consecutive output samples of one workgroup of the channel kernel."""
+    return int(_phone_lib().gtcrn_batch_phone_chunk())
+
+
+def phone_plan_host(p_phone, codecs, B, seed, step, item0=0):
+    """gtcrn_batch_phone_plan_host: the phone plan the device would draw for (seed, step), computed on the host.  codecs: names
+    from PHONE_CODECS, or the integer mask.  Returns a PHONE_PLAN_DTYPE array of B items (codec = -1: a wide-band row)."""
+    mask = int(codecs) if isinstance(codecs, (int, np.integer)) else _phone_mask(codecs)
+    ss = np.array([int(seed) & _U64, int(step) & _U64], np.uint64)
+    plan = np.zeros(max(int(B), 0), PHONE_PLAN_DTYPE)
+    _check(_phone_lib().gtcrn_batch_phone_plan_host(float(p_phone), mask, int(B), int(item0), ss.ctypes.data,
+                                                    plan.ctypes.data if plan.size else None))
+    return plan
+
+
+def phone_plan_to_device(plan, device):
+    """A PHONE_PLAN_DTYPE array -> the (B, 2) int32 device tensor ``BatchSource.draw(phone_plan=...)`` takes."""
+    import torch
+    p = np.ascontiguousarray(plan, PHONE_PLAN_DTYPE)
+    return torch.from_numpy(p.view(np.int32).reshape(p.size, 2).copy()).to(device)
+
+
+def phone_channel_host(noisy, clean=None, plan=None, target="narrow"):
+    """gtcrn_batch_phone_host: the channel on host arrays, by the very functions the kernel compiles.  noisy, clean: (B, L)
+    float32 arrays (clean may be None); plan: a PHONE_PLAN_DTYPE array of B items.  -> (noisy, clean or None, records)."""
+    src_n = np.ascontiguousarray(noisy, np.float32)
+    if src_n.ndim != 2:
+        raise GtcrnError("noisy must be a (B, L) array")
+    B, L = src_n.shape
+    src_c = None if clean is None else np.ascontiguousarray(clean, np.float32)
+    if src_c is not None and src_c.shape != src_n.shape:
+        raise GtcrnError("clean must have noisy's shape")
+    pl = np.ascontiguousarray(plan, PHONE_PLAN_DTYPE)
+    if pl.shape != (B,):
+        raise GtcrnError(f"plan must hold {B} items")
+    out_n = np.empty_like(src_n)
+    out_c = None if src_c is None else np.empty_like(src_c)
+    rec = np.zeros(B, PHONE_RECORD_DTYPE)
+    _check(_phone_lib().gtcrn_batch_phone_host(
+        src_n.ctypes.data, L, None if src_c is None else src_c.ctypes.data, L, pl.ctypes.data, B, L, out_n.ctypes.data, L,
+        None if out_c is None else out_c.ctypes.data, L, _phone_target(target), rec.ctypes.data))
+    return out_n, out_c, rec
+
+
+def _phone_rows(t, what, like=None):
+    """(tensor, row stride) of a (B, L) float32 device tensor with contiguous rows."""
+    import torch
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.numel() == 0
+            or (t.shape[1] > 1 and t.stride(1) != 1)):
+        raise GtcrnError(f"{what} must be a (B, L) float32 CUDA (ROCm) tensor with contiguous rows")
+    if like is not None and (t.device != like.device or tuple(t.shape) != tuple(like.shape)):
+        raise GtcrnError(f"{what} must have the noisy tensor's shape and device")
+    stride = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if stride < t.shape[1]:
+        raise GtcrnError(f"{what}: rows overlap")
+    return t, stride
+
+
+def phone_channel(noisy, clean=None, codec="ulaw", target="narrow", out=None, records=None):
+    """gtcrn_batch_phone on a caller's tensors, e.g. test audio for the 8 kHz live forms: (B, L) float32 device tensors
+    (clean may be None).  codec: a name from PHONE_CODECS for every row, or a (B, 2) int32 device tensor of gtcrn_phone_item
+    rows (codec -1: the row is copied).  target: "narrow" (clean goes through the band, no codec) or "wide" (clean is
+    copied).  out: the tensor, or the (noisy, clean) pair, to write (not the inputs: the channel is not in place); records:
+    a (B, 4) int32 tensor.  -> (noisy, clean or None, records).  Asynchronous on the current stream; allocates only what
+    is not given."""
+    import torch
+    L_ = _phone_lib()
+    tg = _phone_target(target)
+    (noisy, ns) = _phone_rows(noisy, "noisy")
+    B, L = noisy.shape
+    cs = 0
+    if clean is not None:
+        clean, cs = _phone_rows(clean, "clean", noisy)
+    if isinstance(codec, str):
+        if codec not in PHONE_CODECS:
+            raise GtcrnError(f"codec is one of {tuple(PHONE_CODECS)} or a plan tensor, got {codec!r}")
+        plan = torch.tensor([[PHONE_CODECS[codec], 0]], device=noisy.device, dtype=torch.int32).repeat(B, 1)
+    else:
+        plan = codec
+        if (not isinstance(plan, torch.Tensor) or plan.device != noisy.device or plan.dtype != torch.int32
+                or tuple(plan.shape) != (B, 2) or not plan.is_contiguous()):
+            raise GtcrnError(f"a codec plan must be a contiguous ({B}, 2) int32 tensor on {noisy.device}")
+    if out is None:
+        out_n, out_c = torch.empty_like(noisy, memory_format=torch.contiguous_format), None
+        if clean is not None:
+            out_c = torch.empty_like(clean, memory_format=torch.contiguous_format)
+    else:
+        out_n, out_c = (out, None) if clean is None else out
+    (out_n, ons) = _phone_rows(out_n, "out noisy", noisy)
+    ocs = 0
+    if clean is not None:
+        out_c, ocs = _phone_rows(out_c, "out clean", noisy)
+    if records is None:
+        records = torch.zeros((B, 4), device=noisy.device, dtype=torch.int32)
+    elif (not isinstance(records, torch.Tensor) or records.device != noisy.device or records.dtype != torch.int32
+          or tuple(records.shape) != (B, 4) or not records.is_contiguous()):
+        raise GtcrnError(f"records must be a contiguous ({B}, 4) int32 tensor on {noisy.device}")
+    with torch.cuda.device(noisy.device):
+        _check(L_.gtcrn_batch_phone(noisy.data_ptr(), ns, clean.data_ptr() if clean is not None else None, cs, plan.data_ptr(), B, L,
+                                    out_n.data_ptr(), ons, out_c.data_ptr() if out_c is not None else None, ocs, tg,
+                                    records.data_ptr(), _stream_ptr()))
+    return out_n, out_c, records
 
 
 class Corpus:
@@ -436,13 +585,25 @@ class BatchSource:
     windows of ``active_window`` samples (1600: 100 ms) whose mean square exceeds it, each side by its own activity
     (gtcrn_batch_mix_active in place of the two mix calls above, in every combination with ``rirs=``, ``target_ms=`` and
     ``target=``).  ``records`` is then (B, 16) int32, ``records_numpy()`` ACTIVE_RECORD_DTYPE, ``active_threshold`` the integer
-    threshold; ``achieved_snr_db`` reads the SNR back.  None: the draw above, call for call."""
+    threshold; ``achieved_snr_db`` reads the SNR back.  None: the draw above, call for call.
+    ``p_phone=`` (every form above): each row of the finished batch is a telephone row with that probability -- band-limited to
+    4 kHz and passed through one of ``phone_codecs`` ("pcm": linear 8 kHz PCM, "ulaw", "alaw"), drawn per row (gtcrn_batch_phone,
+    a post-pass: the draw above runs unchanged into two raw buffers the source owns, the channel writes ``noisy`` / ``clean``).
+    ``phone_target``: "narrow" -- ``clean`` of a telephone row is band-limited too, without the codec -- or "wide" -- it stays
+    as drawn.  ``phone_plan`` is the drawn (B, 2) int32 plan, ``phone_records_numpy()`` the records.  0: the draw above, call for
+    call, and nothing more is allocated."""
 
     def __init__(self, speech, noise=None, paired_clean=None, B=1, L=64000, seed=0, snr_db=(-5.0, 20.0), level_db=(-35.0, -15.0),
                  granule=1, item0=0, rirs=None, p_reverb=0.0, reverb_form=0, target_ms=None, target=None, active_db=None,
-                 active_window=1600):
+                 active_window=1600, p_phone=0.0, phone_codecs=("pcm", "ulaw", "alaw"), phone_target="narrow"):
         import torch
         _batch_lib()
+        self.p_phone, self.phone_mask, self.phone_target = float(p_phone), _phone_mask(phone_codecs), phone_target
+        _phone_target(phone_target)
+        if not 0.0 <= self.p_phone <= 1.0:               # (a NaN fails both comparisons)
+            raise GtcrnError("p_phone must lie in 0 .. 1")
+        if self.p_phone > 0.0:
+            _phone_lib()
         if (noise is None) == (paired_clean is None):
             raise GtcrnError("give exactly one of noise= (mix) and paired_clean= (pairs)")
         self.active_db, self.active_window, self.active_threshold = None, None, None
@@ -517,6 +678,13 @@ class BatchSource:
                 self._rws = torch.empty(reverb_split_workspace_bytes(B, L), device=dev, dtype=torch.uint8)
         elif self.p_reverb != 0.0:
             raise GtcrnError("p_reverb needs rirs=")
+        self.phone_plan = self.phone_records = None
+        if self.p_phone > 0.0:
+            ls = (L + 3) // 4 * 4                        # raw rows of whole 16 bytes
+            self._raw_noisy = torch.empty((B, ls), device=dev, dtype=torch.float32)[:, :L]
+            self._raw_clean = torch.empty((B, ls), device=dev, dtype=torch.float32)[:, :L]
+            self.phone_plan = torch.full((B, 2), -1, device=dev, dtype=torch.int32)    # gtcrn_phone_item rows
+            self.phone_records = torch.zeros((B, 4), device=dev, dtype=torch.int32)    # gtcrn_phone_record rows
 
     # ---- the step word ----------------------------------------------------------------------------------------------
     def set_step(self, k):
@@ -549,6 +717,18 @@ class BatchSource:
     def split_records_numpy(self):
         """The split records of the most recent draw (a source with ``target_ms=``)."""
         return self.split_records.cpu().numpy().view(REVERB_SPLIT_RECORD_DTYPE).reshape(self.B)
+
+    def phone_plan_numpy(self):
+        """The phone plan of the most recent draw (a source with ``p_phone`` > 0)."""
+        if self.phone_plan is None:
+            raise GtcrnError("phone_plan_numpy needs a source with p_phone > 0")
+        return self.phone_plan.cpu().numpy().view(PHONE_PLAN_DTYPE).reshape(self.B)
+
+    def phone_records_numpy(self):
+        """The phone records of the most recent draw (a source with ``p_phone`` > 0)."""
+        if self.phone_records is None:
+            raise GtcrnError("phone_records_numpy needs a source with p_phone > 0")
+        return self.phone_records.cpu().numpy().view(PHONE_RECORD_DTYPE).reshape(self.B)
 
     # ---- drawing ----------------------------------------------------------------------------------------------------
     def _rows(self, t, what):
@@ -587,12 +767,47 @@ class BatchSource:
                                                  self.reverb_plan.data_ptr(), _stream_ptr()))
         return self.reverb_plan
 
-    def draw(self, clips=None, plan=None, out=None, passes=7, reverb_plan=None):
+    def draw_phone_plan(self):
+        """Fills ``self.phone_plan`` for the current (seed, step); the step word is read, never moved (so this goes before
+        ``draw_plan``)."""
+        import torch
+        if self.phone_plan is None:
+            raise GtcrnError("draw_phone_plan needs a source with p_phone > 0")
+        with torch.cuda.device(self.device):
+            _check(lib().gtcrn_batch_phone_plan(self.p_phone, self.phone_mask, self.B, self.item0, self.seed_step.data_ptr(),
+                                                self.phone_plan.data_ptr(), _stream_ptr()))
+        return self.phone_plan
+
+    def draw(self, clips=None, plan=None, out=None, passes=7, reverb_plan=None, phone_plan=None):
         """-> (noisy, clean), (B, L) float32: ``self.noisy`` / ``self.clean`` or the pair given as ``out`` (row strides
         >= L).  plan: a (B, 8) int32 device tensor of gtcrn_batch_item rows to use instead of drawing one (the step word
         then stays).  reverb_plan (a source with ``rirs=``): a (B, 2) int32 device tensor of gtcrn_reverb_item rows to use
-        instead of drawing one.  Asynchronous on the current stream, allocates nothing, capturable.  passes: measurement
-        hook of the mix form (gtcrn_batch_mix)."""
+        instead of drawing one.  phone_plan (a source with ``p_phone`` > 0): a (B, 2) int32 device tensor of gtcrn_phone_item
+        rows to use instead of drawing one.  Asynchronous on the current stream, allocates nothing, capturable.  passes:
+        measurement hook of the mix form (gtcrn_batch_mix)."""
+        import torch
+        if self.phone_plan is None:
+            if phone_plan is not None:
+                raise GtcrnError("phone_plan= needs a source with p_phone > 0")
+            return self._draw_rows(clips, plan, out, passes, reverb_plan)
+        if phone_plan is None:
+            pp = self.draw_phone_plan()                  # before the batch plan: that one moves the step word
+        else:
+            pp = phone_plan
+            if (not isinstance(pp, torch.Tensor) or pp.device != self.device or pp.dtype != torch.int32
+                    or tuple(pp.shape) != (self.B, 2) or not pp.is_contiguous()):
+                raise GtcrnError(f"phone_plan must be a contiguous ({self.B}, 2) int32 tensor on {self.device}")
+        noisy, clean = (self.noisy, self.clean) if out is None else out
+        (noisy, ns), (clean, cs) = self._rows(noisy, "noisy"), self._rows(clean, "clean")
+        raw_n, raw_c = self._draw_rows(clips, plan, (self._raw_noisy, self._raw_clean), passes, reverb_plan)
+        with torch.cuda.device(self.device):
+            _check(lib().gtcrn_batch_phone(raw_n.data_ptr(), raw_n.stride(0), raw_c.data_ptr(), raw_c.stride(0), pp.data_ptr(),
+                                           self.B, self.L, noisy.data_ptr(), ns, clean.data_ptr(), cs,
+                                           PHONE_TARGETS[self.phone_target], self.phone_records.data_ptr(), _stream_ptr()))
+        return noisy, clean
+
+    def _draw_rows(self, clips, plan, out, passes, reverb_plan):
+        """The draw without the telephone channel: every form of the class docstring, into ``out``."""
         import torch
         rp = None
         if reverb_plan is not None:

@@ -1089,6 +1089,69 @@ int gtcrn_batch_mix_active(const short *d_speech_pcm, const long long *d_speech_
                            long clean_stride, int window, long long threshold, gtcrn_batch_active_record *d_records,
                            void *d_workspace, int passes, void *stream);
 
+/* ---- telephone-channel rows: exact 8 kHz band + G.711 -------------------------------------------------------------------------
+ * The live side serves 8 kHz streams and G.711 packets; a telephone stream reaches the 16 kHz model with nothing above 4 kHz and
+ * with the log-PCM noise floor of a G.711 hop.  gtcrn_batch_phone gives a drawn share of the rows of a batch both properties.  It
+ * is a post-pass over the float rows a draw has written, so it composes with every draw form without entering their kernels, and
+ * it is integers only, so that a few lines of numpy restate it bit for bit (tests/phone_checker.py).
+ *
+ * Filter table: 129 integers T[0 .. 128].  h is the 16 kHz -> 8 kHz design of "sample-rate conversion" above: up / down = 1 / 2,
+ * q = 2, half = 64, fc = 0.9375 * 0.5 / 2, Kaiser beta = 8.95926, scaled to sum(h) = 1, in double on the host;
+ * T[n] = rint(32768 h[n]).  sum(T) = 32766, max(T) = T[64] = 15360, sum |T| = 69558, ten taps are 0, T[n] = T[128 - n]; no
+ * 32768 h[n] lies within 0.003 of a rounding tie, so two double designs cannot disagree.  Within +0.002 / -0.112 dB up to
+ * 3500 Hz, at least 70 dB down from 4500 Hz on (-70.3 dB at 8 kHz: the even and the odd taps sum to 16378 and 16388).
+ * gtcrn_batch_phone_taps (host only) returns 129 and fills h_taps exactly as the kernel uses it.
+ *
+ * Per row, a source row r of L floats, J = ceil(L / 2):
+ *   1. p_i = clip(rint(32768 r_i), -32768, 32767): the _pcm16 rounding, half to even.
+ *   2. v_j = sat16((sum_i p_i T[2j - i + 64] + 2^14) >> 15), j < J, over 0 <= i < L with the tap index in 0 .. 128: samples
+ *      outside the row are zero (centred, no delay); the shift is arithmetic, so the rounding is half up.
+ *   3. w_j = v_j (codec 0, linear 8 kHz PCM), D_mu[E_mu(v_j)] (codec 1) or D_A[E_A(v_j)] (codec 2): E and D of "G.711 payloads".
+ *   4. z_i = sat16((sum_j w_j T[i - 2j + 64] + 2^13) >> 14), i < L, over 0 <= j < J.
+ *   5. out_i = float(z_i) / 32768 (exact).
+ * sat16 clips to -32768 .. 32767.  Every sum is exact; |sum| <= 69558 * 32768 does not fit 32 bits, and the kernel does not
+ * wrap: 32-bit partial sums over tap subsets whose sum |T| * 32768 < 2^31, joined in 64 bits (csrc/phone.h).
+ *
+ * Phone plan: one 8-byte gtcrn_phone_item {codec, reserved} per row, drawn from the batch plan's Philox4x32-10 with the same
+ * key and counter, block k = 3 (0 and 1 are the batch plan, 2 the reverb plan: none of their draws move), t = its four words:
+ * the row is a phone row iff unit24(t0) < p_phone, and its codec is then the mulhi(t1, popcount(codec_mask))-th set bit of
+ * codec_mask counted from the low end (bit 0 linear, bit 1 mu-law, bit 2 A-law); codec = -1: a wide-band row.
+ * gtcrn_batch_phone_plan runs on the device, reads d_seed_step and never advances it: it goes BEFORE gtcrn_batch_plan in the
+ * stream, as the reverb plan does.  gtcrn_batch_phone_plan_host is the same function body on host pointers.  p_phone outside
+ * 0 .. 1 or codec_mask outside 1 .. 7 -> GTCRN_ERR_ARG.
+ *
+ * gtcrn_batch_phone: for a phone row, noisy = steps 1 - 5 of the source noisy row; clean = steps 1, 2, 4, 5 of the source clean
+ * row with target = 0 ("narrow": the same band, no codec -- a mask model cannot restore a band its input does not have) or the
+ * source clean row, copied, with target = 1 ("wide").  A row with codec = -1 is copied to both outputs bit for bit; a plan
+ * entry outside -1 .. 2 counts as -1.  d_src_clean and d_clean may both be NULL (noisy only).  d_records[b] = {codec,
+ * saturated_down, saturated_up, reserved}: the counts of sat16 clips in steps 2 and 4 of the noisy row (0 for a wide-band row).
+ * Asynchronous on `stream`, allocates nothing, capturable: a small launch that writes the records and one launch over (row,
+ * chunk, side), a workgroup per gtcrn_batch_phone_chunk() consecutive outputs, the 128-sample halo recomputed.  GTCRN_ERR_ARG
+ * before any launch: B <= 0, L <= 0 or L >= 2^31, a null row buffer, plan or records, one of the clean pair NULL and the other
+ * not, a stride below L, target outside {0, 1}, a misaligned pointer, and a source range that overlaps a destination range
+ * (the halo reads make in-place use a race).  A NaN or Inf in one source row leaves that row's output and record unspecified
+ * and changes no bit of any other row.  No load falls outside [0, L) of a row, whatever the plan holds.
+ * gtcrn_batch_phone_host: the same arguments on host pointers, no device and no stream; it runs the very functions the kernel
+ * compiles (csrc/phone.h), as gtcrn_batch_plan_host does for the plan.
+ *
+ * Out of scope: a 300 Hz high-pass or an IRS send / receive characteristic; other codecs; packet loss and jitter; a channel in
+ * front of the mix (speech through the phone, noise added after); corpora at 8 kHz; a per-row target. */
+#define GTCRN_PHONE_TAPS 129
+typedef struct { int codec, reserved; } gtcrn_phone_item;                                  /* 8 bytes */
+typedef struct { int codec, saturated_down, saturated_up, reserved; } gtcrn_phone_record;  /* 16 bytes */
+int gtcrn_batch_phone_taps(int *h_taps /* [129] */);
+int gtcrn_batch_phone_chunk(void);
+int gtcrn_batch_phone_plan(float p_phone, int codec_mask, int B, long item0, const unsigned long long *d_seed_step,
+                           gtcrn_phone_item *d_plan, void *stream);
+int gtcrn_batch_phone_plan_host(float p_phone, int codec_mask, int B, long item0, const unsigned long long *h_seed_step,
+                                gtcrn_phone_item *h_plan);
+int gtcrn_batch_phone(const float *d_src_noisy, long src_noisy_stride, const float *d_src_clean, long src_clean_stride,
+                      const gtcrn_phone_item *d_plan, int B, long L, float *d_noisy, long noisy_stride, float *d_clean,
+                      long clean_stride, int target, gtcrn_phone_record *d_records, void *stream);
+int gtcrn_batch_phone_host(const float *h_src_noisy, long src_noisy_stride, const float *h_src_clean, long src_clean_stride,
+                           const gtcrn_phone_item *h_plan, int B, long L, float *h_noisy, long noisy_stride, float *h_clean,
+                           long clean_stride, int target, gtcrn_phone_record *h_records);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
