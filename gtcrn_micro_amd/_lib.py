@@ -225,6 +225,14 @@ def lib():
     L.gtcrn_score_debug.argtypes = [_vp, ci, ci, _vp, cl, _vp]
     L.gtcrn_score_timing.argtypes = [_vp, ci]
     L.gtcrn_score_timing_read.argtypes = [_vp, ci, ctypes.c_char_p, ci, _c_f32p]
+    L.gtcrn_score_ext_workspace_bytes.restype = ctypes.c_size_t
+    L.gtcrn_score_ext_workspace_bytes.argtypes = [ci, cl]
+    L.gtcrn_score_ext.argtypes = [_vp, _vp, cl, _vp, cl, _vp, cl, ci, ci, _vp, _vp, _vp]
+    L.gtcrn_score_segsnr_frames.restype = cl
+    L.gtcrn_score_segsnr_frames.argtypes = [cl]
+    L.gtcrn_score_segsnr_window.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.gtcrn_score_ext_stages.argtypes = []
+    L.gtcrn_score_ext_timing_read.argtypes = [_vp, ci, ctypes.c_char_p, ci, _c_f32p]
     # training batches from a resident corpus (an earlier library has none of these: data.BatchSource then fails at its creation)
     if hasattr(L, "gtcrn_batch_plan"):
         L.gtcrn_batch_plan.argtypes = [_vp, ci, _vp, ci, ci, cl, cl, ci, cf, cf, cf, cf, _vp, _vp, ci, _vp, _vp]
@@ -1739,6 +1747,8 @@ class Resampler:
 
 SCORE_BITS = {"sdr": 1, "sisnr": 2, "stoi": 4}
 SCORE_STAGES = 6
+SCORE_EXT_BITS = dict(SCORE_BITS, estoi=8, segsnr=16)
+SCORE_EXT_SEGS_PER_WG = 8      # ESTOI segments per workgroup (csrc/metrics.h: SX_SEGS_PER_WG), for the tests' edge lengths
 
 
 def score_taps():
@@ -1774,12 +1784,15 @@ class Scorer:
         self._h = h
         self._ws = {}          # (B, L) -> workspace
         self._captured = set()
+        self._ws_ext = {}      # the same two for score_ext
+        self._captured_ext = set()
 
     def close(self):
         if getattr(self, "_h", None):
             lib().gtcrn_scorer_destroy(self._h)
             self._h = None
             self._ws = {}
+            self._ws_ext = {}
 
     def __del__(self):
         try:
@@ -1857,6 +1870,61 @@ class Scorer:
         return {"sdr": rec[:, 0], "sisnr": rec[:, 1], "stoi": rec[:, 2], "kept_frames": counts[:, 0],
                 "segments": counts[:, 1], "records": rec}
 
+    def ext_workspace_bytes(self, B, L):
+        n = int(lib().gtcrn_score_ext_workspace_bytes(int(B), int(L)))
+        if n == 0:
+            raise GtcrnError(lib().gtcrn_last_error().decode())
+        return n
+
+    def score_ext(self, ref, inf, lengths=None, what=("sdr", "sisnr", "stoi", "estoi", "segsnr"), out=None):
+        """score() with ESTOI and segmental SNR (gtcrn_score_ext; "scores, extended" in include/gtcrn_micro_hip.h).  Same
+        ref, inf and lengths.  what: names out of "sdr", "sisnr", "stoi", "estoi", "segsnr".  out (optional): a contiguous
+        (B,8) float64 tensor that receives the 64-byte records.  Returns score()'s keys plus float64 "estoi", "segsnr" and
+        int32 "segsnr_frames", all views of "records"; with what out of score()'s three, columns 0 .. 3 are score()'s
+        record bit for bit and the rest is 0.  Asynchronous on the current stream; nothing is copied to the host."""
+        import torch
+        r2, y2 = self._rows(ref, "ref"), self._rows(inf, "inf")
+        if r2.shape != y2.shape:
+            raise GtcrnError(f"ref {tuple(ref.shape)} and inf {tuple(inf.shape)} must have one shape")
+        B, L = r2.shape
+        bits = 0
+        for name in ((what,) if isinstance(what, str) else what):
+            if name not in SCORE_EXT_BITS:
+                raise GtcrnError(f"unknown score {name!r}: choose from {sorted(SCORE_EXT_BITS)}")
+            bits |= SCORE_EXT_BITS[name]
+        lens = None
+        if lengths is not None:
+            lens = torch.as_tensor(lengths).reshape(-1)
+            if lens.numel() != B:
+                raise GtcrnError(f"lengths must hold {B} entries, got {lens.numel()}")
+            if not lens.is_cuda and (int(lens.min()) < 0 or int(lens.max()) > L):
+                raise GtcrnError(f"every length must lie in [0, L={L}]")
+            lens = lens.to(device=r2.device, dtype=torch.int32).contiguous()
+        if out is None:
+            rec = torch.empty((B, 8), device=r2.device, dtype=torch.float64)
+        else:
+            rec = out
+            if (not isinstance(rec, torch.Tensor) or rec.device != r2.device or rec.dtype != torch.float64
+                    or tuple(rec.shape) != (B, 8) or not rec.is_contiguous()):
+                raise GtcrnError(f"out must be a contiguous float64 tensor of shape ({B}, 8) on the inputs' device")
+        ws = None
+        if bits & 28:
+            ws = self._ws_ext.get((B, L))
+            if ws is None:
+                free = [k for k in self._ws_ext if k not in self._captured_ext]
+                if len(free) >= 8:          # as score(): keep the eight most recent shapes
+                    self._ws_ext.pop(free[0])
+                ws = self._ws_ext[(B, L)] = torch.empty(self.ext_workspace_bytes(B, L), device=r2.device, dtype=torch.uint8)
+        if ws is not None and torch.cuda.is_current_stream_capturing():
+            self._captured_ext.add((B, L))  # a graph holds this workspace's address: never dropped
+        with torch.cuda.device(r2.device):
+            _check(lib().gtcrn_score_ext(self._h, r2.data_ptr(), max(r2.stride(0), L), y2.data_ptr(), max(y2.stride(0), L),
+                                         lens.data_ptr() if lens is not None else None, L, B, bits, rec.data_ptr(),
+                                         ws.data_ptr() if ws is not None else None, _stream_ptr()))
+        ints = rec.view(torch.int32)
+        return {"sdr": rec[:, 0], "sisnr": rec[:, 1], "stoi": rec[:, 2], "kept_frames": ints[:, 6], "segments": ints[:, 7],
+                "estoi": rec[:, 4], "segsnr": rec[:, 5], "segsnr_frames": ints[:, 12], "records": rec}
+
     def debug(self, which, b=0):
         """Test hook (gtcrn_score_debug; synchronises): one intermediate of row b of the most recent call with STOI as a
         float32 tensor: 0 the 10 kHz ref, 1 frame energies in dB, 2 the keep mask, 3 / 4 the ref / inf envelopes (15, M)."""
@@ -1878,6 +1946,15 @@ class Scorer:
         for i in range(SCORE_STAGES):
             name, ms = ctypes.create_string_buffer(64), ctypes.c_float()
             _check(lib().gtcrn_score_timing_read(self._h, i, name, 64, ctypes.byref(ms)))
+            res[name.value.decode()] = float(ms.value)
+        return res
+
+    def ext_timing_read(self):
+        """timing_read() for the most recent score_ext (gtcrn_score_ext_timing_read; timing(True) arms both)."""
+        res = {}
+        for i in range(lib().gtcrn_score_ext_stages()):
+            name, ms = ctypes.create_string_buffer(64), ctypes.c_float()
+            _check(lib().gtcrn_score_ext_timing_read(self._h, i, name, 64, ctypes.byref(ms)))
             res[name.value.decode()] = float(ms.value)
         return res
 

@@ -1,4 +1,4 @@
-// metrics.h -- launch interface of metrics.hip: SDR, SI-SNR and STOI of (clean, enhanced) pairs on the device
+// metrics.h -- launch interface of metrics.hip: SDR, SI-SNR, STOI, ESTOI and segmental SNR of (clean, enhanced) pairs on the device
 // ("scores" in include/gtcrn_micro_hip.h).  metrics_host.cpp designs the tables and checks the arguments.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,6 +55,37 @@ struct ScorePlan {
 
 // The launches of one call, in stream order.  ev (optional): SC_STAGES + 1 events recorded around them.
 int launch_score(const ScorePlan& p, hipStream_t s, hipEvent_t* ev);
+
+// ---- gtcrn_score_ext: the same launches, then ESTOI, segmental SNR and the 64-byte record
+constexpr int SX_STAGES = SC_STAGES + 3;                       // launches of one gtcrn_score_ext with everything asked for
+constexpr int SX_FRAME = 480, SX_HOP = 120;                    // segmental SNR: 30 ms frames every 7.5 ms at 16 kHz
+constexpr int SX_SEGS_PER_WG = 8;                              // ESTOI segments per workgroup (two per wave)
+constexpr int SX_RUN = 32;                                     // segmental-SNR frames per workgroup
+
+struct ScoreExtRecord {                // == gtcrn_score_ext_record
+    ScoreRecord base;
+    double estoi, segsnr;
+    int segsnr_frames, zero[3];
+};
+
+__host__ __device__ inline long score_segsnr_frames_of(long n) { return n >= SX_FRAME ? (n - SX_FRAME) / SX_HOP + 1 : 0; }
+
+// The ext workspace: B 32-byte records (what the six kernels above write), then B clip slices of clip_bytes each; a slice
+// is the ScoreLayout slice followed by the clip's d_s (o_ds) and per-frame v (o_v), both double.
+struct ScoreExtPlan {
+    ScorePlan base;                    // out = the records at the head of the workspace, ws behind them, what & 7,
+                                       // lay.clip_bytes = the ext slice
+    int what = 0;                      // all five bits
+    long o_ds = 0, o_v = 0;
+    long max_segments = 0, max_frames = 0;   // S and F of an L-sample clip
+    const double* w480 = nullptr;      // the segmental-SNR window (device)
+    ScoreExtRecord* out = nullptr;
+};
+ScoreExtPlan score_ext_layout(long L);     // base.lay, o_ds, o_v, max_segments, max_frames; the rest left empty
+inline size_t score_ext_bytes(int B, long L) { return (size_t)B * (sizeof(ScoreRecord) + (size_t)score_ext_layout(L).base.lay.clip_bytes); }
+// ev (optional): SX_STAGES + 1 events
+int launch_score_ext(const ScoreExtPlan& p, hipStream_t s, hipEvent_t* ev);
+const char* score_ext_stage_name(int i);
 // test hook: n values of a clip's workspace as floats (kind 0 = double, 1 = int)
 int launch_score_debug_cvt(const void* src, int kind, float* dst, long n, hipStream_t s);
 const char* score_stage_name(int i);

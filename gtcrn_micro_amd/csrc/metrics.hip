@@ -13,6 +13,12 @@
 // hand-off).  That is what makes a record's bits independent of B, the row, L and the neighbours' lengths.
 // A NaN or Inf stays in its clip: every index comes from the clip's length and from counts of kept frames, never from a
 // sample's value, and every store goes to the clip's own slice.
+//
+// gtcrn_score_ext ("scores, extended") runs the envelope chain and k_score_stoi as they are and adds, under the same rules:
+//   k_score_ext_moments  k_score_moments' body, writing the head of a 64-byte record
+//   k_score_estoi        (8 segments, clip): a 15 x 30 envelope pair per 32-lane half in registers, d_s per segment
+//   k_score_segsnr       (32 frames, clip): both rows' samples of the run staged in LDS once, one wave per frame, v per frame
+//   k_score_ext_finish   one workgroup per clip: the means of d_s and v, and the rest of the record
 #include "metrics.h"
 
 #include <cfloat>
@@ -51,10 +57,10 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
 }
 
 // ---- SDR / SI-SNR (eval_intrusive_metrics.py:74-91): fp32 samples, double sums, residuals formed sample by sample
-__global__ __launch_bounds__(TH) void k_score_moments(ScorePlan p) {
-    __shared__ double sh[TH];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    double sdr = 0.0, sisnr = 0.0;
+// (one body for k_score_moments and k_score_ext_moments, which differ in the record they write)
+__device__ __forceinline__ void clip_moments(const ScorePlan& p, int b, double* sh, double& sdr, double& sisnr) {
+    const int tid = threadIdx.x;
+    sdr = 0.0; sisnr = 0.0;
     if (p.what & 3) {
         const int n = clip_len(p, b);
         const float* r = p.ref + (long)b * p.ref_stride;
@@ -80,6 +86,13 @@ __global__ __launch_bounds__(TH) void k_score_moments(ScorePlan p) {
             sisnr = 10.0 * log10((tt + 1e-8) / (ee + 1e-8));
         }
     }
+}
+
+__global__ __launch_bounds__(TH) void k_score_moments(ScorePlan p) {
+    __shared__ double sh[TH];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double sdr, sisnr;
+    clip_moments(p, b, sh, sdr, sisnr);
     if (tid == 0) {
         ScoreRecord rec;
         rec.sdr = (p.what & 1) ? sdr : 0.0;
@@ -289,6 +302,169 @@ __global__ __launch_bounds__(TH) void k_score_stoi(ScorePlan p) {
     }
 }
 
+// ---- gtcrn_score_ext.  The envelope chain and k_score_stoi above run unchanged on p.base (k_score_stoi's 32-byte records
+// go to the head of the ext workspace); the kernels below write SDR / SI-SNR into the 64-byte record, add ESTOI and
+// segmental SNR per segment / frame in the clip's slice, and finish the record.
+
+// k_score_moments with the 64-byte record: SDR and SI-SNR by the same body, everything behind them 0
+__global__ __launch_bounds__(TH) void k_score_ext_moments(ScoreExtPlan p) {
+    __shared__ double sh[TH];
+    const int b = blockIdx.x;
+    double sdr, sisnr;
+    clip_moments(p.base, b, sh, sdr, sisnr);
+    if (threadIdx.x == 0) {
+        ScoreExtRecord rec = {};
+        rec.base.sdr = (p.what & 1) ? sdr : 0.0;
+        rec.base.sisnr = (p.what & 2) ? sisnr : 0.0;
+        p.out[b] = rec;
+    }
+}
+
+// sum over a 32-lane half of the wave in a fixed butterfly; every lane of the half gets the same bits
+// (the four steps inside a row of 16 lanes are DPP moves -- lane ^ 1, lane ^ 2, then the mirror of 8 and of 16 lanes, whose
+// partner lies in the other, already uniform, group -- so that only the last step goes through the LDS crossbar)
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double half_sum(double v) {
+    v += dpp_move<0xB1>(v);      // quad_perm [1, 0, 3, 2]
+    v += dpp_move<0x4E>(v);      // quad_perm [2, 3, 0, 1]
+    v += dpp_move<0x141>(v);     // row_half_mirror
+    v += dpp_move<0x140>(v);     // row_mirror
+    v += __shfl_xor(v, 16, 64);
+    return v;
+}
+
+// ESTOI: one segment per 32-lane half, one frame column per lane (lanes 30, 31 of a half and halves without a segment hold
+// zeros, which every sum ignores); the 15 x 30 pair stays in registers.  d_s depends on nothing but the segment.
+__global__ __launch_bounds__(SX_SEGS_PER_WG * 32) void k_score_estoi(ScoreExtPlan p) {
+    const int b = blockIdx.y, tid = threadIdx.x, t = tid & 31;
+    char* ws = clip_ws(p.base, b);
+    const int M = reinterpret_cast<const int*>(ws)[SC_H_M];
+    const int S = M >= SC_SEG ? M - SC_SEG + 1 : 0;
+    const int s = blockIdx.x * SX_SEGS_PER_WG + (tid >> 5);
+    if (blockIdx.x * SX_SEGS_PER_WG >= S) return;                // (workgroup-uniform)
+    const bool live = s < S && t < SC_SEG;                       // s + t <= S - 1 + 29 = M - 1
+    const float* er = reinterpret_cast<const float*>(ws + p.base.lay.o_env);
+    const float* ei = er + (long)SC_BANDS * p.base.lay.env_stride;
+    double x[SC_BANDS], y[SC_BANDS];
+#pragma unroll
+    for (int j = 0; j < SC_BANDS; ++j) {
+        x[j] = live ? (double)er[(long)j * p.base.lay.env_stride + s + t] : 0.0;
+        y[j] = live ? (double)ei[(long)j * p.base.lay.env_stride + s + t] : 0.0;
+    }
+    // rows: a band's 30 values lose their mean and are divided by (their norm + EPS).  A double division costs some
+    // forty instructions, so a denominator shared by many values is inverted once (1 / 30 and 1 / 15 are constants).
+    constexpr double INV_SEG = 1.0 / (double)SC_SEG, INV_BANDS = 1.0 / (double)SC_BANDS;
+#pragma unroll
+    for (int j = 0; j < SC_BANDS; ++j) {
+        const double mx = half_sum(x[j]) * INV_SEG, my = half_sum(y[j]) * INV_SEG;
+        const double xc = live ? x[j] - mx : 0.0, yc = live ? y[j] - my : 0.0;
+        const double ix = 1.0 / (sqrt(half_sum(xc * xc)) + SC_EPS), iy = 1.0 / (sqrt(half_sum(yc * yc)) + SC_EPS);
+        x[j] = xc * ix;
+        y[j] = yc * iy;
+    }
+    // columns: a frame's 15 values, the same way, in the lane; sum (x / nx) (y / ny) = (sum x y) / (nx ny)
+    double mx = 0.0, my = 0.0;
+#pragma unroll
+    for (int j = 0; j < SC_BANDS; ++j) { mx += x[j]; my += y[j]; }
+    mx *= INV_BANDS; my *= INV_BANDS;
+    double nx = 0.0, ny = 0.0, d = 0.0;
+#pragma unroll
+    for (int j = 0; j < SC_BANDS; ++j) { x[j] -= mx; y[j] -= my; nx += x[j] * x[j]; ny += y[j] * y[j]; d += x[j] * y[j]; }
+    d /= (sqrt(nx) + SC_EPS) * (sqrt(ny) + SC_EPS);
+    d = half_sum(live ? d : 0.0);
+    if (t == 0 && s < S) reinterpret_cast<double*>(ws + p.o_ds)[s] = d / (double)SC_SEG;
+}
+
+// Segmental SNR: a workgroup stages the samples of its SX_RUN consecutive frames of both rows once, a wave takes every
+// fourth frame: lane i holds samples i, i + 64, ... of the frame (and their window values, the same for every frame).
+constexpr int SX_WAVES = 4;
+constexpr int SX_SPAN = (SX_RUN - 1) * SX_HOP + SX_FRAME;         // samples a run reads
+constexpr int SX_PER_LANE = (SX_FRAME + 63) / 64;
+__global__ __launch_bounds__(SX_WAVES * 64) void k_score_segsnr(ScoreExtPlan p) {
+    __shared__ float rs[SX_SPAN];
+    __shared__ float ys[SX_SPAN];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = clip_len(p.base, b);
+    const int F = (int)score_segsnr_frames_of(n);
+    const int f0 = blockIdx.x * SX_RUN;
+    if (f0 >= F) return;                                         // (workgroup-uniform)
+    const float* r = p.base.ref + (long)b * p.base.ref_stride;
+    const float* y = p.base.inf + (long)b * p.base.inf_stride;
+    const int i0 = f0 * SX_HOP;
+    for (int i = tid; i < SX_SPAN; i += SX_WAVES * 64) {         // a frame that exists reads below n; the rest is never used
+        const bool in = i0 + i < n;
+        rs[i] = in ? r[i0 + i] : 0.0f;
+        ys[i] = in ? y[i0 + i] : 0.0f;
+    }
+    double w[SX_PER_LANE];
+#pragma unroll
+    for (int k = 0; k < SX_PER_LANE; ++k) w[k] = lane + 64 * k < SX_FRAME ? p.w480[lane + 64 * k] : 0.0;
+    __syncthreads();
+    double* v = reinterpret_cast<double*>(clip_ws(p.base, b) + p.o_v);
+    for (int q = wv; q < SX_RUN; q += SX_WAVES) {
+        const int f = f0 + q;
+        if (f >= F) break;                                       // (wave-uniform; no workgroup barrier below)
+        double num = 0.0, den = 0.0;
+#pragma unroll
+        for (int k = 0; k < SX_PER_LANE; ++k) {
+            const int i = lane + 64 * k;
+            if (i < SX_FRAME) {
+                const double rv = (double)rs[q * SX_HOP + i], e = rv - (double)ys[q * SX_HOP + i];
+                const double a = w[k] * rv, c = w[k] * e;
+                num += a * a; den += c * c;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o, 64); den += __shfl_xor(den, o, 64); }
+        if (lane == 0) {
+            const double db = 10.0 * log10(num / (den + SC_EPS) + SC_EPS);
+            v[f] = db < -10.0 ? -10.0 : db > 35.0 ? 35.0 : db;   // (a NaN stays a NaN)
+        }
+    }
+}
+
+// Finish: one workgroup per clip sums its d_s and its v (a thread's strided partial, then the tree) and writes the record.
+__global__ __launch_bounds__(TH) void k_score_ext_finish(ScoreExtPlan p) {
+    __shared__ double sh[TH];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const char* ws = clip_ws(p.base, b);
+    int K = 0, S = 0, F = 0;
+    double estoi = 0.0, segsnr = 0.0;
+    if (p.what & 12) {
+        const int* h = reinterpret_cast<const int*>(ws);
+        const int M = h[SC_H_M];
+        K = h[SC_H_K];
+        S = M >= SC_SEG ? M - SC_SEG + 1 : 0;
+    }
+    if (p.what & 8) {
+        estoi = 1e-5;
+        if (S > 0) {
+            const double* d = reinterpret_cast<const double*>(ws + p.o_ds);
+            double part = 0.0;
+            for (int s = tid; s < S; s += TH) part += d[s];
+            estoi = block_sum(part, sh) / (double)S;
+        }
+    }
+    if (p.what & 16) {
+        F = (int)score_segsnr_frames_of(clip_len(p.base, b));
+        const double* v = reinterpret_cast<const double*>(ws + p.o_v);
+        double part = 0.0;
+        for (int f = tid; f < F; f += TH) part += v[f];
+        segsnr = block_sum(part, sh) / (double)F;                // F = 0: 0 / 0 = NaN, as SDR for n = 0
+    }
+    if (tid == 0) {                                              // (k_score_ext_moments wrote SDR, SI-SNR and the zeros)
+        ScoreExtRecord* rec = p.out + b;
+        if (p.what & 4) rec->base.stoi = p.base.out[b].stoi;     // k_score_stoi's 32-byte record in the workspace
+        if (p.what & 12) { rec->base.kept_frames = K; rec->base.segments = S; }
+        rec->estoi = estoi; rec->segsnr = segsnr; rec->segsnr_frames = F;
+    }
+}
+
 template <typename T>
 __global__ void k_score_debug_cvt(const T* __restrict__ src, float* __restrict__ dst, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,6 +517,59 @@ int launch_score(const ScorePlan& p, hipStream_t s, hipEvent_t* ev) {
     } else if (ev) {
         for (int i = 2; i <= SC_STAGES; ++i) mark(i);
     }
+    return (int)hipGetLastError();
+}
+
+ScoreExtPlan score_ext_layout(long L) {
+    auto up = [](long bytes) { return (bytes + 63) & ~63L; };
+    ScoreExtPlan x;
+    x.base.lay = score_layout(L);
+    const long M = x.base.lay.nfr > 1 ? x.base.lay.nfr - 1 : 0;
+    x.max_segments = M >= SC_SEG ? M - SC_SEG + 1 : 0;
+    x.max_frames = score_segsnr_frames_of(L);
+    long o = x.base.lay.clip_bytes;
+    x.o_ds = o;  o += up((x.max_segments + 1) * (long)sizeof(double));
+    x.o_v = o;   o += up((x.max_frames + 1) * (long)sizeof(double));
+    x.base.lay.clip_bytes = o;
+    return x;
+}
+
+const char* score_ext_stage_name(int i) {
+    static const char* const names[SX_STAGES] = {"k_score_ext_moments", "k_score_resample", "k_score_energy", "k_score_mask", "k_score_env",
+                                                 "k_score_stoi", "k_score_estoi", "k_score_segsnr", "k_score_ext_finish"};
+    return i >= 0 && i < SX_STAGES ? names[i] : "";
+}
+
+int launch_score_ext(const ScoreExtPlan& x, hipStream_t s, hipEvent_t* ev) {
+    auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], s); };
+    const ScorePlan& p = x.base;
+    const unsigned B = (unsigned)p.B;
+    mark(0);
+    hipLaunchKernelGGL(k_score_ext_moments, dim3(B), dim3(TH), 0, s, x);
+    mark(1);
+    const long n10 = p.lay.n10, nfr = p.lay.nfr, M = nfr > 1 ? nfr - 1 : 0;
+    if (x.what & 12) {
+        hipLaunchKernelGGL(k_score_resample, dim3((unsigned)((n10 + TH - 1) / TH), B, 2), dim3(TH), 0, s, p);
+        mark(2);
+        if (nfr > 0) hipLaunchKernelGGL(k_score_energy, dim3((unsigned)((nfr + EN_FRAMES - 1) / EN_FRAMES), B), dim3(TH), 0, s, p);
+        mark(3);
+        hipLaunchKernelGGL(k_score_mask, dim3(B), dim3(TH), 0, s, p);
+        mark(4);
+        if (M > 0) hipLaunchKernelGGL(k_score_env, dim3((unsigned)((M + ENV_WAVES - 1) / ENV_WAVES), B, 2), dim3(ENV_WAVES * 64), 0, s, p);
+    } else {
+        mark(2); mark(3); mark(4);
+    }
+    mark(5);
+    if (x.what & 4) hipLaunchKernelGGL(k_score_stoi, dim3(B), dim3(TH), 0, s, p);
+    mark(6);
+    if ((x.what & 8) && x.max_segments > 0)
+        hipLaunchKernelGGL(k_score_estoi, dim3((unsigned)((x.max_segments + SX_SEGS_PER_WG - 1) / SX_SEGS_PER_WG), B), dim3(SX_SEGS_PER_WG * 32), 0, s, x);
+    mark(7);
+    if ((x.what & 16) && x.max_frames > 0)
+        hipLaunchKernelGGL(k_score_segsnr, dim3((unsigned)((x.max_frames + SX_RUN - 1) / SX_RUN), B), dim3(SX_WAVES * 64), 0, s, x);
+    mark(8);
+    if (x.what & 28) hipLaunchKernelGGL(k_score_ext_finish, dim3(B), dim3(TH), 0, s, x);
+    mark(9);
     return (int)hipGetLastError();
 }
 

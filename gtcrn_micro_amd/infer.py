@@ -24,7 +24,8 @@ checkpoint, length-matched to its clean reference (zero-pad / crop, ``:98-102``)
   ``SDR.scp`` / ``SISNR.scp`` / ``STOI.scp`` (``uid value``) and ``RESULTS.txt`` (``METRIC: %.4f``, nan-mean) into the
   enhanced folder in that script's format and in the order of ``inf.scp``.  There is no PESQ line.  The clean
   files are read by the launching thread, which blocks once per batch: the pipeline overlaps less with the flag on.
-  Only 16 kHz clips are scored; the others are listed in ``RESULTS.txt`` as skipped.
+  Only 16 kHz clips are scored; the others are listed in ``RESULTS.txt`` as skipped.  ``--score-ext`` implies it and adds
+  ESTOI and segmental SNR (``gtcrn_score_ext``): ``ESTOI.scp``, ``SSNR.scp`` and ``ESTOI:`` / ``SSNR:`` lines behind the others.
 
     python -m gtcrn_micro_amd.infer --noisy-dir N --clean-dir C --enh-dir E --checkpoint best_model_dns3.tar
 """
@@ -159,6 +160,7 @@ def merge_scp(enh_dir, world):
 
 
 SCORE_METRICS = (("SDR", "sdr"), ("SISNR", "sisnr"), ("STOI", "stoi"))
+SCORE_EXT_METRICS = SCORE_METRICS + (("ESTOI", "estoi"), ("SSNR", "segsnr"))     # --score-ext
 
 
 class _FolderScores:
@@ -169,9 +171,10 @@ class _FolderScores:
     and uploaded (pageable) by the thread that launches the batches, so with --score that thread blocks once per batch
     and the pipeline's overlap is reduced; reading them in the reader pool into pinned slots is the follow-up."""
 
-    def __init__(self, device):
+    def __init__(self, device, ext=False):
         from . import _lib
         self.scorer = _lib.Scorer(device)
+        self.metrics = SCORE_EXT_METRICS if ext else SCORE_METRICS     # ext: Scorer.score_ext, ESTOI and SSNR as well
         self.pending = []        # (item indices, uids, records on the device)
         self.skipped = []        # (uid, why)
 
@@ -204,7 +207,10 @@ class _FolderScores:
         inf = torch.zeros((len(keep), Lc), device=dev)
         inside = torch.arange(m, device=dev)[None, :] < valid[:, None]
         inf[:, :m] = torch.where(inside, rows[:, :m].to(torch.float32) / 32768.0, torch.zeros((), device=dev))
-        res = self.scorer.score(ref, inf, lengths=n_clean)
+        if self.metrics is SCORE_METRICS:
+            res = self.scorer.score(ref, inf, lengths=n_clean)
+        else:
+            res = self.scorer.score_ext(ref, inf, lengths=n_clean)
         self.pending.append(([sel[j] for j in keep], [items[sel[j]][0].split(".wav")[0] for j in keep], res["records"]))
 
     def rows(self):
@@ -214,19 +220,23 @@ class _FolderScores:
         for idx, uids, rec in self.pending:
             r = rec.cpu().numpy()
             for k, uid in enumerate(uids):
-                out.append((idx[k], uid, {"SDR": float(r[k, 0]), "SISNR": float(r[k, 1]), "STOI": float(r[k, 2])}))
+                sc = {"SDR": float(r[k, 0]), "SISNR": float(r[k, 1]), "STOI": float(r[k, 2])}
+                if self.metrics is not SCORE_METRICS:
+                    sc.update(ESTOI=float(r[k, 4]), SSNR=float(r[k, 5]))
+                out.append((idx[k], uid, sc))
         return [(uid, sc) for _, uid, sc in sorted(out, key=lambda t: t[0])]
 
 
-def write_scores(enh_dir, rows, skipped, suffix=""):
+def write_scores(enh_dir, rows, skipped, suffix="", metrics=SCORE_METRICS):
     """SDR.scp / SISNR.scp / STOI.scp (`uid value` per line) and RESULTS.txt (`METRIC: %.4f`, nan-mean), the format of
-    eval_intrusive_metrics.py:124-138 without its PESQ line; clips that were not scored are listed behind the means."""
-    for metric, _ in SCORE_METRICS:
+    eval_intrusive_metrics.py:124-138 without its PESQ line; clips that were not scored are listed behind the means.
+    metrics=SCORE_EXT_METRICS adds ESTOI.scp / SSNR.scp and their two lines behind STOI's."""
+    for metric, _ in metrics:
         with open(os.path.join(enh_dir, f"{metric}.scp{suffix}"), "w") as f:
             for uid, sc in rows:
                 f.write(f"{uid} {sc[metric]!r}\n")
     with open(os.path.join(enh_dir, "RESULTS.txt" + suffix), "w") as f:
-        for metric, _ in SCORE_METRICS:
+        for metric, _ in metrics:
             vals = np.array([sc[metric] for _, sc in rows], np.float64)
             mean = float(np.nanmean(vals)) if np.any(~np.isnan(vals)) else float("nan")
             f.write(f"{metric}: {mean:.4f}\n")
@@ -234,17 +244,17 @@ def write_scores(enh_dir, rows, skipped, suffix=""):
             f.write(f"SKIPPED: {uid} ({why}; only 16 kHz clips are scored)\n")
 
 
-def merge_scores(enh_dir, world):
+def merge_scores(enh_dir, world, metrics=SCORE_METRICS):
     """The per-rank score files -> SDR.scp / SISNR.scp / STOI.scp / RESULTS.txt in rank order, as merge_scp does."""
     per_metric = {}
-    for metric, _ in SCORE_METRICS:
+    for metric, _ in metrics:
         lines = []
         for r in range(world):
             with open(os.path.join(enh_dir, f"{metric}.scp.rank{r}")) as f:
                 lines += [ln.split() for ln in f if ln.strip()]
         per_metric[metric] = lines
-    uids = [uid for uid, _ in per_metric[SCORE_METRICS[0][0]]]
-    rows = [(uid, {m: float(per_metric[m][k][1]) for m, _ in SCORE_METRICS}) for k, uid in enumerate(uids)]
+    uids = [uid for uid, _ in per_metric[metrics[0][0]]]
+    rows = [(uid, {m: float(per_metric[m][k][1]) for m, _ in metrics}) for k, uid in enumerate(uids)]
     skipped = []
     for r in range(world):
         with open(os.path.join(enh_dir, f"RESULTS.txt.rank{r}")) as f:
@@ -252,7 +262,7 @@ def merge_scores(enh_dir, world):
                 if ln.startswith("SKIPPED: "):
                     uid, why = ln[len("SKIPPED: "):].rstrip("\n").split(" (", 1)
                     skipped.append((uid, why.rsplit(";", 1)[0]))
-    write_scores(enh_dir, rows, skipped)
+    write_scores(enh_dir, rows, skipped, metrics=metrics)
 
 
 def _finish_clip(y_row, item, enh_dir):
@@ -270,7 +280,8 @@ def _finish_clip(y_row, item, enh_dir):
 
 
 def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1,
-                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4, atten_lim_db=None, score=False):
+                   barrier=None, pipeline=True, stats=None, stages=3, io_threads=4, atten_lim_db=None, score=False,
+                   score_ext=False):
     """barrier: a callable all ranks call once their lists are written (multi-GPU runs; main() passes
     torch.distributed.barrier); rank 0 then merges the per-rank scp files.
 
@@ -287,7 +298,8 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     atten_lim_db: the attenuation limit in dB for every clip (None: off), applied by the iSTFT launch of the same calls
     (Engine.forward_wave's dry_gain) on the 16 kHz path and the other-rate path alike.
     score=True: every batch's (clean, enhanced) pairs are scored on the device behind it (_FolderScores) and the score
-    files are written next to the scp lists (write_scores).
+    files are written next to the scp lists (write_scores).  score_ext=True implies it and adds ESTOI and segmental SNR
+    (Scorer.score_ext; ESTOI.scp, SSNR.scp and their RESULTS.txt lines).
     stats (optional dict) receives: clips, frames, wall_s, frames_per_s, gpu_busy_frac (device time of the kernel
     sequences / wall time, from events), h2d_bytes, d2h_bytes."""
     import queue
@@ -304,7 +316,7 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     dev = f"cuda:{device}"
     beta = None if atten_lim_db is None else _lib.atten_lim_to_gain(atten_lim_db)
     win = torch.hann_window(512).pow(0.5).to(dev)                   # infer.py:65
-    scores = _FolderScores(device) if score else None
+    scores = _FolderScores(device, ext=score_ext) if score or score_ext else None
     names = sorted(f for f in os.listdir(noisy_dir) if f.endswith("wav"))
     lo, hi = shard_range(len(names), world, rank)
     # pass 1 (headers only): pair every clip with its reference, learn the lengths
@@ -542,12 +554,12 @@ def _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
             for uid, p in lst:
                 f.write(f"{uid} {p}\n")
     if scores is not None:
-        write_scores(enh_dir, scores.rows(), sorted(scores.skipped), suffix)
+        write_scores(enh_dir, scores.rows(), sorted(scores.skipped), suffix, scores.metrics)
     return inf_scp, ref_scp
 
 
 def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batch=64, rank=0, world=1, barrier=None,
-                   agree=None, pipeline=True, stats=None, io_threads=4, atten_lim_db=None, score=False):
+                   agree=None, pipeline=True, stats=None, io_threads=4, atten_lim_db=None, score=False, score_ext=False):
     """Counterpart of infer.py:26-119 for a folder (see ``_enhance_shard``): every rank enhances its contiguous shard of
     the sorted file list, then rank 0 merges the per-rank scp lists.
 
@@ -561,7 +573,7 @@ def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
     try:
         result = _enhance_shard(noisy_dir, clean_dir, enh_dir, checkpoint, device, max_batch, rank, world, barrier,
                                 pipeline=pipeline, stats=stats, io_threads=io_threads, atten_lim_db=atten_lim_db,
-                                score=score)
+                                score=score, score_ext=score_ext)
     except Exception as e:           # re-raised below, after the exchange.  NOT BaseException: a KeyboardInterrupt or
         err = e                      # SystemExit must leave at once instead of waiting in a collective first
     all_ok = err is None
@@ -576,8 +588,8 @@ def enhance_folder(noisy_dir, clean_dir, enh_dir, checkpoint, device=0, max_batc
         raise RuntimeError("enhance_folder: another rank failed; its shard is incomplete, the scp lists were not merged")
     if world > 1 and rank == 0 and (agree is not None or barrier is not None):
         merge_scp(enh_dir, world)
-        if score:
-            merge_scores(enh_dir, world)
+        if score or score_ext:
+            merge_scores(enh_dir, world, SCORE_EXT_METRICS if score_ext else SCORE_METRICS)
     return result
 
 
@@ -596,6 +608,8 @@ def main(argv=None):
     ap.add_argument("--score", action="store_true",
                     help="score every (clean, enhanced) pair on the GPU: SDR.scp, SISNR.scp, STOI.scp and RESULTS.txt "
                          "in the enhanced folder (SDR, SI-SNR, STOI; no PESQ)")
+    ap.add_argument("--score-ext", action="store_true",
+                    help="--score plus ESTOI and segmental SNR: ESTOI.scp, SSNR.scp and their lines in RESULTS.txt")
     ap.add_argument("--stats", action="store_true", help="print this rank's throughput / GPU-busy figures as JSON")
     a = ap.parse_args(argv)
     from .sharding import rank_world
@@ -621,7 +635,7 @@ def main(argv=None):
     try:
         st = {} if a.stats else None
         enhance_folder(a.noisy_dir, a.clean_dir, a.enh_dir, a.checkpoint, dev, a.max_batch, rank, world, barrier, agree,
-                       pipeline=not a.serial, stats=st, atten_lim_db=a.atten_lim_db, score=a.score)
+                       pipeline=not a.serial, stats=st, atten_lim_db=a.atten_lim_db, score=a.score, score_ext=a.score_ext)
         if st is not None:
             import json
             print(json.dumps({"rank": rank, **st}), flush=True)

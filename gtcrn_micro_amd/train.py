@@ -255,7 +255,11 @@ def score_batch(clean, enhanced, scorer, lengths=None, what=("sdr", "sisnr", "st
     PESQ -- PESQ is ITU C code and stays the caller's -- so a checkpoint picked by these numbers is picked by another
     criterion than the reference's.  clean, enhanced: (B,L) float32 device tensors at 16 kHz (validate_batch pads / crops
     the enhanced one to the clean length); scorer: a ``_lib.Scorer`` on their device.  Returns Scorer.score's dict of (B,)
-    device tensors; nothing is copied to the host and the call is asynchronous."""
+    device tensors; nothing is copied to the host and the call is asynchronous.  A `what` that names "estoi" or "segsnr"
+    goes to Scorer.score_ext (64-byte records, the two extra keys); any other takes the path above, with the same bits."""
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if "estoi" in names or "segsnr" in names:
+        return scorer.score_ext(clean, enhanced, lengths=lengths, what=names)
     return scorer.score(clean, enhanced, lengths=lengths, what=what)
 
 

@@ -864,6 +864,59 @@ long gtcrn_score_debug(gtcrn_scorer *s, int which, int b, float *d_dst, long cap
 int gtcrn_score_timing(gtcrn_scorer *s, int on);
 int gtcrn_score_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap, float *ms);
 
+/* ---- scores, extended: ESTOI and segmental SNR next to the three above --------------------------------------------------
+ * gtcrn_score_ext is gtcrn_score with a 64-byte record and two more bits in `what`: 8 (ESTOI) and 16 (segmental SNR), so
+ * `what` is a sum out of 1, 2, 4, 8, 16 in 1 .. 31.  Same rows, strides, lengths, refusals (GTCRN_ERR_ARG before any launch)
+ * and properties as gtcrn_score: asynchronous on `stream`, allocates nothing, never synchronises the host, capturable.  Fields
+ * not asked for are written as 0; kept_frames and segments are written when `what` & 12; zero[] is 0.  d_workspace: 16-byte
+ * aligned, gtcrn_score_ext_workspace_bytes(B, L) bytes (B times a function of L alone, not less than
+ * gtcrn_score_workspace_bytes(B, L)); needed when `what` & 28.  With `what` <= 7 bytes 0 .. 31 of each record are bit for bit
+ * what gtcrn_score writes and bytes 32 .. 63 are 0.  gtcrn_score itself is unchanged and keeps refusing `what` > 7.
+ * EPS = 2^-52; samples are read as fp32; everything below is in double.
+ *
+ * ESTOI (Jensen & Taal 2016; the structure of pystoi's stoi(..., extended=True)).  Steps 1 to 5 of STOI above are shared
+ * unchanged: the 10 kHz stage, the keep mask from ref, the overlap-add, the re-framing, the fp32 envelopes env[j, m] of 15
+ * bands, M = K - 1.  With M >= 30 there are S = M - 29 segments; for segment s, X = env_ref[:, s .. s + 29] and
+ * Y = env_inf[:, s .. s + 29] (15 x 30) each go through the same normalisation:
+ *   1. rows: from every band's 30 values their mean is subtracted, then they are divided by (their 2-norm + EPS);
+ *   2. columns of the result: from every frame's 15 values their mean is subtracted, then they are divided by
+ *      (their 2-norm + EPS).
+ * d_s = (1 / 30) sum over j, t of X~[j, t] Y~[j, t]; estoi = (1 / S) sum over s of d_s.  No clipping, no alpha.  M < 30:
+ * estoi = 1e-5 and segments = 0, as STOI.  pystoi adds EPS-scaled random noise before each normalisation to avoid 0 / 0; this
+ * contract has + EPS in the denominators instead.  As for STOI, decimal parity with pystoi is neither claimed nor tested.
+ * (The kernel multiplies by 1 / 30, by 1 / 15 and by the reciprocal of a row's denominator, and divides a column's sum of
+ * products once by the product of its two denominators: roundings of 1e-16, the same for a segment wherever it is computed.)
+ *
+ * Segmental SNR: this library's own stated contract (Hansen-Pellom form), no parity with any package claimed; on the 16 kHz
+ * rows as given, no mean removal.  With n the clip's length: frames of 480 samples start at s = 0, 120, 240, ... with
+ * s + 480 <= n, F = (n - 480) / 120 + 1 of them (integer division) for n >= 480, else 0.
+ * w[i] = 0.5 (1 - cos(2 pi (i + 1) / 481)), i = 0 .. 479, designed in double on the host.  Per frame, with r of ref and y of inf:
+ *     num = sum (w r)^2,  den = sum (w (r - y))^2      (r - y: the difference of the two fp32 samples, formed in double)
+ *     v   = 10 log10(num / (den + EPS) + EPS), clamped to [-10, 35]
+ * segsnr = (1 / F) sum of v, frames in ascending order; segsnr_frames = F.  F = 0: segsnr = NaN, as SDR for n = 0.
+ *
+ * The properties of "scores" hold for the whole 64-byte record: batch invariance (d_s is a function of its segment, v of its
+ * frame, and each is summed by a thread's strided partial and a fixed tree that depend on S / F alone), non-finite input (a
+ * NaN or Inf in one clip changes no bit of another's record and moves no index), silence (estoi = 0 exactly when either
+ * signal is all zero; segsnr = -10 for a zero ref, about 0 for a zero inf, and 35 with estoi about 1 for a signal against
+ * itself).
+ *
+ * Host only, no device: gtcrn_score_segsnr_frames (F for an n-sample clip, n in 0 .. 2^28), gtcrn_score_segsnr_window (the
+ * 480 window values).  gtcrn_score_ext_stages: the launches of a call with everything asked for (9); gtcrn_score_timing(s, 1)
+ * arms gtcrn_score_ext too, and gtcrn_score_ext_timing_read returns launch `stage`'s name and milliseconds of the most recent
+ * gtcrn_score_ext (gtcrn_score_timing_read keeps serving gtcrn_score alone). */
+typedef struct { gtcrn_score_record base;        /* bytes 0 .. 31 */
+                 double estoi, segsnr;           /* 32, 40 */
+                 int segsnr_frames, zero[3]; } gtcrn_score_ext_record;   /* 64 bytes */
+size_t gtcrn_score_ext_workspace_bytes(int B, long L);
+int gtcrn_score_ext(gtcrn_scorer *s, const float *d_ref, long ref_stride, const float *d_inf, long inf_stride,
+                    const int *d_lengths, long L, int B, int what, gtcrn_score_ext_record *d_out, void *d_workspace,
+                    void *stream);
+long gtcrn_score_segsnr_frames(long n);
+int gtcrn_score_segsnr_window(double *h_w480);
+int gtcrn_score_ext_stages(void);
+int gtcrn_score_ext_timing_read(gtcrn_scorer *s, int stage, char *name, int name_cap, float *ms);
+
 /* ---- training batches from a resident corpus ---------------------------------------------------------------------------
  * Replaces DNS3Dataset.__getitem__ + DataLoader + .to(device) (dataloader.py:113-170, train.py:244-250): the training set
  * lives in device memory as int16 and a batch is cut (and, optionally, mixed) where it lies.  No handle, no host state.
