@@ -143,6 +143,10 @@ def lib():
     if hasattr(L, "gtcrn_wave_stream_set_meters"):
         L.gtcrn_wave_stream_set_meters.argtypes = [_vp, _vp]
         L.gtcrn_level_dbov.argtypes = [ctypes.c_double, ctypes.c_double]
+    # gain ramps (an earlier library has neither symbol: only a state asked for with ramp=True fails, at its creation)
+    if hasattr(L, "gtcrn_wave_stream_set_gain_ramp"):
+        L.gtcrn_wave_stream_set_gain_ramp.argtypes = [_vp, _vp]
+        L.gtcrn_gain_ramp_host.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]
     # G.711 payloads (an earlier library has none of these: a G.711 state or converter then fails at its first call)
     if hasattr(L, "gtcrn_packet_stream_step_g711"):
         L.gtcrn_packet_stream_step_g711.argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
@@ -353,6 +357,18 @@ def level_dbov(energy, nsamples):
         return int(fn(float(energy), float(nsamples)))
     e, n = np.broadcast_arrays(np.asarray(energy, np.float64), np.asarray(nsamples, np.float64))
     return np.array([fn(float(a), float(b)) for a, b in zip(e.ravel(), n.ravel())], np.int32).reshape(e.shape)
+
+
+def gain_ramp(p, g):
+    """The 256 dry gains of a block that ramps from `p`, where the stream's last block ended, to `g` (include/
+    gtcrn_micro_hip.h, "gain ramps"): a float32 array from gtcrn_gain_ramp_host, the function the kernel compiles, on the
+    host."""
+    fn = getattr(lib(), "gtcrn_gain_ramp_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no gain ramps")
+    out = np.empty(256, np.float32)
+    _check(fn(float(np.float32(p)), float(np.float32(g)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+    return out
 
 
 def _gains_of(db, n):
@@ -715,7 +731,7 @@ class Engine:
     def wave_state_bytes():
         return int(lib().gtcrn_wave_stream_state_bytes())
 
-    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False):
+    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False, ramp=False):
         """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
         counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
         one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it).  atten_lim_db (a
@@ -723,7 +739,10 @@ class Engine:
         that every step and flush of the state then applies (WaveStreamState.set_atten_lim_db rewrites them).
         meters=True: the state owns ``state.meters``, (n, 4) float32 records {E_dry, E_out, peak, blocks} per stream (the
         header's "level meters"), zeroed here, which every step and flush through the state then updates on the device
-        (WaveStreamState.reset_meters starts a new window, .levels() reads the RFC 6464 levels)."""
+        (WaveStreamState.reset_meters starts a new window, .levels() reads the RFC 6464 levels).
+        ramp=True: the state owns ``state.gain_ramp``, (n,) float32, the gain each stream's last block ended at (the header's
+        "gain ramps"): a later change of the limit is then spread over the next emitted block instead of landing as a
+        step.  It starts equal to ``state.dry_gain``, which is allocated (zeros: no limit) when atten_lim_db is None."""
         import torch
         n = int(nstreams)
         if n < 1:
@@ -742,7 +761,17 @@ class Engine:
             st.set_atten_lim_db(atten_lim_db)
         if meters:
             st.meters = torch.zeros((n, 4), device=win.device, dtype=torch.float32)
+        if ramp:
+            st._new_gain_ramp()
         return st
+
+    def _set_gain_ramp(self, state):
+        """Hands the state's ramp words to the model ahead of a step or flush, or clears the model's pointer for a state
+        without ramps: two states on one engine do not leak into each other."""
+        fn = getattr(lib(), "gtcrn_wave_stream_set_gain_ramp", None)
+        if fn is None:
+            return                                       # (an earlier library: _new_gain_ramp refused, nothing to clear)
+        _check(fn(self._h, None if state.gain_ramp is None else state.gain_ramp.data_ptr()))
 
     def _set_meters(self, state):
         """Hands the state's records to the model ahead of a step or flush, or clears the model's pointer for a state
@@ -803,6 +832,7 @@ class Engine:
         args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
                 out.stride(0), state.n, L // 256)
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_step_pcm16 if pcm else lib().gtcrn_wave_stream_step
@@ -825,6 +855,7 @@ class Engine:
         args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
                 tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n)
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_flush_pcm16 if pcm else lib().gtcrn_wave_stream_flush
@@ -923,6 +954,7 @@ class Engine:
         fn = lib().gtcrn_wave_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step_slots
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m, x.data_ptr(), x.stride(0),
                       out.data_ptr(), out.stride(0), gain, state.window.data_ptr(), _stream_ptr()))
@@ -940,6 +972,7 @@ class Engine:
         fn = lib().gtcrn_wave_stream_flush_slots_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush_slots
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
                       tail.data_ptr() if r else None, tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), gain,
@@ -1021,10 +1054,11 @@ class Engine:
                                            out.data_ptr(), out.stride(0), B, _stream_ptr()))
         return out[0] if wave.dim() == 1 else out
 
-    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None):
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None, ramp=False):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
         resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz); meters: as in
-        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step).  highband (a float or one per stream, each
+        new_wave_state (taken at 16 kHz, per 256-sample block of the wave step); ramp: as in new_wave_state (made at 16 kHz,
+        over one 256-sample block of the wave step).  highband (a float or one per stream, each
         in [0, 1]; fs = 24000, 32000 or 48000; None: off, the plain calls): the header's "high band" -- the state gets
         ``hb`` (N, rate_stream_hb_state_bytes/4) and the per-stream gains ``hb_gain`` that every step then applies
         (RateStreamState.set_highband_gain rewrites them in place)."""
@@ -1043,6 +1077,8 @@ class Engine:
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
         st.meters = ws.meters
+        if ramp:
+            st._new_gain_ramp()
         return st
 
     def rate_stream_reserve(self, state, nhops):
@@ -1081,6 +1117,7 @@ class Engine:
         args = (self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
                 state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             if state.hb is not None:
                 fn = lib().gtcrn_rate_stream_step_hb_pcm16 if pcm else lib().gtcrn_rate_stream_step_hb
@@ -1105,13 +1142,14 @@ class Engine:
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
     def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None,
-                         highband=None):
+                         highband=None, ramp=False):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
         needs is reserved here.  atten_lim_db: as in new_wave_state; the handle keeps the gains' address
         (gtcrn_packet_stream_set_dry_gain), so a captured period follows later changes of the gains.  meters: as in
         new_wave_state (taken at 16 kHz, per 256-sample block of the wave step; a call without a hop leaves them alone).
+        ramp: as in new_wave_state (made at 16 kHz over one block of the wave step; a call without a hop leaves the words alone).
         g711: "ulaw", "alaw" or None -- the law of the torch.uint8 rows packet_stream_step then takes and returns (RTP payload
         types 0 / 8; float32 and int16 rows stay legal); without a law uint8 rows are refused.
         highband (a float or one per stream, each in [0, 1]; fs = 24000, 32000 or 48000 and a latency that is whole at fs;
@@ -1139,6 +1177,8 @@ class Engine:
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
         st.meters = ws.meters
+        if ramp:
+            st._new_gain_ramp()
         return st
 
     def packet_stream_reset(self, state, lo=0, hi=None):
@@ -1180,6 +1220,7 @@ class Engine:
             hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         state.last_hops = state.next_hops
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
@@ -1200,12 +1241,12 @@ class Engine:
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
     def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False,
-                              g711=None, highband=None):
+                              g711=None, highband=None, ramp=False):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
         one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db and meters: as in
-        new_wave_state, per SLOT.  g711: as in new_packet_state.  highband: as in new_packet_state, one gain per SLOT;
+        new_wave_state, per SLOT; ramp likewise.  g711: as in new_packet_state.  highband: as in new_packet_state, one gain per SLOT;
         packet_stream_reset_slots then zeroes the named slots' rows of ``hb`` too."""
         import torch
         law = g711_law(g711)
@@ -1233,6 +1274,8 @@ class Engine:
         if atten_lim_db is not None:
             st.set_atten_lim_db(atten_lim_db)
         st.meters = ws.meters
+        if ramp:
+            st._new_gain_ramp()
         return st
 
     def _packet_slot_args(self, state, slots, count):
@@ -1274,6 +1317,7 @@ class Engine:
                   else lib().gtcrn_packet_stream_step_slots_hb)
             hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         self._set_meters(state)
+        self._set_gain_ramp(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
@@ -1396,6 +1440,7 @@ class WaveStreamState:
         self.window = window
         self.dry_gain = None        # (N,) float32 on the device: the attenuation limit's dry gains; None: limit off
         self.meters = None          # (N, 4) float32 on the device: {E_dry, E_out, peak, blocks} per stream; None: no metering
+        self.gain_ramp = None       # (N,) float32 on the device: the dry gain each stream's last block ended at; None: no ramps
 
     @property
     def n(self):
@@ -1411,11 +1456,22 @@ class WaveStreamState:
             raise GtcrnError(f"the dry gains must be a contiguous ({self.n},) float32 tensor on {self.model.device}")
         self.dry_gain = gain
 
-    def set_atten_lim_db(self, db, lo=0, hi=None):
+    def _new_gain_ramp(self):
+        """ramp=True of the state's constructor: the ramp words, equal to the gains (zeros where the state has no limit)."""
+        import torch
+        if not hasattr(lib(), "gtcrn_wave_stream_set_gain_ramp"):
+            raise GtcrnError("this library has no gain ramps")
+        if self.dry_gain is None:
+            self.set_dry_gain(torch.zeros((self.n,), device=self.model.device, dtype=torch.float32))
+        self.gain_ramp = self.dry_gain.clone()
+
+    def set_atten_lim_db(self, db, lo=0, hi=None, snap=False):
         """Sets the attenuation limit of streams lo..hi-1 to `db` dB (None or inf: no limit, 0: bypass; a sequence gives
         one limit per stream of the range): rewrites state.dry_gain[lo:hi] on the device, asynchronously on the current
         stream and, for one value, without any allocation; takes effect at the next emitted block, also under the replay of
-        a captured graph.  A state created without a limit gets its gains (zeros: no limit) at the first call here."""
+        a captured graph.  A state created without a limit gets its gains (zeros: no limit) at the first call here.
+        On a state made with ramp=True the change is spread over the next emitted block of each stream; snap=True also
+        writes state.gain_ramp[lo:hi], so the change lands at once, as it does without ramps."""
         import torch
         hi = self.n if hi is None else int(hi)
         lo = int(lo)
@@ -1428,7 +1484,8 @@ class WaveStreamState:
             self.dry_gain[lo:hi].fill_(g)
         else:
             self.dry_gain[lo:hi].copy_(torch.from_numpy(g), non_blocking=True)
-
+        if snap and self.gain_ramp is not None:
+            self.gain_ramp[lo:hi].copy_(self.dry_gain[lo:hi])
 
     def _metered(self):
         if self.meters is None:

@@ -92,6 +92,7 @@ struct gtcrn_model {
     float* d_rate_a = nullptr;  // 16 kHz hand-offs of gtcrn_rate_stream_step (nstreams x 256 nhops each): k_rate_in -> wave step,
     float* d_rate_b = nullptr;  // wave step -> k_rate_out; sized by gtcrn_rate_stream_reserve
     float* d_meters = nullptr;  // the caller's level-meter records (gtcrn_wave_stream_set_meters); NULL: no metering
+    float* d_ramp = nullptr;    // the caller's gain-ramp words (gtcrn_wave_stream_set_gain_ramp); NULL: gain changes step
     long cap_rate = 0;          // capacity of each in (streams * hops)
     bool debug = false;
     bool debug_keep_fused = false;   // gtcrn_debug_enable(m, 2): phase stamps only -- single-frame steps stay ONE launch
@@ -663,6 +664,20 @@ int gtcrn_wave_stream_set_meters(gtcrn_model* m, float* d_meters) {
     return 0;
 }
 
+// Gain ramps (contract: include/gtcrn_micro_hip.h, "gain ramps"): kept like the meters' address; wave_step hands it to the
+// synthesis launch of a call that has gains.  Nothing is launched or read here.
+int gtcrn_wave_stream_set_gain_ramp(gtcrn_model* m, float* d_ramp) {
+    if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_gain_ramp: null model");
+    m->d_ramp = d_ramp;
+    return 0;
+}
+// the host twin: the 256 gains of a block that ramps from p to g, from the function the kernel compiles
+int gtcrn_gain_ramp_host(float p, float g, float* out256) {
+    if (!out256) return fail(GTCRN_ERR_ARG, "gtcrn_gain_ramp_host: null pointer");
+    for (int i = 0; i < 256; ++i) out256[i] = gtk::gain_ramp_at(p, g, i);
+    return 0;
+}
+
 // RFC 6464 audio level of a window of `nsamples` samples with energy `energy` (full scale 1.0): -dBov rounded to the nearest
 // integer, 0 (loudest) .. 127 (silence).  Host arithmetic only.
 int gtcrn_level_dbov(double energy, double nsamples) {
@@ -689,7 +704,8 @@ int refuse_three_launch_form(const std::string& w, const gtcrn_model* m) {
 }  // namespace
 
 // Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given, metered while
-// the model holds a meters address: the rate, packet and packet-slot forms come through here too) of n rows.
+// the model holds a meters address, ramped when d_gain is given while the model holds a ramp address -- timed in the row of
+// the form it stands in for: the rate, packet and packet-slot forms come through here too) of n rows.
 // Without a table the rows are the n streams of a contiguous state range, nhops hops each; with one (the _slots calls)
 // they are the n = max_active rows it names, one hop.
 extern "C++" template <typename S>
@@ -725,7 +741,7 @@ static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wst
     if (rc) return rc;
     tm.begin(m->d_meters ? K_WAVE_SYNTHESIS_METER : d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
     LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, n, nhops, r, flush, ws, d_win,
-                                             m->d_twid, rows, d_gain, m->d_meters, s));
+                                             m->d_twid, rows, d_gain, m->d_meters, m->d_ramp, s));
     tm.end();
     return 0;
 }

@@ -103,20 +103,34 @@ struct Rows {
     const int* slots = nullptr;
     const int* cnt = nullptr;
 };
+// Gain ramps (contract: include/gtcrn_micro_hip.h, "gain ramps"): the dry gain of sample i = 0..255 of a block that ramps
+// from p, where the stream's last emitted block ended, to g -- fl(p + fl(fl(g - p) * r_i)), r_i = (i + 1) / 256 (exact), and
+// g itself at i == 255 or when p == g.  Three fp32 roundings, never a fused multiply-add (the pragma holds under any
+// -ffp-contract of the including file).  One body for the RAMP instantiations of k_wave_synthesis and for
+// gtcrn_gain_ramp_host.
+__host__ __device__ inline float gain_ramp_at(float p, float g, int i) {
+#pragma clang fp contract(off)
+    if (p == g || i == 255) return g;
+    const float d = g - p;
+    const float s = d * ((float)(i + 1) * 0.00390625f);
+    return p + s;
+}
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
 // wstate (not on flush).  flush = the end-reflected last frame.  gain (optional, device, float[N]): the attenuation limit,
 // mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.  meters (optional,
 // device, 4 floats per stream or slot, 16-byte aligned): the level-meter records, advanced by the METER instantiations, which
-// read `gain` at run time (nullptr or not); nullptr: the launches above.
+// read `gain` at run time (nullptr or not); nullptr: the launches above.  ramp (optional, device, one float per stream or
+// slot, indexed as gain is): the gain ramps -- with gain AND ramp the RAMP instantiations run, which read ramp[idx], ramp the
+// call's first block from it to gain[idx] and store gain[idx] there; without either pointer ramp is not touched.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
                          const float* win, const float* twid, float* spec, Rows rows, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, hipStream_t s);
+                          float* meters, float* ramp, hipStream_t s);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;

@@ -764,6 +764,12 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 // instantiations take the limit as a wave-uniform run-time branch (MIX = false, gain may be null: the plain sample then).
 // wave_sum / wave_max: every lane ends with the same value, the xor butterfly over lane distances 1, 2, 4, 8, 16, 32 in
 // that order (an fp32 add is commutative, so both partners of a step round alike).
+// RAMP (with MIX or METER; gain and ramp both set): the gain ramps (include/gtcrn_micro_hip.h, "gain ramps") -- p = ramp[slot]
+// is the dry gain at which the stream's last emitted block ended.  Both words are the same in every lane (made so for the
+// compiler by a readfirstlane behind hop 0's transform, so `p != g` is a scalar branch and neither load is waited for before
+// the first spectrum is fetched); where they differ, the block of hop 0 mixes sample i with
+// gain_ramp_at(p, g, i) -- this lane's four samples i = 2m, 2m + 1 -- and every other block with g, as MIX does.  A structural
+// zero block stays zeros.  Lane 0 stores g to ramp[slot] behind the hops, in front of the flush's return.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) v = __fadd_rn(v, __shfl_xor(v, d));
@@ -774,7 +780,7 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
     return v;
 }
-template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false>
+template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false, bool RAMP = false>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
                                                                   int N, int nhops, int r, float* __restrict__ wstate,
@@ -783,8 +789,10 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                                                                   const float* __restrict__ gain,
                                                                   const int* __restrict__ slots,
                                                                   const int* __restrict__ cnt,
-                                                                  float* __restrict__ meters) {
+                                                                  float* __restrict__ meters,
+                                                                  float* __restrict__ ramp) {
     static_assert(!(MIX && METER), "the metered instantiations branch on gain at run time");
+    static_assert(!RAMP || MIX || METER, "a ramp needs the mix");
     if constexpr (IDX) N = slot_count(cnt, N);
     __shared__ float2 s_tw[256];
     __shared__ float2 s_tw512[256];
@@ -828,6 +836,8 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
         for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
         rec = *reinterpret_cast<const float4*>(meters + 4 * slot);
     }
+    float p = 0.f;       // RAMP: the gain the stream's last block ended at (loaded here, first read behind hop 0's transform)
+    if constexpr (RAMP) p = ramp[slot];
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
 #pragma unroll
@@ -846,11 +856,26 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
         }
         wave_lds_sync();     // A is rewritten by the next hop's merge
         const bool zero = none || c0 + h == 0;     // call 0 of a stream emits zeros (the one-hop delay)
+        bool ramping = false;                      // RAMP: this block mixes with gain_ramp_at(p, g, i)
+        if constexpr (RAMP) {
+            if (h == 0) {      // (made scalars HERE: in front of the loop the wave would wait for every load issued so far)
+                p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(p)));
+                g = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(g)));
+                ramping = p != g;
+            }
+        }
         float ed = 0.f, eo = 0.f;                  // METER: this lane's partial sums of the hop, ((s0^2 + s1^2) + s2^2) + s3^2
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int m = lane + 64 * q;
             const float a0 = prev[q].x + f[q].x, a1 = prev[q].y + f[q].y;
+            float g0 = g, g1 = g;      // the dry gains of this lane's two samples: g, but inside a ramping block
+            if constexpr (RAMP) {
+                if (ramping) {
+                    g0 = gain_ramp_at(p, g, 2 * m);
+                    g1 = gain_ramp_at(p, g, 2 * m + 1);
+                }
+            }
             if constexpr (METER) {
                 float2 d = dry0[q];
                 if (h > 0) {
@@ -859,8 +884,8 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                 }
                 const float w0 = ola_div(a0, env[q][0]), w1 = ola_div(a1, env[q][1]);
                 // (without gains the plain sample itself: wave_mix(0, x, w) is not w for a non-finite x)
-                const float y0 = zero ? 0.f : (gain ? wave_mix(g, d.x, w0) : w0);
-                const float y1 = zero ? 0.f : (gain ? wave_mix(g, d.y, w1) : w1);
+                const float y0 = zero ? 0.f : (gain ? wave_mix(g0, d.x, w0) : w0);
+                const float y1 = zero ? 0.f : (gain ? wave_mix(g1, d.y, w1) : w1);
                 wave_st(o + 256L * h + 2 * m, y0);
                 wave_st(o + 256L * h + 2 * m + 1, y1);
                 const float x0 = zero ? 0.f : d.x, x1 = zero ? 0.f : d.y;
@@ -873,8 +898,8 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                     const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
                     d = make_float2(wave_ld(xd), wave_ld(xd + 1));
                 }
-                wave_st(o + 256L * h + 2 * m, zero ? 0.f : wave_mix(g, d.x, ola_div(a0, env[q][0])));
-                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : wave_mix(g, d.y, ola_div(a1, env[q][1])));
+                wave_st(o + 256L * h + 2 * m, zero ? 0.f : wave_mix(g0, d.x, ola_div(a0, env[q][0])));
+                wave_st(o + 256L * h + 2 * m + 1, zero ? 0.f : wave_mix(g1, d.y, ola_div(a1, env[q][1])));
             } else {      // (the sample first: the zero then selects between two values, no branch around the division)
                 const float w0 = ola_div(a0, env[q][0]), w1 = ola_div(a1, env[q][1]);
                 wave_st(o + 256L * h + 2 * m, zero ? 0.f : w0);
@@ -891,6 +916,9 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     if constexpr (METER) {
         rec.z = fmaxf(rec.z, wave_max(pk));
         if (lane == 0) *reinterpret_cast<float4*>(meters + 4 * slot) = rec;
+    }
+    if constexpr (RAMP) {
+        if (lane == 0) ramp[slot] = g;
     }
     if constexpr (FLUSH) return;
     // the state: tail = the newest frame's windowed second half; ring = the last 512 input samples; counter (saturating)
@@ -4499,22 +4527,28 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, hipStream_t s) {
+                          float* meters, float* ramp, hipStream_t s) {
     if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
     // a mixed flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
-    if (meters) {       // the metered instantiations read `gain` at run time: one per (S, FLUSH, IDX)
+    if (gain && ramp) {       // the ramped instantiations stand in for the mixed or the metered one: one per (S, FLUSH, IDX, METER)
+        with_flags([&](auto FLUSH, auto IDX, auto METER) {
+            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, !METER.value, IDX.value, METER.value, true>), dim3(grid),
+                               dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops,
+                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp);
+        }, flush, rows.slots != nullptr, meters != nullptr);
+    } else if (meters) {       // the metered instantiations read `gain` at run time: one per (S, FLUSH, IDX)
         with_flags([&](auto FLUSH, auto IDX) {
             hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s,
                                spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain,
-                               rows.slots, rows.cnt, meters);
+                               rows.slots, rows.cnt, meters, ramp);
         }, flush, rows.slots != nullptr);
     } else {
         with_flags([&](auto FLUSH, auto MIX, auto IDX) {
             hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
                                in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
-                               rows.cnt, meters);
+                               rows.cnt, meters, ramp);
         }, flush, gain != nullptr, rows.slots != nullptr);
     }
     GT_LAUNCH_CHECK();
@@ -4522,8 +4556,8 @@ int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out
 }
 template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
 template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, hipStream_t);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {

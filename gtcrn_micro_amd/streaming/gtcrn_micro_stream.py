@@ -229,7 +229,7 @@ class StreamGTCRNMicro(GTCRNMicro):
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
-                        count=None, resident=False, max_active=None, meters=False, g711=None, highband=None):
+                        count=None, resident=False, max_active=None, meters=False, g711=None, highband=None, ramp=False):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -239,6 +239,8 @@ class StreamGTCRNMicro(GTCRNMicro):
         latency); state.set_atten_lim_db changes it while the streams run.
         meters=True: the state owns per-stream level meters (state.meters, state.levels(), state.reset_meters()) that every
         step and flush of it updates.
+        ramp=True: the state owns state.gain_ramp, and a later state.set_atten_lim_db is spread over the next emitted block
+        (16 ms at 16 kHz) instead of landing as a step; set_atten_lim_db(..., snap=True) changes at once.
         state=, slots= (int32 device tensor), count= (device int32, optional): a stream JOINS -- the named slots of the
         existing 16 kHz `state` are reset to the start of a clip (Engine.wave_stream_reset_slots, a capturable kernel) and
         `state` is returned; the other slots are not touched.  Rate states and plain packet states cannot be addressed by
@@ -269,15 +271,15 @@ class StreamGTCRNMicro(GTCRNMicro):
             if packet is None:
                 raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
             return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
-                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband)
+                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband, ramp=ramp)
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
-                                        g711=g711, highband=highband)
+                                        g711=g711, highband=highband, ramp=ramp)
         if int(fs) != 16000:
-            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband)
+            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband, ramp=ramp)
         if highband is not None:
             raise _lib.GtcrnError("highband= needs fs = 24000, 32000 or 48000: a 16 kHz stream has no band above 8 kHz")
-        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters)
+        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters, ramp=ramp)
 
     def step_wave(self, x, state, slots=None, count=None):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a

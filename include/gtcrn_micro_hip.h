@@ -404,8 +404,8 @@ int gtcrn_packet_stream_step_pcm16(gtcrn_packet_stream *ps, void *d_state, void 
  * checks its arguments as the plain form does.  gtcrn_packet_stream_set_dry_gain stores the pointer in the handle (it must
  * cover max_streams floats and stay valid; NULL switches the limit off), so the packet steps keep their signatures and a
  * captured period keeps replaying while gains change.
- * Out of scope: ramping a change of beta inside a block (it would need a per-stream "previous gain" word in the state);
- * the _quant entry points; the spectrogram-level calls (a caller holding spectra mixes them itself: by linearity
+ * A change of beta lands as a step at a block boundary unless the caller asks for a ramp: "gain ramps" below.
+ * Out of scope: the _quant entry points; the spectrogram-level calls (a caller holding spectra mixes them itself: by linearity
  * beta * X + (1 - beta) * forward_spec(X) is this control up to the rounding of an STFT -> iSTFT round trip). */
 int gtcrn_forward_wave_limited(gtcrn_model *m, const float *d_wave, float *d_wave_out, int B, long Lmax,
                                const int *d_lengths, const float *d_gain, const float *d_win, void *stream);
@@ -761,6 +761,57 @@ int gtcrn_g711_encode_pcm16(int law, int p);
  * caller chooses the window by when it zeroes); a voice-activity decision. */
 int gtcrn_wave_stream_set_meters(gtcrn_model *m, float *d_meters);
 int gtcrn_level_dbov(double energy, double nsamples);
+
+/* ---- gain ramps: a change of the dry gain is spread over one block ---------------------------------------------------------
+ * The attenuation limit is the one control that moves DURING a call.  d_gain is read once per call, so a rewritten beta
+ * lands as a step between two adjacent samples: at 0 -> 1 the output jumps from the enhanced to the dry signal, an audible
+ * click.  With a ramp the change is spread linearly over the 256 samples (16 ms at 16 kHz) of the next emitted block.
+ *
+ * d_ramp is a caller-owned device array of one float per stream or slot: the dry gain at which that stream's last emitted
+ * block ended.  gtcrn_wave_stream_set_gain_ramp stores it in the model, exactly as gtcrn_wave_stream_set_meters stores
+ * d_meters; NULL, the default, switches ramps off; a null model is GTCRN_ERR_ARG and no device is touched.  d_ramp is indexed
+ * where the dry gain is read: row n of a contiguous call, d_slots[i] of a slot call, the packet forms' row tables likewise.
+ * It is NOT part of the wave state: every *_state_bytes and GTCRN_ABI_VERSION (1) are what they were.  With d_ramp == NULL,
+ * or with d_gain == NULL, every call launches exactly the kernels it launched before and d_ramp is neither read nor written.
+ *
+ * Per launch.  With d_ramp and d_gain both set, a synthesis launch does the following for every stream it names, with
+ * p = d_ramp[idx] and g = d_gain[idx]:
+ *   - Only the block of hop h == 0 of the call ramps (the flush's block is such a block); later hops of the call use g.
+ *   - A structural zero block stays zeros and does not ramp: the first block of a stream (c0 + h == 0) and a flush that has
+ *     no block.
+ *   - Sample i = 0..255 of the ramping block is wave_mix(beta_i, x_i, w_i), the four-rounding formula of "attenuation limit"
+ *     (no fused multiply-add), with r_i = (i + 1) / 256, exact in fp32, and
+ *         beta_i = g                                   if p == g or i == 255
+ *                = fl( p + fl( fl(g - p) * r_i ) )     otherwise      (every fl() ONE fp32 rounding, no fused multiply-add)
+ *   - At the end of the launch d_ramp[idx] = g, always: after a zero block, after a flush and after a flush without a
+ *     block.  One lane writes it with a plain vector store.
+ *
+ * What follows.
+ *   Steady state is the limited call: with p == g a ramped call equals the limited call bit for bit -- the output, the
+ *     meters and every state tensor.
+ *   A stream that joins snaps: after gtcrn_stream_reset_slots, gtcrn_packet_stream_reset_slots or on a fresh state its first
+ *     block is a structural zero, which sets d_ramp = g; the next block starts at g with no ramp from the previous tenant of
+ *     the slot.  No reset entry point changed.
+ *   The cut of hops into calls does not matter: a call with nhops = 2 equals two one-hop calls, as long as the gain is not
+ *     rewritten between them.  So the packet forms behave the same whether a tick steps a stream 0, 1 or 2 times (they run
+ *     hmax indexed wave steps per tick); a stream with no hop in a tick is not named and keeps its d_ramp.
+ *   The formula: beta_i is monotone from p to g, stays inside [min(p, g), max(p, g)] (so inside [0, 1]), ends exactly at g,
+ *     and its first step from p is (g - p) / 256 -- checked in numpy float32 over 200 000 (p, g) pairs including 0 <-> 1,
+ *     denormals and neighbouring floats, without a violation.  A numpy float32 expression reproduces y bit for bit.
+ *   Rate and packet forms: the ramp is made at 16 kHz inside the wave step (256 samples, 16 ms) and passes the outbound stage
+ *     like everything else; the stage-by-stage contracts hold word for word.
+ *   G.711 forms inherit the ramp: the mix is made in float before companding.
+ *   High band: R(w - gamma a) + gamma x takes the ramped w; its steady-state bypass identity is unchanged.
+ *   Graph capture: the pointer is a captured kernel argument, like d_meters; a captured step follows gains that change between
+ *     replays.
+ *   A ramped launch is timed in the row of the form it stands in for (k_wave_synthesis_mix, or k_wave_synthesis_meter).
+ *
+ * gtcrn_gain_ramp_host is a pure host function: it writes beta_0..255 for one (p, g) with the function the kernel compiles.
+ * Out of scope: ramping gamma, the high-band gain (the follow-up: it needs the same word next to the high band's gains);
+ * gtcrn_forward_wave_limited (offline, one constant gain per clip); ramp lengths other than one block; the _quant and
+ * spectrogram-level calls. */
+int gtcrn_wave_stream_set_gain_ramp(gtcrn_model *m, float *d_ramp);
+int gtcrn_gain_ramp_host(float p, float g, float *out256);
 
 /* ---- non-finite input: what a NaN or Inf in one stream may touch ---------------------------------------------------------
  * The library seats unrelated callers side by side -- four or seven streams in a workgroup, MFMA tiles that straddle two
