@@ -147,6 +147,12 @@ def lib():
     if hasattr(L, "gtcrn_wave_stream_set_gain_ramp"):
         L.gtcrn_wave_stream_set_gain_ramp.argtypes = [_vp, _vp]
         L.gtcrn_gain_ramp_host.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]
+    # level control (an earlier library has none of these: only a state asked for with alc= fails, at its creation)
+    if hasattr(L, "gtcrn_wave_stream_set_alc"):
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.gtcrn_wave_stream_set_alc.argtypes = [_vp, _vp, _vp]
+        L.gtcrn_alc_params_host.argtypes = [ctypes.POINTER(AlcConfig), fp]
+        L.gtcrn_alc_block_host.argtypes = [fp, fp, fp, fp, fp, fp]
     # G.711 payloads (an earlier library has none of these: a G.711 state or converter then fails at its first call)
     if hasattr(L, "gtcrn_packet_stream_step_g711"):
         L.gtcrn_packet_stream_step_g711.argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
@@ -369,6 +375,71 @@ def gain_ramp(p, g):
     out = np.empty(256, np.float32)
     _check(fn(float(np.float32(p)), float(np.float32(g)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
     return out
+
+
+class AlcConfig(ctypes.Structure):
+    """gtcrn_alc_config of include/gtcrn_micro_hip.h, "level control"."""
+    _fields_ = [(k, ctypes.c_double) for k in ("target_dbov", "min_gain_db", "max_gain_db", "rise_db_s", "fall_db_s",
+                                               "ceiling_dbov", "floor_dbov", "ratio_db", "hang_ms", "alpha")] + [("mode", ctypes.c_int)]
+
+
+ALC_DEFAULTS = dict(target_dbov=-26.0, min_gain_db=-6.0, max_gain_db=24.0, rise_db_s=6.0, fall_db_s=30.0, ceiling_dbov=-1.0,
+                    floor_dbov=-45.0, ratio_db=-10.0, hang_ms=200.0, alpha=0.0625, mode=1)     # GTCRN_ALC_DEFAULTS
+
+
+def _alc_fields(alc):
+    """alc= of the state constructors -> the config's fields: "vad" (measure only), True (the defaults) or a mapping."""
+    if isinstance(alc, str):
+        if alc != "vad":
+            raise GtcrnError(f'alc must be None, "vad", True or a mapping of the config\'s fields, got {alc!r}')
+        return dict(ALC_DEFAULTS, mode=0)
+    if alc is True:
+        return dict(ALC_DEFAULTS)
+    if not hasattr(alc, "keys"):
+        raise GtcrnError(f'alc must be None, "vad", True or a mapping of the config\'s fields, got {alc!r}')
+    return dict(ALC_DEFAULTS, **{str(k): alc[k] for k in alc.keys()})
+
+
+def alc_params(**fields):
+    """The 16 parameter words of the level control (include/gtcrn_micro_hip.h, "level control") for the defaults with
+    `fields` replaced: a float32 array from gtcrn_alc_params_host, the one place the words are made."""
+    fn = getattr(lib(), "gtcrn_alc_params_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no level control")
+    unknown = set(fields) - set(ALC_DEFAULTS)
+    if unknown:
+        raise GtcrnError(f"unknown level-control fields {sorted(unknown)}: the config has {sorted(ALC_DEFAULTS)}")
+    f = dict(ALC_DEFAULTS, **fields)
+    cfg = AlcConfig(*[float(f[k]) for k, _ in AlcConfig._fields_[:-1]], int(f["mode"]))
+    out = np.empty(16, np.float32)
+    _check(fn(ctypes.byref(cfg), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+    return out
+
+
+def alc_block(params, record, w, x, m):
+    """One emitted block through gtcrn_alc_block_host, the functions the kernel compiles, on the host: the 16 parameter
+    words, the stream's 8-word record and the 256-sample blocks w (wet), x (dry) and m (what the call would store) ->
+    (y, the record after the block), both float32 arrays.  The structural zero of a stream's first block is the caller's."""
+    fn = getattr(lib(), "gtcrn_alc_block_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no level control")
+    arr = [np.ascontiguousarray(v, np.float32) for v in (params, record, w, x, m)]
+    if [v.shape for v in arr] != [(16,), (8,), (256,), (256,), (256,)]:
+        raise GtcrnError("alc_block takes 16 parameter words, an 8-word record and three blocks of 256 samples")
+    rec, y = arr[1].copy(), np.empty(256, np.float32)
+    ptr = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    _check(fn(ptr(arr[0]), ptr(rec), ptr(arr[2]), ptr(arr[3]), ptr(arr[4]), ptr(y)))
+    return y, rec
+
+
+def _alc_on(alc):
+    """alc= of the state constructors: None and False are off, like meters=False and ramp=False."""
+    return alc is not None and alc is not False
+
+
+def _alc_without_highband(alc, highband):
+    if _alc_on(alc) and highband is not None:
+        raise GtcrnError("alc= and highband= do not go together: the high band's formulas assume the 16 kHz hand-off at unit gain")
 
 
 def _gains_of(db, n):
@@ -731,7 +802,7 @@ class Engine:
     def wave_state_bytes():
         return int(lib().gtcrn_wave_stream_state_bytes())
 
-    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False, ramp=False):
+    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False, ramp=False, alc=None):
         """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
         counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
         one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it).  atten_lim_db (a
@@ -742,7 +813,11 @@ class Engine:
         (WaveStreamState.reset_meters starts a new window, .levels() reads the RFC 6464 levels).
         ramp=True: the state owns ``state.gain_ramp``, (n,) float32, the gain each stream's last block ended at (the header's
         "gain ramps"): a later change of the limit is then spread over the next emitted block instead of landing as a
-        step.  It starts equal to ``state.dry_gain``, which is allocated (zeros: no limit) when atten_lim_db is None."""
+        step.  It starts equal to ``state.dry_gain``, which is allocated (zeros: no limit) when atten_lim_db is None.
+        alc ("vad": measure only; True: the defaults; a mapping of gtcrn_alc_config's fields; None or False: off): the header's "level
+        control" -- the state owns ``state.alc``, (n, 8) float32 records {a, S, hang, voice, voiced, blocks, 0, 0}, and
+        ``state.alc_params``, (16,) float32, which every step and flush through the state then uses (WaveStreamState.voice,
+        .alc_gain_db, .set_alc, .reset_alc)."""
         import torch
         n = int(nstreams)
         if n < 1:
@@ -763,7 +838,20 @@ class Engine:
             st.meters = torch.zeros((n, 4), device=win.device, dtype=torch.float32)
         if ramp:
             st._new_gain_ramp()
+        if _alc_on(alc):
+            st._new_alc(alc)
         return st
+
+    def _set_alc(self, state):
+        """Hands the state's level-control records and parameter words to the model ahead of a step or flush, or clears
+        the model's pointers for a state without: two states on one engine do not leak into each other."""
+        fn = getattr(lib(), "gtcrn_wave_stream_set_alc", None)
+        if fn is None:
+            return                                       # (an earlier library: _new_alc refused, nothing to clear)
+        if state.alc is None:
+            _check(fn(self._h, None, None))
+        else:
+            _check(fn(self._h, state.alc.data_ptr(), state.alc_params.data_ptr()))
 
     def _set_gain_ramp(self, state):
         """Hands the state's ramp words to the model ahead of a step or flush, or clears the model's pointer for a state
@@ -833,6 +921,7 @@ class Engine:
                 out.stride(0), state.n, L // 256)
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_step_pcm16 if pcm else lib().gtcrn_wave_stream_step
@@ -856,6 +945,7 @@ class Engine:
                 tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n)
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             if state.dry_gain is None:
                 fn = lib().gtcrn_wave_stream_flush_pcm16 if pcm else lib().gtcrn_wave_stream_flush
@@ -955,6 +1045,7 @@ class Engine:
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m, x.data_ptr(), x.stride(0),
                       out.data_ptr(), out.stride(0), gain, state.window.data_ptr(), _stream_ptr()))
@@ -973,6 +1064,7 @@ class Engine:
         gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
                       tail.data_ptr() if r else None, tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), gain,
@@ -1054,15 +1146,17 @@ class Engine:
                                            out.data_ptr(), out.stride(0), B, _stream_ptr()))
         return out[0] if wave.dim() == 1 else out
 
-    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None, ramp=False):
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None, ramp=False, alc=None):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
         resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz); meters: as in
         new_wave_state (taken at 16 kHz, per 256-sample block of the wave step); ramp: as in new_wave_state (made at 16 kHz,
         over one 256-sample block of the wave step).  highband (a float or one per stream, each
         in [0, 1]; fs = 24000, 32000 or 48000; None: off, the plain calls): the header's "high band" -- the state gets
         ``hb`` (N, rate_stream_hb_state_bytes/4) and the per-stream gains ``hb_gain`` that every step then applies
-        (RateStreamState.set_highband_gain rewrites them in place)."""
+        (RateStreamState.set_highband_gain rewrites them in place).  alc: as in new_wave_state (made at 16 kHz, per block of
+        the wave step); not together with highband=."""
         import torch
+        _alc_without_highband(alc, highband)
         fs = int(fs)
         hop = _check(lib().gtcrn_rate_stream_hop(fs))
         nhb = rate_stream_hb_state_bytes(fs) // 4 if highband is not None else 0        # (raises without a high band at fs)
@@ -1079,6 +1173,8 @@ class Engine:
         st.meters = ws.meters
         if ramp:
             st._new_gain_ramp()
+        if _alc_on(alc):
+            st._new_alc(alc)
         return st
 
     def rate_stream_reserve(self, state, nhops):
@@ -1118,6 +1214,7 @@ class Engine:
                 state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             if state.hb is not None:
                 fn = lib().gtcrn_rate_stream_step_hb_pcm16 if pcm else lib().gtcrn_rate_stream_step_hb
@@ -1142,7 +1239,7 @@ class Engine:
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
     def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None,
-                         highband=None, ramp=False):
+                         highband=None, ramp=False, alc=None):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
@@ -1155,8 +1252,11 @@ class Engine:
         highband (a float or one per stream, each in [0, 1]; fs = 24000, 32000 or 48000 and a latency that is whole at fs;
         None: off, the plain calls): the header's "high band on the packet forms" -- the state gets ``hb``
         (N, packet_stream_hb_state_bytes / 4), the per-stream gains ``hb_gain`` every step then applies
-        (set_highband_gain rewrites them in place) and ``hb_latency`` in samples at fs; not together with g711=."""
+        (set_highband_gain rewrites them in place) and ``hb_latency`` in samples at fs; not together with g711=.
+        alc: as in new_wave_state (made at 16 kHz, per block of the wave step; a call without a hop leaves the records alone);
+        not together with highband=."""
         import torch
+        _alc_without_highband(alc, highband)
         law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
@@ -1179,6 +1279,8 @@ class Engine:
         st.meters = ws.meters
         if ramp:
             st._new_gain_ramp()
+        if _alc_on(alc):
+            st._new_alc(alc)
         return st
 
     def packet_stream_reset(self, state, lo=0, hi=None):
@@ -1221,6 +1323,7 @@ class Engine:
         state.last_hops = state.next_hops
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
@@ -1241,14 +1344,16 @@ class Engine:
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
     def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False,
-                              g711=None, highband=None, ramp=False):
+                              g711=None, highband=None, ramp=False, alc=None):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
         one-stream group created at phase 0.  Everything a step needs is reserved here.  atten_lim_db and meters: as in
         new_wave_state, per SLOT; ramp likewise.  g711: as in new_packet_state.  highband: as in new_packet_state, one gain per SLOT;
-        packet_stream_reset_slots then zeroes the named slots' rows of ``hb`` too."""
+        packet_stream_reset_slots then zeroes the named slots' rows of ``hb`` too.  alc: as in new_packet_state, one record
+        per SLOT."""
         import torch
+        _alc_without_highband(alc, highband)
         law = g711_law(g711)
         fs, packet = int(fs), int(packet)
         n16 = packet_stream_n16(fs, packet)
@@ -1276,6 +1381,8 @@ class Engine:
         st.meters = ws.meters
         if ramp:
             st._new_gain_ramp()
+        if _alc_on(alc):
+            st._new_alc(alc)
         return st
 
     def _packet_slot_args(self, state, slots, count):
@@ -1318,6 +1425,7 @@ class Engine:
             hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         self._set_meters(state)
         self._set_gain_ramp(state)
+        self._set_alc(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
@@ -1441,6 +1549,9 @@ class WaveStreamState:
         self.dry_gain = None        # (N,) float32 on the device: the attenuation limit's dry gains; None: limit off
         self.meters = None          # (N, 4) float32 on the device: {E_dry, E_out, peak, blocks} per stream; None: no metering
         self.gain_ramp = None       # (N,) float32 on the device: the dry gain each stream's last block ended at; None: no ramps
+        self.alc = None             # (N, 8) float32 on the device: the level-control records; None: no level control
+        self.alc_params = None      # (16,) float32 on the device: the level control's parameter words
+        self.alc_fields = None      # the configuration the words were made from (gtcrn_alc_config's fields), as set_alc keeps it
 
     @property
     def n(self):
@@ -1486,6 +1597,55 @@ class WaveStreamState:
             self.dry_gain[lo:hi].copy_(torch.from_numpy(g), non_blocking=True)
         if snap and self.gain_ramp is not None:
             self.gain_ramp[lo:hi].copy_(self.dry_gain[lo:hi])
+
+    def _new_alc(self, alc):
+        """alc= of the state's constructor: the parameter words and the records, every stream at its initial record."""
+        import torch
+        if not hasattr(lib(), "gtcrn_wave_stream_set_alc"):
+            raise GtcrnError("this library has no level control")
+        self.alc_fields = _alc_fields(alc)        # the configuration set_alc updates
+        words = alc_params(**self.alc_fields)
+        self.alc_params = torch.from_numpy(words).to(self.model.device)
+        self.alc = torch.zeros((self.n, 8), device=self.model.device, dtype=torch.float32)
+        self.reset_alc()
+
+    def _leveled(self):
+        if self.alc is None:
+            raise GtcrnError("the state has no level control: create it with alc=")
+        return self.alc
+
+    def set_alc(self, **fields):
+        """Replaces the given settings of the state's OWN configuration (``state.alc_fields``: what alc= gave, as later calls
+        here left it -- an alc="vad" state stays measure-only unless mode=1 is passed) and rewrites state.alc_params in
+        place, asynchronously on the current stream: the next step, also the next replay of a captured one, follows.
+        Nothing changes when a setting is refused."""
+        import torch
+        self._leveled()
+        merged = dict(self.alc_fields or ALC_DEFAULTS, **fields)
+        words = alc_params(**merged)
+        self.alc_fields = merged
+        self.alc_params.copy_(torch.from_numpy(words), non_blocking=True)
+
+    def reset_alc(self, lo=0, hi=None):
+        """Writes the initial record {1, 0, 0, 0, 0, 0, 0, 0} to streams (slots) lo..hi-1, asynchronously on the current stream
+        and without any allocation.  (A stream's first block does the same on the device: a join needs no call here.)"""
+        a = self._leveled()
+        hi = self.n if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.n:
+            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        a[lo:hi].zero_()
+        a[lo:hi, 0].fill_(1.0)
+
+    def voice(self):
+        """The voice flag of every stream's last emitted block: an (N,) bool tensor on the device, a compare of word 3 of the
+        records.  Asynchronous, no synchronisation: usable inside a captured graph."""
+        return self._leveled()[:, 3] != 0
+
+    def alc_gain_db(self):
+        """The gain every stream's last emitted block ended at, in dB: an (N,) float64 numpy array.  SYNCHRONOUS: word 0 of
+        the records is copied to the host."""
+        return 20.0 * np.log10(self._leveled()[:, 0].detach().cpu().numpy().astype(np.float64))
 
     def _metered(self):
         if self.meters is None:

@@ -31,7 +31,11 @@ def build_native(force=False, verbose=False, stamps=False, exp=False):
     common = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
     # Inference kernels (kernels.hip):
     #  -fno-honor-nans: keeps hipcc from canonicalising (v_max x,x) in front of every v_min/v_max of the PReLU; no
-    #     kernel tests for or produces NaN on finite input.
+    #     kernel tests for or produces NaN on finite input.  The level control's block rule (kernels.h, alc_decide) has to
+    #     survive a NaN or Inf in a stream under this flag: its finiteness test reads the bits (alc_not_finite), and it needs
+    #     only that a NaN passes through the adds and multiplies of the reductions, which the flag does not change.  It also
+    #     relies on hipcc's default correctly rounded fp32 `/` and sqrt (-fhip-fp32-correctly-rounded-divide-sqrt): do not
+    #     add -ffast-math or -fno-hip-fp32-correctly-rounded-divide-sqrt here (tests/test_gpu_alc.py compares bit for bit).
     #  -ffp-contract=on: multiply-adds are fused per source expression (by the front end), not opportunistically by the
     #     back end: every instantiation of a kernel template (one/two/three tiles per wave, offline / streaming /
     #     multi-stream) then rounds identically, which is what makes streamed == chunked == offline hold BIT FOR BIT.

@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -93,6 +95,8 @@ struct gtcrn_model {
     float* d_rate_b = nullptr;  // wave step -> k_rate_out; sized by gtcrn_rate_stream_reserve
     float* d_meters = nullptr;  // the caller's level-meter records (gtcrn_wave_stream_set_meters); NULL: no metering
     float* d_ramp = nullptr;    // the caller's gain-ramp words (gtcrn_wave_stream_set_gain_ramp); NULL: gain changes step
+    float* d_alc = nullptr;     // the caller's level-control records and parameter words (gtcrn_wave_stream_set_alc); NULL: no
+    const float* d_alc_params = nullptr;   // level control
     long cap_rate = 0;          // capacity of each in (streams * hops)
     bool debug = false;
     bool debug_keep_fused = false;   // gtcrn_debug_enable(m, 2): phase stamps only -- single-frame steps stay ONE launch
@@ -678,6 +682,82 @@ int gtcrn_gain_ramp_host(float p, float g, float* out256) {
     return 0;
 }
 
+// Level control (contract: include/gtcrn_micro_hip.h, "level control"): both addresses are kept like the meters'; wave_step
+// hands them to the synthesis launch.  Nothing is launched or read here.
+int gtcrn_wave_stream_set_alc(gtcrn_model* m, float* d_alc, const float* d_alc_params) {
+    if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: null model");
+    if (!d_alc != !d_alc_params) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: the records and the parameters come together");
+    if (reinterpret_cast<uintptr_t>(d_alc) & 31)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: the records must be 32-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_alc_params) & 15)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: the parameters must be 16-byte aligned");
+    m->d_alc = d_alc;
+    m->d_alc_params = d_alc_params;
+    return 0;
+}
+// the parameter words of a configuration: double arithmetic, one rounding to float each
+int gtcrn_alc_params_host(const gtcrn_alc_config* c, float* out16) {
+    if (!c || !out16) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: null pointer");
+    const double v[] = {c->target_dbov, c->min_gain_db, c->max_gain_db, c->rise_db_s, c->fall_db_s, c->ceiling_dbov,
+                        c->floor_dbov, c->ratio_db, c->hang_ms, c->alpha};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: a field is not finite");
+    if (c->min_gain_db > c->max_gain_db) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: min_gain_db above max_gain_db");
+    if (c->rise_db_s < 0 || c->fall_db_s < 0) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: a negative slew rate");
+    if (c->hang_ms < 0 || c->hang_ms > 16.0 * (1 << 24)) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: hang_ms out of range");
+    if (c->alpha < 0 || c->alpha > 1) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: alpha outside [0, 1]");
+    if (c->mode != 0 && c->mode != 1) return fail(GTCRN_ERR_ARG, "gtcrn_alc_params_host: mode must be 0 or 1");
+    const auto p10 = [](double db, double div) { return std::pow(10.0, db / div); };
+    const auto fin = [](double x) { return (float)std::min(x, (double)FLT_MAX); };
+    for (int i = 0; i < 16; ++i) out16[i] = 0.f;
+    out16[0] = std::max(fin(256.0 * p10(c->floor_dbov, 10)), 1e-30f);
+    out16[1] = fin(p10(c->ratio_db, 10));
+    out16[2] = (float)std::ceil(c->hang_ms / 16.0);
+    out16[3] = (float)c->alpha;
+    out16[4] = fin(256.0 * p10(c->target_dbov, 10));
+    out16[5] = std::min(std::max(fin(p10(c->min_gain_db, 20)), FLT_MIN), 1.0f);
+    out16[6] = std::max(fin(p10(c->max_gain_db, 20)), 1.0f);
+    out16[7] = fin(p10(c->rise_db_s * 0.016, 20));
+    out16[8] = (float)p10(-c->fall_db_s * 0.016, 20);
+    out16[9] = fin(p10(c->ceiling_dbov, 20));
+    out16[10] = (float)c->mode;
+    return 0;
+}
+// the host twin: one emitted block through the functions the kernel compiles (lane l holds samples 2l, 2l + 1, 128 + 2l,
+// 129 + 2l; the reductions run the xor butterfly over lane distances 1 .. 32)
+int gtcrn_alc_block_host(const float* params16, float* record8, const float* w256, const float* x256, const float* m256,
+                         float* y256) {
+    if (!params16 || !record8 || !w256 || !x256 || !m256 || !y256) return fail(GTCRN_ERR_ARG, "gtcrn_alc_block_host: null pointer");
+    const auto butterfly = [](float* v, bool sum) {
+        for (int d = 1; d < 64; d <<= 1) {
+            float t[64];
+            for (int l = 0; l < 64; ++l) t[l] = sum ? v[l] + v[l ^ d] : std::fmax(v[l], v[l ^ d]);
+            for (int l = 0; l < 64; ++l) v[l] = t[l];
+        }
+        return v[0];
+    };
+    float ew[64], ex[64], pk[64];
+    for (int l = 0; l < 64; ++l) {
+        const int i[4] = {2 * l, 2 * l + 1, 128 + 2 * l, 129 + 2 * l};
+        ew[l] = gtk::alc_lane_sum(w256[i[0]], w256[i[1]], w256[i[2]], w256[i[3]]);
+        ex[l] = gtk::alc_lane_sum(x256[i[0]], x256[i[1]], x256[i[2]], x256[i[3]]);
+        pk[l] = std::fmax(std::fmax(std::fabs(m256[i[0]]), std::fabs(m256[i[1]])),
+                          std::fmax(std::fabs(m256[i[2]]), std::fabs(m256[i[3]])));
+    }
+    const float* p = params16;
+    const gtk::AlcParams P{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10]};
+    gtk::AlcRecord R{record8[0], record8[1], record8[2], record8[3], record8[4], record8[5]};
+    float a0, a1;
+    gtk::alc_decide(P, R, butterfly(ew, true), butterfly(ex, true), butterfly(pk, false), a0, a1);
+    for (int i = 0; i < 256; ++i) {
+        const float gi = gtk::gain_ramp_at(a0, a1, i);
+        y256[i] = gi * m256[i];
+    }
+    const float rec[8] = {R.a, R.S, R.hang, R.voice, R.voiced, R.blocks, 0.f, 0.f};
+    for (int i = 0; i < 8; ++i) record8[i] = rec[i];
+    return 0;
+}
+
 // RFC 6464 audio level of a window of `nsamples` samples with energy `energy` (full scale 1.0): -dBov rounded to the nearest
 // integer, 0 (loudest) .. 127 (silence).  Host arithmetic only.
 int gtcrn_level_dbov(double energy, double nsamples) {
@@ -704,8 +784,8 @@ int refuse_three_launch_form(const std::string& w, const gtcrn_model* m) {
 }  // namespace
 
 // Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given, metered while
-// the model holds a meters address, ramped when d_gain is given while the model holds a ramp address -- timed in the row of
-// the form it stands in for: the rate, packet and packet-slot forms come through here too) of n rows.
+// the model holds a meters address, ramped when d_gain is given while the model holds a ramp address, level-controlled while
+// the model holds a level-control address -- the last two timed in the row of the form they stand in for: the rate, packet and packet-slot forms come through here too) of n rows.
 // Without a table the rows are the n streams of a contiguous state range, nhops hops each; with one (the _slots calls)
 // they are the n = max_active rows it names, one hop.
 extern "C++" template <typename S>
@@ -741,7 +821,7 @@ static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wst
     if (rc) return rc;
     tm.begin(m->d_meters ? K_WAVE_SYNTHESIS_METER : d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
     LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, n, nhops, r, flush, ws, d_win,
-                                             m->d_twid, rows, d_gain, m->d_meters, m->d_ramp, s));
+                                             m->d_twid, rows, d_gain, m->d_meters, m->d_ramp, m->d_alc, m->d_alc_params, s));
     tm.end();
     return 0;
 }
@@ -1140,6 +1220,8 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
         return fail(GTCRN_ERR_ARG, w + ": the input and output rows overlap (the high-band step is not legal in place)");
     int rc = check_model(m);
     if (rc) return rc;
+    if (hb && m->d_alc)      // (the high band's formulas assume the 16 kHz hand-off at unit gain)
+        return fail(GTCRN_ERR_STATE, w + ": the high band does not go together with level control (gtcrn_wave_stream_set_alc)");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = ensure_workspace(m, nstreams, nhops, s))) return rc;
     if ((rc = ensure_rate_workspace(m, nstreams, nhops, s))) return rc;
@@ -1476,6 +1558,8 @@ static int packet_step(const char* who, gtcrn_packet_stream* ps, void* d_state, 
     gtcrn_model* m = ps->m;
     int rc = check_model(m);
     if (rc) return rc;
+    if (hb && m->d_alc)      // (the high band's formulas assume the 16 kHz hand-off at unit gain)
+        return fail(GTCRN_ERR_STATE, w + ": the high band does not go together with level control (gtcrn_wave_stream_set_alc)");
     if (sl && (rc = refuse_three_launch_form(w, m))) return rc;           // (before the plan: nothing runs on a refusal)
     hipStream_t s = (hipStream_t)stream;
     const PkGeom& p = ps->p;

@@ -115,6 +115,74 @@ __host__ __device__ inline float gain_ramp_at(float p, float g, int i) {
     const float s = d * ((float)(i + 1) * 0.00390625f);
     return p + s;
 }
+// Level control (contract: include/gtcrn_micro_hip.h, "level control"): the block rule, steps 3 .. 9 and 11, once a block's
+// three reductions are known.  One body for the ALC instantiations of k_wave_synthesis and for gtcrn_alc_block_host.  Every
+// operation is one correctly rounded fp32 operation (plain operators: the pragma keeps any -ffp-contract of the including
+// file from fusing them; `/` and sqrt are the IEEE ones on both sides); the finiteness test reads the bits, so it holds in
+// a file compiled with -fno-honor-nans.
+struct AlcParams {      // words 0 .. 10 of d_alc_params
+    float theta, rho, H, alpha, T, a_min, a_max, d_up, d_dn, c, mode;
+};
+struct AlcRecord {      // words 0 .. 5 of a stream's record
+    float a, S, hang, voice, voiced, blocks;
+};
+// v >= 0 or NaN: true where v is not <= FLT_MAX
+__host__ __device__ inline bool alc_not_finite(float v) {
+    return (__builtin_bit_cast(unsigned, v) & 0x7fffffffu) > 0x7f7fffffu;
+}
+// ((s0^2 + s1^2) + s2^2) + s3^2: a lane's partial sum of a block, the meters' order
+__host__ __device__ inline float alc_lane_sum(float s0, float s1, float s2, float s3) {
+#pragma clang fp contract(off)
+    const float q0 = s0 * s0, q1 = s1 * s1, q2 = s2 * s2, q3 = s3 * s3;
+    const float t = q0 + q1;
+    const float u = t + q2;
+    return u + q3;
+}
+// Advances the record by one emitted block with energies Ew (wet), Ex (dry) and pk = max |m|; a0 / a1: the gains at which
+// the block starts and ends, y_i = fl(gain_ramp_at(a0, a1, i) * m_i).
+__host__ __device__ inline void alc_decide(const AlcParams& P, AlcRecord& r, float Ew, float Ex, float pk, float& a0,
+                                           float& a1) {
+#pragma clang fp contract(off)
+    const float a = r.a;
+    float at = a, voice = 0.f, lim = a;
+    bool limited = false;
+    if (!(alc_not_finite(Ew) || alc_not_finite(Ex) || alc_not_finite(pk))) {
+        const float rx = P.rho * Ex;
+        const bool speech = Ew >= P.theta && Ew >= rx;
+        if (speech) {
+            r.hang = P.H;
+            voice = 1.f;
+            if (r.S == 0.f) {
+                r.S = Ew;
+            } else {
+                const float d = Ew - r.S;
+                const float s = P.alpha * d;
+                r.S = r.S + s;
+            }
+        } else if (r.hang > 0.f) {
+            r.hang = r.hang - 1.f;
+            voice = 1.f;
+        }
+        if (voice != 0.f && r.S > 0.f) {
+            const float q = P.T / r.S;
+            const float want = fminf(fmaxf(__builtin_sqrtf(q), P.a_min), P.a_max);
+            const float lo = a * P.d_dn, hi = a * P.d_up;
+            at = fminf(fmaxf(want, lo), hi);
+        }
+        const float top = pk * fmaxf(a, at);
+        if (pk > 0.f && top > P.c) {
+            limited = true;
+            lim = fmaxf(P.a_min, P.c / pk);
+        }
+    }
+    a0 = limited ? fminf(a, lim) : a;
+    a1 = limited ? fminf(at, lim) : at;
+    if (P.mode == 0.f) a0 = a1 = 1.f;
+    r.a = a1;
+    r.voice = voice;
+    r.voiced = r.voiced + voice;
+    r.blocks = r.blocks + 1.f;
+}
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
@@ -123,14 +191,17 @@ __host__ __device__ inline float gain_ramp_at(float p, float g, int i) {
 // device, 4 floats per stream or slot, 16-byte aligned): the level-meter records, advanced by the METER instantiations, which
 // read `gain` at run time (nullptr or not); nullptr: the launches above.  ramp (optional, device, one float per stream or
 // slot, indexed as gain is): the gain ramps -- with gain AND ramp the RAMP instantiations run, which read ramp[idx], ramp the
-// call's first block from it to gain[idx] and store gain[idx] there; without either pointer ramp is not touched.
+// call's first block from it to gain[idx] and store gain[idx] there; without either pointer ramp is not touched.  alc
+// (optional, device, 8 floats per stream or slot, 32-byte aligned) with alc_params (device, 16 floats): the level control --
+// the ALC instantiations run, one per (S, flush, indexed), which take gain, meters and ramp as run-time branches; nullptr:
+// the launches above.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
                          const float* win, const float* twid, float* spec, Rows rows, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, float* ramp, hipStream_t s);
+                          float* meters, float* ramp, float* alc, const float* alc_params, hipStream_t s);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;

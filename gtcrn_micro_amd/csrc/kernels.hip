@@ -770,6 +770,14 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 // the first spectrum is fetched); where they differ, the block of hop 0 mixes sample i with
 // gain_ramp_at(p, g, i) -- this lane's four samples i = 2m, 2m + 1 -- and every other block with g, as MIX does.  A structural
 // zero block stays zeros.  Lane 0 stores g to ramp[slot] behind the hops, in front of the flush's return.
+// ALC: the level control (include/gtcrn_micro_hip.h, "level control") -- one instantiation per (S, FLUSH, IDX), which takes
+// gain, meters and ramp as wave-uniform run-time branches (MIX = METER = RAMP = false).  The wave holds the whole block --
+// this lane's four wet samples w, dry samples x and mixed samples m -- before the first store: E_w, E_x (alc_lane_sum, then
+// wave_sum: the meters' order) and pk = max |m| come first, alc_decide (kernels.h, the host twin's body) advances the record
+// and gives the block's two gains, and y_i = fl(gain_ramp_at(a0, a1, i) m_i) goes to the store and to the meters.  The
+// sixteen parameter words and the record are loaded in front of the loop and made scalars behind hop 0's transform, as the
+// ramp words are; lane 0 stores the record (two 16-byte stores, 32 bytes in all) in front of the flush's return, not after an
+// empty flush.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) v = __fadd_rn(v, __shfl_xor(v, d));
@@ -780,7 +788,7 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
     return v;
 }
-template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false, bool RAMP = false>
+template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false, bool RAMP = false, bool ALC = false>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
                                                                   int N, int nhops, int r, float* __restrict__ wstate,
@@ -790,8 +798,11 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                                                                   const int* __restrict__ slots,
                                                                   const int* __restrict__ cnt,
                                                                   float* __restrict__ meters,
-                                                                  float* __restrict__ ramp) {
+                                                                  float* __restrict__ ramp,
+                                                                  float* __restrict__ alc,
+                                                                  const float* __restrict__ alc_params) {
     static_assert(!(MIX && METER), "the metered instantiations branch on gain at run time");
+    static_assert(!ALC || !(MIX || METER || RAMP), "the level-control instantiations branch on gain, meters and ramp at run time");
     static_assert(!RAMP || MIX || METER, "a ramp needs the mix");
     if constexpr (IDX) N = slot_count(cnt, N);
     __shared__ float2 s_tw[256];
@@ -838,6 +849,20 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     }
     float p = 0.f;       // RAMP: the gain the stream's last block ended at (loaded here, first read behind hop 0's transform)
     if constexpr (RAMP) p = ramp[slot];
+    float4 av[5];        // ALC: the record's two halves and parameter words 0 .. 11, as loaded (every lane the same address)
+    AlcParams P;         // ALC: both made scalars behind hop 0's transform
+    AlcRecord R;
+    if constexpr (ALC) {
+        if (gain) g = gain[slot];
+        if (gain && ramp) p = ramp[slot];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
+        if (meters) rec = *reinterpret_cast<const float4*>(meters + 4 * slot);
+        av[0] = *reinterpret_cast<const float4*>(alc + 8 * slot);
+        av[1] = *reinterpret_cast<const float4*>(alc + 8 * slot + 4);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) av[2 + q] = *reinterpret_cast<const float4*>(alc_params + 4 * q);
+    }
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
 #pragma unroll
@@ -856,6 +881,64 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
         }
         wave_lds_sync();     // A is rewritten by the next hop's merge
         const bool zero = none || c0 + h == 0;     // call 0 of a stream emits zeros (the one-hop delay)
+        if constexpr (ALC) {
+            if (h == 0) {      // (made scalars HERE, as the ramp words below)
+                const auto sc = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+                p = sc(p);
+                g = sc(g);
+                R = AlcRecord{sc(av[0].x), sc(av[0].y), sc(av[0].z), sc(av[0].w), sc(av[1].x), sc(av[1].y)};
+                P = AlcParams{sc(av[2].x), sc(av[2].y), sc(av[2].z), sc(av[2].w), sc(av[3].x), sc(av[3].y),
+                              sc(av[3].z), sc(av[3].w), sc(av[4].x), sc(av[4].y), sc(av[4].z)};
+            }
+            const bool ramps = h == 0 && gain && ramp && p != g;      // this block mixes with gain_ramp_at(p, g, i)
+            float wq[2][2], xq[2][2], mq[2][2], yq[2][2];                // sample 2 (lane + 64 q) + e of the block
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int m = lane + 64 * q;
+                float2 d = dry0[q];
+                if (h > 0) {
+                    const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
+                    d = make_float2(wave_ld(xd), wave_ld(xd + 1));
+                }
+                xq[q][0] = d.x;
+                xq[q][1] = d.y;
+                wq[q][0] = ola_div(prev[q].x + f[q].x, env[q][0]);
+                wq[q][1] = ola_div(prev[q].y + f[q].y, env[q][1]);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const float ge = ramps ? gain_ramp_at(p, g, 2 * m + e) : g;
+                    mq[q][e] = gain ? wave_mix(ge, xq[q][e], wq[q][e]) : wq[q][e];
+                    yq[q][e] = 0.f;
+                }
+                prev[q] = f[q + 2];
+            }
+            float ex = 0.f;
+            if (zero) {
+                if (!none) R = AlcRecord{1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            } else {
+                const float ew = wave_sum(alc_lane_sum(wq[0][0], wq[0][1], wq[1][0], wq[1][1]));
+                ex = wave_sum(alc_lane_sum(xq[0][0], xq[0][1], xq[1][0], xq[1][1]));
+                const float pm = wave_max(fmaxf(fmaxf(fabsf(mq[0][0]), fabsf(mq[0][1])), fmaxf(fabsf(mq[1][0]), fabsf(mq[1][1]))));
+                float a0, a1;
+                alc_decide(P, R, ew, ex, pm, a0, a1);
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) yq[q][e] = __fmul_rn(gain_ramp_at(a0, a1, 2 * (lane + 64 * q) + e), mq[q][e]);
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                wave_st(o + 256L * h + 2 * (lane + 64 * q), yq[q][0]);
+                wave_st(o + 256L * h + 2 * (lane + 64 * q) + 1, yq[q][1]);
+            }
+            if (meters) {      // the meters see y; their E_dry is E_x (the same sums in the same order; 0 for a zero block)
+                rec.x = __fadd_rn(rec.x, ex);
+                rec.y = __fadd_rn(rec.y, wave_sum(alc_lane_sum(yq[0][0], yq[0][1], yq[1][0], yq[1][1])));
+                rec.w = __fadd_rn(rec.w, 1.0f);
+                pk = fmaxf(pk, fmaxf(fmaxf(fabsf(yq[0][0]), fabsf(yq[0][1])), fmaxf(fabsf(yq[1][0]), fabsf(yq[1][1]))));
+            }
+            continue;
+        }
         bool ramping = false;                      // RAMP: this block mixes with gain_ramp_at(p, g, i)
         if constexpr (RAMP) {
             if (h == 0) {      // (made scalars HERE: in front of the loop the wave would wait for every load issued so far)
@@ -920,6 +1003,17 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     if constexpr (RAMP) {
         if (lane == 0) ramp[slot] = g;
     }
+    if constexpr (ALC) {
+        if (meters) rec.z = fmaxf(rec.z, wave_max(pk));      // (wave uniform: every lane takes the shuffles)
+        if (lane == 0) {
+            if (meters) *reinterpret_cast<float4*>(meters + 4 * slot) = rec;
+            if (gain && ramp) ramp[slot] = g;
+            if (!none) {
+                *reinterpret_cast<float4*>(alc + 8 * slot) = make_float4(R.a, R.S, R.hang, R.voice);
+                *reinterpret_cast<float4*>(alc + 8 * slot + 4) = make_float4(R.voiced, R.blocks, 0.f, 0.f);
+            }
+        }
+    }
     if constexpr (FLUSH) return;
     // the state: tail = the newest frame's windowed second half; ring = the last 512 input samples; counter (saturating)
 #pragma unroll
@@ -930,7 +1024,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     for (int q = 0; q < 4; ++q) {
         const int j = 2 * (lane + 64 * q);
         if (q < 2 && nhops == 1) {      // (this lane's own q + 2; MIX and METER hold the pair already)
-            if constexpr (MIX || METER) ring[q] = dry0[q];
+            if constexpr (MIX || METER || ALC) ring[q] = dry0[q];
             else ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);
         } else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
     }
@@ -4527,28 +4621,34 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
                           bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, float* ramp, hipStream_t s) {
+                          float* meters, float* ramp, float* alc, const float* alc_params, hipStream_t s) {
     if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
     // a mixed flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
-    if (gain && ramp) {       // the ramped instantiations stand in for the mixed or the metered one: one per (S, FLUSH, IDX, METER)
+    if (alc) {                // the level-control instantiations read gain, meters and ramp at run time: one per (S, FLUSH, IDX)
+        with_flags([&](auto FLUSH, auto IDX) {
+            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, false, false, true>), dim3(grid),
+                               dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops,
+                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp, alc, alc_params);
+        }, flush, rows.slots != nullptr);
+    } else if (gain && ramp) {       // the ramped instantiations stand in for the mixed or the metered one: one per (S, FLUSH, IDX, METER)
         with_flags([&](auto FLUSH, auto IDX, auto METER) {
             hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, !METER.value, IDX.value, METER.value, true>), dim3(grid),
                                dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops,
-                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp);
+                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp, alc, alc_params);
         }, flush, rows.slots != nullptr, meters != nullptr);
     } else if (meters) {       // the metered instantiations read `gain` at run time: one per (S, FLUSH, IDX)
         with_flags([&](auto FLUSH, auto IDX) {
             hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s,
                                spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain,
-                               rows.slots, rows.cnt, meters, ramp);
+                               rows.slots, rows.cnt, meters, ramp, alc, alc_params);
         }, flush, rows.slots != nullptr);
     } else {
         with_flags([&](auto FLUSH, auto MIX, auto IDX) {
             hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
                                in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
-                               rows.cnt, meters, ramp);
+                               rows.cnt, meters, ramp, alc, alc_params);
         }, flush, gain != nullptr, rows.slots != nullptr);
     }
     GT_LAUNCH_CHECK();
@@ -4556,8 +4656,8 @@ int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out
 }
 template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
 template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, hipStream_t);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, float*, const float*, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, float*, const float*, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {

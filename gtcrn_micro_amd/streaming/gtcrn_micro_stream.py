@@ -229,7 +229,8 @@ class StreamGTCRNMicro(GTCRNMicro):
         return self.engine(spec_t.device).stream_step(state, spec_t)
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
-                        count=None, resident=False, max_active=None, meters=False, g711=None, highband=None, ramp=False):
+                        count=None, resident=False, max_active=None, meters=False, g711=None, highband=None, ramp=False,
+                        alc=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -241,6 +242,9 @@ class StreamGTCRNMicro(GTCRNMicro):
         step and flush of it updates.
         ramp=True: the state owns state.gain_ramp, and a later state.set_atten_lim_db is spread over the next emitted block
         (16 ms at 16 kHz) instead of landing as a step; set_atten_lim_db(..., snap=True) changes at once.
+        alc= ("vad": the voice flag only; True: the default level control; a mapping of its settings): the state owns
+        state.alc and state.alc_params -- a speech-gated output gain, a limiter and state.voice() per stream, made at 16 kHz
+        in every step and flush (state.set_alc, state.alc_gain_db(), state.reset_alc()); not together with highband=.
         state=, slots= (int32 device tensor), count= (device int32, optional): a stream JOINS -- the named slots of the
         existing 16 kHz `state` are reset to the start of a clip (Engine.wave_stream_reset_slots, a capturable kernel) and
         `state` is returned; the other slots are not touched.  Rate states and plain packet states cannot be addressed by
@@ -254,6 +258,8 @@ class StreamGTCRNMicro(GTCRNMicro):
         band above 8 kHz is carried around the model (state.set_highband_gain changes it while the streams run): the rate
         form without packet= (Engine.new_rate_state), the packet form and the resident packet slots with it
         (Engine.new_packet_state / new_packet_slot_state; not with g711=).  None: that band is not in the output."""
+        if _lib._alc_on(alc) and slots is not None:
+            raise _lib.GtcrnError("alc= is given when a state is made, not when slots= resets some of its streams")
         if highband is not None and slots is not None:
             raise _lib.GtcrnError("highband= is given when a state is made, not when slots= resets some of its streams")
         if g711 is not None and (packet is None or slots is not None):
@@ -271,15 +277,16 @@ class StreamGTCRNMicro(GTCRNMicro):
             if packet is None:
                 raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
             return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
-                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband, ramp=ramp)
+                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband, ramp=ramp, alc=alc)
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
-                                        g711=g711, highband=highband, ramp=ramp)
+                                        g711=g711, highband=highband, ramp=ramp, alc=alc)
         if int(fs) != 16000:
-            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband, ramp=ramp)
+            return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband, ramp=ramp,
+                                      alc=alc)
         if highband is not None:
             raise _lib.GtcrnError("highband= needs fs = 24000, 32000 or 48000: a 16 kHz stream has no band above 8 kHz")
-        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters, ramp=ramp)
+        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters, ramp=ramp, alc=alc)
 
     def step_wave(self, x, state, slots=None, count=None):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a

@@ -813,6 +813,116 @@ int gtcrn_level_dbov(double energy, double nsamples);
 int gtcrn_wave_stream_set_gain_ramp(gtcrn_model *m, float *d_ramp);
 int gtcrn_gain_ramp_host(float p, float g, float *out256);
 
+/* ---- level control: a speech-gated output gain, a limiter and a voice flag per stream ---------------------------------------
+ * The synthesis kernel that writes an output block holds the enhanced ("wet") block w, the aligned dry block x ("attenuation
+ * limit") and the block m it is about to store.  With level control it also decides, per block, whether the stream holds
+ * speech (from the wet energy: the evidence a model-based voice activity decision wants), moves a per-stream gain towards a
+ * target level while the stream is voiced, holds the block under a ceiling, and stores y = gain * m instead of m.  No launch,
+ * no pass over the audio and no state layout is added.
+ *
+ * Every operation below is ONE correctly rounded fp32 operation (multiply, add, subtract, divide, square root, min, max,
+ * compare); no fused multiply-add is formed and no log / exp runs on the device, so a numpy float32 statement reproduces the
+ * outputs and the records bit for bit (tests/alc_checker.py).
+ *
+ * Parameters.  d_alc_params: caller-owned device memory, 16 floats, 16-byte aligned, ONE set for the states a call steps; read
+ * at every launch as wave-uniform values; may be rewritten between calls and between replays of a captured graph.
+ *     word 0  theta   absolute block-energy floor, 256 * 10^(floor_dbov / 10), clamped to >= 1e-30
+ *     word 1  rho     wet / dry energy ratio, 10^(ratio_db / 10)
+ *     word 2  H       hangover in blocks, ceil(hang_ms / 16), integer-valued
+ *     word 3  alpha   smoothing of the speech energy, in [0, 1]
+ *     word 4  T       target block energy, 256 * 10^(target_dbov / 10)
+ *     word 5  a_min   lowest gain, 10^(min_gain_db / 20), clamped to (0, 1]
+ *     word 6  a_max   highest gain, 10^(max_gain_db / 20), clamped to >= 1
+ *     word 7  d_up    per-block rise factor, 10^(rise_db_s * 0.016 / 20) >= 1
+ *     word 8  d_dn    per-block fall factor, 10^(-fall_db_s * 0.016 / 20) <= 1
+ *     word 9  c       ceiling amplitude, 10^(ceiling_dbov / 20)
+ *     word 10 mode    1.0: the gain is applied; 0.0: measure only (the voice flag and the counts; y = m)
+ *     words 11..15    reserved, zero
+ * gtcrn_alc_params_host makes the words from a gtcrn_alc_config on the host: double arithmetic, one rounding to float per
+ * word, the clamps above; GTCRN_ERR_ARG for a null pointer, a non-finite field, min_gain_db > max_gain_db, a negative slew
+ * rate or hang_ms, alpha outside [0, 1] or a mode other than 0 / 1.  Defaults (GTCRN_ALC_DEFAULTS): target -26 dBov, gain
+ * range -6 .. +24 dB, rise 6 dB/s, fall 30 dB/s, ceiling -1 dBov, floor -45 dBov, ratio -10 dB, hangover 200 ms, alpha 1/16.
+ *
+ * Record.  d_alc: caller-owned device memory, 8 floats per stream or slot, 32-byte aligned, indexed as the dry gains and the
+ * meters are (row n of a contiguous call, d_slots[i] of a slot call, the packet forms' row tables likewise).
+ *     word 0  a       the gain at which the stream's last emitted block ended
+ *     word 1  S       the smoothed speech block energy (0: no estimate yet)
+ *     word 2  hang    blocks of hangover left
+ *     word 3  voice   1.0 or 0.0 for the last emitted block
+ *     word 4  voiced  blocks counted as voiced
+ *     word 5  blocks  blocks counted
+ *     words 6..7      reserved, zero
+ * The record is NOT part of any state: every *_state_bytes and GTCRN_ABI_VERSION (1) are what they were.
+ *
+ * gtcrn_wave_stream_set_alc stores both addresses in the model, as gtcrn_wave_stream_set_meters stores d_meters; both NULL,
+ * the default, gives the launches of before, and nothing of this section is read or written.  One NULL and one set, a
+ * misaligned address or a null model is GTCRN_ERR_ARG; no device is touched.
+ *
+ * Per emitted block, in hop order.  w_i: the wet sample; x_i: the dry sample of "attenuation limit"; m_i: the sample the call
+ * would store without level control -- wave_mix(beta_i, x_i, w_i) with gains (beta_i ramped as "gain ramps" says), w_i without.
+ *   1. E_w = sum w_i^2 and E_x = sum x_i^2 in the meters' order (lane l holds samples 2l, 2l+1, 128+2l, 129+2l and sums
+ *      ((s0^2 + s1^2) + s2^2) + s3^2; then the xor butterfly over lane distances 1, 2, 4, 8, 16, 32); pk = max |m_i|.
+ *   2. Structural zero, the first block of a stream (c0 + h == 0): the record becomes {1, 0, 0, 0, 0, 0, 0, 0} and the output is
+ *      zeros; steps 3..11 do not run.  So a stream that joins starts fresh and no reset entry point changed.  A flush that has
+ *      no block emits zeros and leaves the record alone.
+ *   3. Non-finite block -- any of E_w, E_x, pk not <= FLT_MAX: a0 = a1 = a, voice = 0, and steps 4..8 do not run: S, hang and
+ *      a stay as they are (finite whatever a stream is fed; the stream recovers without a reset).
+ *   4. speech = E_w >= theta && E_w >= fl(rho * E_x).
+ *   5. speech: hang = H, voice = 1.  Else hang > 0: hang = hang - 1, voice = 1.  Else voice = 0.
+ *   6. speech: S = (S == 0) ? E_w : fl(S + fl(alpha * fl(E_w - S))).  Hangover blocks do not move S.
+ *   7. a_t = a.  If voice && S > 0:  a* = min(max(sqrt(T / S), a_min), a_max),  a_t = min(max(a*, fl(a d_dn)), fl(a d_up)).
+ *      The gain moves only while the stream is voiced: pauses are not pumped.
+ *   8. Limiter.  If pk > 0 && fl(pk * max(a, a_t)) > c:  L = max(a_min, c / pk),  a0 = min(a, L),  a1 = min(a_t, L); else
+ *      a0 = a, a1 = a_t.  The one place a gain step may land between two samples (a0 != a); no look-ahead, no latency.  The
+ *      limiter never goes below a_min: past that the int16 rounding saturates as it does without level control.
+ *   9. mode == 0: a0 = a1 = 1.
+ *  10. y_i = fl(gain_ramp_at(a0, a1, i) * m_i), gain_ramp_at the function of "gain ramps".  y_i goes to the store (one int16
+ *      rounding in the PCM16 forms, companding in the G.711 forms) and, where meters are set, to the meters (E_dry stays the
+ *      dry block's).
+ *  11. a = a1, voiced += voice, blocks += 1.
+ *
+ * What follows.
+ *   a stays in [a_min, a_max] and S stays finite, always, while the range words are not narrowed.  After a rewrite that puts
+ *     a outside the new range (a_max lowered below a, or a_min raised above it) nothing snaps: a moves back into the range at
+ *     the slew rate (d_dn or d_up per block) over the following voiced blocks and holds where it is while the stream is not
+ *     voiced; from the block at which it is inside the range again it stays inside.
+ *   With mode == 0 the outputs, every state tensor, the meters and the ramp words equal the call without level control bit
+ *     for bit (1 * m is m); the record still carries voice, voiced, blocks, S and hang, and a == 1.
+ *   The record does not depend on how the hops are cut into calls.  Slot and contiguous forms give the same bits.  Rows a
+ *     call does not step are neither read nor written.
+ *   A NaN or Inf in one stream moves no bit of another stream's output or record ("non-finite input").
+ *   Rate, packet and G.711 forms: the gain is made at 16 kHz inside the wave step and passes the outbound stage like
+ *     everything else.  Not together with the high band, whose formulas assume the 16 kHz hand-off at unit gain: while the
+ *     model holds a level-control address every gtcrn_rate_stream_step_hb* and gtcrn_packet_stream_step*_hb* call returns
+ *     GTCRN_ERR_STATE and launches nothing.
+ *   Graph capture: both pointers are captured kernel arguments; a captured step follows parameter words rewritten between
+ *     replays.
+ *   A launch with level control is timed in the row of the form it stands in for (k_wave_synthesis, k_wave_synthesis_mix or
+ *     k_wave_synthesis_meter), as a ramped launch is: the timing list is what it was.
+ *
+ * gtcrn_alc_block_host is a pure host function: one block (steps 1, 3..11; the caller handles step 2) through the functions the
+ * kernel compiles -- params16 and the 256-sample blocks w, x, m in, y out, record8 advanced in place.
+ * Out of scope: gtcrn_forward_wave* (offline), the spectrogram-level and _quant calls, one parameter set per stream, a
+ * per-stream on / off other than separate states. */
+typedef struct gtcrn_alc_config {
+    double target_dbov;    /* the level the voiced blocks are moved to */
+    double min_gain_db;    /* gain range */
+    double max_gain_db;
+    double rise_db_s;      /* slew rates of the gain, dB per second */
+    double fall_db_s;
+    double ceiling_dbov;   /* the limiter's ceiling */
+    double floor_dbov;     /* a block below this wet level is not speech */
+    double ratio_db;       /* ... nor one whose wet / dry energy ratio is below this */
+    double hang_ms;        /* hangover */
+    double alpha;          /* smoothing of the speech energy */
+    int mode;              /* 1: apply the gain; 0: measure only */
+} gtcrn_alc_config;
+#define GTCRN_ALC_DEFAULTS {-26.0, -6.0, 24.0, 6.0, 30.0, -1.0, -45.0, -10.0, 200.0, 0.0625, 1}
+int gtcrn_wave_stream_set_alc(gtcrn_model *m, float *d_alc, const float *d_alc_params);
+int gtcrn_alc_params_host(const gtcrn_alc_config *config, float *out16);
+int gtcrn_alc_block_host(const float *params16, float *record8, const float *w256, const float *x256, const float *m256,
+                         float *y256);
+
 /* ---- non-finite input: what a NaN or Inf in one stream may touch ---------------------------------------------------------
  * The library seats unrelated callers side by side -- four or seven streams in a workgroup, MFMA tiles that straddle two
  * streams, time spans that run across utterance boundaries -- and a float sample is whatever the caller sent.  The contract
