@@ -442,6 +442,35 @@ def _alc_without_highband(alc, highband):
         raise GtcrnError("alc= and highband= do not go together: the high band's formulas assume the 16 kHz hand-off at unit gain")
 
 
+def _attach_live(st, atten_lim_db, meters, ramp, alc):
+    """The options of a fresh state behind its reset, in this order: the limit, the meter records (True: new zeroed ones;
+    else the records, or None, of the wave state it was made from), the ramp words and the level control."""
+    import torch
+    if atten_lim_db is not None:
+        st.set_atten_lim_db(atten_lim_db)
+    st.meters = torch.zeros((st.n, 4), device=st.window.device, dtype=torch.float32) if meters is True else meters
+    if ramp:
+        st._new_gain_ramp()
+    if _alc_on(alc):
+        st._new_alc(alc)
+    return st
+
+
+def _stream_range(n, lo, hi):
+    """lo, hi (None: n) of a call on streams lo..hi-1 of n, as ints."""
+    hi = n if hi is None else int(hi)
+    lo = int(lo)
+    if not 0 <= lo < hi <= n:
+        raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {n})")
+    return lo, hi
+
+
+def _entry(name, x):
+    """The entry point `name` for float32 rows x, its _pcm16 twin for int16 ones."""
+    import torch
+    return getattr(lib(), name + "_pcm16" if x.dtype == torch.int16 else name)
+
+
 def _gains_of(db, n):
     """db: None, a number, or a sequence of n of them -> a float (one gain for all) or a float32 array of n gains."""
     if db is None or np.isscalar(db):
@@ -768,10 +797,7 @@ class Engine:
         self._check_on_device(state, "state")
         if state.dim() != 2 or state.shape[1] != self.state_bytes() // 4 or not state.is_contiguous():
             raise GtcrnError(f"state must be a contiguous (N, {self.state_bytes() // 4}) tensor of new_state")
-        hi = state.shape[0] if hi is None else int(hi)
-        lo = int(lo)
-        if not 0 <= lo < hi <= state.shape[0]:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.shape[0]})")
+        lo, hi = _stream_range(state.shape[0], lo, hi)
         with self._dev():
             _check(lib().gtcrn_stream_reset(self._h, state[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
 
@@ -832,15 +858,13 @@ class Engine:
         st = WaveStreamState(self.new_state(n),
                              torch.empty((n, self.wave_state_bytes() // 4), device=win.device, dtype=torch.float32), win)
         self.wave_stream_reset(st)
-        if atten_lim_db is not None:
-            st.set_atten_lim_db(atten_lim_db)
-        if meters:
-            st.meters = torch.zeros((n, 4), device=win.device, dtype=torch.float32)
-        if ramp:
-            st._new_gain_ramp()
-        if _alc_on(alc):
-            st._new_alc(alc)
-        return st
+        return _attach_live(st, atten_lim_db, True if meters else None, ramp, alc)
+
+    def _bind_live(self, state):
+        """Ahead of every step or flush through a state: its meters, ramp words and level control go to the model."""
+        self._set_meters(state)
+        self._set_gain_ramp(state)
+        self._set_alc(state)
 
     def _set_alc(self, state):
         """Hands the state's level-control records and parameter words to the model ahead of a step or flush, or clears
@@ -873,10 +897,7 @@ class Engine:
 
     def wave_stream_reset(self, state, lo=0, hi=None):
         """Resets streams lo..hi-1 (both states) to the start of a new clip."""
-        hi = state.n if hi is None else int(hi)
-        lo = int(lo)
-        if not 0 <= lo < hi <= state.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        lo, hi = _stream_range(state.n, lo, hi)
         with self._dev():
             _check(lib().gtcrn_wave_stream_reset(self._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
                                                  hi - lo, _stream_ptr()))
@@ -906,54 +927,41 @@ class Engine:
             raise GtcrnError(f"out must be a {like.dtype} tensor of shape ({like.shape[0]}, {cols}) with contiguous rows")
         return out
 
+    def _wave_call(self, name, state, x, out, rows, r=None):
+        """gtcrn_wave_stream_<name>, or its _limited / _pcm16 twin, on checked rows: x holds a step's hops (r None) or a flush's
+        tails of r samples; `rows` names the streams -- (slots, count, max_active) of a _slots call, in front of the samples,
+        or (nstreams[, nhops]) behind them."""
+        io = (x.data_ptr() if r != 0 else None, x.stride(0) if r != 0 else 0, *(() if r is None else (r,)), out.data_ptr(),
+              out.stride(0))
+        gain = () if state.dry_gain is None else (state.dry_gain.data_ptr(),)
+        if name.endswith("_slots"):
+            args = rows + io + (gain or (None,))
+        else:
+            args, name = io + rows + gain, name + ("_limited" if gain else "")
+        self._bind_live(state)
+        with self._dev():
+            _check(_entry("gtcrn_wave_stream_" + name, x)(self._h, state.model.data_ptr(), state.wave.data_ptr(), *args,
+                                                          state.window.data_ptr(), _stream_ptr()))
+        return out
+
     def wave_stream_step(self, state, x, out=None):
         """x (N, 256*nhops) float32 or int16 -> the enhanced (N, 256*nhops), same dtype, one hop late (call 0 of a
         stream emits zeros).  Asynchronous on the current stream; no allocation when `out` is given and
         reserve(N, nhops) was called (capturable)."""
-        import torch
         x = self._wave_rows(state, x, "x")
         L = x.shape[1]
         if L < 256 or L % 256:
             raise GtcrnError(f"x must hold a whole number of 256-sample hops per stream, got {L}")
-        out = self._wave_out(out, x, L)
-        pcm = x.dtype == torch.int16
-        args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(),
-                out.stride(0), state.n, L // 256)
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
-        with self._dev():
-            if state.dry_gain is None:
-                fn = lib().gtcrn_wave_stream_step_pcm16 if pcm else lib().gtcrn_wave_stream_step
-                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
-            else:
-                fn = lib().gtcrn_wave_stream_step_limited_pcm16 if pcm else lib().gtcrn_wave_stream_step_limited
-                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
-        return out
+        return self._wave_call("step", state, x, self._wave_out(out, x, L), (state.n, L // 256))
 
     def wave_stream_flush(self, state, tail, out=None):
         """tail (N, r) float32 or int16, r = 0..255: the samples after the last whole hop -> the last 256 enhanced
         samples of every stream.  Ends the streams (reset them before reuse)."""
-        import torch
         tail = self._wave_rows(state, tail, "tail")
         r = tail.shape[1]
         if r > 255:
             raise GtcrnError(f"the tail holds 0..255 samples, got {r}: push whole hops with wave_stream_step first")
-        out = self._wave_out(out, tail, 256)
-        pcm = tail.dtype == torch.int16
-        args = (self._h, state.model.data_ptr(), state.wave.data_ptr(), tail.data_ptr() if r else None,
-                tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), state.n)
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
-        with self._dev():
-            if state.dry_gain is None:
-                fn = lib().gtcrn_wave_stream_flush_pcm16 if pcm else lib().gtcrn_wave_stream_flush
-                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
-            else:
-                fn = lib().gtcrn_wave_stream_flush_limited_pcm16 if pcm else lib().gtcrn_wave_stream_flush_limited
-                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
-        return out
+        return self._wave_call("flush", state, tail, self._wave_out(out, tail, 256), (state.n,), r)
 
     # ---- stream slots (contract: include/gtcrn_micro_hip.h, "stream slots") ------------------------------------------
     def _slot_args(self, slots, count, max_active):
@@ -1038,38 +1046,17 @@ class Engine:
         """One hop for the rows a call names: x (M, 256) float32 or int16, row i = the stream in slot slots[i] of `state`
         -> (M, 256), same dtype, each stream one hop late.  Applies state.dry_gain (per slot) when set.  Asynchronous; no
         allocation when `out` is given and reserve(M, 1) was called (capturable)."""
-        import torch
         x, m, cnt = self._slot_rows(state, slots, x, count, max_active, "x", 256)
-        out = self._wave_out(out, x, 256)
-        fn = lib().gtcrn_wave_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_wave_stream_step_slots
-        gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
-        with self._dev():
-            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m, x.data_ptr(), x.stride(0),
-                      out.data_ptr(), out.stride(0), gain, state.window.data_ptr(), _stream_ptr()))
-        return out
+        return self._wave_call("step_slots", state, x, self._wave_out(out, x, 256), (slots.data_ptr(), cnt, m))
 
     def wave_stream_flush_slots(self, state, slots, tail, count=None, out=None, max_active=None):
         """tail (M, r), r = 0..255: the samples after the last whole hop of the named streams -> their last 256 enhanced
         samples.  Ends those streams (wave_stream_reset_slots before a slot is reused); the others are not touched."""
-        import torch
         tail, m, cnt = self._slot_rows(state, slots, tail, count, max_active, "tail")
         r = tail.shape[1]
         if r > 255:
             raise GtcrnError(f"the tail holds 0..255 samples, got {r}: push whole hops with wave_stream_step_slots first")
-        out = self._wave_out(out, tail, 256)
-        fn = lib().gtcrn_wave_stream_flush_slots_pcm16 if tail.dtype == torch.int16 else lib().gtcrn_wave_stream_flush_slots
-        gain = state.dry_gain.data_ptr() if state.dry_gain is not None else None
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
-        with self._dev():
-            _check(fn(self._h, state.model.data_ptr(), state.wave.data_ptr(), slots.data_ptr(), cnt, m,
-                      tail.data_ptr() if r else None, tail.stride(0) if r else 0, r, out.data_ptr(), out.stride(0), gain,
-                      state.window.data_ptr(), _stream_ptr()))
-        return out
+        return self._wave_call("flush_slots", state, tail, self._wave_out(out, tail, 256), (slots.data_ptr(), cnt, m), r)
 
     def wave_stream_reset_slots(self, state, slots, count=None, max_active=None):
         """Resets the named slots (both states) to the start of a new clip, with a kernel: asynchronous and capturable."""
@@ -1168,14 +1155,7 @@ class Engine:
             st.hb_gain = torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.float32)
             st.set_highband_gain(highband)
         self.rate_stream_reset(st)
-        if atten_lim_db is not None:
-            st.set_atten_lim_db(atten_lim_db)
-        st.meters = ws.meters
-        if ramp:
-            st._new_gain_ramp()
-        if _alc_on(alc):
-            st._new_alc(alc)
-        return st
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
 
     def rate_stream_reserve(self, state, nhops):
         """Sizes every buffer a rate step of `nhops` hops needs: after it a step allocates nothing (capturable)."""
@@ -1183,12 +1163,9 @@ class Engine:
 
     def rate_stream_reset(self, state, lo=0, hi=None):
         """Resets streams lo..hi-1 (all three states) to the start of a new clip."""
-        hi = state.n if hi is None else int(hi)
-        lo = int(lo)
         if not isinstance(state, RateStreamState):
             raise GtcrnError("state must come from new_rate_state")
-        if not 0 <= lo < hi <= state.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        lo, hi = _stream_range(state.n, lo, hi)
         with self._dev():
             _check(lib().gtcrn_rate_stream_reset(self._h, state.rs_in._h, state.rs_out._h, state.model[lo:hi].data_ptr(),
                                                  state.wave[lo:hi].data_ptr(), state.rate[lo:hi].data_ptr(), hi - lo,
@@ -1201,7 +1178,6 @@ class Engine:
         same dtype, state.latency samples late.  Asynchronous on the current stream; no allocation when `out` is given
         and rate_stream_reserve(state, nhops) was called.  A state with highband= runs gtcrn_rate_stream_step_hb: `out`
         must not overlap x (the call is not legal in place)."""
-        import torch
         if not isinstance(state, RateStreamState):
             raise GtcrnError("state must come from new_rate_state")
         x = self._wave_rows(state, x, "x")
@@ -1209,23 +1185,18 @@ class Engine:
         if L < state.hop or L % state.hop:
             raise GtcrnError(f"x must hold a whole number of {state.hop}-sample hops per stream, got {L}")
         out = self._wave_out(out, x, L)
-        pcm = x.dtype == torch.int16
         args = (self._h, state.rs_in._h, state.rs_out._h, state.model.data_ptr(), state.wave.data_ptr(),
                 state.rate.data_ptr(), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), state.n, L // state.hop)
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
+        win, gain = state.window.data_ptr(), None if state.dry_gain is None else state.dry_gain.data_ptr()
+        self._bind_live(state)
         with self._dev():
             if state.hb is not None:
-                fn = lib().gtcrn_rate_stream_step_hb_pcm16 if pcm else lib().gtcrn_rate_stream_step_hb
-                _check(fn(*args, state.dry_gain.data_ptr() if state.dry_gain is not None else None, state.window.data_ptr(),
-                          state.hb.data_ptr(), state.hb_gain.data_ptr(), _stream_ptr()))
-            elif state.dry_gain is None:
-                fn = lib().gtcrn_rate_stream_step_pcm16 if pcm else lib().gtcrn_rate_stream_step
-                _check(fn(*args, state.window.data_ptr(), _stream_ptr()))
+                _check(_entry("gtcrn_rate_stream_step_hb", x)(*args, gain, win, state.hb.data_ptr(), state.hb_gain.data_ptr(),
+                                                              _stream_ptr()))
+            elif gain is None:
+                _check(_entry("gtcrn_rate_stream_step", x)(*args, win, _stream_ptr()))
             else:
-                fn = lib().gtcrn_rate_stream_step_limited_pcm16 if pcm else lib().gtcrn_rate_stream_step_limited
-                _check(fn(*args, state.dry_gain.data_ptr(), state.window.data_ptr(), _stream_ptr()))
+                _check(_entry("gtcrn_rate_stream_step_limited", x)(*args, gain, win, _stream_ptr()))
         return out
 
     def rate_stream_handoff(self, state, nhops, which=0):
@@ -1274,24 +1245,14 @@ class Engine:
         st.g711 = law
         st._new_highband(nhb, highband)
         self.packet_stream_reset(st)
-        if atten_lim_db is not None:
-            st.set_atten_lim_db(atten_lim_db)
-        st.meters = ws.meters
-        if ramp:
-            st._new_gain_ramp()
-        if _alc_on(alc):
-            st._new_alc(alc)
-        return st
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
 
     def packet_stream_reset(self, state, lo=0, hi=None):
         """Resets streams lo..hi-1 (all three states).  They join the group at its current phase: state.phase zeros in
         front of their input, the group's latency."""
-        hi = state.n if hi is None else int(hi)
-        lo = int(lo)
         if not isinstance(state, PacketStreamState) or isinstance(state, PacketSlotState):
             raise GtcrnError("state must come from new_packet_state")
-        if not 0 <= lo < hi <= state.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {state.n})")
+        lo, hi = _stream_range(state.n, lo, hi)
         with self._dev():
             _check(lib().gtcrn_packet_stream_reset(state._h, state.model[lo:hi].data_ptr(), state.wave[lo:hi].data_ptr(),
                                                    state.pkt[lo:hi].data_ptr(), hi - lo, _stream_ptr()))
@@ -1312,18 +1273,16 @@ class Engine:
         if x.shape[1] != state.packet:
             raise GtcrnError(f"x must hold one packet of {state.packet} samples per stream, got {x.shape[1]}")
         out = self._wave_out(out, x, state.packet)
-        fn = lib().gtcrn_packet_stream_step_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step
+        fn = _entry("gtcrn_packet_stream_step", x)
         law = (state.g711,) if x.dtype == torch.uint8 else ()
         if law:
             fn = lib().gtcrn_packet_stream_step_g711
         hb = ()
         if state.hb is not None:
-            fn = lib().gtcrn_packet_stream_step_hb_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_hb
+            fn = _entry("gtcrn_packet_stream_step_hb", x)
             hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
         state.last_hops = state.next_hops
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
+        self._bind_live(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), x.data_ptr(),
@@ -1376,14 +1335,7 @@ class Engine:
         st._new_highband(nhb, highband)
         if st.hb is not None:
             st.hb.zero_()
-        if atten_lim_db is not None:
-            st.set_atten_lim_db(atten_lim_db)
-        st.meters = ws.meters
-        if ramp:
-            st._new_gain_ramp()
-        if _alc_on(alc):
-            st._new_alc(alc)
-        return st
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
 
     def _packet_slot_args(self, state, slots, count):
         if not isinstance(state, PacketSlotState):
@@ -1414,18 +1366,15 @@ class Engine:
         if x.stride(1) != 1:
             x = x.contiguous()
         out = self._wave_out(out, x, state.packet)
-        fn = lib().gtcrn_packet_stream_step_slots_pcm16 if x.dtype == torch.int16 else lib().gtcrn_packet_stream_step_slots
+        fn = _entry("gtcrn_packet_stream_step_slots", x)
         law = (state.g711,) if x.dtype == torch.uint8 else ()
         if law:
             fn = lib().gtcrn_packet_stream_step_slots_g711
         hb = ()
         if state.hb is not None:
-            fn = (lib().gtcrn_packet_stream_step_slots_hb_pcm16 if x.dtype == torch.int16
-                  else lib().gtcrn_packet_stream_step_slots_hb)
+            fn = _entry("gtcrn_packet_stream_step_slots_hb", x)
             hb = (state.hb.data_ptr(), state.hb_gain.data_ptr())
-        self._set_meters(state)
-        self._set_gain_ramp(state)
-        self._set_alc(state)
+        self._bind_live(state)
         with self._dev():
             # (a one-row tensor may report any stride)
             _check(fn(state._h, state.model.data_ptr(), state.wave.data_ptr(), state.pkt.data_ptr(), state.phase.data_ptr(),
@@ -1584,10 +1533,7 @@ class WaveStreamState:
         On a state made with ramp=True the change is spread over the next emitted block of each stream; snap=True also
         writes state.gain_ramp[lo:hi], so the change lands at once, as it does without ramps."""
         import torch
-        hi = self.n if hi is None else int(hi)
-        lo = int(lo)
-        if not 0 <= lo < hi <= self.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        lo, hi = _stream_range(self.n, lo, hi)
         g = _gains_of(db, hi - lo)
         if self.dry_gain is None:
             self.set_dry_gain(torch.zeros((self.n,), device=self.model.device, dtype=torch.float32))
@@ -1630,10 +1576,7 @@ class WaveStreamState:
         """Writes the initial record {1, 0, 0, 0, 0, 0, 0, 0} to streams (slots) lo..hi-1, asynchronously on the current stream
         and without any allocation.  (A stream's first block does the same on the device: a join needs no call here.)"""
         a = self._leveled()
-        hi = self.n if hi is None else int(hi)
-        lo = int(lo)
-        if not 0 <= lo < hi <= self.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        lo, hi = _stream_range(self.n, lo, hi)
         a[lo:hi].zero_()
         a[lo:hi, 0].fill_(1.0)
 
@@ -1656,10 +1599,7 @@ class WaveStreamState:
         """Starts a new window for streams (slots) lo..hi-1: zeroes their records, asynchronously on the current stream and
         without any allocation (a memset: capturable)."""
         m = self._metered()
-        hi = self.n if hi is None else int(hi)
-        lo = int(lo)
-        if not 0 <= lo < hi <= self.n:
-            raise GtcrnError(f"stream range [{lo}, {hi}) outside [0, {self.n})")
+        lo, hi = _stream_range(self.n, lo, hi)
         m[lo:hi].zero_()
 
     def levels(self):

@@ -93,10 +93,7 @@ struct gtcrn_model {
     float* d_spec_b = nullptr;
     float* d_rate_a = nullptr;  // 16 kHz hand-offs of gtcrn_rate_stream_step (nstreams x 256 nhops each): k_rate_in -> wave step,
     float* d_rate_b = nullptr;  // wave step -> k_rate_out; sized by gtcrn_rate_stream_reserve
-    float* d_meters = nullptr;  // the caller's level-meter records (gtcrn_wave_stream_set_meters); NULL: no metering
-    float* d_ramp = nullptr;    // the caller's gain-ramp words (gtcrn_wave_stream_set_gain_ramp); NULL: gain changes step
-    float* d_alc = nullptr;     // the caller's level-control records and parameter words (gtcrn_wave_stream_set_alc); NULL: no
-    const float* d_alc_params = nullptr;   // level control
+    gtk::WaveOpts live;         // the caller's buffers of gtcrn_wave_stream_set_meters / _gain_ramp / _alc (gain: per call)
     long cap_rate = 0;          // capacity of each in (streams * hops)
     bool debug = false;
     bool debug_keep_fused = false;   // gtcrn_debug_enable(m, 2): phase stamps only -- single-frame steps stay ONE launch
@@ -664,7 +661,7 @@ int gtcrn_wave_stream_set_meters(gtcrn_model* m, float* d_meters) {
     if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_meters: null model");
     if (reinterpret_cast<uintptr_t>(d_meters) & 15)
         return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_meters: the records must be 16-byte aligned");
-    m->d_meters = d_meters;
+    m->live.meters = d_meters;
     return 0;
 }
 
@@ -672,7 +669,7 @@ int gtcrn_wave_stream_set_meters(gtcrn_model* m, float* d_meters) {
 // synthesis launch of a call that has gains.  Nothing is launched or read here.
 int gtcrn_wave_stream_set_gain_ramp(gtcrn_model* m, float* d_ramp) {
     if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_gain_ramp: null model");
-    m->d_ramp = d_ramp;
+    m->live.ramp = d_ramp;
     return 0;
 }
 // the host twin: the 256 gains of a block that ramps from p to g, from the function the kernel compiles
@@ -691,8 +688,8 @@ int gtcrn_wave_stream_set_alc(gtcrn_model* m, float* d_alc, const float* d_alc_p
         return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: the records must be 32-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_alc_params) & 15)
         return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_alc: the parameters must be 16-byte aligned");
-    m->d_alc = d_alc;
-    m->d_alc_params = d_alc_params;
+    m->live.alc = d_alc;
+    m->live.alc_params = d_alc_params;
     return 0;
 }
 // the parameter words of a configuration: double arithmetic, one rounding to float each
@@ -783,11 +780,10 @@ int refuse_three_launch_form(const std::string& w, const gtcrn_model* m) {
 }
 }  // namespace
 
-// Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis (mixed when d_gain is given, metered while
-// the model holds a meters address, ramped when d_gain is given while the model holds a ramp address, level-controlled while
-// the model holds a level-control address -- the last two timed in the row of the form they stand in for: the rate, packet and packet-slot forms come through here too) of n rows.
-// Without a table the rows are the n streams of a contiguous state range, nhops hops each; with one (the _slots calls)
-// they are the n = max_active rows it names, one hop.
+// Every gtcrn_wave_stream_* entry point: analysis -> the model step -> synthesis of n rows; the rate, packet and packet-slot
+// forms come through here too.  The synthesis takes the model's buffers (m->live) and the call's d_gain as one gtk::WaveOpts;
+// gtk::synth_mode picks the kernel from it and gtk::synth_timed_as the timing row.  Without a table the rows are the n
+// streams of a contiguous state range, nhops hops each; with one (the _slots calls) the n = max_active rows it names, one hop.
 extern "C++" template <typename S>
 static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wstate, const S* d_in, long in_stride, S* d_out,
                      long out_stride, int n, int nhops, bool flush, int r, const float* d_gain, const float* d_win,
@@ -819,9 +815,12 @@ static int wave_step(const char* who, gtcrn_model* m, void* d_state, void* d_wst
     rc = indexed ? fused_stream_step(m, m->d_spec_a, sb, sf, m->d_spec_b, sb, sf, n, ms, rows, s)
                  : run_model(m, m->d_spec_a, sb, sf, st, m->d_spec_b, sb, sf, st, n, nhops, ms, s);
     if (rc) return rc;
-    tm.begin(m->d_meters ? K_WAVE_SYNTHESIS_METER : d_gain ? K_WAVE_SYNTHESIS_MIX : K_WAVE_SYNTHESIS);
+    gtk::WaveOpts o = m->live;
+    o.gain = d_gain;
+    constexpr int row[] = {K_WAVE_SYNTHESIS, K_WAVE_SYNTHESIS_MIX, K_WAVE_SYNTHESIS_METER};      // Synth::Plain, Mix, Meter
+    tm.begin(row[(int)gtk::synth_timed_as(o)]);
     LAUNCH_TRY(gtk::launch_wave_synthesis<S>(m->d_spec_b, d_in, in_stride, d_out, out_stride, n, nhops, r, flush, ws, d_win,
-                                             m->d_twid, rows, d_gain, m->d_meters, m->d_ramp, m->d_alc, m->d_alc_params, s));
+                                             m->d_twid, rows, o, s));
     tm.end();
     return 0;
 }
@@ -1220,7 +1219,7 @@ static int rate_stream_impl(const char* who, gtcrn_model* m, gtcrn_resampler* in
         return fail(GTCRN_ERR_ARG, w + ": the input and output rows overlap (the high-band step is not legal in place)");
     int rc = check_model(m);
     if (rc) return rc;
-    if (hb && m->d_alc)      // (the high band's formulas assume the 16 kHz hand-off at unit gain)
+    if (hb && m->live.alc)     // (the high band's formulas assume the 16 kHz hand-off at unit gain)
         return fail(GTCRN_ERR_STATE, w + ": the high band does not go together with level control (gtcrn_wave_stream_set_alc)");
     hipStream_t s = (hipStream_t)stream;
     if ((rc = ensure_workspace(m, nstreams, nhops, s))) return rc;
@@ -1558,7 +1557,7 @@ static int packet_step(const char* who, gtcrn_packet_stream* ps, void* d_state, 
     gtcrn_model* m = ps->m;
     int rc = check_model(m);
     if (rc) return rc;
-    if (hb && m->d_alc)      // (the high band's formulas assume the 16 kHz hand-off at unit gain)
+    if (hb && m->live.alc)     // (the high band's formulas assume the 16 kHz hand-off at unit gain)
         return fail(GTCRN_ERR_STATE, w + ": the high band does not go together with level control (gtcrn_wave_stream_set_alc)");
     if (sl && (rc = refuse_three_launch_form(w, m))) return rc;           // (before the plan: nothing runs on a refusal)
     hipStream_t s = (hipStream_t)stream;

@@ -103,11 +103,57 @@ struct Rows {
     const int* slots = nullptr;
     const int* cnt = nullptr;
 };
+// The optional buffers of a live synthesis launch: device memory, per stream or (slot table) per SLOT; nullptr: off
+struct WaveOpts {
+    const float* gain = nullptr;          // the attenuation limit: one dry gain per stream
+    float* meters = nullptr;              // the level-meter records: 4 floats per stream, 16-byte aligned
+    float* ramp = nullptr;                // the gain ramps: one float per stream; without `gain` it is not touched
+    float* alc = nullptr;                 // the level control: 8 floats per stream, 32-byte aligned, and with them always
+    const float* alc_params = nullptr;    // the 16 parameter words
+};
+enum class Synth {      // what k_wave_synthesis does with them: one instantiation per mode and (S, FLUSH, IDX)
+    Plain,      // the enhanced block as it is
+    // The attenuation limit -- every emitted sample becomes wave_mix(gain[n], dry, sample), in float, before the int16 form's
+    // one rounding; the zeros of a first call or an empty flush stay zeros.  Hop h emits block c0 + h - 1: its dry samples
+    // are the ring's newest 256 (h == 0: the pairs this lane loads for the ring shift at nhops == 1) or input hop h - 1.
+    Mix,
+    // The level meters (include/gtcrn_micro_hip.h, "level meters") -- the record meters[4 slot .. 4 slot + 3] = {E_dry,
+    // E_out, peak, blocks} is read once, advanced per hop from the emitted floats y and Mix's dry samples x (both 0 for a
+    // structural zero block) and stored once by lane 0, before the flush's return.  gain is a run-time branch (null: no mix).
+    Meter,
+    // Mix / Meter with the gain ramps (include/gtcrn_micro_hip.h, "gain ramps"; gain and ramp both set) -- p = ramp[slot] is
+    // the dry gain at which the stream's last emitted block ended.  Both words are the same in every lane (made so for the
+    // compiler by a readfirstlane behind hop 0's transform, so `p != g` is a scalar branch and neither load is waited for
+    // before the first spectrum is fetched); where they differ, the block of hop 0 mixes sample i with gain_ramp_at(p, g, i)
+    // -- this lane's four samples i = 2m, 2m + 1 -- and every other block with g, as Mix does.  A structural zero block
+    // stays zeros.  Lane 0 stores g to ramp[slot] behind the hops, in front of the flush's return.
+    MixRamp, MeterRamp,
+    // The level control (include/gtcrn_micro_hip.h, "level control") -- gain, meters and ramp are run-time branches.  The
+    // wave holds the whole block -- this lane's four wet samples w, dry samples x and mixed samples m -- before the first
+    // store: E_w, E_x (alc_lane_sum, then wave_sum: the meters' order) and pk = max |m| come first, alc_decide (the host
+    // twin's body) advances the record and gives the block's two gains, and y_i = fl(gain_ramp_at(a0, a1, i) m_i) goes to the
+    // store and the meters.  The parameter words and the record become scalars behind hop 0's transform, as the ramp words
+    // do; lane 0 stores the record (two 16-byte stores) before the flush's return, not after an empty flush.
+    Alc
+};
+constexpr Synth synth_mode(const WaveOpts& o) {      // the ONLY place that turns the pointers into a mode
+    return o.alc ? Synth::Alc : o.gain && o.ramp ? (o.meters ? Synth::MeterRamp : Synth::MixRamp)
+         : o.meters ? Synth::Meter : o.gain ? Synth::Mix : Synth::Plain;
+}
+// The timing row of a launch (api.cpp): ramps and level control are timed in the row of the form they stand in for.
+constexpr Synth synth_timed_as(const WaveOpts& o) { return o.meters ? Synth::Meter : o.gain ? Synth::Mix : Synth::Plain; }
+// synth_mode over all 16 null / non-null combinations B; bit 0 of B: gain, 1: meters, 2: ramp, 3: alc with alc_params
+template <int... B>
+constexpr bool synth_is(Synth want, float x = 0.f) {
+    float* const p[2] = {nullptr, &x};
+    return ((synth_mode({p[B & 1], p[B >> 1 & 1], p[B >> 2 & 1], p[B >> 3], p[B >> 3]}) == want) && ...);
+}
+static_assert(synth_is<0, 4>(Synth::Plain) && synth_is<1>(Synth::Mix) && synth_is<2, 3, 6>(Synth::Meter));
+static_assert(synth_is<5>(Synth::MixRamp) && synth_is<7>(Synth::MeterRamp) && synth_is<8, 9, 10, 11, 12, 13, 14, 15>(Synth::Alc));
 // Gain ramps (contract: include/gtcrn_micro_hip.h, "gain ramps"): the dry gain of sample i = 0..255 of a block that ramps
 // from p, where the stream's last emitted block ended, to g -- fl(p + fl(fl(g - p) * r_i)), r_i = (i + 1) / 256 (exact), and
 // g itself at i == 255 or when p == g.  Three fp32 roundings, never a fused multiply-add (the pragma holds under any
-// -ffp-contract of the including file).  One body for the RAMP instantiations of k_wave_synthesis and for
-// gtcrn_gain_ramp_host.
+// -ffp-contract of the including file).  One body for the ramped modes of k_wave_synthesis and for gtcrn_gain_ramp_host.
 __host__ __device__ inline float gain_ramp_at(float p, float g, int i) {
 #pragma clang fp contract(off)
     if (p == g || i == 255) return g;
@@ -116,7 +162,7 @@ __host__ __device__ inline float gain_ramp_at(float p, float g, int i) {
     return p + s;
 }
 // Level control (contract: include/gtcrn_micro_hip.h, "level control"): the block rule, steps 3 .. 9 and 11, once a block's
-// three reductions are known.  One body for the ALC instantiations of k_wave_synthesis and for gtcrn_alc_block_host.  Every
+// three reductions are known.  One body for the Alc mode of k_wave_synthesis and for gtcrn_alc_block_host.  Every
 // operation is one correctly rounded fp32 operation (plain operators: the pragma keeps any -ffp-contract of the including
 // file from fusing them; `/` and sqrt are the IEEE ones on both sides); the finiteness test reads the bits, so it holds in
 // a file compiled with -fno-honor-nans.
@@ -186,22 +232,13 @@ __host__ __device__ inline void alc_decide(const AlcParams& P, AlcRecord& r, flo
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major
 // (N, nhops, 257, 2); synthesis (after the model step): spec -> out (N rows of out_stride, 256 nhops samples), advances
-// wstate (not on flush).  flush = the end-reflected last frame.  gain (optional, device, float[N]): the attenuation limit,
-// mixed into the emitted block by the MIX instantiations of k_wave_synthesis; nullptr: the plain ones.  meters (optional,
-// device, 4 floats per stream or slot, 16-byte aligned): the level-meter records, advanced by the METER instantiations, which
-// read `gain` at run time (nullptr or not); nullptr: the launches above.  ramp (optional, device, one float per stream or
-// slot, indexed as gain is): the gain ramps -- with gain AND ramp the RAMP instantiations run, which read ramp[idx], ramp the
-// call's first block from it to gain[idx] and store gain[idx] there; without either pointer ramp is not touched.  alc
-// (optional, device, 8 floats per stream or slot, 32-byte aligned) with alc_params (device, 16 floats): the level control --
-// the ALC instantiations run, one per (S, flush, indexed), which take gain, meters and ramp as run-time branches; nullptr:
-// the launches above.
+// wstate (not on flush).  flush = the end-reflected last frame.  o: the optional buffers; synth_mode(o) picks the kernel.
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
                          const float* win, const float* twid, float* spec, Rows rows, hipStream_t s);
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, float* ramp, float* alc, const float* alc_params, hipStream_t s);
+                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, WaveOpts o, hipStream_t s);
 // sample-rate conversion (gtcrn_resample / gtcrn_rate_stream_*): polyphase FIR, taps as a phase table of `up` rows of ntp
 // floats (ntp a multiple of 4, rows zero-padded; device memory, 16-byte aligned).  SI / SO = float or short (int16 PCM).
 constexpr int RS_THREADS = 256;

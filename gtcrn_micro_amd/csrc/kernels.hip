@@ -753,31 +753,9 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_analysis(const S* __res
 // One wave per stream, its hops in order: merge, inverse FFT, window and / 256 as k_istft; the overlap-add runs in
 // registers (lane's first-half samples 2m, 2m+1, m = lane + 64 q, q < 2, meet the previous frame's 256 + 2m, 256 + 2m + 1,
 // which the same lane holds at q + 2).  Then the state advances: tail, input ring (last 512 samples), hop counter.
-// FLUSH emits the stream's last block and leaves the wave state as it is (the stream has ended).
-// MIX: the attenuation limit -- every emitted sample becomes wave_mix(gain[n], dry, sample), in float, before the one
-// rounding of the int16 form; the zeros of a stream's first call and of an empty flush stay zeros.  The block of hop h is
-// block c0 + h - 1, so its dry samples are the ring's newest 256 (h == 0: the float2 pairs this lane loads for the ring
-// shift at nhops == 1 anyway) or hop h - 1 of this call's input rows.
-// METER: the level meters (include/gtcrn_micro_hip.h, "level meters") -- the stream's record meters[4 slot .. 4 slot + 3] =
-// {E_dry, E_out, peak, blocks} is read once, advanced hop by hop from the emitted floats y and the dry samples x that MIX
-// would use (both 0 for a structural zero block), and stored once by lane 0, in front of the flush's return.  The metered
-// instantiations take the limit as a wave-uniform run-time branch (MIX = false, gain may be null: the plain sample then).
+// FLUSH emits the stream's last block and leaves the wave state as it is (the stream has ended).  MODE: Synth (kernels.h).
 // wave_sum / wave_max: every lane ends with the same value, the xor butterfly over lane distances 1, 2, 4, 8, 16, 32 in
 // that order (an fp32 add is commutative, so both partners of a step round alike).
-// RAMP (with MIX or METER; gain and ramp both set): the gain ramps (include/gtcrn_micro_hip.h, "gain ramps") -- p = ramp[slot]
-// is the dry gain at which the stream's last emitted block ended.  Both words are the same in every lane (made so for the
-// compiler by a readfirstlane behind hop 0's transform, so `p != g` is a scalar branch and neither load is waited for before
-// the first spectrum is fetched); where they differ, the block of hop 0 mixes sample i with
-// gain_ramp_at(p, g, i) -- this lane's four samples i = 2m, 2m + 1 -- and every other block with g, as MIX does.  A structural
-// zero block stays zeros.  Lane 0 stores g to ramp[slot] behind the hops, in front of the flush's return.
-// ALC: the level control (include/gtcrn_micro_hip.h, "level control") -- one instantiation per (S, FLUSH, IDX), which takes
-// gain, meters and ramp as wave-uniform run-time branches (MIX = METER = RAMP = false).  The wave holds the whole block --
-// this lane's four wet samples w, dry samples x and mixed samples m -- before the first store: E_w, E_x (alc_lane_sum, then
-// wave_sum: the meters' order) and pk = max |m| come first, alc_decide (kernels.h, the host twin's body) advances the record
-// and gives the block's two gains, and y_i = fl(gain_ramp_at(a0, a1, i) m_i) goes to the store and to the meters.  The
-// sixteen parameter words and the record are loaded in front of the loop and made scalars behind hop 0's transform, as the
-// ramp words are; lane 0 stores the record (two 16-byte stores, 32 bytes in all) in front of the flush's return, not after an
-// empty flush.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) v = __fadd_rn(v, __shfl_xor(v, d));
@@ -788,7 +766,7 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
     return v;
 }
-template <typename S, bool FLUSH, bool MIX = false, bool IDX = false, bool METER = false, bool RAMP = false, bool ALC = false>
+template <typename S, bool FLUSH, bool IDX, Synth MODE>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
                                                                   int N, int nhops, int r, float* __restrict__ wstate,
@@ -801,9 +779,8 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                                                                   float* __restrict__ ramp,
                                                                   float* __restrict__ alc,
                                                                   const float* __restrict__ alc_params) {
-    static_assert(!(MIX && METER), "the metered instantiations branch on gain at run time");
-    static_assert(!ALC || !(MIX || METER || RAMP), "the level-control instantiations branch on gain, meters and ramp at run time");
-    static_assert(!RAMP || MIX || METER, "a ramp needs the mix");
+    constexpr bool MIX = MODE == Synth::Mix || MODE == Synth::MixRamp, METER = MODE == Synth::Meter || MODE == Synth::MeterRamp;
+    constexpr bool RAMP = MODE == Synth::MixRamp || MODE == Synth::MeterRamp, ALC = MODE == Synth::Alc;
     if constexpr (IDX) N = slot_count(cnt, N);
     __shared__ float2 s_tw[256];
     __shared__ float2 s_tw512[256];
@@ -4602,6 +4579,11 @@ static void with_flags(F&& f, bool b, R... rest) {
     if (b) with_flags<Bs..., true>(f, rest...);
     else with_flags<Bs..., false>(f, rest...);
 }
+template <Synth M = Synth::Plain, class F, class... R>      // the same with a synthesis mode m in front of the flags
+static void with_mode(F&& f, Synth m, R... flags) {
+    if (m == M) with_flags([&](auto... bs) { f(std::integral_constant<Synth, M>{}, bs...); }, flags...);
+    else if constexpr (M != Synth::Alc) with_mode<Synth((int)M + 1)>(f, m, flags...);
+}
 
 template <typename S>
 int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, bool flush, const float* wstate,
@@ -4620,44 +4602,23 @@ int launch_wave_analysis(const S* in, long in_stride, int N, int nhops, int r, b
 }
 template <typename S>
 int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out, long out_stride, int N, int nhops, int r,
-                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, const float* gain,
-                          float* meters, float* ramp, float* alc, const float* alc_params, hipStream_t s) {
+                          bool flush, float* wstate, const float* win, const float* twid, Rows rows, WaveOpts o, hipStream_t s) {
     if (rows.slots && nhops != 1) return (int)hipErrorInvalidValue;
     const int grid = (N + FFT_WAVES - 1) / FFT_WAVES;
     const float2* tw = reinterpret_cast<const float2*>(twid);
     // a mixed flush with r == 0 may come without a tail pointer: its one block takes its dry samples from the ring alone
-    if (alc) {                // the level-control instantiations read gain, meters and ramp at run time: one per (S, FLUSH, IDX)
-        with_flags([&](auto FLUSH, auto IDX) {
-            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, false, false, true>), dim3(grid),
-                               dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops,
-                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp, alc, alc_params);
-        }, flush, rows.slots != nullptr);
-    } else if (gain && ramp) {       // the ramped instantiations stand in for the mixed or the metered one: one per (S, FLUSH, IDX, METER)
-        with_flags([&](auto FLUSH, auto IDX, auto METER) {
-            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, !METER.value, IDX.value, METER.value, true>), dim3(grid),
-                               dim3(FFT_WAVES * 64), 0, s, spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops,
-                               flush ? r : 0, wstate, win, tw, gain, rows.slots, rows.cnt, meters, ramp, alc, alc_params);
-        }, flush, rows.slots != nullptr, meters != nullptr);
-    } else if (meters) {       // the metered instantiations read `gain` at run time: one per (S, FLUSH, IDX)
-        with_flags([&](auto FLUSH, auto IDX) {
-            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, false, IDX.value, true>), dim3(grid), dim3(FFT_WAVES * 64), 0, s,
-                               spec, in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain,
-                               rows.slots, rows.cnt, meters, ramp, alc, alc_params);
-        }, flush, rows.slots != nullptr);
-    } else {
-        with_flags([&](auto FLUSH, auto MIX, auto IDX) {
-            hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, MIX.value, IDX.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
-                               in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, gain, rows.slots,
-                               rows.cnt, meters, ramp, alc, alc_params);
-        }, flush, gain != nullptr, rows.slots != nullptr);
-    }
+    with_mode([&](auto MODE, auto FLUSH, auto IDX) {
+        hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, IDX.value, MODE.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
+                           in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, o.gain, rows.slots,
+                           rows.cnt, o.meters, o.ramp, o.alc, o.alc_params);
+    }, synth_mode(o), flush, rows.slots != nullptr);
     GT_LAUNCH_CHECK();
     return 0;
 }
 template int launch_wave_analysis<float>(const float*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
 template int launch_wave_analysis<short>(const short*, long, int, int, int, bool, const float*, const float*, const float*, float*, Rows, hipStream_t);
-template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, float*, const float*, hipStream_t);
-template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, const float*, float*, float*, float*, const float*, hipStream_t);
+template int launch_wave_synthesis<float>(const float*, const float*, long, float*, long, int, int, int, bool, float*, const float*, const float*, Rows, WaveOpts, hipStream_t);
+template int launch_wave_synthesis<short>(const float*, const short*, long, short*, long, int, int, int, bool, float*, const float*, const float*, Rows, WaveOpts, hipStream_t);
 
 int launch_istft_adjoint(const float* gwave, int B, int T, const float* win, const float* twid, float* gspec, long sb,
                          long sf, long st, hipStream_t s) {

@@ -4,12 +4,15 @@ metrics.hip, batch.hip, reverb.hip) between two source trees, kernel by kernel.
     hipcc --offload-arch=gfx950 <the flags gtcrn_micro_amd/build.py gives that file: the common ones and its per_file
           entry, if it has one> --cuda-device-only -S OLD/gtcrn_micro_amd/csrc/FILE.hip -o old.s
           (and the same for the new tree -> new.s)
-    python tools/asm_compare.py old.s new.s [--drop-arg false]
+    python tools/asm_compare.py old.s new.s [--drop-arg false] [--rename PATTERN REPLACEMENT]...
 
 A kernel is its instruction lines in order: comments and assembler directives dropped, branch labels renumbered by
-position.  Kernels pair up by demangled name without the argument list.  --drop-arg VALUE: a kernel template of the
+position.  Kernels pair up by demangled name without the argument list (cut at the first bracket outside the template
+arguments: an enum argument demangles as (gtk::Synth)3).  --drop-arg VALUE: a kernel template of the
 new file that gained one trailing template argument pairs with the old kernel when that argument is VALUE (only where
-the old file has no kernel of the full name).  Kernels only the new file has are counted, not compared.
+the old file has no kernel of the full name).  --rename PATTERN REPLACEMENT (any number of them): an old kernel whose name
+the regular expression matches pairs with the new kernel of the name re.sub gives, e.g. a template whose flags became one
+enum: --rename '<(\w+), false, true>' '<\1, (ns::Mode)2>'.  Kernels only the new file has are counted, not compared.
 Prints one row per kernel of the old file and a summary line; exit status 1 if any kernel differs or is missing.
 Needs c++filt on the PATH and no GPU.
 """
@@ -36,7 +39,16 @@ def kernels(path):
 def demangled(names):
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
     # (batch.hip keeps its kernels in an unnamed namespace: that bracket is part of the name, not an argument list)
-    return [re.sub(r"\(.*$", "", d.replace("(anonymous namespace)", "{anonymous}")) for d in r.stdout.splitlines()]
+    return [without_args(d.replace("(anonymous namespace)", "{anonymous}")) for d in r.stdout.splitlines()]
+
+
+def without_args(d):
+    depth = 0
+    for i, c in enumerate(d):
+        depth += (c == "<") - (c == ">")
+        if c == "(" and depth == 0:
+            return d[:i]
+    return d
 
 
 def main():
@@ -44,6 +56,7 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--drop-arg", default=None)
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("PATTERN", "REPLACEMENT"))
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
     old = dict(zip(demangled(list(old)), old.values()))
@@ -53,17 +66,25 @@ def main():
             short = re.sub(r", %s>$" % re.escape(a.drop_arg), ">", k)
             if short != k and k not in old and short in old and short not in new:
                 new[short] = new.pop(k)
+    was = {}                 # new name -> old name of the kernels --rename pairs (the first pattern that matches)
+    for k in list(old):
+        to = next((re.sub(pat, repl, k) for pat, repl in a.rename if re.search(pat, k)), k)
+        if to != k:
+            if to in old:
+                sys.exit(f"--rename gives two old kernels the name {to}")
+            old[to], was[to] = old.pop(k), k
     same = bad = 0
     for k in sorted(old):
+        name = f"{was[k]} -> {k}" if k in was else k
         if k not in new:
             bad += 1
-            print(f"MISSING {len(old[k]):6d}            {k}")
+            print(f"MISSING {len(old[k]):6d}            {name}")
         elif old[k] == new[k]:
             same += 1
-            print(f"same    {len(old[k]):6d}            {k}")
+            print(f"same    {len(old[k]):6d}            {name}")
         else:
             bad += 1
-            print(f"DIFFER  {len(old[k]):6d} -> {len(new[k]):6d}  {k}")
+            print(f"DIFFER  {len(old[k]):6d} -> {len(new[k]):6d}  {name}")
     print(f"{same} of {len(old)} kernels compile to the same instructions ({sum(map(len, old.values()))} lines); "
           f"{bad} differ or are missing; {len(set(new) - set(old))} kernels are new")
     return 1 if bad else 0
