@@ -153,6 +153,13 @@ def lib():
         L.gtcrn_wave_stream_set_alc.argtypes = [_vp, _vp, _vp]
         L.gtcrn_alc_params_host.argtypes = [ctypes.POINTER(AlcConfig), fp]
         L.gtcrn_alc_block_host.argtypes = [fp, fp, fp, fp, fp, fp]
+    # tone guard (an earlier library has none of these: only a state asked for with tones= fails, at its creation)
+    if hasattr(L, "gtcrn_wave_stream_set_tone"):
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.gtcrn_wave_stream_set_tone.argtypes = [_vp, _vp, _vp, _vp]
+        L.gtcrn_tone_params_host.argtypes = [ctypes.POINTER(ToneConfig), fp]
+        L.gtcrn_tone_table_host.argtypes = [fp]
+        L.gtcrn_tone_block_host.argtypes = [fp, fp, fp, fp, ctypes.POINTER(ctypes.c_int)]
     # G.711 payloads (an earlier library has none of these: a G.711 state or converter then fails at its first call)
     if hasattr(L, "gtcrn_packet_stream_step_g711"):
         L.gtcrn_packet_stream_step_g711.argtypes = [_vp, _vp, _vp, _vp, _vp, cl, _vp, cl, ci, ci, _vp, _vp]
@@ -442,9 +449,83 @@ def _alc_without_highband(alc, highband):
         raise GtcrnError("alc= and highband= do not go together: the high band's formulas assume the 16 kHz hand-off at unit gain")
 
 
-def _attach_live(st, atten_lim_db, meters, ramp, alc):
+class ToneConfig(ctypes.Structure):
+    """gtcrn_tone_config of include/gtcrn_micro_hip.h, "tone guard"."""
+    _fields_ = [(k, ctypes.c_double) for k in ("min_dbov", "twist_db", "dominance_db", "pair_purity", "single_purity")] + \
+               [(k, ctypes.c_int) for k in ("guard_blocks", "digit_blocks", "single_blocks", "hold_blocks", "mode", "singles")]
+
+
+TONE_DEFAULTS = dict(min_dbov=-45.0, twist_db=8.0, dominance_db=8.0, pair_purity=0.6, single_purity=0.8, guard_blocks=1,
+                     digit_blocks=2, single_blocks=4, hold_blocks=1, mode=1, singles=1)     # GTCRN_TONE_DEFAULTS
+TONE_FREQS = (697, 770, 852, 941, 1209, 1336, 1477, 1633, 1100, 2100)
+
+
+def _tone_fields(tones):
+    """tones= of the state constructors -> the config's fields: "detect" (no guard), True (the defaults) or a mapping."""
+    if isinstance(tones, str):
+        if tones != "detect":
+            raise GtcrnError(f'tones must be None, "detect", True or a mapping of the config\'s fields, got {tones!r}')
+        return dict(TONE_DEFAULTS, mode=0)
+    if tones is True:
+        return dict(TONE_DEFAULTS)
+    if not hasattr(tones, "keys"):
+        raise GtcrnError(f'tones must be None, "detect", True or a mapping of the config\'s fields, got {tones!r}')
+    return dict(TONE_DEFAULTS, **{str(k): tones[k] for k in tones.keys()})
+
+
+def tone_params(**fields):
+    """The 16 parameter words of the tone guard (include/gtcrn_micro_hip.h, "tone guard") for the defaults with `fields`
+    replaced: a float32 array from gtcrn_tone_params_host, the one place the words are made."""
+    fn = getattr(lib(), "gtcrn_tone_params_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no tone guard")
+    unknown = set(fields) - set(TONE_DEFAULTS)
+    if unknown:
+        raise GtcrnError(f"unknown tone-guard fields {sorted(unknown)}: the config has {sorted(TONE_DEFAULTS)}")
+    f = dict(TONE_DEFAULTS, **fields)
+    ints = [f[k] for k, t in ToneConfig._fields_ if t is ctypes.c_int]
+    if any(int(v) != v for v in ints):
+        raise GtcrnError("the tone guard's counts, mode and singles are integers")
+    cfg = ToneConfig(*[float(f[k]) for k, t in ToneConfig._fields_ if t is ctypes.c_double], *[int(v) for v in ints])
+    out = np.empty(16, np.float32)
+    _check(fn(ctypes.byref(cfg), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+    return out
+
+
+def tone_table():
+    """The tone guard's table from gtcrn_tone_table_host: (10, 256, 2) float32, [f, i] = {cos, sin}(2 pi F_f i / 16000)."""
+    fn = getattr(lib(), "gtcrn_tone_table_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no tone guard")
+    out = np.empty((10, 256, 2), np.float32)
+    _check(fn(out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+    return out
+
+
+def tone_block(params, table, record, x):
+    """Steps 1 and 3..5 of one emitted block through gtcrn_tone_block_host, the functions the kernel compiles, on the host:
+    the 16 parameter words, the table, the stream's 8-word record and the 256 dry samples -> (the record after the block,
+    whether the block is passed dry).  The structural zero of a stream's first block and step 7's counts are the caller's."""
+    fn = getattr(lib(), "gtcrn_tone_block_host", None)
+    if fn is None:
+        raise GtcrnError("this library has no tone guard")
+    arr = [np.ascontiguousarray(v, np.float32) for v in (params, table, record, x)]
+    if [v.size for v in arr] != [16, 5120, 8, 256]:
+        raise GtcrnError("tone_block takes 16 parameter words, the 10 x 256 x 2 table, an 8-word record and 256 samples")
+    rec, guard = arr[2].reshape(8).copy(), ctypes.c_int(0)
+    ptr = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    _check(fn(ptr(arr[0]), ptr(arr[1]), ptr(rec), ptr(arr[3]), ctypes.byref(guard)))
+    return rec, bool(guard.value)
+
+
+def _tones_on(tones):
+    """tones= of the state constructors: None and False are off."""
+    return tones is not None and tones is not False
+
+
+def _attach_live(st, atten_lim_db, meters, ramp, alc, tones=None):
     """The options of a fresh state behind its reset, in this order: the limit, the meter records (True: new zeroed ones;
-    else the records, or None, of the wave state it was made from), the ramp words and the level control."""
+    else the records, or None, of the wave state it was made from), the ramp words, the level control and the tone guard."""
     import torch
     if atten_lim_db is not None:
         st.set_atten_lim_db(atten_lim_db)
@@ -453,6 +534,8 @@ def _attach_live(st, atten_lim_db, meters, ramp, alc):
         st._new_gain_ramp()
     if _alc_on(alc):
         st._new_alc(alc)
+    if _tones_on(tones):
+        st._new_tones(tones)
     return st
 
 
@@ -828,7 +911,7 @@ class Engine:
     def wave_state_bytes():
         return int(lib().gtcrn_wave_stream_state_bytes())
 
-    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False, ramp=False, alc=None):
+    def new_wave_state(self, nstreams, window, atten_lim_db=None, meters=False, ramp=False, alc=None, tones=None):
         """State of `nstreams` waveform streams: the model state, the wave state (input ring, overlap-add tail, hop
         counter) and the analysis / synthesis window, checked here once: 512 floats with window[0] == 0 (which the
         one-hop-delay contract rests on; torch.hann_window(512).pow(0.5) of infer.py:65 has it).  atten_lim_db (a
@@ -843,7 +926,12 @@ class Engine:
         alc ("vad": measure only; True: the defaults; a mapping of gtcrn_alc_config's fields; None or False: off): the header's "level
         control" -- the state owns ``state.alc``, (n, 8) float32 records {a, S, hang, voice, voiced, blocks, 0, 0}, and
         ``state.alc_params``, (16,) float32, which every step and flush through the state then uses (WaveStreamState.voice,
-        .alc_gain_db, .set_alc, .reset_alc)."""
+        .alc_gain_db, .set_alc, .reset_alc).
+        tones ("detect": detect only; True: the defaults; a mapping of gtcrn_tone_config's fields; None or False: off): the
+        header's "tone guard" -- the state owns ``state.tones``, (n, 8) float32 records {tone, cand, run, hold, guard, events,
+        guarded, blocks}, ``state.tone_params``, (16,) float32, and ``state.tone_table``; every step and flush through the state
+        then detects DTMF / 1100 Hz / 2100 Hz per stream and (unless "detect") passes the blocks that hold one dry
+        (WaveStreamState.tone, .tone_events, .set_tones, .reset_tones)."""
         import torch
         n = int(nstreams)
         if n < 1:
@@ -858,13 +946,25 @@ class Engine:
         st = WaveStreamState(self.new_state(n),
                              torch.empty((n, self.wave_state_bytes() // 4), device=win.device, dtype=torch.float32), win)
         self.wave_stream_reset(st)
-        return _attach_live(st, atten_lim_db, True if meters else None, ramp, alc)
+        return _attach_live(st, atten_lim_db, True if meters else None, ramp, alc, tones)
 
     def _bind_live(self, state):
         """Ahead of every step or flush through a state: its meters, ramp words and level control go to the model."""
         self._set_meters(state)
         self._set_gain_ramp(state)
         self._set_alc(state)
+        self._set_tones(state)
+
+    def _set_tones(self, state):
+        """Hands the state's tone records, parameter words and table to the model ahead of a step or flush, or clears the
+        model's pointers for a state without: two states on one engine do not leak into each other."""
+        fn = getattr(lib(), "gtcrn_wave_stream_set_tone", None)
+        if fn is None:
+            return                                       # (an earlier library: _new_tones refused, nothing to clear)
+        if state.tones is None:
+            _check(fn(self._h, None, None, None))
+        else:
+            _check(fn(self._h, state.tones.data_ptr(), state.tone_params.data_ptr(), state.tone_table.data_ptr()))
 
     def _set_alc(self, state):
         """Hands the state's level-control records and parameter words to the model ahead of a step or flush, or clears
@@ -1133,7 +1233,8 @@ class Engine:
                                            out.data_ptr(), out.stride(0), B, _stream_ptr()))
         return out[0] if wave.dim() == 1 else out
 
-    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None, ramp=False, alc=None):
+    def new_rate_state(self, nstreams, window, fs, atten_lim_db=None, meters=False, highband=None, ramp=False, alc=None,
+                       tones=None):
         """State of `nstreams` live streams at `fs` Hz (8000, 24000, 32000 or 48000): new_wave_state's plus the two
         resamplers and their per-stream histories.  atten_lim_db: as in new_wave_state (mixed at 16 kHz); meters: as in
         new_wave_state (taken at 16 kHz, per 256-sample block of the wave step); ramp: as in new_wave_state (made at 16 kHz,
@@ -1155,7 +1256,7 @@ class Engine:
             st.hb_gain = torch.zeros((ws.n,), device=ws.wave.device, dtype=torch.float32)
             st.set_highband_gain(highband)
         self.rate_stream_reset(st)
-        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc, tones)
 
     def rate_stream_reserve(self, state, nhops):
         """Sizes every buffer a rate step of `nhops` hops needs: after it a step allocates nothing (capturable)."""
@@ -1210,7 +1311,7 @@ class Engine:
 
     # ---- packet-sized live streaming (contract: include/gtcrn_micro_hip.h, gtcrn_packet_stream_*) -------------------
     def new_packet_state(self, nstreams, window, packet, fs=16000, atten_lim_db=None, meters=False, g711=None,
-                         highband=None, ramp=False, alc=None):
+                         highband=None, ramp=False, alc=None, tones=None):
         """State of a GROUP of `nstreams` live streams whose audio arrives in packets of `packet` samples at `fs` Hz (8000,
         16000, 22050, 24000, 32000, 44100 or 48000; packet * 16000 / fs a whole number in 1..4096): new_wave_state's plus
         the two FIFOs and filter histories per stream and the host handle that holds the group's phase.  Everything a step
@@ -1245,7 +1346,7 @@ class Engine:
         st.g711 = law
         st._new_highband(nhb, highband)
         self.packet_stream_reset(st)
-        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc, tones)
 
     def packet_stream_reset(self, state, lo=0, hi=None):
         """Resets streams lo..hi-1 (all three states).  They join the group at its current phase: state.phase zeros in
@@ -1303,7 +1404,7 @@ class Engine:
 
     # ---- packet stream slots (contract: include/gtcrn_micro_hip.h, "packet stream slots") ----------------------------
     def new_packet_slot_state(self, nslots, window, packet, fs=16000, max_active=None, atten_lim_db=None, meters=False,
-                              g711=None, highband=None, ramp=False, alc=None):
+                              g711=None, highband=None, ramp=False, alc=None, tones=None):
         """State of `nslots` RESIDENT packet streams, each with its own phase: new_packet_state's tensors for nslots streams
         plus ``phase`` (nslots,) int32 on the device.  A call steps the at most `max_active` (None: nslots) slots it names
         (packet_stream_step_slots); streams join by packet_stream_reset_slots, at any tick, and all have the latency of a
@@ -1335,7 +1436,7 @@ class Engine:
         st._new_highband(nhb, highband)
         if st.hb is not None:
             st.hb.zero_()
-        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc)
+        return _attach_live(st, atten_lim_db, ws.meters, ramp, alc, tones)
 
     def _packet_slot_args(self, state, slots, count):
         if not isinstance(state, PacketSlotState):
@@ -1501,6 +1602,10 @@ class WaveStreamState:
         self.alc = None             # (N, 8) float32 on the device: the level-control records; None: no level control
         self.alc_params = None      # (16,) float32 on the device: the level control's parameter words
         self.alc_fields = None      # the configuration the words were made from (gtcrn_alc_config's fields), as set_alc keeps it
+        self.tones = None           # (N, 8) float32 on the device: the tone guard's records; None: no tone guard
+        self.tone_params = None     # (16,) float32 on the device: the tone guard's parameter words
+        self.tone_table = None      # (10, 256, 2) float32 on the device: the tone guard's table
+        self.tone_fields = None     # the configuration the words were made from (gtcrn_tone_config's fields)
 
     @property
     def n(self):
@@ -1589,6 +1694,53 @@ class WaveStreamState:
         """The gain every stream's last emitted block ended at, in dB: an (N,) float64 numpy array.  SYNCHRONOUS: word 0 of
         the records is copied to the host."""
         return 20.0 * np.log10(self._leveled()[:, 0].detach().cpu().numpy().astype(np.float64))
+
+    def _new_tones(self, tones):
+        """tones= of the state's constructor: the parameter words, the table and the records, every record zero."""
+        import torch
+        if not hasattr(lib(), "gtcrn_wave_stream_set_tone"):
+            raise GtcrnError("this library has no tone guard")
+        self.tone_fields = _tone_fields(tones)    # the configuration set_tones updates
+        words = tone_params(**self.tone_fields)
+        self.tone_params = torch.from_numpy(words).to(self.model.device)
+        self.tone_table = torch.from_numpy(tone_table()).to(self.model.device)
+        self.tones = torch.zeros((self.n, 8), device=self.model.device, dtype=torch.float32)
+
+    def _toned(self):
+        if self.tones is None:
+            raise GtcrnError("the state has no tone guard: create it with tones=")
+        return self.tones
+
+    def set_tones(self, **fields):
+        """Replaces the given settings of the state's OWN configuration (``state.tone_fields``: what tones= gave, as later
+        calls here left it -- a tones="detect" state stays detect-only unless mode=1 is passed) and rewrites
+        state.tone_params in place, asynchronously on the current stream: the next step, also the next replay of a captured
+        one, follows.  Nothing changes when a setting is refused."""
+        import torch
+        self._toned()
+        merged = dict(self.tone_fields or TONE_DEFAULTS, **fields)
+        words = tone_params(**merged)
+        self.tone_fields = merged
+        self.tone_params.copy_(torch.from_numpy(words), non_blocking=True)
+
+    def reset_tones(self, lo=0, hi=None):
+        """Zeroes the records of streams (slots) lo..hi-1, asynchronously on the current stream and without any allocation.
+        (A stream's first block does the same on the device: a join needs no call here.)"""
+        t = self._toned()
+        lo, hi = _stream_range(self.n, lo, hi)
+        t[lo:hi].zero_()
+
+    def tone(self):
+        """The reported tone code of every stream's last emitted block (0 none, 1..16 = 1 + 4 row + col of the DTMF grid, 17 =
+        1100 Hz, 18 = 2100 Hz): an (N,) int32 tensor on the device, a conversion of word 0 of the records.  Asynchronous, no
+        synchronisation: usable inside a captured graph."""
+        import torch
+        return self._toned()[:, 0].to(torch.int32)
+
+    def tone_events(self):
+        """The reported onsets of every stream since its records were zeroed: an (N,) int64 numpy array.  SYNCHRONOUS: word 5
+        of the records is copied to the host."""
+        return self._toned()[:, 5].detach().cpu().numpy().astype(np.int64)
 
     def _metered(self):
         if self.meters is None:

@@ -755,6 +755,97 @@ int gtcrn_alc_block_host(const float* params16, float* record8, const float* w25
     return 0;
 }
 
+// Tone guard (contract: include/gtcrn_micro_hip.h, "tone guard"): the three addresses are kept like the meters'; wave_step
+// hands them to the synthesis launch.  Nothing is launched or read here.
+int gtcrn_wave_stream_set_tone(gtcrn_model* m, float* d_tone, const float* d_tone_params, const float* d_tone_table) {
+    if (!m) return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_tone: null model");
+    if (!d_tone != !d_tone_params || !d_tone != !d_tone_table)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_tone: the records, the parameters and the table come together");
+    if (reinterpret_cast<uintptr_t>(d_tone) & 31)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_tone: the records must be 32-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_tone_params) | reinterpret_cast<uintptr_t>(d_tone_table)) & 15)
+        return fail(GTCRN_ERR_ARG, "gtcrn_wave_stream_set_tone: the parameters and the table must be 16-byte aligned");
+    m->live.tone = d_tone;
+    m->live.tone_params = d_tone_params;
+    m->live.tone_table = d_tone_table;
+    return 0;
+}
+// the table: cos and sin of 2 pi F_f i / 16000 in double, rounded once
+int gtcrn_tone_table_host(float* out) {
+    if (!out) return fail(GTCRN_ERR_ARG, "gtcrn_tone_table_host: null pointer");
+    constexpr double F[gtk::TONE_FREQS] = {697, 770, 852, 941, 1209, 1336, 1477, 1633, 1100, 2100};
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int f = 0; f < gtk::TONE_FREQS; ++f)
+        for (int i = 0; i < 256; ++i) {
+            const double a = two_pi * F[f] * i / 16000.0;
+            out[(f * 256 + i) * 2] = (float)std::cos(a);
+            out[(f * 256 + i) * 2 + 1] = (float)std::sin(a);
+        }
+    return 0;
+}
+// the parameter words of a configuration: double arithmetic, one rounding to float each
+int gtcrn_tone_params_host(const gtcrn_tone_config* c, float* out16) {
+    if (!c || !out16) return fail(GTCRN_ERR_ARG, "gtcrn_tone_params_host: null pointer");
+    for (double x : {c->min_dbov, c->twist_db, c->dominance_db, c->pair_purity, c->single_purity})
+        if (!std::isfinite(x)) return fail(GTCRN_ERR_ARG, "gtcrn_tone_params_host: a field is not finite");
+    for (double x : {c->pair_purity, c->single_purity})
+        if (!(x > 0 && x <= 1)) return fail(GTCRN_ERR_ARG, "gtcrn_tone_params_host: a purity outside (0, 1]");
+    for (int k : {c->guard_blocks, c->digit_blocks, c->single_blocks, c->hold_blocks})
+        if (k < 0 || k > (1 << 24)) return fail(GTCRN_ERR_ARG, "gtcrn_tone_params_host: a count is negative or above 2^24");
+    if ((c->mode != 0 && c->mode != 1) || (c->singles != 0 && c->singles != 1))
+        return fail(GTCRN_ERR_ARG, "gtcrn_tone_params_host: mode and singles must be 0 or 1");
+    const auto fin = [](double x) { return (float)std::min(x, (double)FLT_MAX); };
+    for (int i = 0; i < 16; ++i) out16[i] = 0.f;
+    out16[0] = fin(256.0 * std::pow(10.0, c->min_dbov / 10));
+    out16[1] = fin(std::pow(10.0, c->twist_db / 10));
+    out16[2] = fin(std::pow(10.0, -c->dominance_db / 10));
+    out16[3] = (float)c->pair_purity;
+    out16[4] = (float)c->single_purity;
+    out16[5] = (float)c->guard_blocks;
+    out16[6] = (float)c->digit_blocks;
+    out16[7] = (float)c->single_blocks;
+    out16[8] = (float)c->hold_blocks;
+    out16[9] = (float)c->mode;
+    out16[10] = (float)c->singles;
+    return 0;
+}
+// the host twin: steps 1 and 3 .. 5 of one emitted block through the functions the kernel compiles (lane l holds samples 2l,
+// 2l + 1, 128 + 2l, 129 + 2l; the reductions run the xor butterfly over lane distances 1 .. 32)
+int gtcrn_tone_block_host(const float* params16, const float* table, float* record8, const float* x256, int* guard_out) {
+    if (!params16 || !table || !record8 || !x256 || !guard_out) return fail(GTCRN_ERR_ARG, "gtcrn_tone_block_host: null pointer");
+    const auto butterfly = [](float* v) {
+        for (int d = 1; d < 64; d <<= 1) {
+            float t[64];
+            for (int l = 0; l < 64; ++l) t[l] = v[l] + v[l ^ d];
+            for (int l = 0; l < 64; ++l) v[l] = t[l];
+        }
+        return v[0];
+    };
+    float v[64], w[64], P[gtk::TONE_FREQS];
+    for (int l = 0; l < 64; ++l) v[l] = gtk::alc_lane_sum(x256[2 * l], x256[2 * l + 1], x256[128 + 2 * l], x256[129 + 2 * l]);
+    const float ex = butterfly(v);
+    for (int f = 0; f < gtk::TONE_FREQS; ++f) {
+        const float* t = table + 512 * f;
+        for (int l = 0; l < 64; ++l) {
+            const int i[4] = {2 * l, 2 * l + 1, 128 + 2 * l, 129 + 2 * l};
+            v[l] = gtk::tone_lane_dot(x256[i[0]], x256[i[1]], x256[i[2]], x256[i[3]], t[2 * i[0]], t[2 * i[1]], t[2 * i[2]], t[2 * i[3]]);
+            w[l] = gtk::tone_lane_dot(x256[i[0]], x256[i[1]], x256[i[2]], x256[i[3]], t[2 * i[0] + 1], t[2 * i[1] + 1],
+                                      t[2 * i[2] + 1], t[2 * i[3] + 1]);
+        }
+        const float cf = butterfly(v), sf = butterfly(w);
+        P[f] = gtk::tone_power(cf, sf);
+    }
+    const float* p = params16;
+    const gtk::ToneParams TP{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10]};
+    float* r = record8;
+    gtk::ToneRecord R{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+    gtk::tone_decide(TP, R, ex, P);
+    const float rec[8] = {R.tone, R.cand, R.run, R.hold, R.guard, R.events, R.guarded, R.blocks};
+    for (int i = 0; i < 8; ++i) record8[i] = rec[i];
+    *guard_out = TP.mode == 1.f && R.guard != 0.f;
+    return 0;
+}
+
 // RFC 6464 audio level of a window of `nsamples` samples with energy `energy` (full scale 1.0): -dBov rounded to the nearest
 // integer, 0 (loudest) .. 127 (silence).  Host arithmetic only.
 int gtcrn_level_dbov(double energy, double nsamples) {

@@ -110,6 +110,9 @@ struct WaveOpts {
     float* ramp = nullptr;                // the gain ramps: one float per stream; without `gain` it is not touched
     float* alc = nullptr;                 // the level control: 8 floats per stream, 32-byte aligned, and with them always
     const float* alc_params = nullptr;    // the 16 parameter words
+    float* tone = nullptr;                // the tone guard: 8 floats per stream, 32-byte aligned, and with them always
+    const float* tone_params = nullptr;   // the 16 parameter words
+    const float* tone_table = nullptr;    // gtcrn_tone_table_host's 10 x 256 x 2 floats, 16-byte aligned
 };
 enum class Synth {      // what k_wave_synthesis does with them: one instantiation per mode and (S, FLUSH, IDX)
     Plain,      // the enhanced block as it is
@@ -134,22 +137,32 @@ enum class Synth {      // what k_wave_synthesis does with them: one instantiati
     // twin's body) advances the record and gives the block's two gains, and y_i = fl(gain_ramp_at(a0, a1, i) m_i) goes to the
     // store and the meters.  The parameter words and the record become scalars behind hop 0's transform, as the ramp words
     // do; lane 0 stores the record (two 16-byte stores) before the flush's return, not after an empty flush.
-    Alc
+    Alc,
+    // The tone guard (include/gtcrn_micro_hip.h, "tone guard") -- gain, meters, ramp and alc are run-time branches.  Laid out
+    // as Alc: the wave holds w and x before the first store.  E_x and the ten P_f come first (tone_lane_dot per table row, then
+    // wave_sum_uniform: the butterfly's additions as DPP adds), tone_decide (the host twin's body) advances the record, and a
+    // guarded block takes dry gain 1 at every sample; the ramp word p is carried from block to block inside a call.  Level
+    // control and the meters then see m as in Alc.  The parameter words and the record become scalars behind hop 0's
+    // transform; lane 0 stores the record (two 16-byte stores) before the flush's return, not after an empty flush.  Each lane
+    // reads its 4 x 10 table entries per hop from global memory (two 16-byte loads per row, behind the transform).
+    Guard
 };
 constexpr Synth synth_mode(const WaveOpts& o) {      // the ONLY place that turns the pointers into a mode
-    return o.alc ? Synth::Alc : o.gain && o.ramp ? (o.meters ? Synth::MeterRamp : Synth::MixRamp)
+    return o.tone ? Synth::Guard : o.alc ? Synth::Alc : o.gain && o.ramp ? (o.meters ? Synth::MeterRamp : Synth::MixRamp)
          : o.meters ? Synth::Meter : o.gain ? Synth::Mix : Synth::Plain;
 }
 // The timing row of a launch (api.cpp): ramps and level control are timed in the row of the form they stand in for.
 constexpr Synth synth_timed_as(const WaveOpts& o) { return o.meters ? Synth::Meter : o.gain ? Synth::Mix : Synth::Plain; }
-// synth_mode over all 16 null / non-null combinations B; bit 0 of B: gain, 1: meters, 2: ramp, 3: alc with alc_params
+// synth_mode over all 32 null / non-null combinations B; bit 0 of B: gain, 1: meters, 2: ramp, 3: alc with alc_params,
+// 4: tone with tone_params and tone_table
 template <int... B>
 constexpr bool synth_is(Synth want, float x = 0.f) {
     float* const p[2] = {nullptr, &x};
-    return ((synth_mode({p[B & 1], p[B >> 1 & 1], p[B >> 2 & 1], p[B >> 3], p[B >> 3]}) == want) && ...);
+    return ((synth_mode({p[B & 1], p[B >> 1 & 1], p[B >> 2 & 1], p[B >> 3 & 1], p[B >> 3 & 1], p[B >> 4], p[B >> 4], p[B >> 4]}) == want) && ...);
 }
 static_assert(synth_is<0, 4>(Synth::Plain) && synth_is<1>(Synth::Mix) && synth_is<2, 3, 6>(Synth::Meter));
 static_assert(synth_is<5>(Synth::MixRamp) && synth_is<7>(Synth::MeterRamp) && synth_is<8, 9, 10, 11, 12, 13, 14, 15>(Synth::Alc));
+static_assert(synth_is<16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31>(Synth::Guard));
 // Gain ramps (contract: include/gtcrn_micro_hip.h, "gain ramps"): the dry gain of sample i = 0..255 of a block that ramps
 // from p, where the stream's last emitted block ended, to g -- fl(p + fl(fl(g - p) * r_i)), r_i = (i + 1) / 256 (exact), and
 // g itself at i == 255 or when p == g.  Three fp32 roundings, never a fused multiply-add (the pragma holds under any
@@ -228,6 +241,86 @@ __host__ __device__ inline void alc_decide(const AlcParams& P, AlcRecord& r, flo
     r.voice = voice;
     r.voiced = r.voiced + voice;
     r.blocks = r.blocks + 1.f;
+}
+// Tone guard (contract: include/gtcrn_micro_hip.h, "tone guard"): the lane product-sum of step 1 and the block rule, steps
+// 3 .. 5, once a block's eleven reductions are known.  One body for the Guard mode of k_wave_synthesis and for
+// gtcrn_tone_block_host.  Every operation is one correctly rounded fp32 operation; the finiteness test reads the bits.
+constexpr int TONE_FREQS = 10;      // 697, 770, 852, 941 (rows), 1209, 1336, 1477, 1633 (columns), 1100, 2100 Hz
+struct ToneParams {     // words 0 .. 10 of d_tone_params
+    float theta, tau, delta, pi2, pi1, G, N2, N1, H, mode, singles;
+};
+struct ToneRecord {     // a stream's record
+    float tone, cand, run, hold, guard, events, guarded, blocks;
+};
+// ((x0 t0 + x1 t1) + x2 t2) + x3 t3: a lane's partial sum of a block against one table column (cos or sin of one frequency)
+__host__ __device__ inline float tone_lane_dot(float x0, float x1, float x2, float x3, float t0, float t1, float t2, float t3) {
+#pragma clang fp contract(off)
+    const float p0 = x0 * t0, p1 = x1 * t1, p2 = x2 * t2, p3 = x3 * t3;
+    const float t = p0 + p1;
+    const float u = t + p2;
+    return u + p3;
+}
+// fl(fl(c^2) + fl(s^2))
+__host__ __device__ inline float tone_power(float c, float s) {
+#pragma clang fp contract(off)
+    const float cc = c * c, ss = s * s;
+    return cc + ss;
+}
+// the first argmax of four values and its value (constant indices only: the array stays in registers)
+__host__ __device__ inline int tone_argmax4(const float* P, float& best) {
+    int r = 0;
+    best = P[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (P[j] > best) {
+            best = P[j];
+            r = j;
+        }
+    return r;
+}
+// Advances the record by one emitted block with dry energy Ex and powers P[0 .. 9]; r.guard then says whether the block is
+// passed dry (when the mode word is 1).  guarded and blocks are step 7's: the caller adds them behind the block.
+__host__ __device__ inline void tone_decide(const ToneParams& p, ToneRecord& r, float Ex, const float (&P)[TONE_FREQS]) {
+#pragma clang fp contract(off)
+    bool finite = !alc_not_finite(Ex);
+#pragma unroll
+    for (int f = 0; f < TONE_FREQS; ++f) finite = finite && !alc_not_finite(P[f]);
+    float cand = 0.f;
+    if (finite) {
+        float Pr, Pc;
+        const int ir = tone_argmax4(P, Pr), ic = tone_argmax4(P + 4, Pc);
+        const float er = Pr * 0.0078125f, ec = Pc * 0.0078125f;
+        const float tr = p.tau * er, tc = p.tau * ec;
+        const float dr = p.delta * Pr, dc = p.delta * Pc;
+        bool pair = er >= p.theta && ec >= p.theta && ec <= tr && er <= tc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pair = pair && (j == ir || P[j] <= dr);
+            pair = pair && (j == ic || P[4 + j] <= dc);
+        }
+        const float sum = er + ec;
+        const float need = p.pi2 * Ex;
+        pair = pair && sum >= need;
+        if (pair) {
+            cand = (float)(1 + 4 * ir + ic);
+        } else if (p.singles != 0.f) {
+            const float need1 = p.pi1 * Ex;
+            const float e8 = P[8] * 0.0078125f, e9 = P[9] * 0.0078125f;
+            if (e8 >= p.theta && e8 >= need1) cand = 17.f;
+            else if (e9 >= p.theta && e9 >= need1) cand = 18.f;
+        }
+    }
+    // (values, not stores under branches: the record stays in registers)
+    const float run = cand != 0.f ? (cand == r.cand ? r.run + 1.f : 1.f) : 0.f;
+    const float need_g = cand < 17.f ? p.G : p.N1, need_r = cand < 17.f ? p.N2 : p.N1;
+    const bool hit = cand != 0.f && run >= need_g;
+    const bool held = !hit && r.hold > 0.f;
+    const float guard = hit || held ? 1.f : 0.f;
+    const float hold = hit ? p.H : held ? r.hold - 1.f : r.hold;
+    const bool report = cand != 0.f && run >= need_r;
+    const float events = report && r.tone != cand ? r.events + 1.f : r.events;
+    const float tone = report ? cand : guard == 0.f ? 0.f : r.tone;
+    r = ToneRecord{tone, cand, run, hold, guard, events, r.guarded, r.blocks};
 }
 // hop-level waveform streaming of N streams (gtcrn_wave_stream_step / _flush): S = float or short (int16 PCM).
 // analysis: in (N rows of in_stride samples, nhops hops each; flush: r tail samples, nhops = 1) + wstate -> spec, frame-major

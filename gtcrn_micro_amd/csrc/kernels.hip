@@ -766,6 +766,23 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
     return v;
 }
+// wave_sum's value -- the same pairwise additions, so the same bits -- as a wave-uniform scalar and without the LDS crossbar
+// (the Guard mode runs twenty of these per block).  All 64 lanes must be active.  After the steps over distances 1 and 2
+// (quad permutes) the four lanes of a quad hold one value, so the half-row mirror hands lane l what lane l ^ 4 holds, and
+// after that step the row mirror what lane l ^ 8 holds; the four rows' sums are then read as scalars and added as lane 0's
+// butterfly adds them, (r0 + r1) + (r2 + r3).
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float wave_sum_uniform(float v) {
+    v = __fadd_rn(v, dpp_f32<0xB1>(v));       // quad_perm [1, 0, 3, 2]
+    v = __fadd_rn(v, dpp_f32<0x4E>(v));       // quad_perm [2, 3, 0, 1]
+    v = __fadd_rn(v, dpp_f32<0x141>(v));      // row_half_mirror
+    v = __fadd_rn(v, dpp_f32<0x140>(v));      // row_mirror
+    const auto row = [&](int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+    return __fadd_rn(__fadd_rn(row(0), row(16)), __fadd_rn(row(32), row(48)));
+}
 template <typename S, bool FLUSH, bool IDX, Synth MODE>
 __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* __restrict__ spec, const S* __restrict__ in,
                                                                   long in_stride, S* __restrict__ out, long out_stride,
@@ -778,7 +795,11 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
                                                                   float* __restrict__ meters,
                                                                   float* __restrict__ ramp,
                                                                   float* __restrict__ alc,
-                                                                  const float* __restrict__ alc_params) {
+                                                                  const float* __restrict__ alc_params,
+                                                                  float* __restrict__ tone,
+                                                                  const float* __restrict__ tone_params,
+                                                                  const float* __restrict__ tone_table) {
+    constexpr bool GUARD = MODE == Synth::Guard;
     constexpr bool MIX = MODE == Synth::Mix || MODE == Synth::MixRamp, METER = MODE == Synth::Meter || MODE == Synth::MeterRamp;
     constexpr bool RAMP = MODE == Synth::MixRamp || MODE == Synth::MeterRamp, ALC = MODE == Synth::Alc;
     if constexpr (IDX) N = slot_count(cnt, N);
@@ -840,6 +861,26 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
 #pragma unroll
         for (int q = 0; q < 3; ++q) av[2 + q] = *reinterpret_cast<const float4*>(alc_params + 4 * q);
     }
+    float4 tv[5];        // GUARD: the tone record's two halves and parameter words 0 .. 11, as loaded
+    ToneParams TP;       // GUARD: both made scalars behind hop 0's transform
+    ToneRecord TR;
+    if constexpr (GUARD) {
+        if (gain) g = gain[slot];
+        if (gain && ramp) p = ramp[slot];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) dry0[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + 2 * (lane + 64 * q));
+        if (meters) rec = *reinterpret_cast<const float4*>(meters + 4 * slot);
+        if (alc) {
+            av[0] = *reinterpret_cast<const float4*>(alc + 8 * slot);
+            av[1] = *reinterpret_cast<const float4*>(alc + 8 * slot + 4);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) av[2 + q] = *reinterpret_cast<const float4*>(alc_params + 4 * q);
+        }
+        tv[0] = *reinterpret_cast<const float4*>(tone + 8 * slot);
+        tv[1] = *reinterpret_cast<const float4*>(tone + 8 * slot + 4);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) tv[2 + q] = *reinterpret_cast<const float4*>(tone_params + 4 * q);
+    }
     for (int h = 0; h < nhops; ++h) {
         const float* x = spec + ((long)n * nhops + h) * 514;
 #pragma unroll
@@ -895,6 +936,99 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
             } else {
                 const float ew = wave_sum(alc_lane_sum(wq[0][0], wq[0][1], wq[1][0], wq[1][1]));
                 ex = wave_sum(alc_lane_sum(xq[0][0], xq[0][1], xq[1][0], xq[1][1]));
+                const float pm = wave_max(fmaxf(fmaxf(fabsf(mq[0][0]), fabsf(mq[0][1])), fmaxf(fabsf(mq[1][0]), fabsf(mq[1][1]))));
+                float a0, a1;
+                alc_decide(P, R, ew, ex, pm, a0, a1);
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) yq[q][e] = __fmul_rn(gain_ramp_at(a0, a1, 2 * (lane + 64 * q) + e), mq[q][e]);
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                wave_st(o + 256L * h + 2 * (lane + 64 * q), yq[q][0]);
+                wave_st(o + 256L * h + 2 * (lane + 64 * q) + 1, yq[q][1]);
+            }
+            if (meters) {      // the meters see y; their E_dry is E_x (the same sums in the same order; 0 for a zero block)
+                rec.x = __fadd_rn(rec.x, ex);
+                rec.y = __fadd_rn(rec.y, wave_sum(alc_lane_sum(yq[0][0], yq[0][1], yq[1][0], yq[1][1])));
+                rec.w = __fadd_rn(rec.w, 1.0f);
+                pk = fmaxf(pk, fmaxf(fmaxf(fabsf(yq[0][0]), fabsf(yq[0][1])), fmaxf(fabsf(yq[1][0]), fabsf(yq[1][1]))));
+            }
+            continue;
+        }
+        if constexpr (GUARD) {
+            const auto sc = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+            if (h == 0) {      // (made scalars HERE, as the ramp words below)
+                p = sc(p);
+                g = sc(g);
+                if (alc) {
+                    R = AlcRecord{sc(av[0].x), sc(av[0].y), sc(av[0].z), sc(av[0].w), sc(av[1].x), sc(av[1].y)};
+                    P = AlcParams{sc(av[2].x), sc(av[2].y), sc(av[2].z), sc(av[2].w), sc(av[3].x), sc(av[3].y),
+                                  sc(av[3].z), sc(av[3].w), sc(av[4].x), sc(av[4].y), sc(av[4].z)};
+                }
+                TR = ToneRecord{sc(tv[0].x), sc(tv[0].y), sc(tv[0].z), sc(tv[0].w), sc(tv[1].x), sc(tv[1].y), sc(tv[1].z), sc(tv[1].w)};
+                TP = ToneParams{sc(tv[2].x), sc(tv[2].y), sc(tv[2].z), sc(tv[2].w), sc(tv[3].x), sc(tv[3].y),
+                                sc(tv[3].z), sc(tv[3].w), sc(tv[4].x), sc(tv[4].y), sc(tv[4].z)};
+            }
+            float wq[2][2], xq[2][2], mq[2][2], yq[2][2];                // sample 2 (lane + 64 q) + e of the block
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int m = lane + 64 * q;
+                float2 d = dry0[q];
+                if (h > 0) {
+                    const S* xd = in + (long)n * in_stride + 256L * (h - 1) + 2 * m;
+                    d = make_float2(wave_ld(xd), wave_ld(xd + 1));
+                }
+                xq[q][0] = d.x;
+                xq[q][1] = d.y;
+                wq[q][0] = ola_div(prev[q].x + f[q].x, env[q][0]);
+                wq[q][1] = ola_div(prev[q].y + f[q].y, env[q][1]);
+                prev[q] = f[q + 2];
+            }
+            float ex = 0.f;
+            bool dry = false;      // this block is passed dry
+            const bool zs = __builtin_amdgcn_readfirstlane((int)zero) != 0;      // zero as a scalar: the records' branches stay scalar
+            if (zs) {
+                if (!none) {
+                    TR = ToneRecord{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    if (alc) R = AlcRecord{1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                }
+            } else {
+                ex = wave_sum(alc_lane_sum(xq[0][0], xq[0][1], xq[1][0], xq[1][1]));
+                float Pf[TONE_FREQS];
+                // (the table's address is made opaque HERE: hoisted over the transform, the twenty loads hold 80 registers there)
+                typedef float f4 __attribute__((ext_vector_type(4)));
+                const float* tt = tone_table;
+                asm volatile("" : "+s"(tt));
+                const auto* tg = (const __attribute__((address_space(1))) float*)tt;
+#pragma unroll
+                for (int k = 0; k < TONE_FREQS; ++k) {      // this lane's entries: {cos, sin} of samples 2l, 2l + 1 and 128 + 2l, 129 + 2l
+                    const f4 ta = *(const __attribute__((address_space(1))) f4*)(tg + 2 * (256 * k + 2 * lane));
+                    const f4 tb = *(const __attribute__((address_space(1))) f4*)(tg + 2 * (256 * k + 128 + 2 * lane));
+                    const float cf = wave_sum_uniform(tone_lane_dot(xq[0][0], xq[0][1], xq[1][0], xq[1][1], ta.x, ta.z, tb.x, tb.z));
+                    const float sf = wave_sum_uniform(tone_lane_dot(xq[0][0], xq[0][1], xq[1][0], xq[1][1], ta.y, ta.w, tb.y, tb.w));
+                    Pf[k] = tone_power(cf, sf);
+                }
+                tone_decide(TP, TR, sc(ex), Pf);
+                dry = TP.mode == 1.f && TR.guard != 0.f;
+                TR.guarded = TR.guarded + TR.guard;
+                TR.blocks = TR.blocks + 1.f;
+            }
+            // the dry gain: 1 at every sample of a guarded block (entering snaps); otherwise g, ramped from the carried p
+            const float tg = dry ? 1.f : g;
+            const bool ramps = !zs && !dry && gain && ramp && p != g;
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const float ge = ramps ? gain_ramp_at(p, g, 2 * (lane + 64 * q) + e) : tg;
+                    mq[q][e] = gain ? wave_mix(ge, xq[q][e], wq[q][e]) : (dry ? xq[q][e] : wq[q][e]);
+                    yq[q][e] = zs ? 0.f : mq[q][e];
+                }
+            if (gain && ramp) p = tg;
+            if (alc && !zs) {
+                const float ew = wave_sum(alc_lane_sum(wq[0][0], wq[0][1], wq[1][0], wq[1][1]));
                 const float pm = wave_max(fmaxf(fmaxf(fabsf(mq[0][0]), fabsf(mq[0][1])), fmaxf(fabsf(mq[1][0]), fabsf(mq[1][1]))));
                 float a0, a1;
                 alc_decide(P, R, ew, ex, pm, a0, a1);
@@ -991,6 +1125,21 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
             }
         }
     }
+    if constexpr (GUARD) {
+        if (meters) rec.z = fmaxf(rec.z, wave_max(pk));      // (wave uniform: every lane takes the shuffles)
+        if (lane == 0) {
+            if (meters) *reinterpret_cast<float4*>(meters + 4 * slot) = rec;
+            if (gain && ramp) ramp[slot] = p;      // (1 behind a guarded block: the next unguarded one ramps 1 -> g)
+            if (!none) {
+                if (alc) {
+                    *reinterpret_cast<float4*>(alc + 8 * slot) = make_float4(R.a, R.S, R.hang, R.voice);
+                    *reinterpret_cast<float4*>(alc + 8 * slot + 4) = make_float4(R.voiced, R.blocks, 0.f, 0.f);
+                }
+                *reinterpret_cast<float4*>(tone + 8 * slot) = make_float4(TR.tone, TR.cand, TR.run, TR.hold);
+                *reinterpret_cast<float4*>(tone + 8 * slot + 4) = make_float4(TR.guard, TR.events, TR.guarded, TR.blocks);
+            }
+        }
+    }
     if constexpr (FLUSH) return;
     // the state: tail = the newest frame's windowed second half; ring = the last 512 input samples; counter (saturating)
 #pragma unroll
@@ -1001,7 +1150,7 @@ __global__ __launch_bounds__(FFT_WAVES * 64) void k_wave_synthesis(const float* 
     for (int q = 0; q < 4; ++q) {
         const int j = 2 * (lane + 64 * q);
         if (q < 2 && nhops == 1) {      // (this lane's own q + 2; MIX and METER hold the pair already)
-            if constexpr (MIX || METER || ALC) ring[q] = dry0[q];
+            if constexpr (MIX || METER || ALC || GUARD) ring[q] = dry0[q];
             else ring[q] = *reinterpret_cast<const float2*>(ws + WS_RING + 256 + j);
         } else ring[q] = make_float2(wave_ld(xi + j), wave_ld(xi + j + 1));
     }
@@ -4582,7 +4731,7 @@ static void with_flags(F&& f, bool b, R... rest) {
 template <Synth M = Synth::Plain, class F, class... R>      // the same with a synthesis mode m in front of the flags
 static void with_mode(F&& f, Synth m, R... flags) {
     if (m == M) with_flags([&](auto... bs) { f(std::integral_constant<Synth, M>{}, bs...); }, flags...);
-    else if constexpr (M != Synth::Alc) with_mode<Synth((int)M + 1)>(f, m, flags...);
+    else if constexpr (M != Synth::Guard) with_mode<Synth((int)M + 1)>(f, m, flags...);
 }
 
 template <typename S>
@@ -4610,7 +4759,7 @@ int launch_wave_synthesis(const float* spec, const S* in, long in_stride, S* out
     with_mode([&](auto MODE, auto FLUSH, auto IDX) {
         hipLaunchKernelGGL((k_wave_synthesis<S, FLUSH.value, IDX.value, MODE.value>), dim3(grid), dim3(FFT_WAVES * 64), 0, s, spec,
                            in, in_stride, out, out_stride, N, flush ? 1 : nhops, flush ? r : 0, wstate, win, tw, o.gain, rows.slots,
-                           rows.cnt, o.meters, o.ramp, o.alc, o.alc_params);
+                           rows.cnt, o.meters, o.ramp, o.alc, o.alc_params, o.tone, o.tone_params, o.tone_table);
     }, synth_mode(o), flush, rows.slots != nullptr);
     GT_LAUNCH_CHECK();
     return 0;

@@ -230,7 +230,7 @@ class StreamGTCRNMicro(GTCRNMicro):
 
     def init_wave_state(self, nstreams, window, device="cuda", fs=16000, packet=None, atten_lim_db=None, state=None, slots=None,
                         count=None, resident=False, max_active=None, meters=False, g711=None, highband=None, ramp=False,
-                        alc=None):
+                        alc=None, tones=None):
         """State of `nstreams` waveform streams (Engine.new_wave_state); window: the 512-tap analysis / synthesis window
         of the offline call, window[0] == 0 (torch.hann_window(512).pow(0.5) for infer.py's).  fs: the caller's sample
         rate; 8000, 24000, 32000 or 48000 gives the rate form (Engine.new_rate_state: hops of 256 fs / 16000 samples).
@@ -245,6 +245,10 @@ class StreamGTCRNMicro(GTCRNMicro):
         alc= ("vad": the voice flag only; True: the default level control; a mapping of its settings): the state owns
         state.alc and state.alc_params -- a speech-gated output gain, a limiter and state.voice() per stream, made at 16 kHz
         in every step and flush (state.set_alc, state.alc_gain_db(), state.reset_alc()); not together with highband=.
+        tones= ("detect": the detector only; True: the default tone guard; a mapping of its settings): the state owns
+        state.tones -- DTMF digits, 1100 Hz and 2100 Hz are detected per stream at 16 kHz in every step and flush
+        (state.tone(), state.tone_events()) and, unless "detect", the blocks that hold one are passed dry (state.set_tones,
+        state.reset_tones()).
         state=, slots= (int32 device tensor), count= (device int32, optional): a stream JOINS -- the named slots of the
         existing 16 kHz `state` are reset to the start of a clip (Engine.wave_stream_reset_slots, a capturable kernel) and
         `state` is returned; the other slots are not touched.  Rate states and plain packet states cannot be addressed by
@@ -260,6 +264,8 @@ class StreamGTCRNMicro(GTCRNMicro):
         (Engine.new_packet_state / new_packet_slot_state; not with g711=).  None: that band is not in the output."""
         if _lib._alc_on(alc) and slots is not None:
             raise _lib.GtcrnError("alc= is given when a state is made, not when slots= resets some of its streams")
+        if _lib._tones_on(tones) and slots is not None:
+            raise _lib.GtcrnError("tones= is given when a state is made, not when slots= resets some of its streams")
         if highband is not None and slots is not None:
             raise _lib.GtcrnError("highband= is given when a state is made, not when slots= resets some of its streams")
         if g711 is not None and (packet is None or slots is not None):
@@ -277,16 +283,16 @@ class StreamGTCRNMicro(GTCRNMicro):
             if packet is None:
                 raise _lib.GtcrnError("resident=True makes a packet slot state: pass packet= (a 16 kHz wave state is resident as it is)")
             return eng.new_packet_slot_state(nstreams, window, int(packet), int(fs), max_active=max_active,
-                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband, ramp=ramp, alc=alc)
+                                             atten_lim_db=atten_lim_db, meters=meters, g711=g711, highband=highband, ramp=ramp, alc=alc, tones=tones)
         if packet is not None:
             return eng.new_packet_state(nstreams, window, int(packet), int(fs), atten_lim_db=atten_lim_db, meters=meters,
-                                        g711=g711, highband=highband, ramp=ramp, alc=alc)
+                                        g711=g711, highband=highband, ramp=ramp, alc=alc, tones=tones)
         if int(fs) != 16000:
             return eng.new_rate_state(nstreams, window, int(fs), atten_lim_db=atten_lim_db, meters=meters, highband=highband, ramp=ramp,
-                                      alc=alc)
+                                      alc=alc, tones=tones)
         if highband is not None:
             raise _lib.GtcrnError("highband= needs fs = 24000, 32000 or 48000: a 16 kHz stream has no band above 8 kHz")
-        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters, ramp=ramp, alc=alc)
+        return eng.new_wave_state(nstreams, window, atten_lim_db=atten_lim_db, meters=meters, ramp=ramp, alc=alc, tones=tones)
 
     def step_wave(self, x, state, slots=None, count=None):
         """x (N, 256*n) float32 or int16, n >= 1 hops per stream -> the enhanced hops, same dtype, one hop late.  With a

@@ -923,6 +923,119 @@ int gtcrn_alc_params_host(const gtcrn_alc_config *config, float *out16);
 int gtcrn_alc_block_host(const float *params16, float *record8, const float *w256, const float *x256, const float *m256,
                          float *y256);
 
+/* ---- tone guard: DTMF and fax tones are detected per stream and passed dry -------------------------------------------------
+ * A DTMF digit, a fax calling tone (CNG, 1100 Hz) and an answer tone (ANS, 2100 Hz) are stationary narrow-band signals: what
+ * the model removes.  A gateway puts a tone detector beside its suppressor and bypasses the processing while a tone is
+ * present.  The synthesis kernel holds the dry block x aligned with the block it emits ("attenuation limit"), so the detector
+ * and the bypass cost no launch, no latency and no pass over the audio: one 32-byte record per stream.
+ *
+ * Everything is taken at 16 kHz inside the wave step, on the dry block x, whether or not gains are set.  Every operation
+ * below is ONE correctly rounded fp32 operation and no fused multiply-add is formed, so a numpy float32 statement reproduces
+ * the outputs and the records bit for bit (tests/tone_checker.py).
+ *
+ * Table.  gtcrn_tone_table_host(out) writes 10 x 256 x 2 floats, out[(f * 256 + i) * 2 + {0, 1}] = float(cos(a)), float(sin(a)),
+ * a = 2 pi F_f i / 16000 computed in double and rounded once; F = 697, 770, 852, 941 (the DTMF rows), 1209, 1336, 1477, 1633
+ * (the columns), 1100, 2100.  The caller uploads it once as d_tone_table (20 480 bytes, 16-byte aligned).
+ *
+ * Parameters.  d_tone_params: caller-owned device memory, 16 floats, 16-byte aligned, ONE set for the states a call steps; read
+ * at every launch as wave-uniform values; may be rewritten between calls and between replays of a captured graph.
+ *     word 0  theta    256 * 10^(min_dbov / 10), the floor on one tone's block energy              default -45 dBov
+ *     word 1  tau      10^(twist_db / 10)                                                          8 dB
+ *     word 2  delta    10^(-dominance_db / 10)                                                     8 dB
+ *     word 3  pi2      purity of a tone pair, in (0, 1]                                            0.6
+ *     word 4  pi1      purity of a single tone, in (0, 1]                                          0.8
+ *     word 5  G        blocks of the same candidate before the guard acts                          1
+ *     word 6  N2       blocks before a DTMF digit is reported                                      2
+ *     word 7  N1       blocks before a single tone is guarded and reported                         4
+ *     word 8  H        hold, in blocks                                                             1
+ *     word 9  mode     1.0: guard; 0.0: detect only
+ *     word 10 singles  1.0: 1100 / 2100 Hz are looked for; 0.0: DTMF only
+ *     words 11..15     zero
+ * Counts are integer-valued floats.  gtcrn_tone_params_host makes the words from a gtcrn_tone_config: double arithmetic, one
+ * rounding to float per word; GTCRN_ERR_ARG for a null pointer, a non-finite field, a purity outside (0, 1], a negative count
+ * (or one above 2^24) or a mode / singles value other than 0 / 1.
+ *
+ * Record.  d_tone: caller-owned device memory, 8 floats per stream or slot, 32-byte aligned, indexed as the dry gains, the
+ * meters and the level-control records are.
+ *     word 0  tone     the reported code of the last emitted block: 0 none, 1..16 = 1 + 4 row + col, 17 = 1100 Hz, 18 = 2100 Hz
+ *     word 1  cand     the last block's candidate
+ *     word 2  run      its run length
+ *     word 3  hold     blocks of hold left
+ *     word 4  guard    1 if the last block qualified to be passed dry (it was, when mode == 1)
+ *     word 5  events   reported onsets
+ *     word 6  guarded  blocks counted with guard == 1
+ *     word 7  blocks   blocks counted
+ * The record is NOT part of any state: every *_state_bytes and GTCRN_ABI_VERSION (1) are what they were.
+ *
+ * gtcrn_wave_stream_set_tone stores the three addresses in the model, as gtcrn_wave_stream_set_alc stores its two; all NULL,
+ * the default, gives the launches of before, and nothing of this section is read or written.  A mixed call (some NULL, some
+ * set), a misaligned address or a null model is GTCRN_ERR_ARG; no device is touched.
+ *
+ * Per emitted block, in hop order.  x_i: the dry sample of "attenuation limit"; w_i: the wet sample.
+ *   1. E_x in the meters' order.  For each f: c_f = the sum over the block of fl(x_i cos_f,i), s_f the same with sin -- lane l
+ *      holds samples 2l, 2l+1, 128+2l, 129+2l and forms ((p0 + p1) + p2) + p3, then the xor butterfly over lane distances
+ *      1, 2, 4, 8, 16, 32.  P_f = fl(fl(c_f^2) + fl(s_f^2)) and e_f = P_f * 2^-7.
+ *   2. Structural zero, the first block of a stream (c0 + h == 0): the record becomes eight zeros and nothing else runs.  A
+ *      flush that has no block leaves the record alone.
+ *   3. The candidate.  r = the first argmax of P over the rows, c = the first argmax over the columns.  The pair candidate
+ *      1 + 4 r + c needs ALL of: e_r >= theta and e_c >= theta; e_c <= fl(tau e_r) and e_r <= fl(tau e_c); every other row
+ *      P_j <= fl(delta P_r) and every other column P_j <= fl(delta P_c); fl(e_r + e_c) >= fl(pi2 E_x).  Otherwise, with
+ *      singles, the first k of 1100 / 2100 with e_k >= theta && e_k >= fl(pi1 E_x) gives 17 or 18.  Otherwise 0.  If any of
+ *      E_x, P_f is not <= FLT_MAX, the candidate is 0.
+ *   4. The run.  If the candidate is not 0 and equals cand, run += 1; otherwise run = 1 if the candidate is not 0, else 0.
+ *      cand = the candidate.  need_g = cand < 17 ? G : N1, need_r = cand < 17 ? N2 : N1.
+ *   5. Guard and report.  If cand != 0 && run >= need_g: guard = 1, hold = H.  Else if hold > 0: hold -= 1, guard = 1.  Else
+ *      guard = 0.  If cand != 0 && run >= need_r: events += 1 when tone != cand, then tone = cand.  Else if guard == 0:
+ *      tone = 0.  During the hold tone stays.
+ *   6. If mode == 1 && guard == 1 the block's dry gain is 1 at every sample: with gains m_i = wave_mix(1, x_i, w_i), which is
+ *      x_i ("attenuation limit"); without gains m_i = x_i.  With ramp words the ramp word ends the block at 1, and the next
+ *      unguarded block ramps 1 -> g by the rule of "gain ramps": entering snaps, leaving ramps.  With tones set, a block ramps
+ *      from the carried p to its own target at ANY hop of a call (p is carried from block to block inside the launch).
+ *      Otherwise m_i is what the call makes without the guard.
+ *   7. Level control (if set) and the meters (if set) then see m exactly as in "level control" (E_w stays the wet block's).
+ *      After that guarded += guard, blocks += 1.
+ *
+ * What follows.
+ *   With mode == 0 the outputs, every state, the meters, the ramp words and the level-control records equal the call without
+ *     tones bit for bit.  With mode == 1 every unguarded block whose predecessor was unguarded equals that twin too.
+ *   A guarded block is the dry input one hop late, bit for bit, in the float, int16 and G.711 forms.
+ *   The record does not depend on how the hops are cut into calls.  Slot and contiguous forms give the same bits.  Rows a call
+ *     does not step are neither read nor written.
+ *   A NaN or Inf in one stream moves no bit of another stream's output or record; its own candidate is 0 while E_x or a P_f
+ *     is not finite, and the record stays finite.
+ *   Graph capture: the three pointers are captured kernel arguments; a captured step follows rewritten parameter words.
+ *   Rate, packet, packet-slot and G.711 forms inherit the guard through the 16 kHz hand-off.
+ *   High band: the guard only changes beta, and beta = 1 with gamma = 1 is the bypass identity, so the _hb calls stay legal
+ *     with tones set.  They still refuse while a level-control address is set.
+ *   No look-ahead: the block in which a tone starts part-way is emitted as the model made it, and H covers the partial last
+ *     block.
+ *   A launch with tones is timed in the row of the form it stands in for, as a launch with level control is.
+ *
+ * gtcrn_tone_block_host is a pure host function: steps 1 and 3..5 of one block through the functions the kernel compiles,
+ * lane layout and butterfly included -- params16, the table and the 256 dry samples in, record8 advanced in place (words 6
+ * and 7 are step 7's and stay), *guard_out = (mode == 1 && guard == 1).
+ * Out of scope: gtcrn_forward_wave* (offline), the spectrogram-level and _quant calls, one parameter set per stream,
+ * second-harmonic checks, other signalling tones, RFC 4733 packetisation. */
+typedef struct gtcrn_tone_config {
+    double min_dbov;       /* floor on one tone's level */
+    double twist_db;       /* most a row and a column tone may differ */
+    double dominance_db;   /* least the strongest row / column stands above the others of its group */
+    double pair_purity;    /* share of the block's energy the pair holds */
+    double single_purity;  /* ... a single tone holds */
+    int guard_blocks;      /* G */
+    int digit_blocks;      /* N2 */
+    int single_blocks;     /* N1 */
+    int hold_blocks;       /* H */
+    int mode;              /* 1: guard; 0: detect only */
+    int singles;           /* 1: look for 1100 / 2100 Hz too */
+} gtcrn_tone_config;
+#define GTCRN_TONE_DEFAULTS {-45.0, 8.0, 8.0, 0.6, 0.8, 1, 2, 4, 1, 1, 1}
+#define GTCRN_TONE_TABLE_FLOATS 5120
+int gtcrn_wave_stream_set_tone(gtcrn_model *m, float *d_tone, const float *d_tone_params, const float *d_tone_table);
+int gtcrn_tone_params_host(const gtcrn_tone_config *config, float *out16);
+int gtcrn_tone_table_host(float *out /* [GTCRN_TONE_TABLE_FLOATS] */);
+int gtcrn_tone_block_host(const float *params16, const float *table, float *record8, const float *x256, int *guard_out);
+
 /* ---- non-finite input: what a NaN or Inf in one stream may touch ---------------------------------------------------------
  * The library seats unrelated callers side by side -- four or seven streams in a workgroup, MFMA tiles that straddle two
  * streams, time spans that run across utterance boundaries -- and a float sample is whatever the caller sent.  The contract
