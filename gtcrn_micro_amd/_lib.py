@@ -294,6 +294,13 @@ def lib():
         L.gtcrn_batch_phone_plan_host.argtypes = [cf, ci, ci, cl, _vp, _vp]
         L.gtcrn_batch_phone.argtypes = [_vp, cl, _vp, cl, _vp, ci, cl, _vp, cl, _vp, cl, ci, _vp, _vp]
         L.gtcrn_batch_phone_host.argtypes = [_vp, cl, _vp, cl, _vp, ci, cl, _vp, cl, _vp, cl, ci, _vp]
+    # conference rooms: the mix-minus of the loudest talkers (gtcrn_micro_amd/mixer.py)
+    mix_dev = [_vp, cl, ci, _vp, cl, ci, ci, _vp, _vp, ci, ci, _vp, _vp, ci, _vp, _vp, cl, _vp]
+    L.gtcrn_mix_params_host.argtypes = [_vp, _vp]
+    L.gtcrn_mix_rooms.argtypes = mix_dev
+    L.gtcrn_mix_rooms_pcm16.argtypes = mix_dev
+    L.gtcrn_mix_rooms_host.argtypes = mix_dev[:-1]
+    L.gtcrn_mix_rooms_pcm16_host.argtypes = mix_dev[:-1]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

@@ -1479,6 +1479,80 @@ int gtcrn_batch_phone_host(const float *h_src_noisy, long src_noisy_stride, cons
                            const gtcrn_phone_item *h_plan, int B, long L, float *h_noisy, long noisy_stride, float *h_clean,
                            long clean_stride, int target, gtcrn_phone_record *h_records);
 
+/* ---- conference rooms: mix-minus of the loudest talkers ------------------------------------------------------------------------
+ * The one step of a conference bridge that crosses streams: every participant of a room receives the sum of the other talkers,
+ * limited to the K who are speaking, faded over one block when the talkers change.  A post-pass over the enhanced blocks a live
+ * step has just written (any rate, any packet form: rows of n samples), with no handle and in no existing kernel; a caller who
+ * does not mix issues the launches they issued before.  Stated operation by operation, every fl() one correctly rounded fp32
+ * operation (the files are compiled with -ffp-contract=off), so that a page of numpy restates it bit for bit
+ * (tests/mixer_checker.py).
+ *
+ * One call: d_in holds n_in rows of n samples (1 <= n <= 1024) at in_stride, d_out n_out rows at out_stride; the two ranges may not
+ * overlap.  d_room_start[R + 1]: room r holds the seats [d_room_start[r], d_room_start[r + 1]) of d_seats (n_seats of them, 16-byte
+ * aligned), a seat four ints {in_row, out_row, rec, 0}: in_row = -1 the participant sent nothing this tick, out_row = -1 nothing
+ * is to be written for them, rec their record.  d_nrooms (may be NULL) is a device word: rooms at or above *d_nrooms are
+ * skipped, so that one captured call serves a changing set of rooms.  d_rec: n_rec records of 4 floats {g, level, picked, blocks},
+ * 16-byte aligned; a zeroed record is a fresh participant.  d_params: 8 floats, 16-byte aligned, read at launch: {K (1 .. 8, an
+ * integer), theta1 = 10^(floor_dbov / 10), alpha in [0, 1], kappa = 10^(incumbent_db / 10) >= 1, 0, 0, 0, 0}; gtcrn_mix_params_host
+ * makes them (double arithmetic, one rounding to float per word; GTCRN_ERR_ARG for a null pointer, a non-finite field, k outside
+ * 1 .. 8, alpha outside [0, 1], incumbent_db < 0).  Defaults (GTCRN_MIX_DEFAULTS): K = 3, floor -50 dBov, alpha 0.125, 3 dB.  A K
+ * that gtcrn_mix_params_host did not make is clamped to 1 .. 8.  d_voice (may be NULL): float words, that of a seat at
+ * d_voice[rec * voice_stride]; level control's voice flag is read in place with d_voice = d_alc + 3, voice_stride = 8.
+ *
+ * Per live room, the seats in table order (s the samples of a seat's in_row; in the _pcm16 form s = p / 32768, exact):
+ *   1. E: lane l of 64 runs acc = +0; for j = l, l + 64, ... < n: acc = fl(acc + fl(s_j s_j)); then the xor butterfly
+ *      v_l = fl(v_l + v_(l xor d)) over d = 1, 2, 4, 8, 16, 32.
+ *   2. present iff in_row is valid and E <= FLT_MAX (read from the bits: a NaN fails).  A seat that is not present contributes
+ *      nothing, keeps its level and counts as g_old = 0: a non-finite block never reaches another participant.
+ *   3. level = E >= level ? E : fl(level + fl(alpha fl(E - level))).
+ *   4. eligible iff d_voice[rec * voice_stride] != 0, or without d_voice iff E >= fl(theta1 fl(n)).
+ *   5. key = eligible ? (g_old == 1 ? fl(kappa level) : level) : -1, g_old the record's g.
+ *   6. up to K rounds, each taking the unpicked seat of largest key, key > 0, ties to the lowest seat position: t = 1, else 0.
+ *   7. r_i = fl(fl(i + 1) / fl(n)); the gain of sample i is 1 (g_old 1, t 1), r_i (0, 1: fade in), fl(1 - r_i) (1, 0: fade out),
+ *      0 (0, 0).  The contributors are the present seats with g_old + t > 0: at most 2 K while every g = 1 was written by a call
+ *      with K <= 8 (of more than 16, the first 16 in seat order count).
+ *   8. for every seat with a valid out_row: acc = +0; for each contributor c other than this seat, in seat order:
+ *      acc = fl(acc + fl(gain_c,i s_c,i)).  Stored as acc, or in the _pcm16 form as clip(rint(32768 acc), -32768, 32767), the rule
+ *      of gtcrn_f32_to_pcm16.
+ *   9. g = t for a present seat, else 0; picked += t; blocks += 1 for every seat of a live room.
+ * So: a room's outputs and records depend on nothing outside its seats; a lone participant hears zeros; with no change of
+ * talkers the mix is the plain ordered sum; a talker who leaves the pick fades over exactly one block.
+ *
+ * No load or store leaves the buffers, whatever the tables hold: a row index outside [-1, n_in) / [-1, n_out) counts as -1, a
+ * seat with rec outside [0, n_rec) is ignored, a room is skipped when its d_room_start pair decreases, leaves [0, n_seats] or
+ * spans more than GTCRN_MIX_MAX_ROOM seats.  A rec or an out_row named twice in one call is the caller's error: the result is
+ * then unspecified for those seats only.  Output rows that no seat names are not written.
+ *
+ * gtcrn_mix_rooms / gtcrn_mix_rooms_pcm16 take device pointers, are asynchronous on `stream`, allocate nothing and are
+ * capturable: one launch, a workgroup per room.  GTCRN_ERR_ARG before any launch: a negative count, n outside 1 .. 1024, a null
+ * d_room_start, d_seats, d_rec or d_params (or row buffer with rows), a stride below n, voice_stride < 1, a misaligned pointer,
+ * overlapping input and output ranges.  gtcrn_mix_rooms_host / _pcm16_host: the same arguments on host pointers, no device and
+ * no stream; they run the very functions the kernel compiles (csrc/mixer.h).
+ *
+ * Out of scope: rooms whose legs differ in rate or packet length; G.711 bytes in and out (gtcrn_g711_to_f32 / gtcrn_f32_to_g711
+ * stand either side); per-talker gains or panning; more than 8 talkers; a participant in two rooms at once. */
+#define GTCRN_MIX_MAX_ROOM 1024
+typedef struct gtcrn_mix_config {
+    int k;                 /* talkers admitted, 1 .. 8 */
+    double floor_dbov;     /* a block below it is not speech (used without d_voice) */
+    double alpha;          /* release smoothing of the level, 0 .. 1 */
+    double incumbent_db;   /* what a challenger must exceed a talker in the mix by, >= 0 */
+} gtcrn_mix_config;
+#define GTCRN_MIX_DEFAULTS {3, -50.0, 0.125, 3.0}
+int gtcrn_mix_params_host(const gtcrn_mix_config *config, float *out8);
+int gtcrn_mix_rooms(const float *d_in, long in_stride, int n_in, float *d_out, long out_stride, int n_out, int n,
+                    const int *d_room_start, const int *d_seats, int n_seats, int R, const int *d_nrooms, float *d_rec, int n_rec,
+                    const float *d_params, const float *d_voice, long voice_stride, void *stream);
+int gtcrn_mix_rooms_pcm16(const short *d_in, long in_stride, int n_in, short *d_out, long out_stride, int n_out, int n,
+                          const int *d_room_start, const int *d_seats, int n_seats, int R, const int *d_nrooms, float *d_rec,
+                          int n_rec, const float *d_params, const float *d_voice, long voice_stride, void *stream);
+int gtcrn_mix_rooms_host(const float *h_in, long in_stride, int n_in, float *h_out, long out_stride, int n_out, int n,
+                         const int *h_room_start, const int *h_seats, int n_seats, int R, const int *h_nrooms, float *h_rec,
+                         int n_rec, const float *h_params, const float *h_voice, long voice_stride);
+int gtcrn_mix_rooms_pcm16_host(const short *h_in, long in_stride, int n_in, short *h_out, long out_stride, int n_out, int n,
+                               const int *h_room_start, const int *h_seats, int n_seats, int R, const int *h_nrooms, float *h_rec,
+                               int n_rec, const float *h_params, const float *h_voice, long voice_stride);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
