@@ -12,5 +12,7 @@ from . import data  # noqa: F401
 from .data import BatchSource, Corpus, RirBank  # noqa: F401
 from . import mixer  # noqa: F401
 from .mixer import Mixer, mix_params, mix_rooms_host  # noqa: F401
+from . import plc  # noqa: F401
+from .plc import Concealer, plc_params, plc_rows_host  # noqa: F401
 
-__all__ = ["alc_params", "alc_block", "tone_params", "tone_table", "tone_block", "pcm16_to_f32", "f32_to_pcm16", "Engine", "GtcrnError", "Trainer", "stft", "istft", "stft_frames", "make_window", "num_frames", "selftest_mfma", "selftest_split3", "WaveStreamState", "RateStreamState", "PacketStreamState", "PacketSlotState", "Resampler", "resample_taps", "packet_stream_n16", "packet_stream_latency16", "atten_lim_to_gain", "gain_ramp", "level_dbov", "g711_to_f32", "f32_to_g711", "g711_decode_table", "g711_encode_pcm16", "Scorer", "score_taps", "score_bands", "score_frames", "data", "Corpus", "BatchSource", "mixer", "Mixer", "mix_params", "mix_rooms_host"]
+__all__ = ["alc_params", "alc_block", "tone_params", "tone_table", "tone_block", "pcm16_to_f32", "f32_to_pcm16", "Engine", "GtcrnError", "Trainer", "stft", "istft", "stft_frames", "make_window", "num_frames", "selftest_mfma", "selftest_split3", "WaveStreamState", "RateStreamState", "PacketStreamState", "PacketSlotState", "Resampler", "resample_taps", "packet_stream_n16", "packet_stream_latency16", "atten_lim_to_gain", "gain_ramp", "level_dbov", "g711_to_f32", "f32_to_g711", "g711_decode_table", "g711_encode_pcm16", "Scorer", "score_taps", "score_bands", "score_frames", "data", "Corpus", "BatchSource", "mixer", "Mixer", "mix_params", "mix_rooms_host", "plc", "Concealer", "plc_params", "plc_rows_host"]

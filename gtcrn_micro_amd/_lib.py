@@ -301,6 +301,16 @@ def lib():
     L.gtcrn_mix_rooms_pcm16.argtypes = mix_dev
     L.gtcrn_mix_rooms_host.argtypes = mix_dev[:-1]
     L.gtcrn_mix_rooms_pcm16_host.argtypes = mix_dev[:-1]
+    # packet loss concealment (gtcrn_micro_amd/plc.py)
+    plc_dev = [_vp, cl, ci, ci, _vp, _vp, _vp, _vp, cl, _vp, ci, _vp]
+    L.gtcrn_plc_params_host.argtypes = [_vp, _vp]
+    L.gtcrn_plc_rows.argtypes = plc_dev + [_vp]
+    L.gtcrn_plc_rows_pcm16.argtypes = plc_dev + [_vp]
+    L.gtcrn_plc_rows_g711.argtypes = plc_dev + [ci, _vp]
+    L.gtcrn_plc_reset.argtypes = [_vp, cl, _vp, ci, _vp, _vp, ci, _vp, _vp]
+    L.gtcrn_plc_rows_host.argtypes = plc_dev
+    L.gtcrn_plc_rows_pcm16_host.argtypes = plc_dev
+    L.gtcrn_plc_rows_g711_host.argtypes = plc_dev + [ci]
     if L.gtcrn_abi_version() != 1:
         raise GtcrnError("libgtcrn_micro_hip.so ABI version mismatch")
     _lib = L

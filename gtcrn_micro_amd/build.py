@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgtcrn_micro_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["kernels.hip", "api.cpp", "pack.cpp", "train_kernels.hip", "train.cpp", "metrics.hip", "metrics_host.cpp", "batch.hip", "batch_host.cpp", "reverb.hip", "reverb_host.cpp", "phone.hip", "phone_host.cpp", "mixer.hip", "mixer_host.cpp"]
-HEADERS = ["kernels.h", "fft256.h", "stream_ms_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", "batch.h", "reverb.h", "phone.h", "mixer.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
+SOURCES = ["kernels.hip", "api.cpp", "pack.cpp", "train_kernels.hip", "train.cpp", "metrics.hip", "metrics_host.cpp", "batch.hip", "batch_host.cpp", "reverb.hip", "reverb_host.cpp", "phone.hip", "phone_host.cpp", "mixer.hip", "mixer_host.cpp", "plc.hip", "plc_host.cpp"]
+HEADERS = ["kernels.h", "fft256.h", "stream_ms_body.inc", "layout.h", "pack.h", "train_kernels.h", "metrics.h", "batch.h", "reverb.h", "phone.h", "mixer.h", "plc.h", os.path.join("..", "..", "include", "gtcrn_micro_hip.h")]
 
 
 def _stale(target, deps):
@@ -51,11 +51,15 @@ def build_native(force=False, verbose=False, stamps=False, exp=False):
     #     operations in a fixed order (tests/mixer_checker.py restates it bit for bit).  Its fade ramp fl(fl(i + 1) / fl(n)) relies
     #     on hipcc's default correctly rounded fp32 `/` (-fhip-fp32-correctly-rounded-divide-sqrt): do not add -ffast-math or
     #     -fno-hip-fp32-correctly-rounded-divide-sqrt to these files.
+    # Concealment kernels (plc.hip, plc_host.cpp): -ffp-contract=off, because the contract is single stated operations: the lag
+    #     search's score is one rounded product and one rounded quotient in double, the float cross-fade two rounded products and
+    #     a rounded sum, and everything else is integer arithmetic (tests/plc_checker.py restates it bit for bit).
     per_file = {"kernels.hip": ["-fno-honor-nans", "-ffp-contract=on"], "batch.hip": ["-ffp-contract=off"],
                 "batch_host.cpp": ["-ffp-contract=off"], "reverb.hip": ["-ffp-contract=off"],
                 "reverb_host.cpp": ["-ffp-contract=off"], "phone.hip": ["-ffp-contract=off"],
                 "phone_host.cpp": ["-ffp-contract=off"], "mixer.hip": ["-ffp-contract=off"],
-                "mixer_host.cpp": ["-ffp-contract=off"]}
+                "mixer_host.cpp": ["-ffp-contract=off"], "plc.hip": ["-ffp-contract=off"],
+                "plc_host.cpp": ["-ffp-contract=off"]}
     suffix = ""
     lib = LIB
     if stamps:

@@ -1553,6 +1553,97 @@ int gtcrn_mix_rooms_pcm16_host(const short *h_in, long in_stride, int n_in, shor
                                const int *h_room_start, const int *h_seats, int n_seats, int R, const int *h_nrooms, float *h_rec,
                                int n_rec, const float *h_params, const float *h_voice, long voice_stride);
 
+/* ---- packet loss concealment -------------------------------------------------------------------------------------------------------
+ * What a gateway does to a call leg when a packet does not arrive: it makes the audio up.  A pre-pass over the rows a live step is
+ * about to take (any rate, any packet form: rows of n samples, float, int16 or G.711 codes), with no handle and in no existing
+ * kernel; a caller who does not conceal issues the launches they issued before.  Every leg then has a packet every tick, real or
+ * synthesised, and the step, the meters, level control and the mixer run on continuous time.  The arithmetic is this project's
+ * own: the ideas of G.711 Appendix I (pitch-synchronous repetition of the history, a hold, a linear fade-out, a cross-fade back
+ * into the real signal) without its quarter-wavelength overlap-add and with no claim of parity.  Integer arithmetic but for one
+ * stated double expression and the float cross-fade (the files are compiled with -ffp-contract=off), so that a page of numpy
+ * restates outputs, histories and records bit for bit (tests/plc_checker.py).
+ *
+ * The 8 parameter words (int32, 16-byte aligned, read at launch) are {pmin, pmax, W, D, T0, T1, F, fs}, `div` the integer quotient:
+ *   pmin = fs div 200 (shortest lag), pmax = fs 15 div 1000 (longest lag), W = fs div 50 (correlation window, 20 ms),
+ *   D = max(1, fs div 8000) (stride of the coarse search), T0 = hold_ms fs div 1000 (hold), T1 = fade_ms fs div 1000 (fade-out),
+ *   F = max(1, recover_ms fs div 1000) (cross-fade into the real signal);  Lh = pmax + W is the history length (at most
+ *   GTCRN_PLC_MAX_HISTORY, reached at 48 kHz).
+ * gtcrn_plc_params_host is the one place they are made; GTCRN_ERR_ARG with a reason for a null pointer, an fs other than 8000,
+ * 16000, 22050, 24000, 32000, 44100, 48000, hold_ms outside 0 .. 200, fade_ms outside 1 .. 200, recover_ms outside 0 .. 200.
+ * Defaults (GTCRN_PLC_DEFAULTS(fs)): 10, 50 and 5 ms.  Words made elsewhere turn a call into a no-op unless pmin >= 1,
+ * pmin <= pmax, W >= 1, D >= 1, Lh <= min(GTCRN_PLC_MAX_HISTORY, hist_stride), 0 <= T0 <= 65536, 1 <= T1 <= 65536, F >= 1.
+ *
+ * Per-stream state, owned by the caller at fixed addresses, S slots of each:
+ *   d_hist  int16, slot s at d_hist + s hist_stride: a ring of Lh samples.  Logical sample j (0 the oldest, Lh - 1 the newest)
+ *           lives at ring[(pos + j) mod Lh]; nothing beyond Lh is read or written.
+ *   d_rec   four int32 {pos, lag, erased, events}, 16-byte aligned: the ring's write position, the lag of the running (or last)
+ *           erasure, the samples concealed so far in the running erasure (0: none running; saturates at T0 + T1), and the
+ *           counters: events & 0xFFFF erasures, (events >> 16) & 0xFFFF lost packets, each modulo 65536.
+ * A zeroed history and record are a fresh stream.  A record no call wrote is read with pos outside [0, Lh) as 0, lag clamped to
+ * [pmin, pmax], erased clamped to [0, T0 + T1].
+ *
+ * One call: d_x holds M rows of n samples (1 <= n <= 1024) at `stride`; row i belongs to slot d_slots[i] (d_slots NULL: slot i);
+ * d_lost[i] != 0 says that the packet did not arrive, and the row's contents are then ignored; d_count (may be NULL) is a device
+ * word: rows at or beyond *d_count are skipped.  Rows that are skipped and slots that are not named are not touched in any array;
+ * a slot id outside [0, S) makes its row a no-op.  A slot named twice in one call is the caller's error: the result is then
+ * unspecified for that slot only.  Per row, with h the history in logical order and `int16 of` a sample: the sample itself,
+ * pcm_of(x) = clip(rint(32768 x), -32768, 32767) (the rule of gtcrn_f32_to_pcm16; a NaN gives -32768), or D_law[code] of
+ * "G.711 payloads":
+ *   1. received, erased = 0: the row is not written (it stays bit for bit, NaN and Inf included).  The history takes the int16 of
+ *      every sample: appending n samples writes sample j to ring[(pos + j) mod Lh] for j >= max(0, n - Lh) (a row longer than
+ *      the history leaves its last Lh samples) and sets pos = (pos + n) mod Lh.  Only pos of the record is written.
+ *   2. lost, erased = 0 (an erasure begins): m = max |h_j|, s = max(0, bitlength(m) - 10), a_j = h_j >> s (arithmetic), so that
+ *      every product is below 2^20 and every sum below 2^30.  For a lag p and a stride d, over i = 0, d, 2d, ... < W:
+ *      c = sum a[Lh-1-i] a[Lh-1-i-p], e = sum a[Lh-1-i-p]^2 (int32), score = (c > 0 and e > 0) ?
+ *      fl64(fl64(double(c) double(c)) / double(e)) : 0.  Coarse: p = pmin, pmin + D, ... <= pmax at stride D; the largest score
+ *      wins, among equal scores the smallest lag, and only a score > 0 can win.  No winner (silence, a fresh stream): lag = pmax.
+ *      Otherwise refine over max(pmin, p0 - D + 1) .. min(pmax, p0 + D - 1) at stride 1 by the same rule; no winner there: lag = p0.
+ *   3. lost (after 2, or erased > 0): s_i = h[Lh - lag + (i mod lag)], t = erased + i, g(t) = 32768 for t < T0, 0 for t >= T0 + T1,
+ *      else 32768 - ((t - T0) 32768) div T1; o_i = (s_i g(t) + 16384) >> 15.  The row is written as o_i (int16), fl(o_i / 32768)
+ *      (float, exact) or E_law(o_i).  The history takes s, not o (it holds the unattenuated continuation, so a longer erasure
+ *      needs no recursion).  erased = min(erased + n, T0 + T1); events: lost packets + 1, and erasures + 1 after step 2.
+ *   4. received, erased > 0 (recovery): f = min(F, n); for i < f: r_i = ((i + 1) 32768) div f, sa_i step 3's o_i;
+ *      int16: o = (x r + sa (32768 - r) + 16384) >> 15; G.711: the same on x = D_law[code], stored as E_law(o) (so the f faded
+ *      samples are re-encoded; at r = 32768 o = x); float: o = fl(fl(x rf) + fl(saf fl(1 - rf))) with the exact rf = r / 32768,
+ *      saf = sa / 32768.  The rest of the row is not written.  The history takes the int16 of the row as written; erased = 0.
+ * So: no added latency; a stream depends on nothing outside its own row, history and record; the cut of a clip into packets
+ * matters (packets are the units of loss), the grouping of rows into calls does not; a non-finite float sample stays in its own
+ * stream and enters that stream's history as an int16 like any other.
+ *
+ * gtcrn_plc_rows / _pcm16 / _g711 take device pointers, are asynchronous on `stream`, allocate nothing and are capturable: one
+ * launch, a wave per row.  gtcrn_plc_reset zeroes the histories (Lh samples) and records of the named slots (d_slots NULL: slots
+ * 0 .. M - 1) below *d_count, in one launch of its own: a stream joins a captured tick through it.  GTCRN_ERR_ARG before any launch:
+ * a negative count, n outside 1 .. 1024, a null d_lost, d_hist, d_rec or d_params (or row buffer with rows), a stride below n,
+ * hist_stride < 1, a law other than 0 / 1, a misaligned pointer.  gtcrn_plc_rows_host / _pcm16_host / _g711_host: the same
+ * arguments on host pointers, no device and no stream; they run the very functions the kernel compiles (csrc/plc.h).
+ *
+ * Out of scope: parity with G.711 Appendix I or any codec's own concealment; concealment on the output side; jitter buffering
+ * and reordering (d_lost is their result); comfort noise in long erasures; a new pitch estimate inside an erasure; the offline
+ * forward_wave calls. */
+#define GTCRN_PLC_MAX_HISTORY 1680
+typedef struct gtcrn_plc_config {
+    int fs;                /* 8000, 16000, 22050, 24000, 32000, 44100 or 48000 */
+    int hold_ms;           /* full level for this long, 0 .. 200 */
+    int fade_ms;           /* then a linear fade to zero over this long, 1 .. 200 */
+    int recover_ms;        /* cross-fade into the first received packet, 0 .. 200 (at least one sample) */
+} gtcrn_plc_config;
+#define GTCRN_PLC_DEFAULTS(fs) {(fs), 10, 50, 5}
+int gtcrn_plc_params_host(const gtcrn_plc_config *config, int *out8);
+int gtcrn_plc_rows(float *d_x, long stride, int M, int n, const int *d_slots, const int *d_lost, const int *d_count, short *d_hist,
+                   long hist_stride, int *d_rec, int S, const int *d_params, void *stream);
+int gtcrn_plc_rows_pcm16(short *d_x, long stride, int M, int n, const int *d_slots, const int *d_lost, const int *d_count,
+                         short *d_hist, long hist_stride, int *d_rec, int S, const int *d_params, void *stream);
+int gtcrn_plc_rows_g711(unsigned char *d_x, long stride, int M, int n, const int *d_slots, const int *d_lost, const int *d_count,
+                        short *d_hist, long hist_stride, int *d_rec, int S, const int *d_params, int law, void *stream);
+int gtcrn_plc_reset(short *d_hist, long hist_stride, int *d_rec, int S, const int *d_params, const int *d_slots, int M,
+                    const int *d_count, void *stream);
+int gtcrn_plc_rows_host(float *h_x, long stride, int M, int n, const int *h_slots, const int *h_lost, const int *h_count, short *h_hist,
+                        long hist_stride, int *h_rec, int S, const int *h_params);
+int gtcrn_plc_rows_pcm16_host(short *h_x, long stride, int M, int n, const int *h_slots, const int *h_lost, const int *h_count,
+                              short *h_hist, long hist_stride, int *h_rec, int S, const int *h_params);
+int gtcrn_plc_rows_g711_host(unsigned char *h_x, long stride, int M, int n, const int *h_slots, const int *h_lost, const int *h_count,
+                             short *h_hist, long hist_stride, int *h_rec, int S, const int *h_params, int law);
+
 /* ---- standalone streaming conv wrappers -----------------------------------
  * Replaces StreamConv2d.forward / StreamConvTranspose2d.forward
  * (streaming/conversion/convolution.py:107-119, 201-253): out = conv(cat([cache, x], time)),
